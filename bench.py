@@ -14,6 +14,8 @@ strips, the brickmap is replicated per GPU and the packed strips of the step are
 collective (strong scaling: the frames and the batch are the same at every N).
 `value` = rays actually traced by all ranks / wall time of the K timed steps (inputs resident in HBM, gather
 included).  Rank 0 prints ONE JSON line.
+`--dump-outputs DIR`: rank 0 also writes the frames of the last timed step to DIR as .npy files (see dump_outputs), so
+that two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -29,6 +31,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, Chip-level parameters)
+# --dump-outputs: pixels written per step (4 float32 channels + one float64 index each: 48 MiB, under the 64 MB cap; a
+# default step, 16 views of 1080p, has 33 M pixels)
+DUMP_PIXELS = 1 << 21
 
 WORKLOADS = {
     # name: (world X, Y, Z, factor, generator, width, height, shadow, bounce_samples)
@@ -80,7 +85,13 @@ def parse():
     ap.add_argument("--force-gather", action="store_true",
                     help="development only: with ONE rank, run the N>1 code path anyway (packed strips, two-deep "
                          "pipeline, gather on a one-rank NCCL communicator, de-interleave) and check the frames")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the frames of the last timed step to DIR as .npy (float32 pixels, "
+                         "a fixed seeded sample when the step has more than %d pixels)" % DUMP_PIXELS)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
@@ -253,6 +264,8 @@ def run(args):
     st = ctx.frame_stats()  # rays traced by this rank in the K timed steps (always counted by the kernel)
     rays_local = st.total_rays()
     kernel_ms = [a.elapsed_time(b) for a, b in events]
+    if args.dump_outputs and rank == 0:  # before anything below renders into the same frame buffers again
+        dump_outputs(args.dump_outputs, pipe.frame_of(args.warmup + args.steps - 1) if pipe else frames)
 
     # algorithmic bytes of the same K launches, from the probe-counting kernel variant, untimed
     for k in range(args.steps):
@@ -530,6 +543,26 @@ def run(args):
         dist.barrier()
         dist.destroy_process_group()
     return result if rank == 0 else None
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the (V, H, W, 4) uint8 frames of one step, as a caller of RenderViews receives them, written as
+    out_dir/frame_pixels.npy ((n, 4) float32, the channels in framebuffer order) and out_dir/frame_pixel_index.npy ((n,)
+    float64, the flat index (view * H + row) * W + column of each pixel).  Every pixel when the step has at most
+    DUMP_PIXELS of them, otherwise a sample of DUMP_PIXELS pixels drawn with a fixed seed: the same pixels for the same
+    arguments, in every run and every build."""
+    import torch
+
+    V, H, W, C = frames.shape
+    n = V * H * W
+    if n <= DUMP_PIXELS:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+    pixels = frames.reshape(n, C)[torch.from_numpy(idx).to(frames.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_pixels.npy"), pixels.astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
 
 
 def host_cores() -> int:
