@@ -5,6 +5,7 @@
 //
 //   voxelapp_headless [world_edge=256] [frames=2] [out_prefix=frame] [width=320] [height=180] [shaded=0]
 //                     [camera_path_file] [dump_every_frame=0] [views_per_launch=1] [frames_in_flight=1] [device_world=XxYxZ]
+//                     [edit_script]
 //
 // shaded: 0 = the checked-in debug view, 1 = shaded with shadow + 1 bounce sample, checkerboard on, 2 = the same with the
 // checkerboard off (whole frames).  frames_in_flight=2 renders through Graphics::RenderScreenAsync / WaitFrame: frame k+1 is
@@ -18,6 +19,10 @@
 // '#' starts a comment); `frames` is then the number of lines.  With dump_every_frame=1 each frame is also written
 // as <out_prefix>_NNNN.ppm (under checkerboard rendering a frame keeps the other half of the previous one).
 // views_per_launch > 1 renders that many poses per launch through Graphics::RenderScreens (no checkerboard then).
+// edit_script (voxel editing, VoxelRaytracer3D::EditVoxels): one op per line, "frame kind value ax ay az bx by bz" --
+// kind 0 = box a..b (inclusive voxels), 1 = sphere of centre a and radius bx (by = bz = 0); value 1 = set, 0 = clear --
+// applied in file order before that frame is rendered ('#' starts a comment; with views_per_launch > 1, before the launch
+// that holds the frame).  A '-' skips it.
 #include "../include/GPUDDA/Renderer.h"
 #include "../include/GPUDDA/VoxelWorldBuilder.h"
 #include "../include/vxrt.h"
@@ -53,6 +58,33 @@ int main(int argc, char** argv)
     if (argc > 11 && std::sscanf(argv[11], "%ux%ux%u", &wx, &wy, &wz) != 3) {
         std::cerr << "device_world must look like 8192x512x8192" << std::endl;
         return 2;
+    }
+
+    struct EditLine {
+        int frame;
+        vxrt_edit_op op;
+    };
+    std::vector<EditLine> edits;
+    if (argc > 12 && std::string(argv[12]) != "-") {
+        std::ifstream in(argv[12]);
+        if (!in) {
+            std::cerr << "cannot open edit script " << argv[12] << std::endl;
+            return 2;
+        }
+        std::string line;
+        while (std::getline(in, line)) {
+            const size_t hash = line.find('#');
+            if (hash != std::string::npos)
+                line.resize(hash);
+            EditLine e{};
+            if (std::sscanf(line.c_str(), "%d %d %d %d %d %d %d %d %d", &e.frame, &e.op.kind, &e.op.value, &e.op.a[0], &e.op.a[1],
+                            &e.op.a[2], &e.op.b[0], &e.op.b[1], &e.op.b[2]) == 9)
+                edits.push_back(e);
+            else if (line.find_first_not_of(" \t\r") != std::string::npos) {
+                std::cerr << "edit script: cannot read \"" << line << "\"" << std::endl;
+                return 2;
+            }
+        }
     }
 
     struct Pose {
@@ -128,6 +160,24 @@ int main(int argc, char** argv)
         SetRenderSwitches(s);
     }
 
+    // the edit script's ops of frames [from, to), in file order, in calls of at most VXRT_EDIT_MAX_OPS ops
+    auto apply_edits = [&](int from, int to) {
+        std::vector<vxrt_edit_op> ops;
+        for (const EditLine& e : edits)
+            if (e.frame >= from && e.frame < to)
+                ops.push_back(e.op);
+        for (size_t k = 0; k < ops.size(); k += VXRT_EDIT_MAX_OPS) {
+            const size_t n = ops.size() - k < VXRT_EDIT_MAX_OPS ? ops.size() - k : VXRT_EDIT_MAX_OPS;
+            vxrt_edit_stats st{};
+            if (raytracer->EditVoxels(ops.data() + k, n, &st) != VXRT_OK) {
+                std::cerr << "edit before frame " << from << ": " << vxrt_last_error() << std::endl;
+                std::exit(3);
+            }
+            std::printf("edit before frame %d: %zu ops, %llu bricks touched, %llu created, %llu freed\n", from, n,
+                        (unsigned long long)st.bricks_touched, (unsigned long long)st.bricks_created, (unsigned long long)st.bricks_freed);
+        }
+    };
+
     void* d_pixels = nullptr;
     if (hipMalloc(&d_pixels, (size_t)width * height * sizeof(BGRA8888)) != hipSuccess)
         return 1;
@@ -181,6 +231,7 @@ int main(int argc, char** argv)
         for (int i = 0; i < nframes + 2; ++i) {
             auto f0 = std::chrono::high_resolution_clock::now();
             if (i < nframes) {
+                apply_edits(i, i + 1);
                 if (!path.empty()) {
                     cam_pos = path[(size_t)i].pos;
                     cam_eular = path[(size_t)i].euler;
@@ -220,6 +271,7 @@ int main(int argc, char** argv)
         for (int first = 0; first < nframes; first += batch) {
             const int n = nframes - first < batch ? nframes - first : batch;
             std::vector<ScreenView> views((size_t)n);
+            apply_edits(first, first + n);
             auto f0 = std::chrono::high_resolution_clock::now();
             for (int j = 0; j < n; ++j) {
                 if (!path.empty()) {
@@ -246,6 +298,7 @@ int main(int argc, char** argv)
             cam_pos = path[(size_t)i].pos;
             cam_eular = path[(size_t)i].euler;
         }
+        apply_edits(i, i + 1);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
         RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);

@@ -21,6 +21,8 @@
 #include <vector>
 
 struct vxrt_ctx;
+struct vxrt_edit_op;     // include/vxrt.h
+struct vxrt_edit_stats;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -124,6 +126,11 @@ public:
     vxrt_ctx* Context();        // uploads pending tables first
     // CreateVoxels + GenerateLowresVoxelBuffer + Upload* in one on-device step (no dense intermediate)
     void BuildProceduralWorld(uint3 size, int factor, int generator = 1);
+    // voxel editing (an extension; the reference lists "Fully modifiable terrain" as to do, README.md:16): box / sphere
+    // set and clear ops applied in order to the resident world (vxrt_edit_voxels); pending uploads are flushed first.
+    // Return the vxrt_status of the call (0 = done; on failure the world is unchanged).
+    int EditVoxels(const vxrt_edit_op* ops, size_t n, vxrt_edit_stats* stats = nullptr);
+    int ReserveBricks(size_t capacity_bricks);  // grow the brick pool ahead of edits (vxrt_edit_reserve)
 
 private:
     void Flush();

@@ -161,6 +161,50 @@ int vxrt_stream_focus(vxrt_ctx *ctx, const float focus[3], float radius, vxrt_st
 int vxrt_stream_resident(vxrt_ctx *ctx, uint8_t *flags, uint64_t n_chunks);
 int vxrt_stream_close(vxrt_ctx *ctx);
 
+/* ---- voxel editing -- an EXTENSION: the reference lists "Fully modifiable terrain" as to do (README.md:16).  An edit is a
+ * list of shape operations applied in order to the voxels of the resident world; afterwards the resident tables are exactly
+ * what GenerateLowresVoxelBuffer (VolumeRaytracer.cuh:379-516) builds from the edited dense grid -- coarse bits, per-cell
+ * extents and brick contents; only the pool slot numbers may differ -- so every frame and batch afterwards equals the frame
+ * of that rebuilt world.
+ *   Membership: integer arithmetic only.  A box covers every voxel v with a <= v <= b on each axis; a sphere every voxel
+ *     with dx^2 + dy^2 + dz^2 <= r^2 (d = v - a, evaluated without overflow in 64 bits).  Shapes are clipped to the world;
+ *     a shape wholly outside it, or an empty box (a > b on some axis), is a no-op.  A voxel takes the value of the LAST op
+ *     of the list that covers it, and otherwise keeps its value.
+ *   Validation before any change: an unknown kind, a value other than 0 or 1, a negative radius, nonzero b[1] / b[2] on a
+ *     sphere, n_ops > VXRT_EDIT_MAX_OPS, or ops == NULL with n_ops > 0 return VXRT_ERR_INVALID; no world gives
+ *     VXRT_ERR_NO_WORLD; a streamed world (vxrt_stream_open) gives VXRT_ERR_INVALID (a cache is not edited).
+ *   All or nothing: a call that fails -- VXRT_ERR_NOMEM when the pool cannot grow included -- leaves the world unchanged.
+ *   Ordering: like vxrt_stream_focus, the call synchronises the device before it touches the tables and returns when the
+ *     edit is complete: a launch issued before the call sees the old world, one issued after it the new world.
+ *     Accumulation histories (vxrt_render_flags.d_accum) are the caller's to reset.
+ *   Brick life cycle: a brick that becomes empty is freed -- its cell reads as empty (VXRT_EMPTY_SLOT, coarse bit 0, the
+ *     builder's empty extents), its slot is zeroed and goes on a free list.  A cell that becomes non-empty takes the
+ *     lowest free slot, else the next slot past the high-water mark; when the capacity is exhausted the pool grows by
+ *     1.5x or more (one copy of the pool; vxrt_edit_reserve grows it ahead of time).  Slot assignment is a host-side scan
+ *     in cell order: the same world and the same calls give a byte-identical vxrt_download_world, pool included.
+ *   A call that changes no voxel leaves the tables untouched.
+ *   vxrt_world_info.nslots is the high-water slot count; vxrt_download_world returns that many bricks, freed ones zero.
+ *   vxrt_save_world of a world that an edit has changed writes a COMPACTED pool: live bricks only, numbered in the
+ *   tables' tiled cell order as the builders number them, so the file opens with vxrt_stream_open as well.
+ *   Precondition: no two cells share a brick slot (true of every world the builders, the loader and the editor make).
+ * The cost is proportional to the bricks in the union of the ops' clipped brick boxes (bricks_touched), not to the world;
+ * each touched brick needs f^3 / 8 bytes of device scratch for the duration of the call. */
+#define VXRT_EDIT_MAX_OPS 1024
+typedef enum vxrt_edit_kind { VXRT_EDIT_BOX = 0, VXRT_EDIT_SPHERE = 1 } vxrt_edit_kind;
+typedef struct vxrt_edit_op {
+    int32_t kind;  /* vxrt_edit_kind */
+    int32_t value; /* 1 = set solid, 0 = clear */
+    int32_t a[3];  /* BOX: inclusive min voxel; SPHERE: centre voxel */
+    int32_t b[3];  /* BOX: inclusive max voxel; SPHERE: b[0] = radius >= 0, b[1] = b[2] = 0 */
+} vxrt_edit_op;
+typedef struct vxrt_edit_stats {
+    uint64_t bricks_touched, bricks_created, bricks_freed; /* by this call */
+    uint64_t bricks_live, pool_slots, pool_capacity;       /* after it; pool_slots = high-water slot count = nslots */
+} vxrt_edit_stats;
+int vxrt_edit_voxels(vxrt_ctx *ctx, const vxrt_edit_op *ops, uint32_t n_ops, vxrt_edit_stats *stats_or_null);
+/* grow the pool to at least capacity_bricks now, so that later edits need no copy (never shrinks it) */
+int vxrt_edit_reserve(vxrt_ctx *ctx, uint64_t capacity_bricks);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],
@@ -224,8 +268,8 @@ typedef struct vxrt_render_flags {
      * calculateColor (Renderer.cu:90-168) is added to the history and the MEAN is tonemapped and stored; the first frame of
      * a history (accum_reset != 0, or frames == 0) stores the colour itself.  Miss pixels, the debug view and the overlays
      * are written as without it.  With a static camera and one frame number per call the bounce noise averages out as 1/n;
-     * the caller resets the history when the camera moves.  vxrt_render only (a multi-view launch has no per-view
-     * history). */
+     * the caller resets the history when the camera moves -- or when vxrt_edit_voxels changes the world.  vxrt_render
+     * only (a multi-view launch has no per-view history). */
     float *d_accum;
     int32_t accum_reset;
     int32_t reserved_;

@@ -22,7 +22,10 @@ EXPORTS = [
     "vxrt_render_flags_default", "vxrt_render", "vxrt_render_views", "vxrt_compact_rows", "vxrt_frame_stats_get",
     "vxrt_deinterleave_strips", "vxrt_deinterleave_views", "vxrt_trace_batch", "vxrt_trace_batch_host",
     "vxrt_set_batch_max_steps", "vxrt_stream_open", "vxrt_stream_focus", "vxrt_stream_resident", "vxrt_stream_close",
+    "vxrt_edit_voxels", "vxrt_edit_reserve",
 ]
+EDIT_BOX, EDIT_SPHERE = 0, 1
+EDIT_MAX_OPS = 1024
 
 
 class WorldDesc(C.Structure):
@@ -59,6 +62,19 @@ class StreamStats(C.Structure):
     _fields_ = [("chunks_total", C.c_uint64), ("chunks_occupied", C.c_uint64), ("chunks_resident", C.c_uint64),
                 ("bricks_resident", C.c_uint64), ("chunks_loaded", C.c_uint64), ("chunks_evicted", C.c_uint64),
                 ("chunks_missing", C.c_uint64), ("bytes_read", C.c_uint64)]
+
+
+class EditOp(C.Structure):
+    """vxrt_edit_op: BOX a = inclusive min voxel, b = inclusive max voxel; SPHERE a = centre, b = (radius, 0, 0)."""
+    _fields_ = [("kind", C.c_int32), ("value", C.c_int32), ("a", C.c_int32 * 3), ("b", C.c_int32 * 3)]
+
+    def __repr__(self):
+        return "EditOp(kind=%d, value=%d, a=%s, b=%s)" % (self.kind, self.value, list(self.a), list(self.b))
+
+
+class EditStats(C.Structure):
+    _fields_ = [("bricks_touched", C.c_uint64), ("bricks_created", C.c_uint64), ("bricks_freed", C.c_uint64),
+                ("bricks_live", C.c_uint64), ("pool_slots", C.c_uint64), ("pool_capacity", C.c_uint64)]
 
 
 class RenderFlags(C.Structure):
@@ -150,6 +166,8 @@ def load() -> C.CDLL:
     L.vxrt_stream_focus.argtypes = [C.c_void_p, f3, C.c_float, C.POINTER(StreamStats)]
     L.vxrt_stream_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.vxrt_stream_close.argtypes = [C.c_void_p]
+    L.vxrt_edit_voxels.argtypes = [C.c_void_p, C.POINTER(EditOp), C.c_uint32, C.POINTER(EditStats)]
+    L.vxrt_edit_reserve.argtypes = [C.c_void_p, C.c_uint64]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

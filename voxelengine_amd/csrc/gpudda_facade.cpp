@@ -221,6 +221,20 @@ void VoxelRaytracer3D::BuildProceduralWorld(uint3 size, int f, int generator)
     dirty = false;
 }
 
+int VoxelRaytracer3D::EditVoxels(const vxrt_edit_op* ops, size_t n, vxrt_edit_stats* stats)
+{
+    Flush();
+    if (n > VXRT_EDIT_MAX_OPS)
+        return VXRT_ERR_INVALID;
+    return vxrt_edit_voxels(ctx, ops, (uint32_t)n, stats);
+}
+
+int VoxelRaytracer3D::ReserveBricks(size_t capacity_bricks)
+{
+    Flush();
+    return vxrt_edit_reserve(ctx, (uint64_t)capacity_bricks);
+}
+
 RayTraceResults<float3> VoxelRaytracer3D::Raytrace(std::vector<float3> origin, std::vector<float3> ray)
 {
     const size_t n = origin.size();

@@ -2,6 +2,7 @@
 // Owns the HBM-resident world tables, the camera/lighting state the reference keeps in
 // process globals (hFrameInfo / g_env, VoxelRT/Renderer.cu:24-25,89) and the launches.
 #include "../../include/vxrt.h"
+#include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <set>
 #include <string>
 #include <utility>
 #include <vector>
@@ -29,6 +31,12 @@ hipError_t layout_bits(const uint32_t* src, uint32_t* dst, const int cd[3], bool
 hipError_t layout_meta(const uint2* src, uint2* dst, const int cd[3], bool to_hbm);
 hipError_t layout_bricks(const uint32_t* src, uint32_t* dst, uint64_t nbricks, int f, bool to_hbm);  // src == dst: in place
 hipError_t chunk_tables(uint2* meta, uint32_t* coarse, const uint2* d_chunk_meta, int tx, int ty, int tz, int cx, int cz);
+// voxel editing (vxrt_edit.hip)
+hipError_t edit_bricks(const uint32_t* cells, uint32_t n, const EditOpDev* ops, uint32_t nops, const uint2* meta,
+                       const uint32_t* pool, uint32_t* scratch, uint32_t* ext, uint2* info, int f, int cx, int cz);
+hipError_t edit_commit(const uint32_t* cells, const uint32_t* new_slot, uint32_t n, const uint32_t* zero, uint32_t nzero,
+                       const uint32_t* scratch, const uint32_t* ext, uint32_t* pool, uint2* meta, uint32_t* coarse, int f);
+hipError_t gather_bricks(const uint32_t* pool, const uint32_t* idx, uint32_t n, uint32_t* dst, int f);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -84,6 +92,27 @@ struct vxrt_ctx {
     hipEvent_t views_busy[16] = {};
     int batch_max_steps = vxrt::kMaxSteps;  // Raytrace's maxSteps for the batch API (vxrt_set_batch_max_steps)
     struct StreamState* stream = nullptr;   // chunk streaming (vxrt_stream_*), or NULL
+    // voxel editing (vxrt_edit_voxels): slots below nslots that hold no brick, and whether an edit has changed the world
+    // since it was made resident (vxrt_save_world then compacts the pool)
+    std::set<uint32_t> free_slots;
+    bool edited = false;
+    struct DevBuf {  // grow-only device scratch of the edit calls
+        void* p = nullptr;
+        size_t bytes = 0;
+        hipError_t reserve(size_t n)
+        {
+            if (n <= bytes)
+                return hipSuccess;
+            (void)hipFree(p);
+            p = nullptr;
+            bytes = 0;
+            hipError_t e = hipMalloc(&p, n);
+            if (e == hipSuccess)
+                bytes = n;
+            return e;
+        }
+        void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
+    } edit_in, edit_scratch, edit_out, edit_plan;
 };
 constexpr unsigned kViewSlots = 16;  // multi-view launches that may be in flight at once on one context
 constexpr unsigned kTileCounterRing = 64;  // render launches that may be in flight at once on one context
@@ -106,6 +135,8 @@ static void free_world(vxrt_ctx* c)
     c->d_pool = nullptr;
     c->has_world = false;
     c->ncells = c->nslots = c->pool_capacity_slots = 0;
+    c->free_slots.clear();
+    c->edited = false;
 }
 
 // shared by upload and the device builder
@@ -156,6 +187,20 @@ void fill_view(vxrt_ctx* c, int factor, const int cd[3])
     v.pool_hi = c->guard_no_slack ? v.pool_end : v.pool_lo + c->pool_alloc_bytes / 4;
 }
 
+// The pool's allocation: `slots` bricks of `bw` words (at least one), behind and followed by one brick of addressable slack
+// (the tracer's one load beyond a table, below).  Shared by every world path and the edit's pool growth.
+static hipError_t alloc_pool(uint64_t bw, uint64_t slots, void** alloc, uint64_t* alloc_bytes, uint32_t** pool)
+{
+    const uint64_t pool_bytes = (slots ? slots : 1) * bw * sizeof(uint32_t);
+    const uint64_t pool_slack = (bw * sizeof(uint32_t) + 255) / 256 * 256;
+    hipError_t e = hipMalloc(alloc, pool_bytes + 2 * pool_slack);
+    if (e != hipSuccess)
+        return e;
+    *alloc_bytes = pool_bytes + 2 * pool_slack;
+    *pool = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(*alloc) + pool_slack);
+    return hipSuccess;
+}
+
 int alloc_world(vxrt_ctx* c, int factor, const int cd[3], uint64_t pool_slots)
 {
     free_world(c);
@@ -170,11 +215,7 @@ int alloc_world(vxrt_ctx* c, int factor, const int cd[3], uint64_t pool_slots)
     c->coarse_alloc_bytes = coarse_bytes + 2 * coarse_slack;
     c->d_coarse = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(c->coarse_alloc) + coarse_slack);
     VX_HIP(hipMalloc((void**)&c->d_meta, c->ncells * sizeof(uint2)));
-    const uint64_t pool_bytes = (pool_slots ? pool_slots : 1) * bw * sizeof(uint32_t);
-    const uint64_t pool_slack = (bw * sizeof(uint32_t) + 255) / 256 * 256;
-    VX_HIP(hipMalloc(&c->pool_alloc, pool_bytes + 2 * pool_slack));
-    c->pool_alloc_bytes = pool_bytes + 2 * pool_slack;
-    c->d_pool = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(c->pool_alloc) + pool_slack);
+    VX_HIP(alloc_pool(bw, pool_slots, &c->pool_alloc, &c->pool_alloc_bytes, &c->d_pool));
     c->pool_capacity_slots = pool_slots;
     return VXRT_OK;
 }
@@ -322,6 +363,10 @@ int vxrt_destroy(vxrt_ctx* c)
     if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_queues) (void)hipFree(c->d_queues);
     if (c->d_views) (void)hipFree(c->d_views);
+    c->edit_in.release();
+    c->edit_scratch.release();
+    c->edit_out.release();
+    c->edit_plan.release();
     for (hipEvent_t& e : c->counter_busy)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t& e : c->views_busy)
@@ -1109,15 +1154,33 @@ int vxrt_save_world(vxrt_ctx* c, const char* path)
     std::vector<unsigned char> stage(kFileChunk);
     const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
     struct Temps {
-        uint32_t *coarse = nullptr, *pool = nullptr;
+        uint32_t *coarse = nullptr, *pool = nullptr, *order = nullptr;
         uint2* meta = nullptr;
-        ~Temps() { (void)hipFree(coarse); (void)hipFree(meta); (void)hipFree(pool); }
+        ~Temps() { (void)hipFree(coarse); (void)hipFree(meta); (void)hipFree(pool); (void)hipFree(order); }
     } T;
     VX_HIP(hipMalloc((void**)&T.coarse, h.coarse_bytes));
     VX_HIP(hipMalloc((void**)&T.meta, h.meta_bytes));
-    VX_HIP(hipMalloc((void**)&T.pool, std::max<uint64_t>(4, std::min<uint64_t>(kFileChunk, h.pool_bytes))));
     VX_HIP(vxrt::layout_bits(c->d_coarse, T.coarse, cd, false));
     VX_HIP(vxrt::layout_meta(c->d_meta, T.meta, cd, false));
+    // A world changed by vxrt_edit_voxels holds freed slots and bricks out of cell order: the file gets its live bricks
+    // only, renumbered in the tiled cell order of the tables (as the builders number them), gathered by new number.
+    std::vector<uint32_t> order;  // old slot of every brick of the file
+    if (c->edited) {
+        std::vector<uint2> meta(c->ncells);
+        VX_HIP(hipMemcpy(meta.data(), T.meta, h.meta_bytes, hipMemcpyDeviceToHost));
+        for (uint2& m : meta)
+            if (m.x != VXRT_EMPTY_SLOT) {
+                order.push_back(m.x);
+                m.x = (uint32_t)(order.size() - 1);
+            }
+        VX_HIP(hipMemcpy(T.meta, meta.data(), h.meta_bytes, hipMemcpyHostToDevice));
+        h.nslots = order.size();
+        h.pool_bytes = h.nslots * (uint64_t)c->view.brick_words * 4;
+        VX_HIP(hipMalloc((void**)&T.order, std::max<size_t>(4, order.size() * sizeof(uint32_t))));
+        if (!order.empty())
+            VX_HIP(hipMemcpy(T.order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    VX_HIP(hipMalloc((void**)&T.pool, std::max<uint64_t>(4, std::min<uint64_t>(kFileChunk, h.pool_bytes))));
     const void* src[3] = {T.coarse, T.meta, nullptr};
     const uint64_t bytes[3] = {h.coarse_bytes, h.meta_bytes, h.pool_bytes};
     const uint64_t brick_bytes = (uint64_t)c->view.brick_words * 4;
@@ -1125,7 +1188,11 @@ int vxrt_save_world(vxrt_ctx* c, const char* path)
         StreamSum cs;
         for (uint64_t off = 0; off < bytes[t]; off += kFileChunk) {
             const size_t n = (size_t)std::min<uint64_t>(kFileChunk, bytes[t] - off);
-            if (t == 2) {  // kFileChunk is a whole number of bricks
+            if (t == 2 && c->edited) {  // compacted: gather by new number, then re-order in place
+                VX_HIP(vxrt::gather_bricks(c->d_pool, T.order + off / brick_bytes, (uint32_t)(n / brick_bytes), T.pool, c->view.f));
+                VX_HIP(vxrt::layout_bricks(T.pool, T.pool, n / brick_bytes, c->view.f, false));
+                VX_HIP(hipMemcpy(stage.data(), T.pool, n, hipMemcpyDeviceToHost));
+            } else if (t == 2) {  // kFileChunk is a whole number of bricks
                 VX_HIP(vxrt::layout_bricks(c->d_pool + off / 4, T.pool, n / brick_bytes, c->view.f, false));
                 VX_HIP(hipMemcpy(stage.data(), T.pool, n, hipMemcpyDeviceToHost));
             } else {
@@ -1527,6 +1594,209 @@ int vxrt_stream_close(vxrt_ctx* c)
     VX_HIP(hipDeviceSynchronize());
     vxrt::free_world(c);  // drops the stream state with the tables
     return VXRT_OK;
+}
+
+}  // extern "C"
+
+// ---- voxel editing (include/vxrt.h): host side of the two kernels of vxrt_edit.hip -----------------------------------------
+namespace vxrt {
+
+// the pool to `capacity` bricks: a new allocation with the allocator's slack, the live slots copied, the old one freed.
+// Called with the device idle.  On failure nothing has changed.
+static int grow_pool(vxrt_ctx* c, uint64_t capacity)
+{
+    const uint64_t bw = c->view.brick_words;
+    void* alloc = nullptr;
+    uint64_t alloc_bytes = 0;
+    uint32_t* pool = nullptr;
+    hipError_t e = alloc_pool(bw, capacity, &alloc, &alloc_bytes, &pool);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("brick pool growth to ") + std::to_string(capacity) + " bricks: " + hipGetErrorString(e));
+    }
+    if (c->nslots)
+        e = hipMemcpy(pool, c->d_pool, c->nslots * bw * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(alloc);
+        return fail(VXRT_ERR_HIP, std::string("brick pool growth: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(c->pool_alloc);
+    c->pool_alloc = alloc;
+    c->pool_alloc_bytes = alloc_bytes;
+    c->d_pool = pool;
+    c->pool_capacity_slots = capacity;
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    fill_view(c, c->view.f, cd);  // pool, pool_end, pool_lo, pool_hi follow the new allocation
+    return VXRT_OK;
+}
+
+// the touched brick cells: the union of the ops' clipped brick boxes, deduplicated, in HBM cell order
+static void edit_cells(const std::vector<EditOpDev>& ops, int f, int cx, int cz, uint64_t ncells, std::vector<uint32_t>& cells)
+{
+    uint64_t total = 0;
+    for (const EditOpDev& op : ops) {
+        uint64_t v = 1;
+        for (int a = 0; a < 3; ++a)
+            v *= (uint64_t)(op.hi[a] / f - op.lo[a] / f + 1);
+        total += v;
+    }
+    cells.clear();
+    if (total <= ncells) {  // the usual case: a list of the boxes' cells, sorted
+        cells.reserve(total);
+        for (const EditOpDev& op : ops)
+            for (int y = op.lo[1] / f; y <= op.hi[1] / f; ++y)
+                for (int z = op.lo[2] / f; z <= op.hi[2] / f; ++z)
+                    for (int x = op.lo[0] / f; x <= op.hi[0] / f; ++x)
+                        cells.push_back((uint32_t)hbm_index(x, y, z, cx, cz));
+        std::sort(cells.begin(), cells.end());
+        cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
+    } else {  // boxes that overlap more than the world holds: one flag per cell
+        std::vector<uint8_t> mark(ncells, 0);
+        for (const EditOpDev& op : ops)
+            for (int y = op.lo[1] / f; y <= op.hi[1] / f; ++y)
+                for (int z = op.lo[2] / f; z <= op.hi[2] / f; ++z)
+                    for (int x = op.lo[0] / f; x <= op.hi[0] / f; ++x)
+                        mark[hbm_index(x, y, z, cx, cz)] = 1;
+        for (uint64_t i = 0; i < ncells; ++i)
+            if (mark[i])
+                cells.push_back((uint32_t)i);
+    }
+}
+
+}  // namespace vxrt
+
+extern "C" {
+
+int vxrt_edit_voxels(vxrt_ctx* c, const vxrt_edit_op* ops, uint32_t n_ops, vxrt_edit_stats* out)
+{
+    using vxrt::EditOpDev;
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (n_ops > vxrt::kEditMaxOps)
+        return fail(VXRT_ERR_INVALID, "more than VXRT_EDIT_MAX_OPS ops in one call");
+    if (!ops && n_ops)
+        return fail(VXRT_ERR_INVALID, "ops is NULL");
+    const int f = c->has_world ? c->view.f : 1;
+    const int X = c->has_world ? c->view.cx * f : 1, Y = c->has_world ? c->view.cy * f : 1, Z = c->has_world ? c->view.cz * f : 1;
+    std::vector<EditOpDev> dev;
+    dev.reserve(n_ops);
+    for (uint32_t k = 0; k < n_ops; ++k) {
+        EditOpDev d;
+        bool noop = false;
+        if (vxrt::edit_prepare(ops[k].kind, ops[k].value, ops[k].a, ops[k].b, X, Y, Z, d, noop))
+            return fail(VXRT_ERR_INVALID, "edit op " + std::to_string(k) +
+                                              ": unknown kind, value not 0 / 1, negative radius or nonzero b[1] / b[2] on a sphere");
+        if (!noop)
+            dev.push_back(d);
+    }
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(hipDeviceSynchronize());  // no launch may read the tables while they change
+    vxrt_edit_stats st{};
+    auto finish = [&]() {
+        st.pool_slots = c->nslots;
+        st.pool_capacity = c->pool_capacity_slots;
+        st.bricks_live = c->nslots - c->free_slots.size();
+        if (out)
+            *out = st;
+        return VXRT_OK;
+    };
+    std::vector<uint32_t> cells;
+    vxrt::edit_cells(dev, f, c->view.cx, c->view.cz, c->ncells, cells);
+    const uint32_t n = (uint32_t)cells.size();
+    st.bricks_touched = n;
+    if (n == 0)
+        return finish();
+    const uint64_t bw = c->view.brick_words;
+    // device scratch: ops and cells in; images, extents and {old slot, flags} out; the plan in
+    const size_t ops_bytes = dev.size() * sizeof(EditOpDev);
+    hipError_t e = c->edit_in.reserve(ops_bytes + (size_t)n * 4);
+    if (e == hipSuccess)
+        e = c->edit_scratch.reserve((size_t)n * bw * 4);
+    if (e == hipSuccess)
+        e = c->edit_out.reserve((size_t)n * 12);
+    if (e == hipSuccess)
+        e = c->edit_plan.reserve((size_t)n * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("edit scratch for ") + std::to_string(n) + " bricks: " + hipGetErrorString(e));
+    }
+    unsigned char* in = static_cast<unsigned char*>(c->edit_in.p);
+    const EditOpDev* d_ops = reinterpret_cast<const EditOpDev*>(in);
+    const uint32_t* d_cells = reinterpret_cast<const uint32_t*>(in + ops_bytes);
+    uint32_t* d_img = static_cast<uint32_t*>(c->edit_scratch.p);
+    uint2* d_info = static_cast<uint2*>(c->edit_out.p);
+    uint32_t* d_ext = reinterpret_cast<uint32_t*>(d_info + n);
+    {
+        std::vector<unsigned char> host_in(ops_bytes + (size_t)n * 4);
+        memcpy(host_in.data(), dev.data(), ops_bytes);
+        memcpy(host_in.data() + ops_bytes, cells.data(), (size_t)n * 4);
+        VX_HIP(hipMemcpy(in, host_in.data(), host_in.size(), hipMemcpyHostToDevice));
+    }
+    VX_HIP(vxrt::edit_bricks(d_cells, n, d_ops, (uint32_t)dev.size(), c->d_meta, c->d_pool, d_img, d_ext, d_info, f,
+                             c->view.cx, c->view.cz));
+    std::vector<uint2> info(n);
+    VX_HIP(hipMemcpy(info.data(), d_info, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> old_slot(n);
+    std::vector<uint8_t> flags(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        old_slot[i] = info[i].x;
+        flags[i] = (uint8_t)info[i].y;
+    }
+    vxrt::EditPlan P;
+    vxrt::edit_plan_slots(old_slot.data(), flags.data(), n, c->free_slots, c->nslots, P);  // (undone below on failure)
+    if (P.changed == 0)  // no voxel changed: the tables stay untouched
+        return finish();
+    int rc = VXRT_OK;
+    if (P.nslots >= (1ull << 32) - 2)
+        rc = fail(VXRT_ERR_NOMEM, "brick slots exhausted (32-bit slot numbers)");
+    else if (P.nslots > c->pool_capacity_slots)
+        rc = vxrt::grow_pool(c, vxrt::edit_grown_capacity(c->pool_capacity_slots, P.nslots));
+    if (rc) {
+        vxrt::edit_plan_undo(P, c->free_slots);
+        return rc;
+    }
+    uint32_t* d_new = static_cast<uint32_t*>(c->edit_plan.p);
+    uint32_t* d_zero = d_new + n;
+    std::vector<uint32_t> plan(P.new_slot);
+    plan.insert(plan.end(), P.zero.begin(), P.zero.end());
+    e = hipMemcpy(d_new, plan.data(), plan.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = vxrt::edit_commit(d_cells, d_new, n, d_zero, (uint32_t)P.zero.size(), d_img, d_ext, c->d_pool, c->d_meta,
+                              c->d_coarse, f);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        vxrt::edit_plan_undo(P, c->free_slots);
+        return fail(VXRT_ERR_HIP, std::string("edit commit: ") + hipGetErrorString(e));
+    }
+    c->nslots = P.nslots;
+    c->edited = true;
+    st.bricks_created = P.created;
+    st.bricks_freed = P.freed;
+    return finish();
+}
+
+int vxrt_edit_reserve(vxrt_ctx* c, uint64_t capacity_bricks)
+{
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
+    if (capacity_bricks >= (1ull << 32) - 2)
+        return fail(VXRT_ERR_INVALID, "capacity beyond 32-bit slot numbers");
+    if (capacity_bricks <= c->pool_capacity_slots)
+        return VXRT_OK;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(hipDeviceSynchronize());
+    return vxrt::grow_pool(c, capacity_bricks);
 }
 
 }  // extern "C"

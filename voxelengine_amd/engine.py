@@ -161,6 +161,21 @@ class Context:
     def stream_close(self) -> None:
         N.check(self._L.vxrt_stream_close(self._h))
 
+    # ---- voxel editing (extension, include/vxrt.h) ---------------------------------------------------------------
+    def edit_voxels(self, ops) -> "N.EditStats":
+        """Apply a list of box / sphere set and clear ops (EditBox, EditSphere, or (kind, value, a, b) tuples) to the
+        resident world, in order: the last op covering a voxel sets it.  Synchronises the device before and after; all or
+        nothing on failure.  Returns what the call did to the brick pool."""
+        ops = [o if isinstance(o, N.EditOp) else _edit_op(*o) for o in ops]
+        arr = (N.EditOp * max(len(ops), 1))(*ops)
+        st = N.EditStats()
+        N.check(self._L.vxrt_edit_voxels(self._h, arr if ops else None, len(ops), C.byref(st)))
+        return st
+
+    def edit_reserve(self, capacity_bricks: int) -> None:
+        """Grow the brick pool to at least ``capacity_bricks`` now, so that later edits need no pool copy."""
+        N.check(self._L.vxrt_edit_reserve(self._h, int(capacity_bricks)))
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -317,6 +332,24 @@ class Context:
 
     def synchronize(self) -> None:
         N.check(self._L.vxrt_synchronize(self._h))
+
+
+def _edit_op(kind: int, value: int, a, b) -> "N.EditOp":
+    op = N.EditOp()
+    op.kind, op.value = int(kind), int(value)
+    op.a = (C.c_int32 * 3)(*[int(v) for v in a])
+    op.b = (C.c_int32 * 3)(*[int(v) for v in b])
+    return op
+
+
+def EditBox(lo, hi, value: int = 1) -> "N.EditOp":
+    """Every voxel v with lo <= v <= hi on each axis (inclusive) set (value 1) or cleared (value 0)."""
+    return _edit_op(N.EDIT_BOX, value, lo, hi)
+
+
+def EditSphere(centre, radius: int, value: int = 1) -> "N.EditOp":
+    """Every voxel v with |v - centre|^2 <= radius^2 (integers) set (value 1) or cleared (value 0)."""
+    return _edit_op(N.EDIT_SPHERE, value, centre, (radius, 0, 0))
 
 
 def grid_is_wide(cdims) -> bool:
