@@ -22,7 +22,9 @@
 // edit_script (voxel editing, VoxelRaytracer3D::EditVoxels): one op per line, "frame kind value ax ay az bx by bz" --
 // kind 0 = box a..b (inclusive voxels), 1 = sphere of centre a and radius bx (by = bz = 0); value 1 = set, 0 = clear --
 // applied in file order before that frame is rendered ('#' starts a comment; with views_per_launch > 1, before the launch
-// that holds the frame).  A '-' skips it.
+// that holds the frame).  A '-' skips it.  Two more kinds copy and paste (VoxelRaytracer3D::ReadRegion / StampVoxels):
+// kind 2 = copy the box of origin a and dims b into clipboard slot `value`; kind 3 = paste clipboard slot `value` with its
+// voxel (0,0,0) at a, in mode bx (0 = replace, 1 = union, 2 = subtract; by = bz = 0).
 #include "../include/GPUDDA/Renderer.h"
 #include "../include/GPUDDA/VoxelWorldBuilder.h"
 #include "../include/vxrt.h"
@@ -36,6 +38,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -160,22 +163,58 @@ int main(int argc, char** argv)
         SetRenderSwitches(s);
     }
 
-    // the edit script's ops of frames [from, to), in file order, in calls of at most VXRT_EDIT_MAX_OPS ops
+    // the edit script's lines of frames [from, to), in file order: box / sphere ops in calls of at most VXRT_EDIT_MAX_OPS
+    // ops, a copy or paste line after the ops before it
+    struct Clip {
+        int32_t dims[3];
+        std::vector<uint32_t> bits;
+    };
+    std::map<int, Clip> clipboard;
     auto apply_edits = [&](int from, int to) {
         std::vector<vxrt_edit_op> ops;
-        for (const EditLine& e : edits)
-            if (e.frame >= from && e.frame < to)
-                ops.push_back(e.op);
-        for (size_t k = 0; k < ops.size(); k += VXRT_EDIT_MAX_OPS) {
-            const size_t n = ops.size() - k < VXRT_EDIT_MAX_OPS ? ops.size() - k : VXRT_EDIT_MAX_OPS;
-            vxrt_edit_stats st{};
-            if (raytracer->EditVoxels(ops.data() + k, n, &st) != VXRT_OK) {
-                std::cerr << "edit before frame " << from << ": " << vxrt_last_error() << std::endl;
-                std::exit(3);
+        auto flush_ops = [&]() {
+            for (size_t k = 0; k < ops.size(); k += VXRT_EDIT_MAX_OPS) {
+                const size_t n = ops.size() - k < VXRT_EDIT_MAX_OPS ? ops.size() - k : VXRT_EDIT_MAX_OPS;
+                vxrt_edit_stats st{};
+                if (raytracer->EditVoxels(ops.data() + k, n, &st) != VXRT_OK) {
+                    std::cerr << "edit before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("edit before frame %d: %zu ops, %llu bricks touched, %llu created, %llu freed\n", from, n,
+                            (unsigned long long)st.bricks_touched, (unsigned long long)st.bricks_created, (unsigned long long)st.bricks_freed);
             }
-            std::printf("edit before frame %d: %zu ops, %llu bricks touched, %llu created, %llu freed\n", from, n,
-                        (unsigned long long)st.bricks_touched, (unsigned long long)st.bricks_created, (unsigned long long)st.bricks_freed);
+            ops.clear();
+        };
+        for (const EditLine& e : edits) {
+            if (e.frame < from || e.frame >= to)
+                continue;
+            if (e.op.kind == 2) {  // copy
+                flush_ops();
+                Clip& c = clipboard[e.op.value];
+                for (int k = 0; k < 3; ++k)
+                    c.dims[k] = e.op.b[k];
+                if (raytracer->ReadRegion(e.op.a, c.dims, c.bits) != VXRT_OK) {
+                    std::cerr << "copy before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("copy before frame %d: slot %d, %zu words\n", from, e.op.value, c.bits.size());
+            } else if (e.op.kind == 3) {  // paste
+                flush_ops();
+                const auto it = clipboard.find(e.op.value);
+                vxrt_edit_stats st{};
+                if (it == clipboard.end() || e.op.b[1] != 0 || e.op.b[2] != 0 ||
+                    raytracer->StampVoxels(e.op.a, it->second.dims, it->second.bits.data(), e.op.b[0], &st) != VXRT_OK) {
+                    std::cerr << "paste before frame " << from << ": " << (it == clipboard.end() ? "empty clipboard slot" : vxrt_last_error())
+                              << std::endl;
+                    std::exit(3);
+                }
+                std::printf("paste before frame %d: slot %d, %llu bricks touched, %llu created, %llu freed\n", from, e.op.value,
+                            (unsigned long long)st.bricks_touched, (unsigned long long)st.bricks_created, (unsigned long long)st.bricks_freed);
+            } else {
+                ops.push_back(e.op);
+            }
         }
+        flush_ops();
     };
 
     void* d_pixels = nullptr;

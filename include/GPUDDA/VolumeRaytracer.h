@@ -131,6 +131,14 @@ public:
     // Return the vxrt_status of the call (0 = done; on failure the world is unchanged).
     int EditVoxels(const vxrt_edit_op* ops, size_t n, vxrt_edit_stats* stats = nullptr);
     int ReserveBricks(size_t capacity_bricks);  // grow the brick pool ahead of edits (vxrt_edit_reserve)
+    // region readback and voxel stamps (extensions, include/vxrt.h): the voxels of the box origin .. origin + dims - 1 into
+    // `bits` in the region layout (vxrt_read_region_host), and such a region written back at `origin` in a vxrt_stamp_mode
+    // (vxrt_edit_stamps; the host words are copied to the device here).  Pending uploads are flushed first.  Return the
+    // vxrt_status of the call (copy / paste: ReadRegion, then StampVoxels; undo: ReadRegion before an edit, then
+    // StampVoxels with VXRT_STAMP_REPLACE).
+    int ReadRegion(const int32_t origin[3], const int32_t dims[3], std::vector<uint32_t>& bits);
+    int StampVoxels(const int32_t origin[3], const int32_t dims[3], const uint32_t* bits, int mode,
+                    vxrt_edit_stats* stats = nullptr);
 
 private:
     void Flush();

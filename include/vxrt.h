@@ -205,6 +205,47 @@ int vxrt_edit_voxels(vxrt_ctx *ctx, const vxrt_edit_op *ops, uint32_t n_ops, vxr
 /* grow the pool to at least capacity_bricks now, so that later edits need no copy (never shrinks it) */
 int vxrt_edit_reserve(vxrt_ctx *ctx, uint64_t capacity_bricks);
 
+/* ---- region readback and voxel stamps -- an EXTENSION (with the editing above: copy, paste and undo of the resident
+ * world).  Copy and paste are a read followed by a stamp; undo is a read of an edit's bounding box before the edit and a
+ * VXRT_STAMP_REPLACE stamp of it afterwards.
+ * Region bit layout (shared by vxrt_read_region and vxrt_edit_stamps).  A region is a box of dims[0] x dims[1] x dims[2]
+ * voxels whose voxel (0,0,0) is world voxel origin.  Row (y, z) of the region is ceil(dims[0] / 32) 32-bit words, rows in
+ * order y fastest, then z: voxel (x, y, z) is bit (x & 31) of word (y + dims[1] * z) * ceil(dims[0] / 32) + (x >> 5).
+ * Words per region: vxrt_region_words(dims).  Padding bits at the end of a row are written 0 by a read and ignored by a stamp. */
+uint64_t vxrt_region_words(const int32_t dims[3]); /* 0 for dims outside 1 <= dims[k], dims[0] * dims[1] * dims[2] <= 2^36 */
+
+/* Asynchronous on `stream`, like vxrt_trace_batch.  Voxels outside the world read 0.  origin may be negative or beyond the
+ * world; 1 <= dims[k], dims[0] * dims[1] * dims[2] <= 2^36.  A streamed world gives VXRT_ERR_INVALID (a cache is not read).
+ * NULL arguments and bad dims give VXRT_ERR_INVALID, no world VXRT_ERR_NO_WORLD.  The read never loads outside the tables. */
+int vxrt_read_region(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t *d_bits, void *stream);
+int vxrt_read_region_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t *bits); /* synchronous */
+
+/* Voxel stamps: a list of dense bit volumes (region layout above) written into the resident world in order.
+ *   Semantics: let m be the stamp's bit at v - origin.  REPLACE covers every voxel v of the stamp's box and sets it to m;
+ *     UNION covers the voxels with m = 1 and sets them to 1; SUBTRACT covers the voxels with m = 1 and clears them.
+ *     Stamps are clipped to the world (a stamp wholly outside it is a no-op).  A voxel takes the value the LAST stamp of
+ *     the list that covers it gives it, and otherwise keeps its value.
+ *   Validation before any change: an unknown mode, nonzero reserved, dims[k] < 1, more than 2^36 voxels, d_bits == NULL,
+ *     n_stamps > VXRT_EDIT_MAX_OPS, or stamps == NULL with n_stamps > 0 return VXRT_ERR_INVALID; no world gives
+ *     VXRT_ERR_NO_WORLD; a streamed world gives VXRT_ERR_INVALID.
+ *   Everything else is vxrt_edit_voxels' contract above: all or nothing (VXRT_ERR_NOMEM on pool growth included), the
+ *     device synchronised before and after the call, the brick life cycle, deterministic slot assignment, a call that
+ *     changes no voxel writes nothing, vxrt_edit_stats, and the compacting save.
+ *   Because the call synchronises the device before it reads any stamp, a stamp may use bits that a vxrt_read_region on
+ *     any stream produced just before the call: the undo pattern (read, edit, stamp back) needs no synchronisation of its
+ *     own.  The stamp bits must stay valid until the call returns.
+ *   Stamps and box / sphere ops are not mixed in one call (two calls, in the order wanted).
+ * The cost is proportional to the bricks in the union of the stamps' clipped brick boxes (bricks_touched). */
+typedef enum vxrt_stamp_mode { VXRT_STAMP_REPLACE = 0, VXRT_STAMP_UNION = 1, VXRT_STAMP_SUBTRACT = 2 } vxrt_stamp_mode;
+typedef struct vxrt_stamp {
+    const uint32_t *d_bits;  /* device, region layout above */
+    int32_t origin[3];       /* world voxel of the stamp's voxel (0,0,0); may lie partly or wholly outside the world */
+    int32_t dims[3];
+    int32_t mode;            /* vxrt_stamp_mode */
+    int32_t reserved;        /* 0 */
+} vxrt_stamp;
+int vxrt_edit_stamps(vxrt_ctx *ctx, const vxrt_stamp *stamps, uint32_t n_stamps, vxrt_edit_stats *stats_or_null);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

@@ -23,9 +23,11 @@ EXPORTS = [
     "vxrt_deinterleave_strips", "vxrt_deinterleave_views", "vxrt_trace_batch", "vxrt_trace_batch_host",
     "vxrt_set_batch_max_steps", "vxrt_stream_open", "vxrt_stream_focus", "vxrt_stream_resident", "vxrt_stream_close",
     "vxrt_edit_voxels", "vxrt_edit_reserve",
+    "vxrt_region_words", "vxrt_read_region", "vxrt_read_region_host", "vxrt_edit_stamps",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
+STAMP_REPLACE, STAMP_UNION, STAMP_SUBTRACT = 0, 1, 2
 
 
 class WorldDesc(C.Structure):
@@ -75,6 +77,12 @@ class EditOp(C.Structure):
 class EditStats(C.Structure):
     _fields_ = [("bricks_touched", C.c_uint64), ("bricks_created", C.c_uint64), ("bricks_freed", C.c_uint64),
                 ("bricks_live", C.c_uint64), ("pool_slots", C.c_uint64), ("pool_capacity", C.c_uint64)]
+
+
+class StampDesc(C.Structure):
+    """vxrt_stamp: a dense bit volume (region layout, include/vxrt.h) written at `origin` in `mode`."""
+    _fields_ = [("d_bits", C.c_void_p), ("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("mode", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class RenderFlags(C.Structure):
@@ -168,6 +176,11 @@ def load() -> C.CDLL:
     L.vxrt_stream_close.argtypes = [C.c_void_p]
     L.vxrt_edit_voxels.argtypes = [C.c_void_p, C.POINTER(EditOp), C.c_uint32, C.POINTER(EditStats)]
     L.vxrt_edit_reserve.argtypes = [C.c_void_p, C.c_uint64]
+    L.vxrt_region_words.restype = C.c_uint64
+    L.vxrt_region_words.argtypes = [C.POINTER(C.c_int32)]
+    L.vxrt_read_region.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    L.vxrt_read_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+    L.vxrt_edit_stamps.argtypes = [C.c_void_p, C.POINTER(StampDesc), C.c_uint32, C.POINTER(EditStats)]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

@@ -235,6 +235,41 @@ int VoxelRaytracer3D::ReserveBricks(size_t capacity_bricks)
     return vxrt_edit_reserve(ctx, (uint64_t)capacity_bricks);
 }
 
+int VoxelRaytracer3D::ReadRegion(const int32_t origin[3], const int32_t dims[3], std::vector<uint32_t>& bits)
+{
+    Flush();
+    const uint64_t words = vxrt_region_words(dims);
+    if (words == 0)
+        return VXRT_ERR_INVALID;
+    bits.assign((size_t)words, 0u);
+    return vxrt_read_region_host(ctx, origin, dims, bits.data());
+}
+
+int VoxelRaytracer3D::StampVoxels(const int32_t origin[3], const int32_t dims[3], const uint32_t* bits, int mode,
+                                  vxrt_edit_stats* stats)
+{
+    Flush();
+    const uint64_t words = vxrt_region_words(dims);
+    if (words == 0 || !bits)
+        return VXRT_ERR_INVALID;
+    void* d_bits = nullptr;
+    if (hipMalloc(&d_bits, (size_t)words * 4) != hipSuccess)
+        return VXRT_ERR_NOMEM;
+    int rc = hipMemcpy(d_bits, bits, (size_t)words * 4, hipMemcpyHostToDevice) == hipSuccess ? VXRT_OK : VXRT_ERR_HIP;
+    if (rc == VXRT_OK) {
+        vxrt_stamp s{};
+        s.d_bits = static_cast<const uint32_t*>(d_bits);
+        for (int k = 0; k < 3; ++k) {
+            s.origin[k] = origin[k];
+            s.dims[k] = dims[k];
+        }
+        s.mode = mode;
+        rc = vxrt_edit_stamps(ctx, &s, 1, stats);
+    }
+    (void)hipFree(d_bits);
+    return rc;
+}
+
 RayTraceResults<float3> VoxelRaytracer3D::Raytrace(std::vector<float3> origin, std::vector<float3> ray)
 {
     const size_t n = origin.size();

@@ -4,6 +4,7 @@
 #include "../../include/vxrt.h"
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
+#include "vxrt_region.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -37,6 +38,11 @@ hipError_t edit_bricks(const uint32_t* cells, uint32_t n, const EditOpDev* ops, 
 hipError_t edit_commit(const uint32_t* cells, const uint32_t* new_slot, uint32_t n, const uint32_t* zero, uint32_t nzero,
                        const uint32_t* scratch, const uint32_t* ext, uint32_t* pool, uint2* meta, uint32_t* coarse, int f);
 hipError_t gather_bricks(const uint32_t* pool, const uint32_t* idx, uint32_t n, uint32_t* dst, int f);
+// region readback and voxel stamps (vxrt_region.hip)
+hipError_t read_region(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
+                       uint32_t* out, hipStream_t stream);
+hipError_t stamp_bricks(const uint32_t* cells, uint32_t n, const StampDev* stamps, uint32_t nst, const uint2* meta,
+                        const uint32_t* pool, uint32_t* scratch, uint32_t* ext, uint2* info, int f, int cx, int cz);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -1632,11 +1638,13 @@ static int grow_pool(vxrt_ctx* c, uint64_t capacity)
     return VXRT_OK;
 }
 
-// the touched brick cells: the union of the ops' clipped brick boxes, deduplicated, in HBM cell order
-static void edit_cells(const std::vector<EditOpDev>& ops, int f, int cx, int cz, uint64_t ncells, std::vector<uint32_t>& cells)
+// the touched brick cells: the union of the ops' clipped brick boxes, deduplicated, in HBM cell order (ops: edit ops or
+// stamps, anything with a clipped voxel box lo / hi)
+template <class Op>
+static void edit_cells(const std::vector<Op>& ops, int f, int cx, int cz, uint64_t ncells, std::vector<uint32_t>& cells)
 {
     uint64_t total = 0;
-    for (const EditOpDev& op : ops) {
+    for (const Op& op : ops) {
         uint64_t v = 1;
         for (int a = 0; a < 3; ++a)
             v *= (uint64_t)(op.hi[a] / f - op.lo[a] / f + 1);
@@ -1645,7 +1653,7 @@ static void edit_cells(const std::vector<EditOpDev>& ops, int f, int cx, int cz,
     cells.clear();
     if (total <= ncells) {  // the usual case: a list of the boxes' cells, sorted
         cells.reserve(total);
-        for (const EditOpDev& op : ops)
+        for (const Op& op : ops)
             for (int y = op.lo[1] / f; y <= op.hi[1] / f; ++y)
                 for (int z = op.lo[2] / f; z <= op.hi[2] / f; ++z)
                     for (int x = op.lo[0] / f; x <= op.hi[0] / f; ++x)
@@ -1654,7 +1662,7 @@ static void edit_cells(const std::vector<EditOpDev>& ops, int f, int cx, int cz,
         cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
     } else {  // boxes that overlap more than the world holds: one flag per cell
         std::vector<uint8_t> mark(ncells, 0);
-        for (const EditOpDev& op : ops)
+        for (const Op& op : ops)
             for (int y = op.lo[1] / f; y <= op.hi[1] / f; ++y)
                 for (int z = op.lo[2] / f; z <= op.hi[2] / f; ++z)
                     for (int x = op.lo[0] / f; x <= op.hi[0] / f; ++x)
@@ -1663,6 +1671,99 @@ static void edit_cells(const std::vector<EditOpDev>& ops, int f, int cx, int cz,
             if (mark[i])
                 cells.push_back((uint32_t)i);
     }
+}
+
+// The host tail of an edit call, shared by vxrt_edit_voxels and vxrt_edit_stamps: the device synchronised, the touched
+// cells' scratch reserved, the per-brick kernel (`launch`: the ops in, images, extents and {old slot, flags} out, in
+// k_edit_bricks' format), the flags read back, the slot plan, pool growth, k_edit_commit, and the rollback of the free
+// list when a step after planning fails.  `ops`: the validated, clipped ops as the kernel reads them (copied as bytes).
+template <class Op, class Launch>
+static int edit_run(vxrt_ctx* c, const std::vector<Op>& ops, Launch launch, vxrt_edit_stats* out)
+{
+    const int f = c->view.f;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(hipDeviceSynchronize());  // no launch may read the tables while they change
+    vxrt_edit_stats st{};
+    auto finish = [&]() {
+        st.pool_slots = c->nslots;
+        st.pool_capacity = c->pool_capacity_slots;
+        st.bricks_live = c->nslots - c->free_slots.size();
+        if (out)
+            *out = st;
+        return VXRT_OK;
+    };
+    std::vector<uint32_t> cells;
+    edit_cells(ops, f, c->view.cx, c->view.cz, c->ncells, cells);
+    const uint32_t n = (uint32_t)cells.size();
+    st.bricks_touched = n;
+    if (n == 0)
+        return finish();
+    const uint64_t bw = c->view.brick_words;
+    // device scratch: ops and cells in; images, extents and {old slot, flags} out; the plan in
+    const size_t ops_bytes = ops.size() * sizeof(Op);
+    hipError_t e = c->edit_in.reserve(ops_bytes + (size_t)n * 4);
+    if (e == hipSuccess)
+        e = c->edit_scratch.reserve((size_t)n * bw * 4);
+    if (e == hipSuccess)
+        e = c->edit_out.reserve((size_t)n * 12);
+    if (e == hipSuccess)
+        e = c->edit_plan.reserve((size_t)n * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("edit scratch for ") + std::to_string(n) + " bricks: " + hipGetErrorString(e));
+    }
+    unsigned char* in = static_cast<unsigned char*>(c->edit_in.p);
+    const Op* d_ops = reinterpret_cast<const Op*>(in);
+    const uint32_t* d_cells = reinterpret_cast<const uint32_t*>(in + ops_bytes);
+    uint32_t* d_img = static_cast<uint32_t*>(c->edit_scratch.p);
+    uint2* d_info = static_cast<uint2*>(c->edit_out.p);
+    uint32_t* d_ext = reinterpret_cast<uint32_t*>(d_info + n);
+    {
+        std::vector<unsigned char> host_in(ops_bytes + (size_t)n * 4);
+        memcpy(host_in.data(), ops.data(), ops_bytes);
+        memcpy(host_in.data() + ops_bytes, cells.data(), (size_t)n * 4);
+        VX_HIP(hipMemcpy(in, host_in.data(), host_in.size(), hipMemcpyHostToDevice));
+    }
+    VX_HIP(launch(d_cells, n, d_ops, (uint32_t)ops.size(), d_img, d_ext, d_info));
+    std::vector<uint2> info(n);
+    VX_HIP(hipMemcpy(info.data(), d_info, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> old_slot(n);
+    std::vector<uint8_t> flags(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        old_slot[i] = info[i].x;
+        flags[i] = (uint8_t)info[i].y;
+    }
+    EditPlan P;
+    edit_plan_slots(old_slot.data(), flags.data(), n, c->free_slots, c->nslots, P);  // (undone below on failure)
+    if (P.changed == 0)  // no voxel changed: the tables stay untouched
+        return finish();
+    int rc = VXRT_OK;
+    if (P.nslots >= (1ull << 32) - 2)
+        rc = fail(VXRT_ERR_NOMEM, "brick slots exhausted (32-bit slot numbers)");
+    else if (P.nslots > c->pool_capacity_slots)
+        rc = grow_pool(c, edit_grown_capacity(c->pool_capacity_slots, P.nslots));
+    if (rc) {
+        edit_plan_undo(P, c->free_slots);
+        return rc;
+    }
+    uint32_t* d_new = static_cast<uint32_t*>(c->edit_plan.p);
+    uint32_t* d_zero = d_new + n;
+    std::vector<uint32_t> plan(P.new_slot);
+    plan.insert(plan.end(), P.zero.begin(), P.zero.end());
+    e = hipMemcpy(d_new, plan.data(), plan.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = edit_commit(d_cells, d_new, n, d_zero, (uint32_t)P.zero.size(), d_img, d_ext, c->d_pool, c->d_meta, c->d_coarse, f);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        edit_plan_undo(P, c->free_slots);
+        return fail(VXRT_ERR_HIP, std::string("edit commit: ") + hipGetErrorString(e));
+    }
+    c->nslots = P.nslots;
+    c->edited = true;
+    st.bricks_created = P.created;
+    st.bricks_freed = P.freed;
+    return finish();
 }
 
 }  // namespace vxrt
@@ -1695,91 +1796,94 @@ int vxrt_edit_voxels(vxrt_ctx* c, const vxrt_edit_op* ops, uint32_t n_ops, vxrt_
         return fail(VXRT_ERR_NO_WORLD, "no world resident");
     if (c->stream)
         return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
-    VX_HIP(hipSetDevice(c->device));
-    VX_HIP(hipDeviceSynchronize());  // no launch may read the tables while they change
-    vxrt_edit_stats st{};
-    auto finish = [&]() {
-        st.pool_slots = c->nslots;
-        st.pool_capacity = c->pool_capacity_slots;
-        st.bricks_live = c->nslots - c->free_slots.size();
-        if (out)
-            *out = st;
-        return VXRT_OK;
+    auto launch = [&](const uint32_t* d_cells, uint32_t n, const EditOpDev* d_ops, uint32_t nops, uint32_t* d_img,
+                      uint32_t* d_ext, uint2* d_info) {
+        return vxrt::edit_bricks(d_cells, n, d_ops, nops, c->d_meta, c->d_pool, d_img, d_ext, d_info, f, c->view.cx, c->view.cz);
     };
-    std::vector<uint32_t> cells;
-    vxrt::edit_cells(dev, f, c->view.cx, c->view.cz, c->ncells, cells);
-    const uint32_t n = (uint32_t)cells.size();
-    st.bricks_touched = n;
-    if (n == 0)
-        return finish();
-    const uint64_t bw = c->view.brick_words;
-    // device scratch: ops and cells in; images, extents and {old slot, flags} out; the plan in
-    const size_t ops_bytes = dev.size() * sizeof(EditOpDev);
-    hipError_t e = c->edit_in.reserve(ops_bytes + (size_t)n * 4);
-    if (e == hipSuccess)
-        e = c->edit_scratch.reserve((size_t)n * bw * 4);
-    if (e == hipSuccess)
-        e = c->edit_out.reserve((size_t)n * 12);
-    if (e == hipSuccess)
-        e = c->edit_plan.reserve((size_t)n * 8);
+    return vxrt::edit_run(c, dev, launch, out);
+}
+
+uint64_t vxrt_region_words(const int32_t dims[3])
+{
+    return dims ? vxrt::region_words(dims) : 0;
+}
+
+int vxrt_read_region(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t* d_bits, void* stream)
+{
+    if (!c || !origin || !dims || !d_bits)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (vxrt::region_words(dims) == 0)
+        return fail(VXRT_ERR_INVALID, "region dims: each at least 1, at most 2^36 voxels");
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not read");
+    VX_HIP(hipSetDevice(c->device));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::read_region(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, d_bits, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_read_region_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t* bits)
+{
+    if (!c || !origin || !dims || !bits)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    const uint64_t words = vxrt::region_words(dims);
+    if (words == 0)
+        return fail(VXRT_ERR_INVALID, "region dims: each at least 1, at most 2^36 voxels");
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not read");
+    VX_HIP(hipSetDevice(c->device));
+    struct Temp {
+        uint32_t* p = nullptr;
+        ~Temp() { (void)hipFree(p); }
+    } T;
+    hipError_t e = hipMalloc((void**)&T.p, words * 4);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(VXRT_ERR_NOMEM, std::string("edit scratch for ") + std::to_string(n) + " bricks: " + hipGetErrorString(e));
+        return fail(VXRT_ERR_NOMEM, std::string("region read of ") + std::to_string(words) + " words: " + hipGetErrorString(e));
     }
-    unsigned char* in = static_cast<unsigned char*>(c->edit_in.p);
-    const EditOpDev* d_ops = reinterpret_cast<const EditOpDev*>(in);
-    const uint32_t* d_cells = reinterpret_cast<const uint32_t*>(in + ops_bytes);
-    uint32_t* d_img = static_cast<uint32_t*>(c->edit_scratch.p);
-    uint2* d_info = static_cast<uint2*>(c->edit_out.p);
-    uint32_t* d_ext = reinterpret_cast<uint32_t*>(d_info + n);
-    {
-        std::vector<unsigned char> host_in(ops_bytes + (size_t)n * 4);
-        memcpy(host_in.data(), dev.data(), ops_bytes);
-        memcpy(host_in.data() + ops_bytes, cells.data(), (size_t)n * 4);
-        VX_HIP(hipMemcpy(in, host_in.data(), host_in.size(), hipMemcpyHostToDevice));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::read_region(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, T.p, nullptr));
+    VX_HIP(hipMemcpy(bits, T.p, words * 4, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+int vxrt_edit_stamps(vxrt_ctx* c, const vxrt_stamp* stamps, uint32_t n_stamps, vxrt_edit_stats* out)
+{
+    using vxrt::StampDev;
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (n_stamps > vxrt::kEditMaxOps)
+        return fail(VXRT_ERR_INVALID, "more than VXRT_EDIT_MAX_OPS stamps in one call");
+    if (!stamps && n_stamps)
+        return fail(VXRT_ERR_INVALID, "stamps is NULL");
+    const int f = c->has_world ? c->view.f : 1;
+    const int X = c->has_world ? c->view.cx * f : 1, Y = c->has_world ? c->view.cy * f : 1, Z = c->has_world ? c->view.cz * f : 1;
+    std::vector<StampDev> dev;
+    dev.reserve(n_stamps);
+    for (uint32_t k = 0; k < n_stamps; ++k) {
+        const vxrt_stamp& s = stamps[k];
+        StampDev d;
+        bool noop = false;
+        if (vxrt::stamp_prepare(s.d_bits, s.origin, s.dims, s.mode, s.reserved, X, Y, Z, d, noop))
+            return fail(VXRT_ERR_INVALID, "stamp " + std::to_string(k) +
+                                              ": unknown mode, nonzero reserved, d_bits NULL, or dims outside 1 .. 2^36 voxels");
+        if (!noop)
+            dev.push_back(d);
     }
-    VX_HIP(vxrt::edit_bricks(d_cells, n, d_ops, (uint32_t)dev.size(), c->d_meta, c->d_pool, d_img, d_ext, d_info, f,
-                             c->view.cx, c->view.cz));
-    std::vector<uint2> info(n);
-    VX_HIP(hipMemcpy(info.data(), d_info, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> old_slot(n);
-    std::vector<uint8_t> flags(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        old_slot[i] = info[i].x;
-        flags[i] = (uint8_t)info[i].y;
-    }
-    vxrt::EditPlan P;
-    vxrt::edit_plan_slots(old_slot.data(), flags.data(), n, c->free_slots, c->nslots, P);  // (undone below on failure)
-    if (P.changed == 0)  // no voxel changed: the tables stay untouched
-        return finish();
-    int rc = VXRT_OK;
-    if (P.nslots >= (1ull << 32) - 2)
-        rc = fail(VXRT_ERR_NOMEM, "brick slots exhausted (32-bit slot numbers)");
-    else if (P.nslots > c->pool_capacity_slots)
-        rc = vxrt::grow_pool(c, vxrt::edit_grown_capacity(c->pool_capacity_slots, P.nslots));
-    if (rc) {
-        vxrt::edit_plan_undo(P, c->free_slots);
-        return rc;
-    }
-    uint32_t* d_new = static_cast<uint32_t*>(c->edit_plan.p);
-    uint32_t* d_zero = d_new + n;
-    std::vector<uint32_t> plan(P.new_slot);
-    plan.insert(plan.end(), P.zero.begin(), P.zero.end());
-    e = hipMemcpy(d_new, plan.data(), plan.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = vxrt::edit_commit(d_cells, d_new, n, d_zero, (uint32_t)P.zero.size(), d_img, d_ext, c->d_pool, c->d_meta,
-                              c->d_coarse, f);
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        vxrt::edit_plan_undo(P, c->free_slots);
-        return fail(VXRT_ERR_HIP, std::string("edit commit: ") + hipGetErrorString(e));
-    }
-    c->nslots = P.nslots;
-    c->edited = true;
-    st.bricks_created = P.created;
-    st.bricks_freed = P.freed;
-    return finish();
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
+    auto launch = [&](const uint32_t* d_cells, uint32_t n, const StampDev* d_st, uint32_t nst, uint32_t* d_img,
+                      uint32_t* d_ext, uint2* d_info) {
+        return vxrt::stamp_bricks(d_cells, n, d_st, nst, c->d_meta, c->d_pool, d_img, d_ext, d_info, f, c->view.cx, c->view.cz);
+    };
+    return vxrt::edit_run(c, dev, launch, out);
 }
 
 int vxrt_edit_reserve(vxrt_ctx* c, uint64_t capacity_bricks)

@@ -176,6 +176,53 @@ class Context:
         """Grow the brick pool to at least ``capacity_bricks`` now, so that later edits need no pool copy."""
         N.check(self._L.vxrt_edit_reserve(self._h, int(capacity_bricks)))
 
+    # ---- region readback and voxel stamps (extension, include/vxrt.h) ----------------------------------------------
+    def read_region(self, origin, dims, out=None, stream: int | None = None):
+        """The voxels of the box ``origin`` .. ``origin + dims - 1`` as region words (include/vxrt.h: x in 32-bit words,
+        rows y fastest, then z; voxels outside the world read 0) in a device tensor of ``region_words(dims)`` int32 (the
+        bits of uint32 words), or into ``out``.  Asynchronous on ``stream`` (default: torch's current stream)."""
+        import torch
+        n = region_words(dims)
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int32, device="cuda:%d" % self.device)
+        elif out.numel() * out.element_size() < 4 * n:
+            raise ValueError("out holds fewer than region_words(dims) words")
+        N.check(self._L.vxrt_read_region(self._h, _i3(origin), _i3(dims), _ptr(out), _stream(stream)))
+        return out[:n] if out.dim() == 1 and out.element_size() == 4 else out
+
+    def read_region_host(self, origin, dims) -> np.ndarray:
+        """The voxels of the box ``origin`` .. ``origin + dims - 1`` as a bool [x, y, z] numpy grid (synchronous)."""
+        words = np.empty(max(region_words(dims), 1), np.uint32)
+        N.check(self._L.vxrt_read_region_host(self._h, _i3(origin), _i3(dims), words.ctypes.data))
+        return unpack_region(words, dims)
+
+    def edit_stamps(self, stamps) -> "N.EditStats":
+        """Write a list of Stamp(origin, bits, mode) into the resident world in order: the last stamp covering a voxel
+        decides it (include/vxrt.h).  ``bits``: a device tensor of region words, or a bool [x, y, z] numpy grid (packed
+        and copied to the device here).  Synchronises the device before and after; all or nothing on failure."""
+        import torch
+        keep, descs = [], []
+        for s in stamps:
+            bits, dims = s.bits, s.dims
+            if isinstance(bits, np.ndarray):
+                dims = tuple(int(v) for v in bits.shape) if dims is None else dims
+                bits = torch.from_numpy(pack_region(bits).view(np.int32)).to("cuda:%d" % self.device)
+            elif dims is None:
+                raise ValueError("a stamp of device words needs its dims")
+            keep.append(bits)
+            d = N.StampDesc()
+            d.d_bits = _ptr(bits)
+            d.origin = _i3(s.origin)
+            d.dims = _i3(dims)
+            d.mode = int(s.mode)
+            d.reserved = 0
+            descs.append(d)
+        arr = (N.StampDesc * max(len(descs), 1))(*descs)
+        st = N.EditStats()
+        N.check(self._L.vxrt_edit_stamps(self._h, arr if descs else None, len(descs), C.byref(st)))
+        del keep
+        return st
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -350,6 +397,46 @@ def EditBox(lo, hi, value: int = 1) -> "N.EditOp":
 def EditSphere(centre, radius: int, value: int = 1) -> "N.EditOp":
     """Every voxel v with |v - centre|^2 <= radius^2 (integers) set (value 1) or cleared (value 0)."""
     return _edit_op(N.EDIT_SPHERE, value, centre, (radius, 0, 0))
+
+
+@dataclass
+class Stamp:
+    """A voxel stamp (include/vxrt.h, vxrt_stamp): ``bits`` a bool [x, y, z] numpy grid, or a device tensor of region
+    words with ``dims`` given; ``mode`` STAMP_REPLACE (0), STAMP_UNION (1) or STAMP_SUBTRACT (2)."""
+    origin: tuple
+    bits: object
+    mode: int = N.STAMP_REPLACE
+    dims: tuple | None = None
+
+
+def _i3(v):
+    return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def region_words(dims) -> int:
+    """Words of a region of ``dims`` voxels (vxrt_region_words): ceil(dims[0] / 32) * dims[1] * dims[2]; 0 for bad dims."""
+    return int(N.load().vxrt_region_words(_i3(dims)))
+
+
+def pack_region(vox) -> np.ndarray:
+    """bool [x, y, z] -> region words (uint32): each x row padded to a multiple of 32 bits, rows y fastest, then z."""
+    v = np.asarray(vox, bool)
+    X, Y, Z = v.shape
+    wpr = (X + 31) // 32
+    rows = np.zeros((Z, Y, wpr * 32), bool)
+    rows[:, :, :X] = v.transpose(2, 1, 0)
+    return np.packbits(rows, axis=-1, bitorder="little").view(np.uint32).reshape(-1)
+
+
+def unpack_region(words, dims) -> np.ndarray:
+    """region words (uint32 numpy array, or a tensor of int32 / uint32) -> bool [x, y, z]"""
+    if hasattr(words, "cpu"):
+        words = words.cpu().numpy()
+    X, Y, Z = (int(d) for d in dims)
+    wpr = (X + 31) // 32
+    w = np.ascontiguousarray(words).view(np.uint32)[: wpr * Y * Z].reshape(Z, Y, wpr)
+    bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[:, :, :X]
+    return bits.astype(bool).transpose(2, 1, 0)
 
 
 def grid_is_wide(cdims) -> bool:
