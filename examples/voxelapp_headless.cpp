@@ -5,7 +5,7 @@
 //
 //   voxelapp_headless [world_edge=256] [frames=2] [out_prefix=frame] [width=320] [height=180] [shaded=0]
 //                     [camera_path_file] [dump_every_frame=0] [views_per_launch=1] [frames_in_flight=1] [device_world=XxYxZ]
-//                     [edit_script]
+//                     [edit_script] [walk=0]
 //
 // shaded: 0 = the checked-in debug view, 1 = shaded with shadow + 1 bounce sample, checkerboard on, 2 = the same with the
 // checkerboard off (whole frames).  frames_in_flight=2 renders through Graphics::RenderScreenAsync / WaitFrame: frame k+1 is
@@ -25,6 +25,10 @@
 // that holds the frame).  A '-' skips it.  Two more kinds copy and paste (VoxelRaytracer3D::ReadRegion / StampVoxels):
 // kind 2 = copy the box of origin a and dims b into clipboard slot `value`; kind 3 = paste clipboard slot `value` with its
 // voxel (0,0,0) at a, in mode bx (0 = replace, 1 = union, 2 = subtract; by = bz = 0).
+// walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
+// the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
+// each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
+// body's centre.  One line per frame: "walk frame N lo <%a x3> hi <%a x3> flags F".
 #include "../include/GPUDDA/Renderer.h"
 #include "../include/GPUDDA/VoxelWorldBuilder.h"
 #include "../include/vxrt.h"
@@ -89,6 +93,8 @@ int main(int argc, char** argv)
             }
         }
     }
+
+    const bool walk = argc > 13 && atoi(argv[13]) != 0;
 
     struct Pose {
         float3 pos, euler;
@@ -217,6 +223,43 @@ int main(int argc, char** argv)
         flush_ops();
     };
 
+    // the camera pose of frame i: the path's (or the fixed camera), then with walk=1 the body moved toward it
+    const float half[3] = {2.0f, 6.0f, 2.0f};
+    vxrt_body body{};
+    bool body_placed = false;
+    auto pose_for = [&](int i) {
+        if (!path.empty()) {
+            cam_pos = path[(size_t)i].pos;
+            cam_eular = path[(size_t)i].euler;
+        }
+        if (!walk)
+            return;
+        const float target[3] = {cam_pos.x, cam_pos.y, cam_pos.z};
+        for (int k = 0; k < 3; ++k) {
+            if (!body_placed) {
+                body.lo[k] = target[k] - half[k];
+                body.hi[k] = target[k] + half[k];
+            }
+            const float d = target[k] - (body.lo[k] + half[k]);
+            const float m = (float)VXRT_BODY_MAX_DELTA;
+            body.delta[k] = d > m ? m : (d < -m ? -m : d);
+        }
+        body_placed = true;
+        float lohi[6];
+        uint32_t flags = 0;
+        if (raytracer->MoveBoxes(&body, 1, lohi, &flags) != VXRT_OK) {
+            std::cerr << "walk, frame " << i << ": " << vxrt_last_error() << std::endl;
+            std::exit(3);
+        }
+        for (int k = 0; k < 3; ++k) {
+            body.lo[k] = lohi[k];
+            body.hi[k] = lohi[3 + k];
+        }
+        cam_pos = make_float3(body.lo[0] + half[0], body.lo[1] + half[1], body.lo[2] + half[2]);
+        std::printf("walk frame %d lo %a %a %a hi %a %a %a flags %u\n", i, body.lo[0], body.lo[1], body.lo[2], body.hi[0],
+                    body.hi[1], body.hi[2], flags);
+    };
+
     void* d_pixels = nullptr;
     if (hipMalloc(&d_pixels, (size_t)width * height * sizeof(BGRA8888)) != hipSuccess)
         return 1;
@@ -271,10 +314,7 @@ int main(int argc, char** argv)
             auto f0 = std::chrono::high_resolution_clock::now();
             if (i < nframes) {
                 apply_edits(i, i + 1);
-                if (!path.empty()) {
-                    cam_pos = path[(size_t)i].pos;
-                    cam_eular = path[(size_t)i].euler;
-                }
+                pose_for(i);
                 GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
                 const FrameTicket t = RenderScreenAsync(raytracer, width, height, d_ring[i % 3], cam_pos, cam_forward, cam_up, cam_right);
                 // the copy runs on its own stream behind the frame, so the render streams never wait for the copy engine
@@ -313,10 +353,7 @@ int main(int argc, char** argv)
             apply_edits(first, first + n);
             auto f0 = std::chrono::high_resolution_clock::now();
             for (int j = 0; j < n; ++j) {
-                if (!path.empty()) {
-                    cam_pos = path[(size_t)(first + j)].pos;
-                    cam_eular = path[(size_t)(first + j)].euler;
-                }
+                pose_for(first + j);
                 GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
                 views[(size_t)j] = ScreenView{d_views[(size_t)j], cam_pos, cam_forward, cam_up, cam_right};
             }
@@ -333,11 +370,8 @@ int main(int argc, char** argv)
             (void)hipFree(p);
     }
     for (int i = 0; batch <= 1 && in_flight < 2 && i < nframes; ++i) {
-        if (!path.empty()) {
-            cam_pos = path[(size_t)i].pos;
-            cam_eular = path[(size_t)i].euler;
-        }
         apply_edits(i, i + 1);
+        pose_for(i);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
         RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);

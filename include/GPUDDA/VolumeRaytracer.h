@@ -23,6 +23,7 @@
 struct vxrt_ctx;
 struct vxrt_edit_op;     // include/vxrt.h
 struct vxrt_edit_stats;
+struct vxrt_body;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -139,6 +140,13 @@ public:
     int ReadRegion(const int32_t origin[3], const int32_t dims[3], std::vector<uint32_t>& bits);
     int StampVoxels(const int32_t origin[3], const int32_t dims[3], const uint32_t* bits, int mode,
                     vxrt_edit_stats* stats = nullptr);
+    // box collision queries (extensions, include/vxrt.h): n bodies moved axis by axis in `order` (a permutation of
+    // {0, 1, 2}; y, x, z when NULL) and stopped at the first solid voxel each leading face would enter -- lohi_out gets
+    // n x 6 floats (lo, hi), flags_or_null the VXRT_BODY_* bits (vxrt_move_boxes_host) -- and the solid voxels each body
+    // overlaps (vxrt_overlap_boxes_host).  Host arrays; pending uploads are flushed first.  Return the vxrt_status.
+    int MoveBoxes(const vxrt_body* bodies, size_t n, float* lohi_out, uint32_t* flags_or_null = nullptr,
+                  const int32_t* order = nullptr);
+    int OverlapBoxes(const vxrt_body* bodies, size_t n, uint32_t* counts, uint32_t* flags_or_null = nullptr);
 
 private:
     void Flush();

@@ -246,6 +246,56 @@ typedef struct vxrt_stamp {
 } vxrt_stamp;
 int vxrt_edit_stamps(vxrt_ctx *ctx, const vxrt_stamp *stamps, uint32_t n_stamps, vxrt_edit_stats *stats_or_null);
 
+/* ---- box collision queries -- an EXTENSION (with the editing above: bodies kept out of a world that changes).  A body is
+ * an axis-aligned box of world voxel coordinates, lo < hi, and a displacement.  Queries read the resident world only.
+ *   Voxels.  Voxel v occupies [v, v+1) on each axis.  A box (lo, hi) overlaps the integer range [floor(lo[b]),
+ *     ceil(hi[b]) - 1] on axis b: faces that only touch do not overlap.  Voxels outside the world are empty, as they are
+ *     for vxrt_read_region.
+ *   Move (vxrt_move_boxes).  The body moves axis by axis in `order`, a permutation of {0, 1, 2}; each axis uses the box as
+ *     the earlier axes left it.  On axis a, let d = delta[a]; d == 0 (-0 included) does nothing.
+ *     d > 0: e = hi[a] + d.  The candidates are the slabs v in [ceil(hi[a]), ceil(e) - 1] crossed with the overlap ranges
+ *       of the other two axes.  If a candidate voxel is solid, let F be the least such v: the body is blocked,
+ *       lo[a] = lo[a] + ((float)F - hi[a]), then hi[a] = (float)F exactly, and flag bit a is set.  Otherwise
+ *       lo[a] = lo[a] + d and hi[a] = e.
+ *     d < 0 (the mirror): e = lo[a] + d.  The candidates are [floor(e), floor(lo[a]) - 1].  If one is solid, let G be the
+ *       greatest: hi[a] = hi[a] + ((float)(G + 1) - lo[a]), then lo[a] = (float)(G + 1) exactly, and the flag is set.
+ *       Otherwise lo[a] = e and hi[a] = hi[a] + d.
+ *     Every + / - above is one binary32 operation rounded to nearest, with no contraction.
+ *     Consequences: voxels the box already overlaps are ignored, so a body stuck in terrain can move out; a body resting on
+ *     a face stays on it (the next step has F = ceil(hi) and is blocked with no move); nothing tunnels, every slab the
+ *     leading face sweeps is tested.
+ *   Overlap (vxrt_overlap_boxes).  The count is the number of solid voxels in [floor(lo), ceil(hi) - 1] on all three axes;
+ *     delta is ignored.
+ *   Validity (per body, like the ray validity rule of vxrt_trace_batch).  A body is valid when, on every axis k, every
+ *     component is finite, lo[k] < hi[k], hi[k] - lo[k] <= VXRT_BODY_MAX_EXTENT (evaluated in binary32),
+ *     |delta[k]| <= VXRT_BODY_MAX_DELTA, and |lo[k]| and |hi[k]| are below 2^24.  An invalid body is returned unchanged
+ *     (count 0) with flags VXRT_BODY_INVALID.  The bounds cap the swept slab of one axis at 65 x 65 x 64 voxels.
+ *   Call rules (as vxrt_read_region): asynchronous on `stream`.  A NULL ctx, or an `order` that is NULL or not a
+ *     permutation, gives VXRT_ERR_INVALID; then n == 0 is a no-op (VXRT_OK); then a NULL required pointer gives
+ *     VXRT_ERR_INVALID, no world VXRT_ERR_NO_WORLD, a streamed world VXRT_ERR_INVALID (a cache is not queried).  The
+ *     ranges are clipped to the world before any load, so no load falls outside the tables.  Each body's results are its
+ *     own: they do not depend on the launch shape, the scheduling or the other bodies.  d_flags_or_null may be NULL.
+ * The cost follows the row words the bodies touch: about (cross-section rows) x (swept x words) per axis. */
+#define VXRT_BODY_MAX_EXTENT 64 /* voxels, per axis */
+#define VXRT_BODY_MAX_DELTA 64  /* voxels, per axis */
+#define VXRT_BODY_BLOCKED_X 1u
+#define VXRT_BODY_BLOCKED_Y 2u
+#define VXRT_BODY_BLOCKED_Z 4u
+#define VXRT_BODY_INVALID 8u
+typedef struct vxrt_body {
+    float lo[3], hi[3], delta[3]; /* 36 bytes; device arrays of n bodies */
+} vxrt_body;
+/* d_lohi_out: n x 6 floats, lo[3] then hi[3] of each body after the move; d_flags_or_null: n words of VXRT_BODY_* bits */
+int vxrt_move_boxes(vxrt_ctx *ctx, const vxrt_body *d_bodies, uint64_t n, const int32_t order[3], float *d_lohi_out,
+                    uint32_t *d_flags_or_null, void *stream);
+/* d_counts: n words */
+int vxrt_overlap_boxes(vxrt_ctx *ctx, const vxrt_body *d_bodies, uint64_t n, uint32_t *d_counts, uint32_t *d_flags_or_null,
+                       void *stream);
+/* the same on host arrays: copied in and out, synchronous (like vxrt_trace_batch_host) */
+int vxrt_move_boxes_host(vxrt_ctx *ctx, const vxrt_body *bodies, uint64_t n, const int32_t order[3], float *lohi_out,
+                         uint32_t *flags_or_null);
+int vxrt_overlap_boxes_host(vxrt_ctx *ctx, const vxrt_body *bodies, uint64_t n, uint32_t *counts, uint32_t *flags_or_null);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

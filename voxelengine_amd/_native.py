@@ -24,10 +24,13 @@ EXPORTS = [
     "vxrt_set_batch_max_steps", "vxrt_stream_open", "vxrt_stream_focus", "vxrt_stream_resident", "vxrt_stream_close",
     "vxrt_edit_voxels", "vxrt_edit_reserve",
     "vxrt_region_words", "vxrt_read_region", "vxrt_read_region_host", "vxrt_edit_stamps",
+    "vxrt_move_boxes", "vxrt_overlap_boxes", "vxrt_move_boxes_host", "vxrt_overlap_boxes_host",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
 STAMP_REPLACE, STAMP_UNION, STAMP_SUBTRACT = 0, 1, 2
+BODY_MAX_EXTENT, BODY_MAX_DELTA = 64, 64
+BODY_BLOCKED_X, BODY_BLOCKED_Y, BODY_BLOCKED_Z, BODY_INVALID = 1, 2, 4, 8
 
 
 class WorldDesc(C.Structure):
@@ -181,6 +184,11 @@ def load() -> C.CDLL:
     L.vxrt_read_region.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
     L.vxrt_read_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     L.vxrt_edit_stamps.argtypes = [C.c_void_p, C.POINTER(StampDesc), C.c_uint32, C.POINTER(EditStats)]
+    L.vxrt_move_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p,
+                                  C.c_void_p]
+    L.vxrt_overlap_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_move_boxes_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    L.vxrt_overlap_boxes_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

@@ -245,6 +245,20 @@ int VoxelRaytracer3D::ReadRegion(const int32_t origin[3], const int32_t dims[3],
     return vxrt_read_region_host(ctx, origin, dims, bits.data());
 }
 
+int VoxelRaytracer3D::MoveBoxes(const vxrt_body* bodies, size_t n, float* lohi_out, uint32_t* flags_or_null,
+                                const int32_t* order)
+{
+    Flush();
+    static const int32_t yxz[3] = {1, 0, 2};
+    return vxrt_move_boxes_host(ctx, bodies, n, order ? order : yxz, lohi_out, flags_or_null);
+}
+
+int VoxelRaytracer3D::OverlapBoxes(const vxrt_body* bodies, size_t n, uint32_t* counts, uint32_t* flags_or_null)
+{
+    Flush();
+    return vxrt_overlap_boxes_host(ctx, bodies, n, counts, flags_or_null);
+}
+
 int VoxelRaytracer3D::StampVoxels(const int32_t origin[3], const int32_t dims[3], const uint32_t* bits, int mode,
                                   vxrt_edit_stats* stats)
 {

@@ -43,6 +43,11 @@ hipError_t read_region(const uint2* meta, const uint32_t* pool, int f, const int
                        uint32_t* out, hipStream_t stream);
 hipError_t stamp_bricks(const uint32_t* cells, uint32_t n, const StampDev* stamps, uint32_t nst, const uint2* meta,
                         const uint32_t* pool, uint32_t* scratch, uint32_t* ext, uint2* info, int f, int cx, int cz);
+// box collision queries (vxrt_collide.hip)
+hipError_t move_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
+                      const int order[3], float* lohi, uint32_t* flags, hipStream_t stream);
+hipError_t overlap_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
+                         uint32_t* counts, uint32_t* flags, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -1884,6 +1889,144 @@ int vxrt_edit_stamps(vxrt_ctx* c, const vxrt_stamp* stamps, uint32_t n_stamps, v
         return vxrt::stamp_bricks(d_cells, n, d_st, nst, c->d_meta, c->d_pool, d_img, d_ext, d_info, f, c->view.cx, c->view.cz);
     };
     return vxrt::edit_run(c, dev, launch, out);
+}
+
+// ---- box collision queries -------------------------------------------------------------------------------------------
+static bool collide_order(const int32_t* order, int out[3])
+{
+    if (!order)
+        return false;
+    unsigned seen = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (order[k] < 0 || order[k] > 2)
+            return false;
+        seen |= 1u << order[k];
+        out[k] = order[k];
+    }
+    return seen == 7u;
+}
+
+// the checks every collision call makes after ctx / order / n, in the order of include/vxrt.h
+static int collide_ready(vxrt_ctx* c)
+{
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not queried");
+    return VXRT_OK;
+}
+
+int vxrt_move_boxes(vxrt_ctx* c, const vxrt_body* d_bodies, uint64_t n, const int32_t order[3], float* d_lohi_out,
+                    uint32_t* d_flags_or_null, void* stream)
+{
+    int ord[3];
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (!collide_order(order, ord))
+        return fail(VXRT_ERR_INVALID, "order must be a permutation of {0, 1, 2}");
+    if (n == 0)
+        return VXRT_OK;
+    if (!d_bodies || !d_lohi_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = collide_ready(c))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::move_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)d_bodies, n, ord, d_lohi_out, d_flags_or_null,
+                            (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_overlap_boxes(vxrt_ctx* c, const vxrt_body* d_bodies, uint64_t n, uint32_t* d_counts, uint32_t* d_flags_or_null,
+                       void* stream)
+{
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (n == 0)
+        return VXRT_OK;
+    if (!d_bodies || !d_counts)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = collide_ready(c))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::overlap_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)d_bodies, n, d_counts, d_flags_or_null,
+                               (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+// device copies of the bodies and the results of a host call, freed on every path
+struct CollideTemp {
+    void* p = nullptr;
+    ~CollideTemp() { (void)hipFree(p); }
+};
+
+int vxrt_move_boxes_host(vxrt_ctx* c, const vxrt_body* bodies, uint64_t n, const int32_t order[3], float* lohi_out,
+                         uint32_t* flags_or_null)
+{
+    int ord[3];
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (!collide_order(order, ord))
+        return fail(VXRT_ERR_INVALID, "order must be a permutation of {0, 1, 2}");
+    if (n == 0)
+        return VXRT_OK;
+    if (!bodies || !lohi_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = collide_ready(c))
+        return rc;
+    if (n > (1ull << 36))
+        return fail(VXRT_ERR_INVALID, "too many bodies for one host call");
+    VX_HIP(hipSetDevice(c->device));
+    CollideTemp T;
+    const size_t bb = (size_t)n * sizeof(vxrt_body), ob = (size_t)n * 24, fb = (size_t)n * 4;
+    hipError_t e = hipMalloc(&T.p, bb + ob + fb);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("move_boxes_host: ") + hipGetErrorString(e));
+    }
+    char* base = (char*)T.p;
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(hipMemcpy(base, bodies, bb, hipMemcpyHostToDevice));
+    VX_HIP(vxrt::move_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)base, n, ord, (float*)(base + bb),
+                            (uint32_t*)(base + bb + ob), nullptr));
+    VX_HIP(hipMemcpy(lohi_out, base + bb, ob, hipMemcpyDeviceToHost));
+    if (flags_or_null)
+        VX_HIP(hipMemcpy(flags_or_null, base + bb + ob, fb, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+int vxrt_overlap_boxes_host(vxrt_ctx* c, const vxrt_body* bodies, uint64_t n, uint32_t* counts, uint32_t* flags_or_null)
+{
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (n == 0)
+        return VXRT_OK;
+    if (!bodies || !counts)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = collide_ready(c))
+        return rc;
+    if (n > (1ull << 36))
+        return fail(VXRT_ERR_INVALID, "too many bodies for one host call");
+    VX_HIP(hipSetDevice(c->device));
+    CollideTemp T;
+    const size_t bb = (size_t)n * sizeof(vxrt_body), cb = (size_t)n * 4;
+    hipError_t e = hipMalloc(&T.p, bb + 2 * cb);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("overlap_boxes_host: ") + hipGetErrorString(e));
+    }
+    char* base = (char*)T.p;
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(hipMemcpy(base, bodies, bb, hipMemcpyHostToDevice));
+    VX_HIP(vxrt::overlap_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)base, n, (uint32_t*)(base + bb),
+                               (uint32_t*)(base + bb + cb), nullptr));
+    VX_HIP(hipMemcpy(counts, base + bb, cb, hipMemcpyDeviceToHost));
+    if (flags_or_null)
+        VX_HIP(hipMemcpy(flags_or_null, base + bb + cb, cb, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
 }
 
 int vxrt_edit_reserve(vxrt_ctx* c, uint64_t capacity_bricks)

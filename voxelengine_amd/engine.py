@@ -223,6 +223,43 @@ class Context:
         del keep
         return st
 
+    # ---- box collision queries (extension, include/vxrt.h) -----------------------------------------------------------
+    def move_boxes(self, bodies, order=(1, 0, 2), stream: int | None = None):
+        """Move boxes through the resident world axis by axis in ``order`` (default y, x, z), stopping each axis at the
+        first solid voxel its leading face would enter (include/vxrt.h, vxrt_move_boxes).  ``bodies``: (n, 9) float32 rows
+        lo[3], hi[3], delta[3] -- a cuda tensor (asynchronous on ``stream``, default torch's current stream; returns device
+        tensors) or a numpy array (the host path, synchronous; returns numpy arrays).  Returns (lohi (n, 6) float32, flags
+        (n,) of BODY_BLOCKED_X / _Y / _Z bits, or BODY_INVALID)."""
+        order = (C.c_int32 * 3)(*[int(v) for v in order])
+        if isinstance(bodies, np.ndarray) or isinstance(bodies, (list, tuple)):
+            b = _bodies_np(bodies)
+            lohi = np.empty((len(b), 6), np.float32)
+            flags = np.empty(len(b), np.uint32)
+            N.check(self._L.vxrt_move_boxes_host(self._h, b.ctypes.data, len(b), order, lohi.ctypes.data, flags.ctypes.data))
+            return lohi, flags
+        import torch
+        b = _bodies_dev(bodies)
+        lohi = torch.empty((b.shape[0], 6), dtype=torch.float32, device=b.device)
+        flags = torch.empty(b.shape[0], dtype=torch.int32, device=b.device)
+        N.check(self._L.vxrt_move_boxes(self._h, _ptr(b), b.shape[0], order, _ptr(lohi), _ptr(flags), _stream(stream)))
+        return lohi, flags
+
+    def overlap_boxes(self, bodies, stream: int | None = None):
+        """The number of solid voxels each box overlaps (include/vxrt.h, vxrt_overlap_boxes; delta ignored).  ``bodies`` as
+        for move_boxes.  Returns (counts (n,), flags (n,): 0, or BODY_INVALID with count 0)."""
+        if isinstance(bodies, np.ndarray) or isinstance(bodies, (list, tuple)):
+            b = _bodies_np(bodies)
+            counts = np.empty(len(b), np.uint32)
+            flags = np.empty(len(b), np.uint32)
+            N.check(self._L.vxrt_overlap_boxes_host(self._h, b.ctypes.data, len(b), counts.ctypes.data, flags.ctypes.data))
+            return counts, flags
+        import torch
+        b = _bodies_dev(bodies)
+        counts = torch.empty(b.shape[0], dtype=torch.int32, device=b.device)
+        flags = torch.empty(b.shape[0], dtype=torch.int32, device=b.device)
+        N.check(self._L.vxrt_overlap_boxes(self._h, _ptr(b), b.shape[0], _ptr(counts), _ptr(flags), _stream(stream)))
+        return counts, flags
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -407,6 +444,38 @@ class Stamp:
     bits: object
     mode: int = N.STAMP_REPLACE
     dims: tuple | None = None
+
+
+@dataclass
+class Body:
+    """An axis-aligned box of world voxel coordinates (include/vxrt.h, vxrt_body) and the displacement a move_boxes call
+    applies to it; ``Body.pack`` makes the (n, 9) float32 rows the queries take."""
+    lo: tuple
+    hi: tuple
+    delta: tuple = (0.0, 0.0, 0.0)
+
+    def row(self) -> np.ndarray:
+        return np.asarray([*self.lo, *self.hi, *self.delta], np.float32)
+
+    @staticmethod
+    def pack(bodies) -> np.ndarray:
+        return np.stack([b.row() for b in bodies]) if len(bodies) else np.zeros((0, 9), np.float32)
+
+
+def _bodies_np(bodies) -> np.ndarray:
+    if isinstance(bodies, (list, tuple)) and (len(bodies) == 0 or isinstance(bodies[0], Body)):
+        bodies = Body.pack(bodies)
+    b = np.ascontiguousarray(bodies, np.float32)
+    if b.ndim != 2 or b.shape[1] != 9:
+        raise ValueError("bodies must be (n, 9) float32: lo[3], hi[3], delta[3]")
+    return b
+
+
+def _bodies_dev(bodies):
+    import torch
+    if bodies.dtype != torch.float32 or bodies.dim() != 2 or bodies.shape[1] != 9:
+        raise ValueError("bodies must be an (n, 9) float32 tensor: lo[3], hi[3], delta[3]")
+    return bodies.contiguous()
 
 
 def _i3(v):
