@@ -24,7 +24,10 @@
 // applied in file order before that frame is rendered ('#' starts a comment; with views_per_launch > 1, before the launch
 // that holds the frame).  A '-' skips it.  Two more kinds copy and paste (VoxelRaytracer3D::ReadRegion / StampVoxels):
 // kind 2 = copy the box of origin a and dims b into clipboard slot `value`; kind 3 = paste clipboard slot `value` with its
-// voxel (0,0,0) at a, in mode bx (0 = replace, 1 = union, 2 = subtract; by = bz = 0).
+// voxel (0,0,0) at a, in mode bx (0 = replace, 1 = union, 2 = subtract; by = bz = 0).  Kind 4 collapses the floating
+// islands of the box of origin a and dims b (VoxelRaytracer3D::FindIslands, anchored on the box's six faces and world y = 0,
+// then a subtract stamp of them): one line "collapse before frame N: C components, I islands, V island voxels, ..." with the
+// stamp's brick counts.  A dig that severs an overhang, then a collapse around it, removes the overhang.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -204,6 +207,19 @@ int main(int argc, char** argv)
                     std::exit(3);
                 }
                 std::printf("copy before frame %d: slot %d, %zu words\n", from, e.op.value, c.bits.size());
+            } else if (e.op.kind == 4) {  // collapse islands
+                flush_ops();
+                std::vector<uint32_t> floating;
+                vxrt_island_summary sum{};
+                vxrt_edit_stats st{};
+                if (raytracer->FindIslands(e.op.a, e.op.b, VXRT_ISLAND_ANCHOR_FACES | VXRT_ISLAND_ANCHOR_FLOOR, floating, sum) != VXRT_OK ||
+                    raytracer->StampVoxels(e.op.a, e.op.b, floating.data(), VXRT_STAMP_SUBTRACT, &st) != VXRT_OK) {
+                    std::cerr << "collapse before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("collapse before frame %d: %u components, %u islands, %u island voxels, %llu bricks touched, %llu created, "
+                            "%llu freed\n", from, sum.components, sum.islands, sum.island_voxels, (unsigned long long)st.bricks_touched,
+                            (unsigned long long)st.bricks_created, (unsigned long long)st.bricks_freed);
             } else if (e.op.kind == 3) {  // paste
                 flush_ops();
                 const auto it = clipboard.find(e.op.value);

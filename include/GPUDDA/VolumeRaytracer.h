@@ -24,6 +24,8 @@ struct vxrt_ctx;
 struct vxrt_edit_op;     // include/vxrt.h
 struct vxrt_edit_stats;
 struct vxrt_body;
+struct vxrt_island;
+struct vxrt_island_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -147,6 +149,13 @@ public:
     int MoveBoxes(const vxrt_body* bodies, size_t n, float* lohi_out, uint32_t* flags_or_null = nullptr,
                   const int32_t* order = nullptr);
     int OverlapBoxes(const vxrt_body* bodies, size_t n, uint32_t* counts, uint32_t* flags_or_null = nullptr);
+    // floating islands (extension, include/vxrt.h, vxrt_find_islands_host): the island voxels of the box origin .. origin +
+    // dims - 1 under the VXRT_ISLAND_ANCHOR_* bits `anchors` into `floating` (region words: a subtract stamp at origin
+    // deletes them), the summary, and optionally the per-voxel component ids and up to max_islands table rows.  Pending
+    // uploads are flushed first.  Returns the vxrt_status.
+    int FindIslands(const int32_t origin[3], const int32_t dims[3], uint32_t anchors, std::vector<uint32_t>& floating,
+                    vxrt_island_summary& summary, std::vector<vxrt_island>* islands = nullptr, uint32_t max_islands = 4096,
+                    std::vector<uint32_t>* labels = nullptr);
 
 private:
     void Flush();

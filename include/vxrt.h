@@ -296,6 +296,60 @@ int vxrt_move_boxes_host(vxrt_ctx *ctx, const vxrt_body *bodies, uint64_t n, con
                          uint32_t *flags_or_null);
 int vxrt_overlap_boxes_host(vxrt_ctx *ctx, const vxrt_body *bodies, uint64_t n, uint32_t *counts, uint32_t *flags_or_null);
 
+/* ---- floating islands -- an EXTENSION (with the editing above: terrain cut loose by an edit found on the device).  A call
+ * looks at one box B = [origin, origin + dims) of world voxels: 1 <= dims[k], dims[0] * dims[1] * dims[2] <= 2^28, and
+ * origin[k] + dims[k] <= 2^31 - 1.  B may lie partly outside the world; voxels outside the world are empty, as for
+ * vxrt_read_region.
+ *   Components.  Two solid voxels of B are connected when they share a face (6-connectivity: edges and corners do not
+ *     connect).  Paths never leave B.
+ *   Component id.  1 + x + dims[0] * (y + dims[1] * z) of the component's first voxel in that order (x fastest, then y,
+ *     then z: the region order of vxrt_read_region).  The id does not depend on the algorithm or the scheduling.
+ *   Anchors.  Bits 0-5 of `anchors` are the faces x-lo, x-hi, y-lo, y-hi, z-lo, z-hi of B: a voxel on a set face is an
+ *     anchor voxel.  VXRT_ISLAND_ANCHOR_FLOOR makes every voxel at world y = 0 an anchor voxel.  Other bits give
+ *     VXRT_ERR_INVALID.  anchors = 0 makes every component an island (plain component labelling, e.g. of a pasted piece).
+ *   Island.  A component with no anchor voxel.
+ *   Property.  With all six face bits set, every island is a connected piece of the WHOLE world that lies wholly inside B's
+ *     interior: every path out of B passes through a face voxel, which would anchor it.  So "edit, then look at the edit's
+ *     box grown by a margin of one voxel or more" finds exactly the pieces the edit cut loose there; it is not a heuristic.
+ * Outputs:
+ *   d_floating: the island voxels in region bit layout (vxrt_region_words(dims) words, padding bits 0).  It is a
+ *     VXRT_STAMP_SUBTRACT stamp at `origin` that deletes the islands.
+ *   d_labels_or_null: one uint32 per voxel in region order (dims[0] * dims[1] * dims[2] words, no padding): 0 for an empty
+ *     voxel, otherwise its component id -- every component, anchored ones included.
+ *   d_islands_or_null: one vxrt_island per island in ascending id, at most max_islands rows.  lo / hi are world voxels, hi
+ *     exclusive; voxels is the island's voxel count.
+ *   d_summary: components, islands (the true count even when the table was cut short) and island_voxels (all islands).
+ * Workspace.  d_work holds vxrt_islands_workspace_bytes(dims) bytes, at most 8.5 * voxels + 4 KiB and about 4.6 * voxels
+ *   once dims[0] >= 32 (the box's bits, one uint32 parent per voxel and three bits per voxel of root / anchor / prefix
+ *   words): 1.2 GiB for a 2^28-voxel box with dims[0] >= 32.  The caller owns it, so calls on different streams share no
+ *   hidden scratch; the library allocates nothing per call.
+ * Call rules (as vxrt_read_region): asynchronous on `stream`.  A NULL ctx, origin, dims, d_work, d_floating or d_summary,
+ *   bad dims or bad anchor bits give VXRT_ERR_INVALID; no world VXRT_ERR_NO_WORLD; a streamed world VXRT_ERR_INVALID (a
+ *   cache is not queried).  The call never loads outside the tables.  Results are bit-identical from call to call. */
+#define VXRT_ISLAND_ANCHOR_X_LO 0x01u
+#define VXRT_ISLAND_ANCHOR_X_HI 0x02u
+#define VXRT_ISLAND_ANCHOR_Y_LO 0x04u
+#define VXRT_ISLAND_ANCHOR_Y_HI 0x08u
+#define VXRT_ISLAND_ANCHOR_Z_LO 0x10u
+#define VXRT_ISLAND_ANCHOR_Z_HI 0x20u
+#define VXRT_ISLAND_ANCHOR_FACES 0x3Fu
+#define VXRT_ISLAND_ANCHOR_FLOOR 0x40u
+typedef struct vxrt_island {
+    uint32_t id, voxels;  /* component id (above), voxel count */
+    int32_t lo[3], hi[3]; /* world voxels, hi exclusive; 32 bytes */
+} vxrt_island;
+typedef struct vxrt_island_summary {
+    uint32_t components, islands, island_voxels;
+} vxrt_island_summary;
+uint64_t vxrt_islands_workspace_bytes(const int32_t dims[3]); /* 0 for dims outside the contract */
+int vxrt_find_islands(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t anchors, void *d_work,
+                      uint32_t *d_floating, uint32_t *d_labels_or_null, vxrt_island *d_islands_or_null, uint32_t max_islands,
+                      vxrt_island_summary *d_summary, void *stream);
+/* the same on host buffers, synchronous; allocates its own workspace (like vxrt_read_region_host) */
+int vxrt_find_islands_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t anchors,
+                           uint32_t *floating, uint32_t *labels_or_null, vxrt_island *islands_or_null, uint32_t max_islands,
+                           vxrt_island_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

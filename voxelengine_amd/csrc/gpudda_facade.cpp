@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -257,6 +258,26 @@ int VoxelRaytracer3D::OverlapBoxes(const vxrt_body* bodies, size_t n, uint32_t* 
 {
     Flush();
     return vxrt_overlap_boxes_host(ctx, bodies, n, counts, flags_or_null);
+}
+
+int VoxelRaytracer3D::FindIslands(const int32_t origin[3], const int32_t dims[3], uint32_t anchors,
+                                  std::vector<uint32_t>& floating, vxrt_island_summary& summary,
+                                  std::vector<vxrt_island>* islands, uint32_t max_islands, std::vector<uint32_t>* labels)
+{
+    Flush();
+    const uint64_t words = vxrt_region_words(dims);
+    if (words == 0 || vxrt_islands_workspace_bytes(dims) == 0)
+        return VXRT_ERR_INVALID;
+    floating.assign((size_t)words, 0u);
+    if (labels)
+        labels->assign((size_t)dims[0] * dims[1] * dims[2], 0u);
+    if (islands)
+        islands->assign(max_islands, vxrt_island{});
+    const int rc = vxrt_find_islands_host(ctx, origin, dims, anchors, floating.data(), labels ? labels->data() : nullptr,
+                                          islands ? islands->data() : nullptr, islands ? max_islands : 0u, &summary);
+    if (islands)
+        islands->resize(rc == VXRT_OK ? std::min<size_t>(summary.islands, max_islands) : 0);
+    return rc;
 }
 
 int VoxelRaytracer3D::StampVoxels(const int32_t origin[3], const int32_t dims[3], const uint32_t* bits, int mode,

@@ -4,6 +4,7 @@
 #include "../../include/vxrt.h"
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
+#include "vxrt_islands.hpp"
 #include "vxrt_region.hpp"
 
 #include <algorithm>
@@ -48,6 +49,10 @@ hipError_t move_boxes(const uint2* meta, const uint32_t* pool, int f, const int 
                       const int order[3], float* lohi, uint32_t* flags, hipStream_t stream);
 hipError_t overlap_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
                          uint32_t* counts, uint32_t* flags, hipStream_t stream);
+// floating islands (vxrt_islands.hip)
+hipError_t find_islands(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
+                        uint32_t anchors, void* work, uint32_t* floating, uint32_t* labels, vxrt_island* table,
+                        uint32_t max_islands, vxrt_island_summary* summary, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -2025,6 +2030,88 @@ int vxrt_overlap_boxes_host(vxrt_ctx* c, const vxrt_body* bodies, uint64_t n, ui
     VX_HIP(hipMemcpy(counts, base + bb, cb, hipMemcpyDeviceToHost));
     if (flags_or_null)
         VX_HIP(hipMemcpy(flags_or_null, base + bb + cb, cb, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- floating islands ------------------------------------------------------------------------------------------------
+uint64_t vxrt_islands_workspace_bytes(const int32_t dims[3])
+{
+    vxrt::IslandsLayout L;
+    return dims && vxrt::islands_layout(dims, L) ? L.total_bytes : 0;
+}
+
+// the checks both island calls make after their NULL checks, in the order of include/vxrt.h
+static int islands_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t anchors)
+{
+    vxrt::IslandsLayout L;
+    if (!vxrt::islands_layout(dims, L))
+        return fail(VXRT_ERR_INVALID, "island box dims: each at least 1, at most 2^28 voxels");
+    for (int k = 0; k < 3; ++k)
+        if ((int64_t)origin[k] + dims[k] > INT32_MAX)
+            return fail(VXRT_ERR_INVALID, "island box: origin + dims beyond 2^31 - 1");
+    if (anchors & ~vxrt::kIslAnchorMask)
+        return fail(VXRT_ERR_INVALID, "anchors: only VXRT_ISLAND_ANCHOR_* bits");
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not queried");
+    return VXRT_OK;
+}
+
+int vxrt_find_islands(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t anchors, void* d_work,
+                      uint32_t* d_floating, uint32_t* d_labels_or_null, vxrt_island* d_islands_or_null, uint32_t max_islands,
+                      vxrt_island_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !d_work || !d_floating || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = islands_ready(c, origin, dims, anchors))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::find_islands(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, anchors, d_work, d_floating, d_labels_or_null,
+                              d_islands_or_null, max_islands, d_summary, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_find_islands_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t anchors, uint32_t* floating,
+                           uint32_t* labels_or_null, vxrt_island* islands_or_null, uint32_t max_islands,
+                           vxrt_island_summary* summary)
+{
+    if (!c || !origin || !dims || !floating || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = islands_ready(c, origin, dims, anchors))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::IslandsLayout L;
+    vxrt::islands_layout(dims, L);
+    const size_t fb = (size_t)vxrt::region_words(dims) * 4u, lb = labels_or_null ? (size_t)L.nvox * 4u : 0;
+    const size_t tb = islands_or_null ? (size_t)max_islands * sizeof(vxrt_island) : 0;
+    auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
+    CollideTemp T;
+    hipError_t e = hipMalloc(&T.p, up(L.total_bytes) + up(fb) + up(lb) + up(tb) + sizeof(vxrt_island_summary));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("find_islands_host: ") + hipGetErrorString(e));
+    }
+    char* base = (char*)T.p;
+    char* d_float = base + up(L.total_bytes);
+    char* d_lab = d_float + up(fb);
+    char* d_tab = d_lab + up(lb);
+    char* d_sum = d_tab + up(tb);
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::find_islands(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, anchors, base, (uint32_t*)d_float,
+                              labels_or_null ? (uint32_t*)d_lab : nullptr, islands_or_null ? (vxrt_island*)d_tab : nullptr,
+                              islands_or_null ? max_islands : 0u, (vxrt_island_summary*)d_sum, nullptr));
+    VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_island_summary), hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(floating, d_float, fb, hipMemcpyDeviceToHost));
+    if (labels_or_null)
+        VX_HIP(hipMemcpy(labels_or_null, d_lab, lb, hipMemcpyDeviceToHost));
+    if (islands_or_null) {
+        const size_t rows = summary->islands < max_islands ? summary->islands : max_islands;
+        if (rows)
+            VX_HIP(hipMemcpy(islands_or_null, d_tab, rows * sizeof(vxrt_island), hipMemcpyDeviceToHost));
+    }
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }

@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
@@ -260,6 +261,62 @@ class Context:
         N.check(self._L.vxrt_overlap_boxes(self._h, _ptr(b), b.shape[0], _ptr(counts), _ptr(flags), _stream(stream)))
         return counts, flags
 
+    # ---- floating islands (extension, include/vxrt.h) ----------------------------------------------------------------
+    def find_islands(self, origin, dims, anchors: int = N.ISLAND_ANCHOR_FACES | N.ISLAND_ANCHOR_FLOOR, labels: bool = False,
+                     max_islands: int = 4096, stream: int | None = None) -> "Islands":
+        """The 6-connected components of the solid voxels of the box ``origin`` .. ``origin + dims - 1`` that touch no anchor
+        (include/vxrt.h, vxrt_find_islands: by default the box's six faces and world y = 0).  Runs on ``stream`` (default:
+        torch's current stream) and waits for it to return the table and the summary.  Returns an Islands: the island
+        voxels as device region words (a subtract stamp at ``origin``), the per-voxel component ids when ``labels``, and
+        up to ``max_islands`` table rows in ascending id."""
+        import torch
+        dims = tuple(int(v) for v in dims)
+        ws = int(self._L.vxrt_islands_workspace_bytes(_i3(dims)))
+        dev = "cuda:%d" % self.device
+        work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
+        floating = torch.empty(max(region_words(dims), 1), dtype=torch.int32, device=dev)
+        nvox = dims[0] * dims[1] * dims[2] if ws else 0
+        lab = torch.empty(max(nvox, 1), dtype=torch.int32, device=dev) if labels else None
+        table = torch.empty((max(int(max_islands), 1), 8), dtype=torch.int32, device=dev)
+        summary = torch.zeros(3, dtype=torch.int32, device=dev)
+        s = _stream(stream)
+        N.check(self._L.vxrt_find_islands(self._h, _i3(origin), _i3(dims), int(anchors), _ptr(work), _ptr(floating), _ptr(lab),
+                                          _ptr(table), int(max_islands), _ptr(summary), s))
+        torch.cuda.ExternalStream(s, device=dev).synchronize()
+        comps, islands, voxels = (int(v) for v in summary.cpu().numpy().view(np.uint32))
+        rows = table[: min(islands, int(max_islands))].cpu().numpy()
+        return Islands(origin=tuple(int(v) for v in origin), dims=dims, floating=floating[: region_words(dims)],
+                       labels=lab[:nvox] if labels else None, table=_island_table(rows),
+                       summary=IslandSummary(comps, islands, voxels))
+
+    def find_islands_host(self, origin, dims, anchors: int = N.ISLAND_ANCHOR_FACES | N.ISLAND_ANCHOR_FLOOR,
+                          labels: bool = False, max_islands: int = 4096) -> "Islands":
+        """find_islands through the synchronous host call (vxrt_find_islands_host): numpy outputs, floating as a bool
+        [x, y, z] grid and labels as uint32 [x, y, z]."""
+        dims = tuple(int(v) for v in dims)
+        n = region_words(dims)
+        floating = np.zeros(max(n, 1), np.uint32)
+        nvox = dims[0] * dims[1] * dims[2] if n else 0
+        lab = np.zeros(max(nvox, 1), np.uint32) if labels else None
+        table = np.zeros((max(int(max_islands), 1), 8), np.int32)
+        summary = np.zeros(3, np.uint32)
+        N.check(self._L.vxrt_find_islands_host(self._h, _i3(origin), _i3(dims), int(anchors), floating.ctypes.data,
+                                               lab.ctypes.data if labels else None, table.ctypes.data, int(max_islands),
+                                               summary.ctypes.data))
+        comps, islands, voxels = (int(v) for v in summary)
+        return Islands(origin=tuple(int(v) for v in origin), dims=dims, floating=unpack_region(floating, dims),
+                       labels=lab[:nvox].reshape(dims[::-1]).transpose(2, 1, 0) if labels else None,
+                       table=_island_table(table[: min(islands, int(max_islands))]),
+                       summary=IslandSummary(comps, islands, voxels))
+
+    def collapse_islands(self, origin, dims, anchors: int = N.ISLAND_ANCHOR_FACES | N.ISLAND_ANCHOR_FLOOR,
+                         max_islands: int = 4096):
+        """find_islands, then one STAMP_SUBTRACT edit_stamps of its floating voxels at ``origin``: the islands are deleted.
+        Returns (Islands, EditStats)."""
+        isl = self.find_islands(origin, dims, anchors, max_islands=max_islands)
+        st = self.edit_stamps([Stamp(isl.origin, isl.floating, N.STAMP_SUBTRACT, isl.dims)])
+        return isl, st
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -460,6 +517,38 @@ class Body:
     @staticmethod
     def pack(bodies) -> np.ndarray:
         return np.stack([b.row() for b in bodies]) if len(bodies) else np.zeros((0, 9), np.float32)
+
+
+ISLAND_DTYPE = np.dtype([("id", "<u4"), ("voxels", "<u4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])  # vxrt_island
+
+
+class IslandSummary(NamedTuple):
+    """vxrt_island_summary: components of the box, islands among them (the true count), voxels of all islands"""
+    components: int
+    islands: int
+    island_voxels: int
+
+
+def _island_table(rows) -> np.ndarray:
+    return np.ascontiguousarray(rows, np.int32).reshape(-1, 8).view(ISLAND_DTYPE).reshape(-1)
+
+
+@dataclass
+class Islands:
+    """The result of Context.find_islands: ``floating`` the island voxels (region words on the device; a bool grid from
+    find_islands_host), ``labels`` the component id of every voxel (or None), ``table`` a numpy array of ISLAND_DTYPE rows
+    (id, voxels, lo[3], hi[3] in world voxels, hi exclusive) in ascending id, ``summary`` an IslandSummary."""
+    origin: tuple
+    dims: tuple
+    floating: object
+    labels: object
+    table: np.ndarray
+    summary: IslandSummary
+
+    def bodies(self, delta=(0.0, 0.0, 0.0)) -> list:
+        """One Body per table row -- the island's box, displaced by ``delta`` -- for move_boxes (falling debris).  A box
+        wider than BODY_MAX_EXTENT on some axis is an invalid body there: move_boxes returns it unchanged with BODY_INVALID."""
+        return [Body(tuple(float(v) for v in r["lo"]), tuple(float(v) for v in r["hi"]), tuple(delta)) for r in self.table]
 
 
 def _bodies_np(bodies) -> np.ndarray:
