@@ -27,7 +27,10 @@
 // voxel (0,0,0) at a, in mode bx (0 = replace, 1 = union, 2 = subtract; by = bz = 0).  Kind 4 collapses the floating
 // islands of the box of origin a and dims b (VoxelRaytracer3D::FindIslands, anchored on the box's six faces and world y = 0,
 // then a subtract stamp of them): one line "collapse before frame N: C components, I islands, V island voxels, ..." with the
-// stamp's brick counts.  A dig that severs an overhang, then a collapse around it, removes the overhang.
+// stamp's brick counts.  A dig that severs an overhang, then a collapse around it, removes the overhang.  Kind 5 computes a
+// navigation field over the box of origin a and dims b (VoxelRaytracer3D::NavField, the default agent width 1, height 2,
+// climb 1, drop 3) with one goal, the cell that holds frame N's camera position (floor of each coordinate), and prints one
+// line "nav frame N nodes .. reached .. levels .. max_dist ..".
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -220,6 +223,20 @@ int main(int argc, char** argv)
                 std::printf("collapse before frame %d: %u components, %u islands, %u island voxels, %llu bricks touched, %llu created, "
                             "%llu freed\n", from, sum.components, sum.islands, sum.island_voxels, (unsigned long long)st.bricks_touched,
                             (unsigned long long)st.bricks_created, (unsigned long long)st.bricks_freed);
+            } else if (e.op.kind == 5) {  // navigation field toward the camera's cell
+                flush_ops();
+                const float3 cp = path.empty() ? cam_pos : path[(size_t)from].pos;
+                const int32_t goal[3] = {(int32_t)std::floor(cp.x), (int32_t)std::floor(cp.y), (int32_t)std::floor(cp.z)};
+                const vxrt_nav_agent agent{1, 2, 1, 3};
+                std::vector<uint32_t> walkable;
+                std::vector<uint8_t> next;
+                vxrt_nav_summary sum{};
+                if (raytracer->NavField(e.op.a, e.op.b, agent, goal, 1, 1u << 24, walkable, next, sum) != VXRT_OK) {
+                    std::cerr << "nav before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("nav frame %d nodes %u reached %u levels %u max_dist %u\n", from, sum.nodes, sum.reached, sum.levels,
+                            sum.max_dist_found);
             } else if (e.op.kind == 3) {  // paste
                 flush_ops();
                 const auto it = clipboard.find(e.op.value);

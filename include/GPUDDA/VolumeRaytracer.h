@@ -26,6 +26,8 @@ struct vxrt_edit_stats;
 struct vxrt_body;
 struct vxrt_island;
 struct vxrt_island_summary;
+struct vxrt_nav_agent;
+struct vxrt_nav_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -156,6 +158,17 @@ public:
     int FindIslands(const int32_t origin[3], const int32_t dims[3], uint32_t anchors, std::vector<uint32_t>& floating,
                     vxrt_island_summary& summary, std::vector<vxrt_island>* islands = nullptr, uint32_t max_islands = 4096,
                     std::vector<uint32_t>* labels = nullptr);
+    // navigation fields (extension, include/vxrt.h, vxrt_nav_field_host): the walkable bits (region words), one next code
+    // per cell and optionally the distances of the box origin .. origin + dims - 1 for `agent` toward the n_goals world
+    // cells `goals` (3 int32 each), and the summary.  Pending uploads are flushed first.  Returns the vxrt_status.
+    int NavField(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent, const int32_t* goals,
+                 uint32_t n_goals, uint32_t max_dist, std::vector<uint32_t>& walkable, std::vector<uint8_t>& next,
+                 vxrt_nav_summary& summary, std::vector<uint32_t>* dist = nullptr);
+    // the paths of n start cells along the next codes of a NavField of the same box and agent (vxrt_nav_paths, through
+    // device copies; synchronous): the moves made, the VXRT_NAV_* status and optionally the cells, max_steps + 1 per start
+    int NavPaths(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent, const std::vector<uint8_t>& next,
+                 const int32_t* starts, size_t n, uint32_t max_steps, std::vector<uint32_t>& lengths,
+                 std::vector<uint32_t>& status, std::vector<int32_t>* cells = nullptr);
 
 private:
     void Flush();

@@ -350,6 +350,88 @@ int vxrt_find_islands_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t
                            uint32_t *floating, uint32_t *labels_or_null, vxrt_island *islands_or_null, uint32_t max_islands,
                            vxrt_island_summary *summary);
 
+/* ---- navigation fields -- an EXTENSION (with the editing above: where a body can walk, and which way is the goal).  A call
+ * looks at one box B = [origin, origin + dims) of world cells, with the limits of vxrt_find_islands: 1 <= dims[k],
+ * dims[0] * dims[1] * dims[2] <= 2^28, origin[k] + dims[k] <= 2^31 - 1.  Voxels outside the world are empty.
+ *   Agent.  vxrt_nav_agent: 1 <= width <= 8, 1 <= height <= 32, 0 <= climb <= 8, 0 <= drop <= 32.  A cell c = (x, y, z) is
+ *     the agent's minimum corner; the agent occupies A(c) = [x, x+width) x [y, y+height) x [z, z+width).
+ *     free(c): every voxel of A(c) is empty (this reads the world, not only B).
+ *     supported(c): some voxel of [x, x+width) x {y-1} x [z, z+width) is solid.
+ *     A node is a cell of B that is free and supported.
+ *   Moves.  From node c, one candidate per direction d in the order (+x, -x, +z, -z) and per dy in the order (0, +1, ..,
+ *     +climb, -1, .., -drop); the target is t = c + d + (0, dy, 0).  The move is valid when t is a node and
+ *       dy = 0: nothing more;
+ *       dy > 0: free(c + (0, k, 0)) for k = 1 .. dy (the agent rises in place, then steps over);
+ *       dy < 0: free(c + d + (0, k, 0)) for k = dy+1 .. 0 (the agent steps over the edge, then falls).
+ *     Every cell these conditions name lies in B when t does.  Moves are not symmetric: a cliff is dropped, not climbed.
+ *     Move code = 1 + (direction index) * (1 + climb + drop) + (index of dy in its order): 1 .. 164.
+ *   Goals.  Up to VXRT_NAV_MAX_GOALS cells (3 int32 each).  A goal that is not a node is ignored and counted.
+ *     dist(c) is the least number of valid moves from node c to any goal node; above max_dist (1 <= max_dist <= 2^24), or
+ *     with no path, c is unreachable.  next(c) is 0 for a goal node; for another reachable node, the code of the first
+ *     valid move in code order whose target t has dist(t) = dist(c) - 1; VXRT_NAV_NONE for non-nodes and unreachable nodes.
+ *     dist and next are functions of the world, B, the agent, the goals and max_dist alone, not of the algorithm or the
+ *     scheduling.
+ * Outputs of vxrt_nav_field, all in region order (x fastest, then y, then z, as vxrt_read_region):
+ *   d_walkable: the node bits in region bit layout (vxrt_region_words(dims) words, padding bits 0).
+ *   d_next: one byte per cell (required).
+ *   d_dist_or_null: one uint32 per cell, 0xFFFFFFFF for unreachable cells and non-nodes.
+ *   d_summary: nodes; goals_used (goal entries that are nodes, repeats counted) and goals_ignored (the others); reached
+ *     (reachable nodes, goal nodes included); max_dist_found; levels = max_dist_found + 1, or 0 when no goal is used;
+ *     tiles_total, the BFS tiles of B (32 x 16 x 16 cells: ceil(dims[0] / 32) * ceil(dims[1] / 16) * ceil(dims[2] / 16));
+ *     tile_visits, the (level, tile) pairs the call processed (the work follows the frontier: a level visits the tiles
+ *     next to the cells the level before reached, not all of B).
+ * Workspace.  d_work holds vxrt_nav_workspace_bytes(dims, agent) bytes, 0 outside the contract.  With W = width,
+ *   H = height, r(n) = n rounded up to a multiple of 64, wb = ceil(dims[0] / 32), wh = ceil((dims[0] + W - 1) / 32),
+ *   hy = dims[1] + H, hz = dims[2] + W - 1, nb = wb * dims[1] * dims[2], n = dims[0] * dims[1] * dims[2] and T = tiles_total:
+ *     bytes = 4 * (r(wh * hy * hz) + r(wb * hy * hz) + 2 * r(wb * dims[1] * hz) + 4 * r(nb) + r(n) + r(6 * T) + 64)
+ *   (the halo's bits, the erosion passes, free / visited / two frontier planes, the distances, the tile lists): a little over
+ *   4 bytes per cell.  The caller owns it; the library allocates nothing per call.
+ * Call rules.  vxrt_nav_field runs on `stream`, after the work already queued there, and RETURNS WHEN THE FIELD IS COMPLETE:
+ *   the number of BFS levels depends on the data, so the host reads a termination flag from the device every few levels
+ *   (a stream synchronisation).  vxrt_nav_paths is asynchronous on `stream`.  A NULL ctx, origin, dims, agent, d_work,
+ *   d_walkable, d_next or d_summary, d_goals NULL with n_goals > 0, bad dims, agent or max_dist, or n_goals >
+ *   VXRT_NAV_MAX_GOALS give VXRT_ERR_INVALID; no world VXRT_ERR_NO_WORLD; a streamed world VXRT_ERR_INVALID (a cache is not
+ *   queried).  n_goals = 0 gives a field with no goal: walkable is filled, every cell is unreachable.  The call never loads
+ *   outside the tables.  Results are bit-identical from call to call.
+ * Paths (vxrt_nav_paths).  The input is a field description (origin, dims, agent, d_next of a vxrt_nav_field call) and n
+ *   start cells (3 int32 each, world cells).  For each start the kernel follows the next codes for at most max_steps moves
+ *   (max_steps <= 65535); it reads no world data, only the codes.  d_cells_or_null: n x (max_steps + 1) x 3 int32, the
+ *   cells visited from the start on, each path padded with its last cell; d_lengths: the moves made; d_status:
+ *   VXRT_NAV_AT_GOAL (the path ends on a goal node), VXRT_NAV_NO_PATH (the start is not a reachable node; also a code
+ *   that no vxrt_nav_field call writes there, met on the way), VXRT_NAV_TRUNCATED (max_steps moves made, no goal yet) or
+ *   VXRT_NAV_OUTSIDE (the start is not in B).  A NULL ctx, field, field d_next, d_starts, d_lengths or d_status, bad
+ *   dims or agent, or max_steps > 65535 give VXRT_ERR_INVALID; then n == 0 is a no-op.  No world is needed.
+ * vxrt_nav_field_host copies goals in and the outputs out (host buffers, the same sizes), allocates its own workspace and
+ *   is synchronous. */
+#define VXRT_NAV_MAX_GOALS 4096
+#define VXRT_NAV_NONE 0xFFu
+#define VXRT_NAV_MAX_STEPS 65535
+#define VXRT_NAV_AT_GOAL 0u
+#define VXRT_NAV_NO_PATH 1u
+#define VXRT_NAV_TRUNCATED 2u
+#define VXRT_NAV_OUTSIDE 3u
+typedef struct vxrt_nav_agent {
+    int32_t width, height, climb, drop;
+} vxrt_nav_agent;
+typedef struct vxrt_nav_summary {
+    uint32_t nodes, goals_used, goals_ignored, reached, max_dist_found, levels, tiles_total, tile_visits;
+} vxrt_nav_summary;
+typedef struct vxrt_nav_field_desc {
+    int32_t origin[3], dims[3];
+    vxrt_nav_agent agent;
+    const uint8_t *d_next; /* the d_next of a vxrt_nav_field call on this box and agent */
+} vxrt_nav_field_desc;
+uint64_t vxrt_nav_workspace_bytes(const int32_t dims[3], const vxrt_nav_agent *agent); /* 0 outside the contract */
+int vxrt_nav_field(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent *agent,
+                   const int32_t *d_goals, uint32_t n_goals, uint32_t max_dist, void *d_work, uint32_t *d_walkable,
+                   uint8_t *d_next, uint32_t *d_dist_or_null, vxrt_nav_summary *d_summary, void *stream);
+int vxrt_nav_paths(vxrt_ctx *ctx, const vxrt_nav_field_desc *field, const int32_t *d_starts, uint64_t n, uint32_t max_steps,
+                   int32_t *d_cells_or_null, uint32_t *d_lengths, uint32_t *d_status, void *stream);
+/* the field on host buffers, synchronous; allocates its own workspace */
+int vxrt_nav_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent *agent,
+                        const int32_t *goals, uint32_t n_goals, uint32_t max_dist, uint32_t *walkable, uint8_t *next,
+                        uint32_t *dist_or_null, vxrt_nav_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

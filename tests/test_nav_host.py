@@ -1,0 +1,305 @@
+"""CPU checks of navigation fields (include/vxrt.h, vxrt_nav_field / vxrt_nav_paths): the two restatements of
+tests/ref_nav.py against each other and on hand-derived cases, and the kernels' nav code (csrc/vxrt_nav.hpp) compiled for
+the host (tests/tools/nav_check.cpp) against them -- walkable bits, dist, next, summary and paths bit-equal, every index
+checked."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import ref_nav as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+U = R.UNREACHED
+AGENTS = [(1, 2, 1, 3), (2, 3, 0, 1), (1, 1, 2, 8), (3, 2, 1, 2), (8, 32, 8, 32)]
+
+
+def _both(world, origin, dims, agent, goals, max_dist=1 << 24):
+    """both restatements, asserted equal; returns the numpy one"""
+    a = R.nav_field(world, origin, dims, agent, goals, max_dist)
+    if R.have_scipy():
+        b = R.nav_field_scipy(world, origin, dims, agent, goals, max_dist)
+        for k in ("walkable", "dist", "next"):
+            assert np.array_equal(a[k], b[k]), k
+        assert a["summary"] == b["summary"]
+    return a
+
+
+def _random_world(rng, shape, density):
+    w = rng.random(shape) < density
+    w[:, 0, :] = True
+    return w
+
+
+def _some_nodes(r, origin, n, rng):
+    p = np.argwhere(r["walkable"])
+    if len(p) == 0:
+        return []
+    return [tuple(int(v) for v in p[i] + origin) for i in rng.choice(len(p), min(n, len(p)), replace=False)]
+
+
+@pytest.mark.parametrize("agent", AGENTS)
+def test_the_two_restatements_agree_on_random_grids(agent):
+    rng = np.random.default_rng(sum(agent))
+    for density, origin, dims in [(0.1, (0, 0, 0), (24, 16, 24)), (0.25, (3, -2, 1), (21, 17, 19)), (0.05, (-4, 0, -3), (30, 12, 9))]:
+        w = _random_world(rng, (24, 20, 24), density)
+        probe = R.nav_field(w, origin, dims, agent, [])
+        goals = _some_nodes(probe, origin, 3, rng) + [(0, 50, 0)]
+        for md in (1 << 24, 4):
+            r = _both(w, origin, dims, agent, goals, md)
+            assert r["summary"][2] >= 1
+
+
+def _floor(X=12, Y=6, Z=12):
+    w = np.zeros((X, Y, Z), bool)
+    w[:, 0, :] = True
+    return w
+
+
+def test_flat_floor_is_manhattan_distance():
+    w = _floor()
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(4, 1, 7)])
+    x, z = np.meshgrid(np.arange(12), np.arange(12), indexing="ij")
+    assert np.array_equal(r["dist"][:, 1, :], np.abs(x - 4) + np.abs(z - 7))
+    assert (r["dist"][:, 0, :] == U).all() and (r["dist"][:, 2:, :] == U).all()
+    assert r["summary"] == (144, 1, 0, 144, 7 + 7, 15)
+    assert r["next"][4, 1, 7] == 0 and r["next"][0, 1, 7] == 1 and r["next"][11, 1, 7] == 1 + 5  # +x, then -x
+    assert r["next"][4, 1, 0] == 1 + 2 * 5 and r["next"][4, 1, 11] == 1 + 3 * 5                  # +z, then -z
+
+
+def test_one_voxel_step_needs_climb_one():
+    w = _floor()
+    w[6:, 1, :] = True                      # a step up at x = 6
+    goal = [(9, 2, 5)]
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), goal)
+    assert r["dist"][2, 1, 5] == 4 + 3 and r["next"][5, 1, 5] == 2  # +x with dy = +1
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 0, 3), goal)
+    assert r["dist"][2, 1, 5] == U and r["next"][5, 1, 5] == R.NONE
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 0, 3), [(2, 1, 5)])  # down the step is fine without climb
+    assert r["dist"][9, 2, 5] == 3 + 1 + 3 and r["next"][6, 2, 5] == 1 + 4 + 1  # -x, dy = -1 (4 codes per direction)
+
+
+def test_cliff_of_three_dropped_not_climbed():
+    w = _floor()
+    w[6:, 1:4, :] = True                    # a plateau three voxels high at x >= 6
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(2, 1, 5)])
+    assert r["dist"][6, 4, 5] == 4 and r["next"][6, 4, 5] == 1 + 5 + 1 + 3  # -x, dy = -3
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 2), [(2, 1, 5)])
+    assert r["dist"][6, 4, 5] == U
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(8, 4, 5)])
+    assert (r["dist"][:6, 1, :] == U).all() and r["dist"][7, 4, 5] == 1
+
+
+def test_low_ceiling_stops_a_tall_agent():
+    w = _floor(12, 8, 5)
+    w[4:8, 3, :] = True                     # a ceiling at y = 3 over x 4 .. 7: two cells of headroom
+    for h, reach in [(2, True), (3, False)]:
+        r = _both(w, (0, 0, 0), (12, 8, 5), (1, h, 1, 3), [(0, 1, 2)])
+        assert (r["dist"][11, 1, 2] != U) == reach
+
+
+def test_one_wide_gap_stops_a_wide_agent():
+    w = np.zeros((12, 8, 13), bool)
+    w[:, 0, :] = True
+    w[:, 1:5, 6] = True
+    w[5, 1:5, 6] = False                    # a 1-wide doorway in a wall at z = 6
+    for width, reach in [(1, True), (2, False)]:
+        r = _both(w, (0, 0, 0), (12, 8, 13), (width, 2, 1, 3), [(2, 1, 1)])
+        assert (r["dist"][2, 1, 10] != U) == reach
+
+
+def test_max_dist_cut():
+    w = _floor()
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(0, 1, 0)], max_dist=5)
+    d = r["dist"][:, 1, :]
+    x, z = np.meshgrid(np.arange(12), np.arange(12), indexing="ij")
+    m = x + z
+    assert np.array_equal(d, np.where(m <= 5, m, U).astype(np.uint32))
+    assert (r["next"][:, 1, :][m > 5] == R.NONE).all() and r["summary"][4:] == (5, 6)
+
+
+def test_goal_in_the_air_is_ignored():
+    w = _floor()
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(3, 3, 3), (3, 1, 3), (50, 1, 3)])
+    assert r["summary"][1:3] == (1, 2)
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(3, 3, 3)])
+    assert r["summary"] == (144, 0, 1, 0, 0, 0) and (r["next"] == R.NONE).all()
+
+
+def test_box_partly_outside_the_world():
+    w = _floor(16, 8, 16)
+    r = _both(w, (-5, -3, 10), (12, 8, 12), (1, 2, 1, 3), [(0, 1, 12)])
+    assert r["summary"][0] == 7 * 6 and r["summary"][3] == 42  # world x 0 .. 6, z 10 .. 15 at y = 1
+    assert r["dist"][5 + 4, 3 + 1, 5] == 4 + 3
+
+
+def test_rising_move_blocked_above_the_start():
+    w = _floor()
+    w[6:, 1, :] = True                      # a step up at x = 6
+    w[5, 3, :] = True                       # a voxel over the cell before the step: no room to rise there
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 2, 1, 3), [(9, 2, 5)])
+    assert r["walkable"][5, 1, 5] and r["dist"][5, 1, 5] == U  # under the voxel the agent (height 2) fits, cannot rise
+    r = _both(w, (0, 0, 0), (12, 6, 12), (1, 1, 1, 3), [(9, 2, 5)])
+    assert r["dist"][5, 1, 5] == 4          # height 1: rising needs (5, 2) alone, which is empty
+    w2 = _floor()
+    w2[6:, 1, :] = True
+    w2[5, 2, :] = True                      # directly above the start: a height-1 agent fits under it, cannot rise
+    r = _both(w2, (0, 0, 0), (12, 6, 12), (1, 1, 1, 3), [(9, 2, 5)])
+    assert r["walkable"][5, 1, 5] and r["dist"][5, 1, 5] == U
+
+
+def test_paths_decode():
+    w = _floor()
+    w[6:, 1:4, :] = True
+    agent = (1, 2, 1, 3)
+    r = _both(w, (0, 0, 0), (12, 6, 12), agent, [(2, 1, 5)])
+    cells, lengths, status = R.decode_paths(r["next"], (0, 0, 0), agent, [(8, 4, 5), (2, 1, 5), (0, 3, 0), (40, 1, 1), (0, 1, 0)], 6)
+    assert status.tolist() == [R.AT_GOAL, R.AT_GOAL, R.NO_PATH, R.OUTSIDE, R.TRUNCATED]
+    assert lengths.tolist() == [6, 0, 0, 0, 6]
+    assert cells[0, -1].tolist() == [2, 1, 5] and cells[0, 2].tolist() == [6, 4, 5] and cells[0, 3].tolist() == [5, 1, 5]
+
+
+# ---- the kernels' nav code on the host ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("nav") / "nav_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "tools", "hoststub"),
+                           "-I" + os.path.join(ROOT, "oracle"), "-o", exe, os.path.join(ROOT, "tests", "tools", "nav_check.cpp"),
+                           "-x", "c", os.path.join(ROOT, "oracle", "vxo_trace.c"), os.path.join(ROOT, "oracle", "vxo_world.c"),
+                           os.path.join(ROOT, "oracle", "vxo_render.c"), "-lm", "-lpthread", "-w"])
+    return exe
+
+
+def _run_harness(harness, tmp_path, world, factor, origin, dims, agent, goals, max_dist, starts, max_steps):
+    from oracle import vxo
+    X, Y, Z = world.shape
+    goals = np.asarray(goals, np.int32).reshape(-1, 3)
+    starts = np.asarray(starts, np.int32).reshape(-1, 3)
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(inp, "wb") as f:
+        f.write(np.asarray([factor, X, Y, Z, *origin, *dims, *agent, max_dist, len(goals), len(starts), max_steps], np.int32).tobytes())
+        f.write(goals.tobytes())
+        f.write(starts.tobytes())
+        f.write(vxo.dense_from_voxels(world).tobytes())
+    out = subprocess.run([harness, str(inp), str(outp)], capture_output=True, text=True)
+    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
+    raw = np.fromfile(outp, np.uint8)
+    n = dims[0] * dims[1] * dims[2]
+    nb = (dims[0] + 31) // 32 * dims[1] * dims[2]
+    u32 = lambda a, k: np.frombuffer(raw[a:a + 4 * k].tobytes(), np.uint32)
+    grid = lambda a: a.reshape(dims[2], dims[1], dims[0]).transpose(2, 1, 0)
+    p = 0
+    summary = tuple(int(v) for v in u32(p, 8)); p += 32
+    walk = u32(p, nb); p += 4 * nb
+    dist = grid(u32(p, n)); p += 4 * n
+    nxt = grid(raw[p:p + n]); p += n
+    nc = len(starts) * (max_steps + 1) * 3
+    cells = u32(p, nc).view(np.int32).reshape(len(starts), max_steps + 1, 3); p += 4 * nc
+    lengths = u32(p, len(starts)); p += 4 * len(starts)
+    status = u32(p, len(starts))
+    return summary, walk, dist, nxt, cells, lengths, status
+
+
+def _assert_harness(harness, tmp_path, world, factor, origin, dims, agent, goals, max_dist=1 << 24, max_steps=40, nstarts=64):
+    import voxelengine_amd as vx
+    want = R.nav_field_scipy(world, origin, dims, agent, goals, max_dist) if R.have_scipy() else \
+        R.nav_field(world, origin, dims, agent, goals, max_dist)
+    rng = np.random.default_rng(len(goals) + dims[0])
+    starts = np.stack([rng.integers(origin[k] - 2, origin[k] + dims[k] + 2, nstarts) for k in range(3)], 1)
+    nodes = np.argwhere(want["walkable"])
+    if len(nodes):
+        starts[: nstarts // 2] = nodes[rng.integers(0, len(nodes), nstarts // 2)] + np.asarray(origin)
+    s, walk, dist, nxt, cells, lengths, status = _run_harness(harness, tmp_path, world, factor, origin, dims, agent, goals,
+                                                              max_dist, starts, max_steps)
+    assert s[:6] == want["summary"]
+    tiles = (dims[0] + 31) // 32 * ((dims[1] + 15) // 16) * ((dims[2] + 15) // 16)
+    assert s[6] == tiles and (s[7] >= s[5] if s[1] else s[7] == 0)
+    assert np.array_equal(walk, vx.pack_region(want["walkable"]))
+    assert np.array_equal(dist, want["dist"]) and np.array_equal(nxt, want["next"])
+    c, l, st = R.decode_paths(want["next"], origin, agent, starts, max_steps)
+    assert np.array_equal(cells, c) and np.array_equal(lengths, l) and np.array_equal(status, st)
+    return want, s
+
+
+def test_host_code_on_the_hand_derived_cases(harness, tmp_path):
+    world = np.zeros((64, 64, 64), bool)  # the oracle's brickmap: dims multiples of 8 bricks
+    world[:, 0, :] = True
+    world[30:, 1:4, :] = True          # a cliff of 3
+    world[40:, 4, :] = True            # a step on the plateau
+    world[10:20, 3, 10:20] = True      # a low ceiling
+    world[:, 1:6, 50] = True
+    world[33, 1:6, 50] = False         # a 1-wide door
+    for origin, dims, agent, goals, md in [((0, 0, 0), (64, 16, 64), (1, 2, 1, 3), [(5, 1, 5)], 1 << 24),
+                                           ((0, 0, 0), (64, 16, 64), (2, 3, 1, 2), [(50, 5, 10), (5, 1, 60)], 1 << 24),
+                                           ((-7, -3, 20), (50, 20, 40), (1, 1, 2, 8), [(0, 1, 30)], 17),
+                                           ((0, 0, 0), (64, 16, 64), (1, 2, 1, 3), [(5, 9, 5)], 1 << 24)]:
+        _assert_harness(harness, tmp_path, world, 8, origin, dims, agent, goals, md)
+
+
+@pytest.mark.parametrize("factor,shape,density", [(8, (64, 64, 64), 0.08), (16, (128, 128, 128), 0.2), (32, (256, 256, 256), 0.03)])
+def test_host_code_equals_the_reference_on_random_worlds(harness, tmp_path, factor, shape, density):
+    """boxes with dims not multiples of 32 or 16, partly outside the world, several agents, a max_dist cut"""
+    rng = np.random.default_rng(factor + shape[0])
+    world = _random_world(rng, shape, density)
+    boxes = [((0, 0, 0), (shape[0], 24, shape[2])), ((5, 1, 7), (45, 33, 17)), ((-20, -10, -30), (61, 50, 70)),
+             ((1, 0, 2), (1, 40, 33)), ((7, 2, 3), (70, 1, 1))]
+    for i, (origin, dims) in enumerate(boxes):
+        dims = tuple(min(d, 96) for d in dims)
+        agent = AGENTS[i % len(AGENTS)]
+        probe = R.nav_field(world, origin, dims, agent, [])
+        goals = _some_nodes(probe, origin, 1 + 2 * i, rng) + [(origin[0], origin[1] + dims[1] + 3, origin[2])]
+        _assert_harness(harness, tmp_path, world, factor, origin, dims, agent, goals, 1 << 24 if i % 2 == 0 else 6)
+
+
+def test_host_code_work_follows_the_frontier(harness, tmp_path):
+    snake = R.snake_world(256, 128)
+    world = np.zeros((256, 64, 128), bool)
+    world[:, :snake.shape[1]] = snake
+    want, s = _assert_harness(harness, tmp_path, world, 8, (0, 0, 0), snake.shape, (1, 2, 1, 3), [(0, 1, 0)], max_steps=300,
+                              nstarts=8)
+    assert want["summary"][5] > 1000 and s[7] <= s[5] * s[6] / 16
+
+
+def test_nav_symbols_exported_and_workspace_bytes():
+    import voxelengine_amd as vx
+    lib = vx.load()
+    for name in ("vxrt_nav_workspace_bytes", "vxrt_nav_field", "vxrt_nav_paths", "vxrt_nav_field_host"):
+        assert name in vx.EXPORTS and hasattr(lib, name)
+
+    def ws(d, a=(1, 2, 1, 3)):
+        return int(lib.vxrt_nav_workspace_bytes((C.c_int32 * 3)(*d), (C.c_int32 * 4)(*a)))
+    for bad in [(0, 8, 8), (8, -1, 8), (1 << 10, 1 << 10, (1 << 8) + 1), (1 << 29, 1, 1)]:
+        assert ws(bad) == 0
+    for bad in [(0, 2, 1, 3), (9, 2, 1, 3), (1, 0, 1, 3), (1, 33, 1, 3), (1, 2, -1, 3), (1, 2, 9, 3), (1, 2, 1, -1), (1, 2, 1, 33)]:
+        assert ws((8, 8, 8), bad) == 0
+    assert lib.vxrt_nav_workspace_bytes(None, (C.c_int32 * 4)(1, 2, 1, 3)) == 0
+    assert lib.vxrt_nav_workspace_bytes((C.c_int32 * 3)(8, 8, 8), None) == 0
+
+    def expect(d, a):  # the formula of include/vxrt.h
+        r = lambda n: (n + 63) // 64 * 64
+        W, H = a[0], a[1]
+        wb, wh = (d[0] + 31) // 32, (d[0] + W - 1 + 31) // 32
+        hy, hz = d[1] + H, d[2] + W - 1
+        nb, n = wb * d[1] * d[2], d[0] * d[1] * d[2]
+        T = wb * ((d[1] + 15) // 16) * ((d[2] + 15) // 16)
+        return 4 * (r(wh * hy * hz) + r(wb * hy * hz) + 2 * r(wb * d[1] * hz) + 4 * r(nb) + r(n) + r(6 * T) + 64)
+    for d in [(1, 1, 1), (33, 7, 5), (256, 64, 256), (1024, 128, 1024), (1, 1 << 14, 1 << 14), (1 << 10, 1 << 10, 1 << 8)]:
+        for a in AGENTS:
+            assert ws(d, a) == expect(d, a), (d, a)
+            if d[0] >= 32 and d[1] >= 32:
+                assert ws(d, a) <= 5.5 * d[0] * d[1] * d[2]
+    o3, d3, a4 = (C.c_int32 * 3)(0, 0, 0), (C.c_int32 * 3)(8, 8, 8), (C.c_int32 * 4)(1, 2, 1, 3)
+    assert lib.vxrt_nav_field(None, o3, d3, a4, None, 0, 10, None, None, None, None, None, None) == -1
+    assert lib.vxrt_nav_field_host(None, o3, d3, a4, None, 0, 10, None, None, None, None) == -1
+    assert lib.vxrt_nav_paths(None, None, None, 0, 0, None, None, None, None) == -1
+    assert vx.NavAgent() == (1, 2, 1, 3) and vx.NAV_NONE == 0xFF and vx.NAV_MAX_GOALS == 4096
+    # every code of every agent decodes to its move, and the last code is at most 164
+    for a in AGENTS:
+        ag = vx.NavAgent(*a)
+        for code, dx, dy, dz in R.moves(a):
+            assert vx.nav_move(code, ag) == (dx, dy, dz)
+        assert R.moves(a)[-1][0] == 4 * (1 + a[2] + a[3]) <= 164
+        with pytest.raises(ValueError):
+            vx.nav_move(4 * (1 + a[2] + a[3]) + 1, ag)

@@ -280,6 +280,67 @@ int VoxelRaytracer3D::FindIslands(const int32_t origin[3], const int32_t dims[3]
     return rc;
 }
 
+int VoxelRaytracer3D::NavField(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent, const int32_t* goals,
+                               uint32_t n_goals, uint32_t max_dist, std::vector<uint32_t>& walkable, std::vector<uint8_t>& next,
+                               vxrt_nav_summary& summary, std::vector<uint32_t>* dist)
+{
+    Flush();
+    const uint64_t words = vxrt_region_words(dims);
+    if (words == 0 || vxrt_nav_workspace_bytes(dims, &agent) == 0)
+        return VXRT_ERR_INVALID;
+    const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+    walkable.assign((size_t)words, 0u);
+    next.assign(n, 0u);
+    if (dist)
+        dist->assign(n, 0u);
+    return vxrt_nav_field_host(ctx, origin, dims, &agent, goals, n_goals, max_dist, walkable.data(), next.data(),
+                               dist ? dist->data() : nullptr, &summary);
+}
+
+int VoxelRaytracer3D::NavPaths(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent,
+                               const std::vector<uint8_t>& next, const int32_t* starts, size_t n, uint32_t max_steps,
+                               std::vector<uint32_t>& lengths, std::vector<uint32_t>& status, std::vector<int32_t>* cells)
+{
+    if (vxrt_nav_workspace_bytes(dims, &agent) == 0 || next.size() != (size_t)dims[0] * dims[1] * dims[2] ||
+        max_steps > VXRT_NAV_MAX_STEPS || (n && !starts))
+        return VXRT_ERR_INVALID;
+    lengths.assign(n, 0u);
+    status.assign(n, 0u);
+    const size_t per = 3u * ((size_t)max_steps + 1u);
+    if (cells)
+        cells->assign(n * per, 0);
+    if (n == 0)
+        return VXRT_OK;
+    const size_t nb = (next.size() + 255u) & ~(size_t)255u, sb = (n * 12u + 255u) & ~(size_t)255u;
+    const size_t cb = cells ? (n * per * 4u + 255u) & ~(size_t)255u : 0;
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, nb + sb + cb + 8u * n) != hipSuccess)
+        return VXRT_ERR_NOMEM;
+    int rc = VXRT_ERR_HIP;
+    vxrt_nav_field_desc f{};
+    for (int k = 0; k < 3; ++k) {
+        f.origin[k] = origin[k];
+        f.dims[k] = dims[k];
+    }
+    f.agent = agent;
+    f.d_next = (const uint8_t*)d;
+    int32_t* d_starts = (int32_t*)(d + nb);
+    int32_t* d_cells = cells ? (int32_t*)(d + nb + sb) : nullptr;
+    uint32_t* d_len = (uint32_t*)(d + nb + sb + cb);
+    uint32_t* d_st = d_len + n;
+    if (hipMemcpy(d, next.data(), next.size(), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(d_starts, starts, n * 12u, hipMemcpyHostToDevice) == hipSuccess) {
+        rc = vxrt_nav_paths(ctx, &f, d_starts, n, max_steps, d_cells, d_len, d_st, nullptr);
+        if (rc == VXRT_OK &&
+            (hipMemcpy(lengths.data(), d_len, n * 4u, hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(status.data(), d_st, n * 4u, hipMemcpyDeviceToHost) != hipSuccess ||
+             (cells && hipMemcpy(cells->data(), d_cells, n * per * 4u, hipMemcpyDeviceToHost) != hipSuccess)))
+            rc = VXRT_ERR_HIP;
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
 int VoxelRaytracer3D::StampVoxels(const int32_t origin[3], const int32_t dims[3], const uint32_t* bits, int mode,
                                   vxrt_edit_stats* stats)
 {

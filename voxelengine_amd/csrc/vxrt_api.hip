@@ -5,6 +5,7 @@
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
 #include "vxrt_islands.hpp"
+#include "vxrt_nav.hpp"
 #include "vxrt_region.hpp"
 
 #include <algorithm>
@@ -53,6 +54,11 @@ hipError_t overlap_boxes(const uint2* meta, const uint32_t* pool, int f, const i
 hipError_t find_islands(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
                         uint32_t anchors, void* work, uint32_t* floating, uint32_t* labels, vxrt_island* table,
                         uint32_t max_islands, vxrt_island_summary* summary, hipStream_t stream);
+// navigation fields (vxrt_nav.hip)
+hipError_t nav_field(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
+                     const vxrt_nav_agent& ag, const int32_t* goals, uint32_t ngoals, uint32_t max_dist, void* work,
+                     uint32_t* walkable, uint8_t* next, uint32_t* dist, vxrt_nav_summary* summary, hipStream_t stream);
+hipError_t nav_paths(const NavPathArgs& P, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -2113,6 +2119,126 @@ int vxrt_find_islands_host(vxrt_ctx* c, const int32_t origin[3], const int32_t d
             VX_HIP(hipMemcpy(islands_or_null, d_tab, rows * sizeof(vxrt_island), hipMemcpyDeviceToHost));
     }
     VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- navigation fields -----------------------------------------------------------------------------------------------
+uint64_t vxrt_nav_workspace_bytes(const int32_t dims[3], const vxrt_nav_agent* agent)
+{
+    vxrt::NavLayout L;
+    return dims && agent && vxrt::nav_layout(dims, agent->width, agent->height, agent->climb, agent->drop, L) ? L.total_bytes : 0;
+}
+
+// the checks both field calls make after their NULL checks, in the order of include/vxrt.h
+static int nav_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent* ag, uint32_t n_goals,
+                     uint32_t max_dist)
+{
+    vxrt::NavLayout L;
+    if (!vxrt::nav_agent_ok(ag->width, ag->height, ag->climb, ag->drop))
+        return fail(VXRT_ERR_INVALID, "nav agent: 1 <= width <= 8, 1 <= height <= 32, 0 <= climb <= 8, 0 <= drop <= 32");
+    if (!vxrt::nav_layout(dims, ag->width, ag->height, ag->climb, ag->drop, L))
+        return fail(VXRT_ERR_INVALID, "nav box dims: each at least 1, at most 2^28 cells");
+    for (int k = 0; k < 3; ++k)
+        if ((int64_t)origin[k] + dims[k] > INT32_MAX)
+            return fail(VXRT_ERR_INVALID, "nav box: origin + dims beyond 2^31 - 1");
+    if (max_dist < 1 || max_dist > vxrt::kNavMaxDist)
+        return fail(VXRT_ERR_INVALID, "nav max_dist: 1 .. 2^24");
+    if (n_goals > vxrt::kNavMaxGoals)
+        return fail(VXRT_ERR_INVALID, "nav goals: at most VXRT_NAV_MAX_GOALS");
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not queried");
+    return VXRT_OK;
+}
+
+int vxrt_nav_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent* agent,
+                   const int32_t* d_goals, uint32_t n_goals, uint32_t max_dist, void* d_work, uint32_t* d_walkable,
+                   uint8_t* d_next, uint32_t* d_dist_or_null, vxrt_nav_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !agent || !d_work || !d_walkable || !d_next || !d_summary || (!d_goals && n_goals))
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = nav_ready(c, origin, dims, agent, n_goals, max_dist))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::nav_field(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, *agent, d_goals, n_goals, max_dist, d_work,
+                           d_walkable, d_next, d_dist_or_null, d_summary, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_nav_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent* agent,
+                        const int32_t* goals, uint32_t n_goals, uint32_t max_dist, uint32_t* walkable, uint8_t* next,
+                        uint32_t* dist_or_null, vxrt_nav_summary* summary)
+{
+    if (!c || !origin || !dims || !agent || !walkable || !next || !summary || (!goals && n_goals))
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = nav_ready(c, origin, dims, agent, n_goals, max_dist))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::NavLayout L;
+    vxrt::nav_layout(dims, agent->width, agent->height, agent->climb, agent->drop, L);
+    const size_t wb = (size_t)L.nb * 4u, nb = L.nvox, db = dist_or_null ? (size_t)L.nvox * 4u : 0, gb = (size_t)n_goals * 12u;
+    auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
+    CollideTemp T;
+    hipError_t e = hipMalloc(&T.p, up(L.total_bytes) + up(wb) + up(nb) + up(db) + up(gb) + sizeof(vxrt_nav_summary));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VXRT_ERR_NOMEM, std::string("nav_field_host: ") + hipGetErrorString(e));
+    }
+    char* base = (char*)T.p;
+    char* d_walk = base + up(L.total_bytes);
+    char* d_next = d_walk + up(wb);
+    char* d_dist = d_next + up(nb);
+    char* d_goals = d_dist + up(db);
+    char* d_sum = d_goals + up(gb);
+    if (n_goals)
+        VX_HIP(hipMemcpy(d_goals, goals, gb, hipMemcpyHostToDevice));
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    VX_HIP(vxrt::nav_field(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, *agent, (const int32_t*)d_goals, n_goals, max_dist,
+                           base, (uint32_t*)d_walk, (uint8_t*)d_next, dist_or_null ? (uint32_t*)d_dist : nullptr,
+                           (vxrt_nav_summary*)d_sum, nullptr));
+    VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_nav_summary), hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(walkable, d_walk, wb, hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(next, d_next, nb, hipMemcpyDeviceToHost));
+    if (dist_or_null)
+        VX_HIP(hipMemcpy(dist_or_null, d_dist, db, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+int vxrt_nav_paths(vxrt_ctx* c, const vxrt_nav_field_desc* field, const int32_t* d_starts, uint64_t n, uint32_t max_steps,
+                   int32_t* d_cells_or_null, uint32_t* d_lengths, uint32_t* d_status, void* stream)
+{
+    if (!c || !field || !field->d_next || !d_starts || !d_lengths || !d_status)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    vxrt::NavLayout L;
+    const vxrt_nav_agent& ag = field->agent;
+    if (!vxrt::nav_layout(field->dims, ag.width, ag.height, ag.climb, ag.drop, L))
+        return fail(VXRT_ERR_INVALID, "nav field: bad dims or agent");
+    for (int k = 0; k < 3; ++k)
+        if ((int64_t)field->origin[k] + field->dims[k] > INT32_MAX)
+            return fail(VXRT_ERR_INVALID, "nav field: origin + dims beyond 2^31 - 1");
+    if (max_steps > vxrt::kNavMaxSteps)
+        return fail(VXRT_ERR_INVALID, "nav paths: max_steps above 65535");
+    if (n == 0)
+        return VXRT_OK;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::NavPathArgs P{};
+    P.next = field->d_next;
+    P.starts = d_starts;
+    P.cells = d_cells_or_null;
+    P.lengths = d_lengths;
+    P.status = d_status;
+    P.n = n;
+    P.max_steps = max_steps;
+    for (int k = 0; k < 3; ++k) {
+        P.o[k] = field->origin[k];
+        P.d[k] = field->dims[k];
+    }
+    P.climb = ag.climb;
+    P.drop = ag.drop;
+    VX_HIP(vxrt::nav_paths(P, (hipStream_t)stream));
     return VXRT_OK;
 }
 

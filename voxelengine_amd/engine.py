@@ -317,6 +317,58 @@ class Context:
         st = self.edit_stamps([Stamp(isl.origin, isl.floating, N.STAMP_SUBTRACT, isl.dims)])
         return isl, st
 
+    # ---- navigation fields (extension, include/vxrt.h) ----------------------------------------------------------------
+    def nav_field(self, origin, dims, goals, agent: "NavAgent | None" = None, max_dist: int = 1 << 24, dist: bool = True,
+                  stream: int | None = None) -> "NavField":
+        """The navigation field of the box ``origin`` .. ``origin + dims - 1`` for ``agent`` (default NavAgent()) toward the
+        world cells ``goals`` (an (n, 3) array, n <= NAV_MAX_GOALS): include/vxrt.h, vxrt_nav_field.  Runs on ``stream``
+        (default: torch's current stream) after the work queued there and returns when the field is complete.  Returns a
+        NavField of device tensors (walkable region words, one next code per cell, dist when ``dist``) and the summary.
+
+        A body steered with move_boxes can follow ``NavField.paths``: each move is one cell, ``nav_move(code, agent)``."""
+        import torch
+        agent = agent or NavAgent()
+        dims = tuple(int(v) for v in dims)
+        g = np.ascontiguousarray(np.asarray(goals, np.int32).reshape(-1, 3))
+        ag = agent._c()
+        ws = int(self._L.vxrt_nav_workspace_bytes(_i3(dims), C.byref(ag)))
+        dev = "cuda:%d" % self.device
+        nvox = dims[0] * dims[1] * dims[2] if ws else 0
+        work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
+        walk = torch.empty(max(region_words(dims) if ws else 0, 1), dtype=torch.int32, device=dev)
+        nxt = torch.empty(max(nvox, 1), dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(nvox, 1), dtype=torch.int32, device=dev) if dist else None
+        summary = torch.zeros(8, dtype=torch.int32, device=dev)
+        dg = torch.from_numpy(g).to(dev) if len(g) else None
+        s = _stream(stream)
+        if dg is not None:  # the goals' copy is on torch's current stream: order it before the call's stream
+            torch.cuda.current_stream(dev).synchronize()
+        N.check(self._L.vxrt_nav_field(self._h, _i3(origin), _i3(dims), C.byref(ag), _ptr(dg), len(g), int(max_dist),
+                                       _ptr(work), _ptr(walk), _ptr(nxt), _ptr(dst), _ptr(summary), s))
+        return NavField(origin=tuple(int(v) for v in origin), dims=dims, agent=agent, walkable=walk[: region_words(dims)],
+                        next=nxt[:nvox], dist=dst[:nvox] if dist else None,
+                        summary=NavSummary(*(int(v) for v in summary.cpu().numpy().view(np.uint32))), ctx=self)
+
+    def nav_field_host(self, origin, dims, goals, agent: "NavAgent | None" = None, max_dist: int = 1 << 24) -> "NavField":
+        """nav_field through the synchronous host call (vxrt_nav_field_host): numpy outputs -- walkable as a bool [x, y, z]
+        grid, next as uint8 [x, y, z], dist as uint32 [x, y, z]."""
+        agent = agent or NavAgent()
+        dims = tuple(int(v) for v in dims)
+        g = np.ascontiguousarray(np.asarray(goals, np.int32).reshape(-1, 3))
+        ag = agent._c()
+        n = region_words(dims)
+        nvox = dims[0] * dims[1] * dims[2] if n else 0
+        walk = np.zeros(max(n, 1), np.uint32)
+        nxt = np.zeros(max(nvox, 1), np.uint8)
+        dst = np.zeros(max(nvox, 1), np.uint32)
+        summary = np.zeros(8, np.uint32)
+        N.check(self._L.vxrt_nav_field_host(self._h, _i3(origin), _i3(dims), C.byref(ag), g.ctypes.data if len(g) else None,
+                                            len(g), int(max_dist), walk.ctypes.data, nxt.ctypes.data, dst.ctypes.data,
+                                            summary.ctypes.data))
+        grid = lambda a: a[:nvox].reshape(dims[::-1]).transpose(2, 1, 0)
+        return NavField(origin=tuple(int(v) for v in origin), dims=dims, agent=agent, walkable=unpack_region(walk, dims),
+                        next=grid(nxt), dist=grid(dst), summary=NavSummary(*(int(v) for v in summary)), ctx=self)
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -549,6 +601,90 @@ class Islands:
         """One Body per table row -- the island's box, displaced by ``delta`` -- for move_boxes (falling debris).  A box
         wider than BODY_MAX_EXTENT on some axis is an invalid body there: move_boxes returns it unchanged with BODY_INVALID."""
         return [Body(tuple(float(v) for v in r["lo"]), tuple(float(v) for v in r["hi"]), tuple(delta)) for r in self.table]
+
+
+class NavAgent(NamedTuple):
+    """vxrt_nav_agent: a width x height x width box of cells standing on its minimum corner, that steps up at most
+    ``climb`` cells and down at most ``drop``"""
+    width: int = 1
+    height: int = 2
+    climb: int = 1
+    drop: int = 3
+
+    def _c(self):
+        return (C.c_int32 * 4)(int(self.width), int(self.height), int(self.climb), int(self.drop))
+
+
+class NavSummary(NamedTuple):
+    """vxrt_nav_summary"""
+    nodes: int
+    goals_used: int
+    goals_ignored: int
+    reached: int
+    max_dist_found: int
+    levels: int
+    tiles_total: int
+    tile_visits: int
+
+
+class NavPaths(NamedTuple):
+    """The result of NavField.paths: ``cells`` (n, max_steps + 1, 3) int32 or None, ``lengths`` and ``status`` (NAV_AT_GOAL,
+    NAV_NO_PATH, NAV_TRUNCATED, NAV_OUTSIDE) per start, as device tensors"""
+    cells: object
+    lengths: object
+    status: object
+
+
+def nav_move(code: int, agent: NavAgent) -> tuple:
+    """(dx, dy, dz) of a next code of a field for ``agent`` (include/vxrt.h: 1 + direction * (1 + climb + drop) + dy index,
+    directions +x, -x, +z, -z, dy in the order 0, 1 .. climb, -1 .. -drop)"""
+    per = 1 + agent.climb + agent.drop
+    if not 1 <= code <= 4 * per:
+        raise ValueError("not a move code: %d" % code)
+    k, i = divmod(code - 1, per)
+    dy = 0 if i == 0 else (i if i <= agent.climb else -(i - agent.climb))
+    return ((1, 0, 0), (-1, 0, 0), (0, 0, 1), (0, 0, -1))[k][0], dy, ((1, 0, 0), (-1, 0, 0), (0, 0, 1), (0, 0, -1))[k][2]
+
+
+@dataclass
+class NavField:
+    """The result of Context.nav_field: ``walkable`` the node bits (region words on the device; a bool grid from
+    nav_field_host), ``next`` one code per cell in region order (uint8), ``dist`` one uint32 per cell (0xFFFFFFFF
+    unreachable) or None, ``summary`` a NavSummary."""
+    origin: tuple
+    dims: tuple
+    agent: NavAgent
+    walkable: object
+    next: object
+    dist: object
+    summary: NavSummary
+    ctx: object = field(default=None, repr=False)
+
+    def paths(self, starts, max_steps: int, cells: bool = True, stream: int | None = None) -> NavPaths:
+        """Follow the next codes from each world cell of ``starts`` ((n, 3)) for at most ``max_steps`` moves
+        (vxrt_nav_paths; asynchronous on ``stream``, default torch's current stream).  Needs the device field of
+        Context.nav_field."""
+        import torch
+        if not hasattr(self.next, "data_ptr"):
+            raise ValueError("paths needs the device field of Context.nav_field")
+        dev = self.next.device
+        st = np.ascontiguousarray(np.asarray(starts, np.int32).reshape(-1, 3))
+        n = st.shape[0]
+        st = torch.as_tensor(st if n else np.zeros((1, 3), np.int32)).to(dev)  # never NULL: n == 0 is the call's no-op
+        out = torch.empty((max(n, 1), int(max_steps) + 1, 3), dtype=torch.int32, device=dev) if cells else None
+        lengths = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        a = self.agent
+
+        class _Desc(C.Structure):
+            _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("agent", C.c_int32 * 4), ("d_next", C.c_void_p)]
+        desc = _Desc(_i3(self.origin), _i3(self.dims), a._c(), self.next.data_ptr())
+        s = _stream(stream)
+        if n:
+            torch.cuda.current_stream(dev).synchronize()  # the starts' copy, ordered before the call's stream
+        N.check(self.ctx._L.vxrt_nav_paths(self.ctx._h, C.byref(desc), _ptr(st), n, int(max_steps),
+                                           _ptr(out), _ptr(lengths), _ptr(status), s))
+        return NavPaths(out[:n] if cells else None, lengths[:n], status[:n])
 
 
 def _bodies_np(bodies) -> np.ndarray:
