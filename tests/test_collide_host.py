@@ -2,16 +2,13 @@
 tests/ref_collide.py against each other and on hand-derived cases, and the kernels' per-body code (csrc/vxrt_collide.hpp)
 compiled for the host (tests/tools/collide_check.cpp) against them, bit for bit, with every table index it forms checked."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import ref_collide as R
-from tests.helpers import float_bits
+from tests.helpers import build_harness, float_bits, run_harness_files
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 YXZ, XYZ = (1, 0, 2), (0, 1, 2)
 
@@ -188,12 +185,7 @@ def test_the_two_restatements_agree_on_random_cases(seed):
 # ---- the kernels' per-body code on the host --------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("collide") / "collide_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "tools", "hoststub"),
-                           "-I" + os.path.join(ROOT, "oracle"), "-o", exe, os.path.join(ROOT, "tests", "tools", "collide_check.cpp"),
-                           "-x", "c", os.path.join(ROOT, "oracle", "vxo_trace.c"), os.path.join(ROOT, "oracle", "vxo_world.c"),
-                           os.path.join(ROOT, "oracle", "vxo_render.c"), "-lm", "-lpthread", "-w"])
-    return exe
+    return build_harness(tmp_path_factory, "collide_check")
 
 
 def _run_harness(harness, tmp_path, vox, bodies, factor, order):
@@ -201,17 +193,11 @@ def _run_harness(harness, tmp_path, vox, bodies, factor, order):
     X, Y, Z = vox.shape
     b = np.ascontiguousarray(bodies, F)
     n = len(b)
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.asarray([factor, X, Y, Z, n, *order], np.int32).tobytes())
-        f.write(vxo.dense_from_voxels(vox).tobytes())
-        f.write(b.tobytes())
-    out = subprocess.run([harness, str(inp), str(outp)], capture_output=True, text=True)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
-    raw = np.fromfile(outp, np.uint32)
+    raw, stdout = run_harness_files(harness, tmp_path, [factor, X, Y, Z, n, *order], vxo.dense_from_voxels(vox), b)
+    raw = raw.view(np.uint32)
     lohi = raw[: 6 * n].view(F).reshape(n, 6)
     mf, cnt, of = raw[6 * n: 7 * n], raw[7 * n: 8 * n], raw[8 * n: 9 * n]
-    return lohi, mf, cnt, of, out.stdout
+    return lohi, mf, cnt, of, stdout
 
 
 def test_host_code_on_the_hand_derived_cases(harness, tmp_path):

@@ -2,13 +2,12 @@
 (C: oracle/vxo_edit.c vxo_apply_edits; numpy: oracle/ref_edit.py apply_edits) on hand-derived cases and against each other,
 the per-brick edit logic and the slot plan of the library (voxelengine_amd/csrc/vxrt_edit.hpp) compiled for the host and
 held against the oracle, and the new ABI symbols."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import build_harness, run_harness
+
 BOX, SPHERE = 0, 1
 
 
@@ -93,29 +92,22 @@ def test_c_and_numpy_restatements_agree(vxo):
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("edit") / "edit_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "tools", "hoststub"),
-                           "-I" + os.path.join(ROOT, "oracle"), "-o", exe, os.path.join(ROOT, "tests", "tools", "edit_check.cpp"),
-                           "-x", "c", os.path.join(ROOT, "oracle", "vxo_trace.c"), os.path.join(ROOT, "oracle", "vxo_world.c"),
-                           os.path.join(ROOT, "oracle", "vxo_render.c"), os.path.join(ROOT, "oracle", "vxo_edit.c"), "-lm", "-lpthread", "-w"])
-    return exe
+    return build_harness(tmp_path_factory, "edit_check", "vxo_edit.c")
 
 
 @pytest.mark.parametrize("factor,edge,rounds", [(8, 64, 12), (16, 128, 4), (32, 256, 2)])
 def test_host_brick_logic_equals_the_oracle(harness, factor, edge, rounds):
     """k_edit_bricks' functions (op filter from the last covering op, membership, extents) brick by brick: images and
     packed extents equal the oracle's rebuilt brickmap of the edited dense grid, for every brick of random worlds."""
-    out = subprocess.run([harness, "bricks", str(factor), str(edge), str(rounds)], capture_output=True, text=True)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
-    changed = int(out.stdout.split(" changed")[0].split()[-1])
+    out = run_harness(harness, "bricks", factor, edge, rounds)
+    changed = int(out.split(" changed")[0].split()[-1])
     assert changed > 0
 
 
 def test_host_slot_plan(harness):
     """Deterministic slot assignment: frees first, the lowest free slot next, growth of the high-water mark only when the
     free list is exhausted; the growth rule (1.5x or what is needed); validation and clipping of ops."""
-    out = subprocess.run([harness, "plan"], capture_output=True, text=True)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
+    run_harness(harness, "plan")
 
 
 def test_edit_symbols_exported():

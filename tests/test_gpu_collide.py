@@ -12,24 +12,11 @@ import pytest
 from oracle import ref_edit, ref_region, vxo_edit
 from tests import helpers
 from tests import ref_collide as R
-from tests.helpers import float_bits
+from tests.helpers import eng, float_bits, gen_dense, upload
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 YXZ, XYZ = (1, 0, 2), (0, 1, 2)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    import voxelengine_amd as vx
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return vx, torch
-
-
-def _upload(ctx, w):
-    ctx.upload_world(w.factor, w.cdims, w.coarse_bits, w.brick_slot, w.bounds, w.pool)
 
 
 def _world(vxo, size, factor, density, seed):
@@ -72,7 +59,7 @@ def test_moves_and_counts_equal_the_reference(eng, vxo, factor, size, density):
     w, vox = _world(vxo, size, factor, density, seed=factor + size[0])
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         b = R.random_bodies(np.random.default_rng(size[0] + factor), size, 100_000)
         for order in (YXZ, XYZ):
             _, wf = _assert_move(vx, torch, ctx, vox, b, order)
@@ -96,7 +83,7 @@ def test_results_follow_edits_and_stamps(eng, vxo):
     w, vox = _world(vxo, (128, 128, 128), 16, 0.02, seed=7)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         b = R.random_bodies(np.random.default_rng(8), vox.shape, 50_000)
         before, _ = _assert_move(vx, torch, ctx, vox, b)
         ops = [(0, 1, (0, 40, 0), (127, 42, 127)), (1, 0, (64, 41, 64), (20, 0, 0)), (0, 0, (10, 0, 10), (30, 127, 30))]
@@ -125,7 +112,7 @@ def test_deterministic_on_repeats_batch_splits_and_the_grid_stride_loop(eng, vxo
     w, vox = _world(vxo, (256, 256, 256), 32, 0.02, seed=3)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         b = R.random_bodies(np.random.default_rng(4), vox.shape, 100_000)
         db = _dev(torch, b)
         bits = lambda r: [t.view(torch.int32) for t in r]  # noqa: E731 (invalid bodies keep their NaNs: compare bits)
@@ -156,7 +143,7 @@ def test_side_stream(eng, vxo):
     w, vox = _world(vxo, (64, 64, 64), 8, 0.05, seed=11)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         b = R.random_bodies(np.random.default_rng(12), vox.shape, 20_000)
         s = torch.cuda.Stream()
         with torch.cuda.stream(s):
@@ -187,7 +174,7 @@ def test_refusals(eng, vxo, tmp_path):
         assert L.vxrt_move_boxes_host(ctx._h, hp, 1, yxz, hp, None) == -3
         assert L.vxrt_overlap_boxes_host(ctx._h, hp, 1, hp, None) == -3
         w, _ = _world(vxo, (64, 64, 64), 8, 0.05, seed=1)
-        _upload(ctx, w)
+        upload(ctx, w)
         for bad in ((0, 0, 1), (1, 2, 3), (-1, 0, 1), (2, 1, 2)):                            # not a permutation
             o = (C.c_int32 * 3)(*bad)
             assert L.vxrt_move_boxes(ctx._h, p, 1, o, p, None, None) == -1
@@ -271,8 +258,7 @@ def test_headless_example_walk(vxo, tmp_path):
     got_flags = [int(ln[12]) for ln in lines]
 
     edge = 256
-    from tests.test_gpu_edit import _gen_dense
-    vox = vxo_edit.voxels_from_dense(_gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
+    vox = vxo_edit.voxels_from_dense(gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
     half = np.float32([2, 6, 2])
     lo = hi = None
     want, want_flags = [], []

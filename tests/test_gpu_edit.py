@@ -2,111 +2,17 @@
 terrain" as to do, README.md:16).  After every edit call the resident tables must be what the oracle's brickmap builder
 makes of the oracle-edited dense grid (coarse bits, extents, brick contents; slot numbers excepted), and frames and batches
 must equal the oracle's on that world, byte for byte."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from oracle import vxo_edit
 from tests import helpers
+from tests.helpers import (FACADE_POSES, assert_batch, assert_frames, assert_tables, eng, gen_dense, new_ctx, oracle_frame,
+                           random_ops, upload)
 
 pytestmark = pytest.mark.gpu
 BOX, SPHERE = 0, 1
 W, H = 64, 48
-INV = float(np.float32(1.0) / np.sqrt(np.float32(3.0)))
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    import voxelengine_amd as vx
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return vx, torch
-
-
-def _ctx(vx):
-    c = vx.Context(0)
-    c.SetEnvironment((INV, INV, INV), (2, 2, 2), (0.5, 0.5, 0.5))
-    c.SetFOV(90.0)
-    return c
-
-
-def _gen_dense(vxo, g, X, Y, Z):
-    L = vxo.lib()
-    p = L.vxo_gen_dense(g, X, Y, Z, 16)
-    n = X * Y * Z // 32
-    out = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n,)).copy()
-    L.free(p)
-    return out
-
-
-def _upload(ctx, w):
-    ctx.upload_world(w.factor, w.cdims, w.coarse_bits, w.brick_slot, w.bounds, w.pool)
-
-
-def _assert_tables(ctx, w):
-    """download_world against an oracle world, cell by cell: coarse bits, bounds, brick bits; slot numbers excluded"""
-    d = ctx.download_world()
-    assert tuple(d["cdims"]) == tuple(w.cdims) and d["factor"] == w.factor
-    assert np.array_equal(d["coarse_bits"], w.coarse_bits)
-    assert np.array_equal(d["bounds"].view(np.uint32), w.bounds.view(np.uint32))
-    occ = w.brick_slot != 0xFFFFFFFF
-    assert np.array_equal(d["brick_slot"] != 0xFFFFFFFF, occ)
-    bw = w.factor ** 3 // 32
-    got = d["pool"].reshape(-1, bw)[d["brick_slot"][occ]]
-    want = w.pool.reshape(-1, bw)[w.brick_slot[occ]]
-    assert np.array_equal(got, want)
-    assert len(set(d["brick_slot"][occ].tolist())) == int(occ.sum())     # no slot shared by two cells
-    return d
-
-
-def _frame(vx, ctx, torch, cam, dims, vxo, mode, variant=4):
-    pos, f, u, r = helpers.camera(cam, dims, vxo)
-    ctx.set_kernel_variant(variant)
-    opts = vx.RenderOptions(shadow=True, bounce_samples=1, frame_number=3, mode=mode)
-    if variant == 4:
-        assert ctx.kernel_for_launch(W, H, opts) == 7
-    fb = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
-    ctx.RenderScreen(W, H, fb, pos, f, u, r, opts)
-    ctx.set_kernel_variant(4)
-    return fb.cpu().numpy()
-
-
-def _oracle_frame(vxo, w, cam, dims, mode):
-    pos, f, u, r = helpers.camera(cam, dims, vxo)
-    p = vxo.make_params(W, H, pos, f, u, r, frame_number=3, shadow=1, bounce_samples=1, mode=mode)
-    return w.render(p, fb=np.zeros((H, W, 4), np.uint8), nthreads=16)["fb"]
-
-
-def _assert_frames(vx, ctx, torch, vxo, w, cams="ABCD", variants=(4, 1)):
-    for cam in cams:
-        for mode in (vx.MODE_SHADED, vx.MODE_DEBUG):
-            want = _oracle_frame(vxo, w, cam, w.dims, mode)
-            for v in variants:
-                assert np.array_equal(_frame(vx, ctx, torch, cam, w.dims, vxo, mode, v), want), (cam, mode, v)
-
-
-def _assert_batch(ctx, w, n=3000, seed=0):
-    o, d = helpers.mixed_rays(w.dims, n, seed)
-    g = ctx.Raytrace(o, d)
-    c = w.trace_batch(o, d, nthreads=16)
-    assert np.array_equal(g["steps"], c["steps"]) and np.array_equal(g["voxel"], c["voxel"])
-    assert np.array_equal(helpers.float_bits(g["hitPoint"]), helpers.float_bits(c["pos"]))
-    assert np.array_equal(helpers.float_bits(g["normal"]), helpers.float_bits(c["normal"]))
-
-
-def _random_ops(rng, dims, n, rmax):
-    ops = []
-    for _ in range(n):
-        if rng.random() < 0.5:
-            lo = [int(rng.integers(-8, d + 8)) for d in dims]
-            ops.append((BOX, int(rng.integers(0, 2)), lo, [l + int(rng.integers(-2, max(d // 3, 3))) for l, d in zip(lo, dims)]))
-        else:
-            c = [int(rng.integers(-10, d + 10)) for d in dims]
-            ops.append((SPHERE, int(rng.integers(0, 2)), c, (int(rng.integers(0, rmax)), 0, 0)))
-    return ops
-
 
 WORLDS = [  # (factor, X, Y, Z, how the world is made)
     (8, 64, 64, 64, "upload"),
@@ -120,23 +26,23 @@ WORLDS = [  # (factor, X, Y, Z, how the world is made)
 def test_random_edit_sequences_equal_the_oracle(eng, vxo, factor, X, Y, Z, how):
     vx, torch = eng
     rng = np.random.default_rng(factor * 7 + X)
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx, twin = _ctx(vx), _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx, twin = new_ctx(vx), new_ctx(vx)
     try:
         for c in (ctx, twin):
             if how == "device":
                 c.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, factor)
             else:
-                _upload(c, vxo.World.from_dense(dense, X, Y, Z, factor))
-        _assert_tables(ctx, vxo.World.from_dense(dense, X, Y, Z, factor))
+                upload(c, vxo.World.from_dense(dense, X, Y, Z, factor))
+        assert_tables(ctx, vxo.World.from_dense(dense, X, Y, Z, factor))
         created = freed = 0
         for call in range(20):
-            ops = _random_ops(rng, (X, Y, Z), int(rng.integers(1, 65)), max(min(X, Y, Z) // 2, 4))
+            ops = random_ops(rng, (X, Y, Z), int(rng.integers(1, 65)), max(min(X, Y, Z) // 2, 4))
             st = ctx.edit_voxels(ops)
             st2 = twin.edit_voxels([vx.EditBox(a, b, v) if k == BOX else vx.EditSphere(a, b[0], v) for k, v, a, b in ops])
             dense = vxo_edit.apply_edits(dense, X, Y, Z, ops)
             w = vxo.World.from_dense(dense, X, Y, Z, factor)
-            d = _assert_tables(ctx, w)
+            d = assert_tables(ctx, w)
             assert st.bricks_live == int((w.brick_slot != 0xFFFFFFFF).sum()) and st.pool_slots == d["pool"].size // (factor ** 3 // 32)
             assert st.pool_capacity >= st.pool_slots
             created, freed = created + st.bricks_created, freed + st.bricks_freed
@@ -145,9 +51,9 @@ def test_random_edit_sequences_equal_the_oracle(eng, vxo, factor, X, Y, Z, how):
             assert all(np.array_equal(d[k], d2[k]) for k in ("coarse_bits", "brick_slot", "bounds", "pool"))
             assert (st.bricks_created, st.bricks_freed, st.pool_slots) == (st2.bricks_created, st2.bricks_freed, st2.pool_slots)
             full = call % 5 == 4
-            _assert_frames(vx, ctx, torch, vxo, w, cams="ABCD" if full else "A", variants=(4, 1) if full else (4,))
+            assert_frames(vx, ctx, torch, vxo, w, cams="ABCD" if full else "A", variants=(4, 1) if full else (4,))
             if full:
-                _assert_batch(ctx, w, seed=call)
+                assert_batch(ctx, w, seed=call)
         assert created > 0 and freed > 0
     finally:
         ctx.close()
@@ -158,7 +64,7 @@ def test_freed_slots_are_reused_and_growth_follows_capacity(eng, vxo):
     vx, torch = eng
     X = Y = Z = 128
     F = 16
-    ctx, res = _ctx(vx), _ctx(vx)
+    ctx, res = new_ctx(vx), new_ctx(vx)
     try:
         for c in (ctx, res):
             c.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, F)
@@ -176,15 +82,15 @@ def test_freed_slots_are_reused_and_growth_follows_capacity(eng, vxo):
         assert not d_cleared["pool"].reshape(-1, bw)[info.nslots:].any()     # freed slots are zero
         st_s = ctx.edit_voxels([region])
         assert st_s.bricks_created == 32 and (st_s.pool_slots, st_s.pool_capacity) == (st.pool_slots, st.pool_capacity)
-        dense = vxo_edit.apply_edits(_gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z), X, Y, Z, [region])
+        dense = vxo_edit.apply_edits(gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z), X, Y, Z, [region])
         w = vxo.World.from_dense(dense, X, Y, Z, F)
-        _assert_tables(ctx, w)
-        _assert_frames(vx, ctx, torch, vxo, w, cams="AB", variants=(4,))
+        assert_tables(ctx, w)
+        assert_frames(vx, ctx, torch, vxo, w, cams="AB", variants=(4,))
         # after edit_reserve the same edits need no growth
         res.edit_reserve(info.nslots + 1000)
         st_r = res.edit_voxels([region])
         assert st_r.pool_capacity == info.nslots + 1000 and st_r.bricks_created == 32
-        _assert_tables(res, w)
+        assert_tables(res, w)
         res.edit_reserve(10)                                   # never shrinks
         assert res.edit_voxels([]).pool_capacity == info.nslots + 1000
     finally:
@@ -195,7 +101,7 @@ def test_freed_slots_are_reused_and_growth_follows_capacity(eng, vxo):
 def test_all_or_nothing_and_no_op_calls(eng, vxo, tmp_path):
     vx, torch = eng
     X = Y = Z = 128
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, 16)
         ctx.edit_voxels([(SPHERE, 0, (64, 40, 64), (20, 0, 0))])
@@ -228,13 +134,13 @@ def test_all_or_nothing_and_no_op_calls(eng, vxo, tmp_path):
 
 def test_refusals(eng, vxo, tmp_path):
     vx, torch = eng
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         op = (vx.EditOp * 1)(vx.EditBox((0, 0, 0), (3, 3, 3), 1))
         assert ctx._L.vxrt_edit_voxels(ctx._h, op, 1, None) == -3        # no world
         assert ctx._L.vxrt_edit_reserve(ctx._h, 100) == -3
         w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16)
-        _upload(ctx, w)
+        upload(ctx, w)
         path = str(tmp_path / "s.vxb")
         ctx.save_world(path)
         ctx.stream_open(path, 1000)
@@ -250,12 +156,12 @@ def test_compacting_save_loads_and_streams(eng, vxo, tmp_path):
     X = Y = Z = 256
     F = 16
     rng = np.random.default_rng(5)
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx, other = _ctx(vx), _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx, other = new_ctx(vx), new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, F)
         for _ in range(6):
-            ops = _random_ops(rng, (X, Y, Z), 30, 60)
+            ops = random_ops(rng, (X, Y, Z), 30, 60)
             ctx.edit_voxels(ops)
             dense = vxo_edit.apply_edits(dense, X, Y, Z, ops)
         w = vxo.World.from_dense(dense, X, Y, Z, F)
@@ -265,15 +171,15 @@ def test_compacting_save_loads_and_streams(eng, vxo, tmp_path):
         live = int((w.brick_slot != 0xFFFFFFFF).sum())
         assert info.nslots == live
         other.load_world(path)
-        d = _assert_tables(other, w)
+        d = assert_tables(other, w)
         occ = d["brick_slot"] != 0xFFFFFFFF
         assert np.array_equal(d["brick_slot"][occ], np.arange(live))     # renumbered in cell order, as the builders do
         assert np.array_equal(d["brick_slot"], w.brick_slot)
-        _assert_frames(vx, other, torch, vxo, w, cams="AD", variants=(4,))
+        assert_frames(vx, other, torch, vxo, w, cams="AD", variants=(4,))
         other.stream_open(path, live)
         other.stream_focus((128.0, 128.0, 128.0), 1.0e6)
-        _assert_tables(other, w)
-        _assert_frames(vx, other, torch, vxo, w, cams="A", variants=(4,))
+        assert_tables(other, w)
+        assert_frames(vx, other, torch, vxo, w, cams="A", variants=(4,))
         other.stream_close()
     finally:
         ctx.close()
@@ -284,8 +190,8 @@ def test_launch_before_the_edit_sees_the_old_world(eng, vxo):
     vx, torch = eng
     X = Y = Z = 128
     F = 16
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx = _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, F)
         ops = [(BOX, 0, (0, 0, 0), (127, 127, 63)), (SPHERE, 1, (64, 100, 96), (24, 0, 0))]
@@ -302,8 +208,8 @@ def test_launch_before_the_edit_sees_the_old_world(eng, vxo):
         with torch.cuda.stream(side):
             ctx.RenderScreen(W, H, fb1, pos, f, u, r, opts)
         side.synchronize()
-        want0 = _oracle_frame(vxo, old, "A", old.dims, vx.MODE_SHADED)
-        want1 = _oracle_frame(vxo, new, "A", new.dims, vx.MODE_SHADED)
+        want0 = oracle_frame(vxo, old, "A", old.dims, vx.MODE_SHADED)
+        want1 = oracle_frame(vxo, new, "A", new.dims, vx.MODE_SHADED)
         assert not np.array_equal(want0, want1)
         assert np.array_equal(fb0.cpu().numpy(), want0) and np.array_equal(fb1.cpu().numpy(), want1)
     finally:
@@ -313,7 +219,7 @@ def test_launch_before_the_edit_sees_the_old_world(eng, vxo):
 def test_speculative_loads_stay_in_the_slack_of_a_grown_pool(eng, vxo):
     """The slack contract (tests/test_gpu_parity.py) on this fifth world path: an edited world whose pool has grown."""
     vx, torch = eng
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
         n0 = ctx.world_info().nslots
@@ -350,10 +256,10 @@ def test_pick_and_dig(eng, vxo):
     vx, torch = eng
     X = Y = Z = 128
     F = 8
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx = _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx = new_ctx(vx)
     try:
-        _upload(ctx, vxo.World.from_dense(dense, X, Y, Z, F))
+        upload(ctx, vxo.World.from_dense(dense, X, Y, Z, F))
         rng = np.random.default_rng(3)
         o = np.tile(np.array([[64.0, 120.0, 64.0]], np.float32), (4000, 1))
         d = rng.normal(size=(4000, 3)).astype(np.float32)
@@ -374,20 +280,18 @@ def test_pick_and_dig(eng, vxo):
             c = w.trace_batch(o, d, nthreads=16)
             assert np.array_equal(g2["voxel"], c["voxel"]) and np.array_equal(g2["steps"], c["steps"])
             assert np.array_equal(helpers.float_bits(g2["hitPoint"]), helpers.float_bits(c["pos"]))
-        _assert_tables(ctx, w)
+        assert_tables(ctx, w)
     finally:
         ctx.close()
 
 
-FACADE_POSES = [((64.0, 230.0, 64.0), (-0.45, 0.7, 0.0)), ((70.5, 228.0, 66.0), (-0.5, 0.8, 0.0)),
-                ((80.0, 220.25, 72.0), (-0.6, 1.0, 0.0))]
 FACADE_EDITS = [(1, (SPHERE, 0, (150, 150, 150), (70, 0, 0))), (1, (BOX, 1, (120, 200, 120), (160, 215, 140))),
                 (2, (SPHERE, 1, (110, 190, 100), (18, 0, 0))), (2, (BOX, 0, (0, 0, 0), (255, 120, 60)))]
 
 
 def _facade_oracle_frames(vxo, edits, W_, H_):
     edge = 256
-    dense = _gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge)
+    dense = gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge)
     fb = np.full((H_, W_, 4), 255, np.uint8)
     frames = []
     for frame, (pos, euler) in enumerate(FACADE_POSES):

@@ -13,23 +13,11 @@ import pytest
 from oracle import ref_edit, ref_region, vxo_edit
 from tests import helpers
 from tests import ref_islands as R
+from tests.helpers import FACADE_POSES, assert_tables, eng, gen_dense, upload
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL = R.FACES | R.FLOOR
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    import voxelengine_amd as vx
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return vx, torch
-
-
-def _upload(ctx, w):
-    ctx.upload_world(w.factor, w.cdims, w.coarse_bits, w.brick_slot, w.bounds, w.pool)
 
 
 def _world(vxo, size, factor, density, seed):
@@ -66,7 +54,7 @@ def test_islands_equal_the_reference(eng, vxo, factor, size, density):
     rng = np.random.default_rng(factor * 7 + size[0])
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         boxes = [((0, 0, 0), tuple(min(s, 160) for s in size)), ((-40, -30, -50), (97, 70, 101)),
                  ((size[0] - 50, 3, size[2] - 20), (100, 61, 45)), ((5, 7, 9), (1, 33, 17)), ((2, 1, 0), (200, 1, 3))]
         for _ in range(3):
@@ -91,7 +79,7 @@ def test_spiral_snake_spanning_a_128_box(eng, vxo):
     vox[1:127, 1:127, 1:127] = R.snake((126, 126, 126))
     ctx = vx.Context(0)
     try:
-        _upload(ctx, vxo.World.from_voxels(vox, 16))
+        upload(ctx, vxo.World.from_voxels(vox, 16))
         r, want = _assert_islands(vx, ctx, vox, (0, 0, 0), (128, 128, 128), R.FACES)
         assert r.summary == (1, 1, int(vox.sum())) and r.table[0]["id"] == 1 + 1 + 128 * (1 + 128)
         cut = vox.copy()
@@ -108,7 +96,7 @@ def test_results_follow_edits_and_stamps(eng, vxo):
     w, vox = _world(vxo, (128, 128, 128), 16, 0.25, seed=11)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         rng = np.random.default_rng(12)
         ops = [(0, 0, (0, 40, 0), (127, 44, 127)), (1, 1, (64, 60, 64), (15, 0, 0)), (0, 0, (10, 0, 10), (30, 127, 30))]
         ctx.edit_voxels([vx.EditBox(a, b, v) if k == 0 else vx.EditSphere(a, b[0], v) for k, v, a, b in ops])
@@ -126,13 +114,12 @@ def test_results_follow_edits_and_stamps(eng, vxo):
 
 def test_collapse_leaves_the_oracle_world_and_no_islands(eng, vxo):
     vx, torch = eng
-    from tests.test_gpu_edit import _assert_tables, _gen_dense
     X = Y = Z = 128
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
     vox = vxo_edit.voxels_from_dense(dense, X, Y, Z)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, vxo.World.from_dense(dense, X, Y, Z, 16))
+        upload(ctx, vxo.World.from_dense(dense, X, Y, Z, 16))
         # an overhang on a stem, then a dig through the stem and a pocket of loose voxels under the terrain surface
         ops = [(0, 1, (40, 100, 40), (60, 102, 60)), (0, 1, (50, 60, 50), (51, 99, 51)), (0, 0, (45, 80, 45), (55, 82, 55)),
                (1, 0, (90, 40, 90), (12, 0, 0)), (0, 1, (88, 38, 88), (92, 42, 92))]
@@ -146,7 +133,7 @@ def test_collapse_leaves_the_oracle_world_and_no_islands(eng, vxo):
         assert np.array_equal(R.table_rows(isl.table), want["table"])
         assert st.bricks_touched > 0
         after = ref_region.apply_stamps(vox, [(o, want["floating"], vx.STAMP_SUBTRACT)])
-        _assert_tables(ctx, vxo.World.from_dense(vxo.dense_from_voxels(after), X, Y, Z, 16))
+        assert_tables(ctx, vxo.World.from_dense(vxo.dense_from_voxels(after), X, Y, Z, 16))
         again = ctx.find_islands(o, d)
         assert again.summary.islands == 0 and again.summary.island_voxels == 0
         assert again.summary.components == want["summary"][0] - want["summary"][1]
@@ -173,7 +160,7 @@ def test_truncated_table_keeps_the_true_count(eng, vxo):
     w, vox = _world(vxo, (64, 64, 64), 8, 0.2, seed=3)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         for m in (0, 1, 5):
             r, want = _assert_islands(vx, ctx, vox, (0, 0, 0), (64, 64, 64), ALL, max_islands=m, labels=False)
             assert want["summary"][1] > 5 and len(r.table) == m
@@ -186,7 +173,7 @@ def test_deterministic_across_calls_and_streams(eng, vxo):
     w, vox = _world(vxo, (256, 256, 256), 32, 0.31, seed=5)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         o, d = (-5, 3, 7), (250, 240, 230)
         first = ctx.find_islands(o, d, ALL, labels=True)
         side = torch.cuda.Stream()
@@ -214,7 +201,7 @@ def test_refusals(eng, vxo, tmp_path):
         sm = np.zeros(3, np.uint32)
         assert L.vxrt_find_islands(h, o3, d3, 0, p, fl, None, None, 0, sp, None) == -3        # no world
         assert L.vxrt_find_islands_host(h, o3, d3, 0, host.ctypes.data, None, None, 0, sm.ctypes.data) == -3
-        _upload(ctx, vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16))
+        upload(ctx, vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16))
         for bad in [(0, 8, 8), (8, -1, 8), (1024, 1024, 257)]:                              # bad dims
             assert L.vxrt_find_islands(h, o3, (C.c_int32 * 3)(*bad), 0, p, fl, None, None, 0, sp, None) == -1
         assert L.vxrt_find_islands(h, (C.c_int32 * 3)(2 ** 31 - 4, 0, 0), d3, 0, p, fl, None, None, 0, sp, None) == -1
@@ -240,7 +227,6 @@ def test_refusals(eng, vxo, tmp_path):
 def test_headless_example_collapse_script(vxo, tmp_path):
     """examples/voxelapp_headless: build an overhang on a stem (kind 0), dig through the stem, collapse (kind 4): the printed
     summary equals the reference's, and the last frame equals the oracle's frame of the world without the island"""
-    from tests.test_gpu_region import FACADE_POSES, _gen_dense
     exe = os.path.join(ROOT, "examples", "voxelapp_headless")
     assert os.path.exists(exe), "run __graft_entry__.build() first"
     W_, H_ = 160, 96
@@ -255,7 +241,7 @@ def test_headless_example_collapse_script(vxo, tmp_path):
     out = subprocess.run([exe, str(edge), "0", prefix, str(W_), str(H_), "1", str(path), "1", "1", "1", "0x0x0", str(sf)],
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
-    vox = vxo_edit.voxels_from_dense(_gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
+    vox = vxo_edit.voxels_from_dense(gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
     vox = ref_edit.apply_edits(vox, [(k, v, a, b) for fr, k, v, a, b in script if k != 4])
     o, d = (50, 140, 50), (70, 80, 70)
     want = R.fast(ref_region.read_region(vox, o, d), o, ALL)
@@ -269,7 +255,7 @@ def test_headless_example_collapse_script(vxo, tmp_path):
     f, u, r = vxo.get_directions(euler)
     p0 = FACADE_POSES[0]
     fb0 = vxo.World.from_dense(vxo.dense_from_voxels(ref_edit.apply_edits(
-        vxo_edit.voxels_from_dense(_gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge),
+        vxo_edit.voxels_from_dense(gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge),
         [(k, v, a, b) for fr, k, v, a, b in script if fr == 0])), edge, edge, edge, 32)
     f0, u0, r0 = vxo.get_directions(p0[1])
     prm0 = vxo.make_params(W_, H_, tuple(np.float32(v) for v in p0[0]), f0, u0, r0, frame_number=0, mode=vxo.MODE_SHADED,

@@ -11,23 +11,11 @@ import pytest
 
 from oracle import ref_edit, ref_region
 from tests import ref_nav as R
+from tests.helpers import eng, gen_dense, upload
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AGENTS = [(1, 2, 1, 3), (2, 3, 0, 1), (1, 1, 2, 8), (3, 2, 1, 2), (8, 32, 8, 32)]
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    import voxelengine_amd as vx
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return vx, torch
-
-
-def _upload(ctx, w):
-    ctx.upload_world(w.factor, w.cdims, w.coarse_bits, w.brick_slot, w.bounds, w.pool)
 
 
 def _grid(t, dims, dtype):
@@ -75,7 +63,7 @@ def test_field_equals_the_reference(eng, vxo, factor, size, density):
     rng = np.random.default_rng(factor + 1)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         boxes = [((0, 0, 0), (size[0], 40, size[2])), ((5, 1, 7), (45, 33, 17)), ((-20, -10, -30), (61, 50, 70)),
                  ((1, 0, 2), (1, 40, 33)), ((size[0] - 40, 2, 3), (70, 20, 50))]
         for i, (o, d) in enumerate(boxes):
@@ -93,7 +81,7 @@ def test_field_follows_edits_and_stamps(eng, vxo):
     w, vox = _random(vxo, (128, 128, 128), 16, 0.1, seed=7)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         o, d = (0, 0, 0), (128, 48, 128)
         before = ctx.nav_field(o, d, [(60, 1, 60)], vx.NavAgent())
         rng = np.random.default_rng(8)
@@ -142,7 +130,7 @@ def test_paths_equal_the_decoding(eng, vxo):
     w, vox = _random(vxo, (64, 64, 64), 8, 0.06, seed=21)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         o, d, agent = (0, 0, 0), (64, 24, 64), (1, 2, 1, 3)
         probe = R.nav_field(vox, o, d, agent, [])
         rng = np.random.default_rng(22)
@@ -171,7 +159,7 @@ def test_deterministic_across_calls_and_streams(eng, vxo):
     w, vox = _random(vxo, (256, 256, 256), 32, 0.05, seed=5)
     ctx = vx.Context(0)
     try:
-        _upload(ctx, w)
+        upload(ctx, w)
         o, d = (-5, 0, 7), (250, 60, 230)
         goals = [(100, 1, 100), (3, 1, 200), (200, 1, 5)]
         first = ctx.nav_field(o, d, goals, vx.NavAgent(2, 2, 1, 2))
@@ -200,7 +188,7 @@ def test_snake_corridor_work_follows_the_frontier(eng, vxo):
     vox[:, :snake.shape[1]] = snake
     ctx = vx.Context(0)
     try:
-        _upload(ctx, vxo.World.from_voxels(vox, 8))
+        upload(ctx, vxo.World.from_voxels(vox, 8))
         r, want = _assert_field(vx, ctx, vox, (0, 0, 0), snake.shape, (1, 2, 1, 3), [(0, 1, 0)])
         s = r.summary
         assert s.levels > 1000 and s.tile_visits <= s.levels * s.tiles_total / 16, s
@@ -231,7 +219,7 @@ def test_refusals(eng, vxo, tmp_path):
             return L.vxrt_nav_field_host(h, o, d, a, g.ctypes.data if g is not None else None, n, md, hw.ctypes.data,
                                          hn.ctypes.data, None, hs.ctypes.data)
         assert field() == -3 and host() == -3     # no world
-        _upload(ctx, vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16))
+        upload(ctx, vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16))
         for bad in [(0, 8, 8), (8, -1, 8), (1024, 1024, 257)]:
             assert field(d=(C.c_int32 * 3)(*bad)) == -1
         assert field(o=(C.c_int32 * 3)(2 ** 31 - 4, 0, 0)) == -1
@@ -274,12 +262,11 @@ def test_refusals(eng, vxo, tmp_path):
 
 def test_headless_example_nav_line(vxo, tmp_path):
     """examples/voxelapp_headless kind 5: the printed summary equals the reference's for the camera's cell"""
-    from tests.test_gpu_region import _gen_dense
     from oracle import vxo_edit
     exe = os.path.join(ROOT, "examples", "voxelapp_headless")
     assert os.path.exists(exe), "run __graft_entry__.build() first"
     edge = 256
-    vox = vxo_edit.voxels_from_dense(_gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
+    vox = vxo_edit.voxels_from_dense(gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
     col = vox[100, :, 120]
     top = int(np.nonzero(col)[0].max()) + 1 if col.any() else 0
     pos = (100.5, top + 0.5, 120.5)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import helpers
+from tests.helpers import upload
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +21,6 @@ def eng():
     ctx = vx.Context(0)
     yield vx, ctx, torch
     ctx.close()
-
-
-def _upload(ctx, w):
-    ctx.upload_world(w.factor, w.cdims, w.coarse_bits, w.brick_slot, w.bounds, w.pool)
 
 
 def _assert_batch_equal(gpu, cpu):
@@ -44,7 +41,7 @@ def _assert_batch_equal(gpu, cpu):
 def test_trace_batch_random_worlds(eng, vxo, factor, size, density, seed):
     vx, ctx, _ = eng
     w = helpers.random_voxel_world(vxo, size, factor, density, seed)
-    _upload(ctx, w)
+    upload(ctx, w)
     o, d = helpers.mixed_rays(w.dims, 30000, seed)
     cpu = w.trace_batch(o, d)
     gpu = ctx.Raytrace(o, d, want_stats=True)
@@ -68,7 +65,7 @@ def test_trace_batch_persistent_queue(eng, vxo, n):
     ctx.set_persistent_waves_per_cu(1)   # a small persistent grid: batches of this size take the queue kernel
     try:
         w = helpers.random_voxel_world(vxo, (128, 128, 128), 16, 0.004, 21)
-        _upload(ctx, w)
+        upload(ctx, w)
         o, d = helpers.mixed_rays(w.dims, n, 5)
         cpu = w.trace_batch(o, d)
         gpu = ctx.Raytrace(o, d, want_stats=True)
@@ -94,7 +91,7 @@ def test_invalid_rays_are_defined_misses_and_a_bad_camera_is_rejected(eng, vxo):
     ctx.set_persistent_waves_per_cu(1)   # a small persistent grid: batches of this size take the queue kernel
     try:
         w = helpers.random_voxel_world(vxo, (128, 128, 128), 16, 0.004, 33)
-        _upload(ctx, w)
+        upload(ctx, w)
         n = 300000
         o, d = helpers.mixed_rays(w.dims, n, 11)
         bad = np.zeros(n, bool)
@@ -140,7 +137,7 @@ def test_invalid_rays_are_defined_misses_and_a_bad_camera_is_rejected(eng, vxo):
 def test_trace_batch_terrain_and_empty_inputs(eng, vxo):
     vx, ctx, _ = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     o, d = helpers.mixed_rays(w.dims, 60000, 9)
     _assert_batch_equal(ctx.Raytrace(o, d), w.trace_batch(o, d))
     out = ctx.Raytrace(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32))
@@ -158,7 +155,7 @@ def test_every_kernel_variant_agrees_with_the_oracle(eng, vxo, variant):
     counting one (_render_both)."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     o, d = helpers.mixed_rays(w.dims, 20000, 21)
     cpu = w.trace_batch(o, d)
     default = ctx.kernel_variant
@@ -184,7 +181,7 @@ def test_known_answer_rays_on_gpu(eng, vxo):
     for p in [(26, 12, 11), (26, 10, 11), (18, 11, 11)]:
         v[p] = True
     w = vxo.World.from_voxels(v, 8)
-    _upload(ctx, w)
+    upload(ctx, w)
     up = np.nextafter(np.float32(1.4375), np.float32(np.inf))
     yw = np.float32(np.float32(np.float32(up * np.float32(8)) - np.float32(8)) + np.float32(8))
     default = ctx.kernel_variant
@@ -213,7 +210,7 @@ def test_quirk_cases_on_gpu(eng, vxo):
     try:
         for name, case in quirk_cases.all_cases().items():
             w, o, d = quirk_cases.build_case(vxo, case)
-            _upload(ctx, w)
+            upload(ctx, w)
             e = case["expect"]
             ctx.set_batch_max_steps(case["max_steps"])
             # (a one-ray batch: 7 = the tracer of the headline kernel, with its probe counters and -- `False` -- as timed;
@@ -245,7 +242,7 @@ def test_batch_max_steps_matches_the_oracle(eng, vxo):
     small.set_persistent_waves_per_cu(1)   # a small persistent grid: batches of this size take the queue kernel
     try:
         for c in (ctx, small):
-            _upload(c, w)
+            upload(c, w)
             for ms in (8, 1, 100):
                 c.set_batch_max_steps(ms)
                 got = c.Raytrace(o, d)
@@ -271,7 +268,7 @@ def test_eighty_launches_in_flight_over_four_streams(eng, vxo, depth):
     counters must add up.  depth 2 = the second-bounce instantiation of the kernels (the one with the most private state)."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     W, H = 200, 120
     cams = [helpers.camera(c, w.dims, vxo) for c in "ABCD"]
     inv = float(np.float32(1.0) / np.sqrt(np.float32(3.0)))
@@ -358,7 +355,7 @@ def _assert_frame_equal(cpu, fb, col, hit, st):
 @pytest.mark.parametrize("cam", ["A", "B", "C", "D"])
 def test_render_shaded_primary_only(eng, vxo, cam):
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(eng[1], w)
+    upload(eng[1], w)
     cpu, fb, col, hit, st = _render_both(eng, vxo, w, 200, 120, cam)
     _assert_frame_equal(cpu, fb, col, hit, st)
     assert st.primary_rays == 200 * 120
@@ -367,7 +364,7 @@ def test_render_shaded_primary_only(eng, vxo, cam):
 @pytest.mark.parametrize("cam,gate", [("A", 0), ("D", 0), ("A", 1)])
 def test_render_shadow_and_bounce(eng, vxo, cam, gate):
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(eng[1], w)
+    upload(eng[1], w)
     cpu, fb, col, hit, st = _render_both(eng, vxo, w, 192, 108, cam, frame_number=3, shadow=1, bounce_samples=1,
                                          bounce_all_hits=gate)
     _assert_frame_equal(cpu, fb, col, hit, st)
@@ -380,7 +377,7 @@ def test_render_second_bounce_extension(eng, vxo, cam, gate):
     in oracle/vxo_render.c): sample rays that hit spawn one more ray; more bounce rays than with depth 1, same bits
     as the oracle."""
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(eng[1], w)
+    upload(eng[1], w)
     kw = dict(frame_number=4, shadow=1, bounce_samples=2, bounce_all_hits=gate)
     one = _render_both(eng, vxo, w, 192, 108, cam, **kw)
     two = _render_both(eng, vxo, w, 192, 108, cam, bounce_depth=2, **kw)
@@ -395,7 +392,7 @@ def test_render_checkerboard_and_debug_view(eng, vxo, frame):
     """The shipped configuration: DEBUG_VIEW quadrants + checkerboard (Renderer.cu:4-5); only half the pixels
     are written per frame, the rest keep their previous contents."""
     w = vxo.World.generate(vxo.GEN_HASH_HEIGHTFIELD, 128, 128, 128, 16)
-    _upload(eng[1], w)
+    upload(eng[1], w)
     cpu, fb, col, hit, st = _render_both(eng, vxo, w, 160, 90, "A", frame_number=frame, mode=1, checkerboard=1)
     _assert_frame_equal(cpu, fb, col, hit, st)
     assert st.primary_rays < 160 * 90
@@ -406,7 +403,7 @@ def test_render_checkerboard_and_debug_view(eng, vxo, frame):
 
 def test_render_ortho_and_f8(eng, vxo):
     w = helpers.random_voxel_world(vxo, (128, 64, 128), 8, 0.03, 11)
-    _upload(eng[1], w)
+    upload(eng[1], w)
     cpu, fb, col, hit, st = _render_both(eng, vxo, w, 128, 96, "A", ortho=1, ortho_size=(30.0, 30.0), shadow=1)
     _assert_frame_equal(cpu, fb, col, hit, st)
     cpu, fb, col, hit, st = _render_both(eng, vxo, w, 133, 77, "B", shadow=1, bounce_samples=1)   # ragged frame
@@ -437,7 +434,7 @@ def test_strip_sharding_reassembles_the_frame(eng, vxo, count, rows):
     the single-GPU frame byte for byte."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     W, H = 192, 108
     pos, f, u, r = helpers.camera("A", w.dims, vxo)
     full = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
@@ -467,7 +464,7 @@ def test_tile_hand_out_order_never_changes_the_frame(eng, vxo):
     to the oracle whatever the order, also for a sharded launch grid."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     W, H = 1004, 516   # 126 x 65 tiles, ragged on both edges
     ntiles = ((W + 7) // 8) * ((H + 7) // 8)
     pos, f, u, r = helpers.camera("A", w.dims, vxo)
@@ -507,7 +504,7 @@ def test_tile_queue_hands_out_every_tile_once(eng, vxo, W, H):
     exactly once -- the ray counter equals the pixel count -- and equal the oracle."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16)
-    _upload(ctx, w)
+    upload(ctx, w)
     pos, f, u, r = helpers.camera("A", w.dims, vxo)
     p = vxo.make_params(W, H, pos, f, u, r, frame_number=1)
     want = w.render(p, fb=np.zeros((H, W, 4), np.uint8))["fb"]
@@ -529,7 +526,7 @@ def test_multi_view_launch_equals_single_view_launches(eng, vxo, variant):
     for plain, checkerboard (per-view frame numbers) and strip-sharded launches, and equal to the oracle."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     W, H = 724, 412   # 91 x 52 tiles per view: more tiles than waves, ragged edges
     cams = ["A", "B", "D", "C", "A"]
     frames = [3, 4, 7, 8, 11]
@@ -577,7 +574,7 @@ def test_multi_view_launch_sixteen_views_back_to_back(eng, vxo):
     output buffers.  Every frame of every launch equals the single-view render of that frame."""
     vx, ctx, torch = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
-    _upload(ctx, w)
+    upload(ctx, w)
     W, H = 200, 120
     opts = dict(shadow=True, bounce_samples=1)
     names = ["A", "B", "C", "D"]
@@ -652,7 +649,7 @@ def test_uploaded_tables_come_back_in_the_reference_order(eng, vxo, shape, facto
     on grids whose three dimensions differ, and the re-ordered world traces like the oracle's."""
     vx, ctx, _ = eng
     w = vxo.World.generate(vxo.GEN_INT_TERRAIN, *shape, factor)
-    _upload(ctx, w)
+    upload(ctx, w)
     got = ctx.download_world()
     assert np.array_equal(got["coarse_bits"], w.coarse_bits)
     assert np.array_equal(got["brick_slot"], w.brick_slot)
@@ -692,7 +689,7 @@ def test_wide_grids_run_the_product_kernels(eng, vxo, cells_x, density):
     v[:, 0, :] = True                  # a floor, so that frames have something to shade
     w = vxo.World.from_voxels(v, 8)
     assert w.cdims[0] == cells_x
-    _upload(ctx, w)
+    upload(ctx, w)
     n = 60000
     o, d = helpers.mixed_rays(w.dims, n, cells_x)
     d[::2, 1:] *= np.float32(0.002)    # half of the rays nearly along the long axis
@@ -705,7 +702,7 @@ def test_wide_grids_run_the_product_kernels(eng, vxo, cells_x, density):
     small = vx.Context(0)
     small.set_persistent_waves_per_cu(1)
     try:
-        _upload(small, w)
+        upload(small, w)
         for c, variant in ((ctx, 4), (small, 4), (ctx, 1)):
             c.set_kernel_variant(variant)
             g = c.Raytrace(o, d, want_stats=True)
@@ -727,7 +724,7 @@ def test_kernel_for_launch_reports_the_kernel(eng, vxo):
     1080p frame of primary rays or a 1/8 shard -- and the cross-check variant is reported as itself; the kernels of
     earlier rounds are refused."""
     vx, ctx, torch = eng
-    _upload(ctx, vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32))
+    upload(ctx, vxo.World.generate(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32))
     default = ctx.kernel_variant
     try:
         ctx.set_kernel_variant(4)
@@ -787,9 +784,9 @@ def test_speculative_loads_stay_inside_the_allocators_slack(eng, vxo, tmp_path):
             c.stream_open(path, 4096)
             c.stream_focus((128.0, 128.0, 128.0), 1000.0)
 
-        paths = [("upload", lambda c: _upload(c, w)), ("device builder", lambda c: c.build_world(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)),
+        paths = [("upload", lambda c: upload(c, w)), ("device builder", lambda c: c.build_world(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)),
                  ("brickmap file", load_from_file), ("chunk streaming", stream_from_file)]
-        _upload(ctx, w)
+        upload(ctx, w)
         ctx.save_world(path)
         for c in (ctx, small):
             for name, make in paths:

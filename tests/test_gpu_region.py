@@ -11,23 +11,14 @@ import pytest
 
 from oracle import ref_region, vxo_edit, vxo_region
 from tests import helpers
-from tests.test_gpu_edit import (_assert_batch, _assert_frames, _assert_tables, _ctx, _frame, _gen_dense, _oracle_frame,
-                                 _random_ops, _upload)
+from tests.helpers import (FACADE_POSES, assert_batch, assert_frames, assert_tables, eng, gen_dense, new_ctx, oracle_frame,
+                           random_ops, render_frame, upload)
 
 pytestmark = pytest.mark.gpu
 REPLACE, UNION, SUBTRACT = 0, 1, 2
 BOX, SPHERE = 0, 1
 W, H = 64, 48
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def eng():
-    import torch
-    import voxelengine_amd as vx
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return vx, torch
 
 
 def _random_box(rng, dims, maxd):
@@ -65,15 +56,15 @@ WORLDS = [  # (factor, X, Y, Z, how the world is made)
 def test_reads_equal_the_oracle(eng, vxo, tmp_path, factor, X, Y, Z, how):
     vx, torch = eng
     rng = np.random.default_rng(factor + X + len(how))
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx = _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx = new_ctx(vx)
     try:
         if how == "upload":
-            _upload(ctx, vxo.World.from_dense(dense, X, Y, Z, factor))
+            upload(ctx, vxo.World.from_dense(dense, X, Y, Z, factor))
         elif how == "device":
             ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, factor)
         elif how == "file":
-            other = _ctx(vx)
+            other = new_ctx(vx)
             other.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, factor)
             other.save_world(str(tmp_path / "w.vxb"))
             other.close()
@@ -82,7 +73,7 @@ def test_reads_equal_the_oracle(eng, vxo, tmp_path, factor, X, Y, Z, how):
             ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, factor)
             n0 = ctx.world_info().nslots
             for _ in range(4):
-                ops = _random_ops(rng, (X, Y, Z), 24, 60)
+                ops = random_ops(rng, (X, Y, Z), 24, 60)
                 ctx.edit_voxels(ops)
                 dense = vxo_edit.apply_edits(dense, X, Y, Z, ops)
             st = ctx.edit_voxels([(SPHERE, 1, (128, 220, 128), (30, 0, 0))])
@@ -114,7 +105,7 @@ def test_reads_at_scale_on_the_bench_world(eng):
     """brick-aligned, full-height windows of at least 2^30 voxels of the device-built 8192 x 512 x 8192 world against its
     own download_world tables decoded on the host"""
     vx, torch = eng
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vx.GEN_PERLIN_REF, 8192, 512, 8192, 32)
         d = ctx.download_world()
@@ -156,14 +147,14 @@ def _random_stamp(rng, dims, maxd, ctx, src_vox):
 def test_random_stamp_sequences_equal_the_oracle(eng, vxo, factor, X, Y, Z, how):
     vx, torch = eng
     rng = np.random.default_rng(factor * 3 + X)
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx, twin = _ctx(vx), _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx, twin = new_ctx(vx), new_ctx(vx)
     try:
         for c in (ctx, twin):
             if how == "device":
                 c.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, factor)
             else:
-                _upload(c, vxo.World.from_dense(dense, X, Y, Z, factor))
+                upload(c, vxo.World.from_dense(dense, X, Y, Z, factor))
         created = freed = 0
         modes = set()
         for call in range(12):
@@ -175,16 +166,16 @@ def test_random_stamp_sequences_equal_the_oracle(eng, vxo, factor, X, Y, Z, how)
             dense = vxo_region.apply_stamps(dense, X, Y, Z, [(o, vx.pack_region(m), m.shape, mode) for o, m, mode, _ in stamps])
             assert np.array_equal(vxo_edit.voxels_from_dense(dense, X, Y, Z), ref_region.apply_stamps(vox, [s[:3] for s in stamps]))
             w = vxo.World.from_dense(dense, X, Y, Z, factor)
-            d = _assert_tables(ctx, w)
+            d = assert_tables(ctx, w)
             assert st.bricks_live == int((w.brick_slot != 0xFFFFFFFF).sum())
             created, freed = created + st.bricks_created, freed + st.bricks_freed
             d2 = twin.download_world()      # determinism: the same calls give byte-identical downloads, pool included
             assert all(np.array_equal(d[k], d2[k]) for k in ("coarse_bits", "brick_slot", "bounds", "pool"))
             assert (st.bricks_created, st.bricks_freed, st.pool_slots) == (st2.bricks_created, st2.bricks_freed, st2.pool_slots)
             full = call % 4 == 3
-            _assert_frames(vx, ctx, torch, vxo, w, cams="ABCD" if full else "A", variants=(4, 1) if full else (4,))
+            assert_frames(vx, ctx, torch, vxo, w, cams="ABCD" if full else "A", variants=(4, 1) if full else (4,))
             if full:
-                _assert_batch(ctx, w, seed=call)
+                assert_batch(ctx, w, seed=call)
         assert created > 0 and freed > 0 and modes == {0, 1, 2}
     finally:
         ctx.close()
@@ -199,12 +190,12 @@ def test_undo_restores_tables_and_frames(eng, vxo, side_stream):
     X = Y = Z = 256
     F = 32
     rng = np.random.default_rng(9 + side_stream)
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
     w0 = vxo.World.from_dense(dense, X, Y, Z, F)
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, F)
-        frames0 = {(cam, m): _oracle_frame(vxo, w0, cam, w0.dims, m) for cam in "ABCD" for m in (vx.MODE_SHADED, vx.MODE_DEBUG)}
+        frames0 = {(cam, m): oracle_frame(vxo, w0, cam, w0.dims, m) for cam in "ABCD" for m in (vx.MODE_SHADED, vx.MODE_DEBUG)}
         changed = 0
         for rnd in range(3):
             lo = [int(rng.integers(0, 128)) for _ in range(3)]
@@ -229,10 +220,10 @@ def test_undo_restores_tables_and_frames(eng, vxo, side_stream):
             assert np.array_equal(ctx.read_region_host(lo, dims), ref_region.read_region(edited, lo, dims))
             changed += int(not np.array_equal(edited, vxo_edit.voxels_from_dense(dense, X, Y, Z)))
             ctx.edit_stamps([vx.Stamp(lo, saved, REPLACE, dims)])
-            _assert_tables(ctx, w0)
+            assert_tables(ctx, w0)
             for cam in "ABCD":
                 for m in (vx.MODE_SHADED, vx.MODE_DEBUG):
-                    assert np.array_equal(_frame(vx, ctx, torch, cam, w0.dims, vxo, m), frames0[(cam, m)]), (rnd, cam, m)
+                    assert np.array_equal(render_frame(vx, ctx, torch, cam, w0.dims, vxo, m), frames0[(cam, m)]), (rnd, cam, m)
         assert changed > 0
     finally:
         ctx.close()
@@ -241,9 +232,9 @@ def test_undo_restores_tables_and_frames(eng, vxo, side_stream):
 def test_copy_paste_apart_and_overlapping(eng, vxo):
     vx, torch = eng
     X = Y = Z = 128
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
     vox = vxo_edit.voxels_from_dense(dense, X, Y, Z)
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, 16)
         src, dims = (10, 20, 30), (40, 50, 35)
@@ -261,7 +252,7 @@ def test_copy_paste_apart_and_overlapping(eng, vxo):
         want3 = want2.copy()
         want3[100:, 100:, 100:] |= want[10:38, 20:48, 30:58]
         assert np.array_equal(ctx.read_region_host((0, 0, 0), (X, Y, Z)), want3)
-        _assert_tables(ctx, vxo.World.from_dense(vxo.dense_from_voxels(want3), X, Y, Z, 16))
+        assert_tables(ctx, vxo.World.from_dense(vxo.dense_from_voxels(want3), X, Y, Z, 16))
     finally:
         ctx.close()
 
@@ -279,7 +270,7 @@ def _descs(vx, stamps):
 def test_all_or_nothing_and_zero_union(eng, vxo, tmp_path):
     vx, torch = eng
     X = Y = Z = 128
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, 16)
         ctx.edit_voxels([(SPHERE, 0, (64, 40, 64), (20, 0, 0))])          # freed slots: the world was edited
@@ -314,7 +305,7 @@ def test_all_or_nothing_and_zero_union(eng, vxo, tmp_path):
 
 def test_refusals(eng, vxo, tmp_path):
     vx, torch = eng
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         buf = torch.zeros(1 << 16, dtype=torch.int32, device="cuda")
         o3, d3 = (C.c_int32 * 3)(0, 0, 0), (C.c_int32 * 3)(8, 8, 8)
@@ -324,7 +315,7 @@ def test_refusals(eng, vxo, tmp_path):
         assert ctx._L.vxrt_read_region_host(ctx._h, o3, d3, host.ctypes.data) == -3
         assert ctx._L.vxrt_edit_stamps(ctx._h, st, 1, None) == -3
         w = vxo.World.generate(vxo.GEN_INT_TERRAIN, 128, 128, 128, 16)
-        _upload(ctx, w)
+        upload(ctx, w)
         for bad in [(0, 8, 8), (8, -1, 8), (4096, 4096, 4097)]:                                  # bad dims
             assert ctx._L.vxrt_read_region(ctx._h, o3, (C.c_int32 * 3)(*bad), buf.data_ptr(), None) == -1
             assert ctx._L.vxrt_read_region_host(ctx._h, o3, (C.c_int32 * 3)(*bad), host.ctypes.data) == -1
@@ -349,8 +340,8 @@ def test_read_after_render_on_a_stream_sees_the_renders_world(eng, vxo):
     vx, torch = eng
     X = Y = Z = 128
     F = 16
-    dense = _gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
-    ctx = _ctx(vx)
+    dense = gen_dense(vxo, vxo.GEN_INT_TERRAIN, X, Y, Z)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, X, Y, Z, F)
         ops = [(BOX, 0, (0, 0, 0), (127, 127, 63)), (SPHERE, 1, (64, 100, 96), (24, 0, 0))]
@@ -369,8 +360,8 @@ def test_read_after_render_on_a_stream_sees_the_renders_world(eng, vxo):
             ctx.RenderScreen(W, H, fb1, pos, f, u, r, opts)
             r1 = ctx.read_region((0, 0, 0), (X, Y, Z))
         side.synchronize()
-        assert np.array_equal(fb0.cpu().numpy(), _oracle_frame(vxo, old, "A", old.dims, vx.MODE_SHADED))
-        assert np.array_equal(fb1.cpu().numpy(), _oracle_frame(vxo, new, "A", new.dims, vx.MODE_SHADED))
+        assert np.array_equal(fb0.cpu().numpy(), oracle_frame(vxo, old, "A", old.dims, vx.MODE_SHADED))
+        assert np.array_equal(fb1.cpu().numpy(), oracle_frame(vxo, new, "A", new.dims, vx.MODE_SHADED))
         assert np.array_equal(vx.unpack_region(r0, (X, Y, Z)), vxo_edit.voxels_from_dense(dense, X, Y, Z))
         assert np.array_equal(vx.unpack_region(r1, (X, Y, Z)), vxo_edit.voxels_from_dense(new_dense, X, Y, Z))
     finally:
@@ -380,7 +371,7 @@ def test_read_after_render_on_a_stream_sees_the_renders_world(eng, vxo):
 def test_speculative_loads_stay_in_the_slack_of_a_pool_grown_by_stamps(eng, vxo):
     """The slack contract (tests/test_gpu_parity.py) on a world whose pool grew through vxrt_edit_stamps."""
     vx, torch = eng
-    ctx = _ctx(vx)
+    ctx = new_ctx(vx)
     try:
         ctx.build_world(vxo.GEN_INT_TERRAIN, 256, 256, 256, 32)
         n0 = ctx.world_info().nslots
@@ -406,8 +397,6 @@ def test_speculative_loads_stay_in_the_slack_of_a_pool_grown_by_stamps(eng, vxo)
         ctx.close()
 
 
-FACADE_POSES = [((64.0, 230.0, 64.0), (-0.45, 0.7, 0.0)), ((70.5, 228.0, 66.0), (-0.5, 0.8, 0.0)),
-                ((80.0, 220.25, 72.0), (-0.6, 1.0, 0.0))]
 # frame, kind, value, a, b: kind 2 = copy box (a, dims b) into slot value, kind 3 = paste slot value at a in mode b[0]
 FACADE_SCRIPT = [(1, 2, 0, (100, 100, 100), (60, 90, 50)), (1, 0, 0, (90, 150, 90), (200, 255, 200)),
                  (1, 3, 0, (150, 165, 120), (0, 0, 0)), (2, 3, 0, (40, 170, 30), (1, 0, 0)),
@@ -417,7 +406,7 @@ FACADE_SCRIPT = [(1, 2, 0, (100, 100, 100), (60, 90, 50)), (1, 0, 0, (90, 150, 9
 
 def _script_oracle_frames(vxo, W_, H_):
     edge = 256
-    vox = vxo_edit.voxels_from_dense(_gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
+    vox = vxo_edit.voxels_from_dense(gen_dense(vxo, vxo.GEN_PERLIN_REF, edge, edge, edge), edge, edge, edge)
     clips = {}
     fb = np.full((H_, W_, 4), 255, np.uint8)
     frames = []

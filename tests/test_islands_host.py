@@ -2,15 +2,13 @@
 against each other and on hand-derived cases, and the kernels' island code (csrc/vxrt_islands.hpp) compiled for the host
 (tests/tools/islands_check.cpp) against them -- labels, floating bits, table and summary bit-equal, every index checked."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import ref_islands as R
+from tests.helpers import build_harness, run_harness_files
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL = R.FACES | R.FLOOR
 
 
@@ -125,24 +123,15 @@ def test_box_partly_outside_the_world():
 # ---- the kernels' island code on the host ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("islands") / "islands_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "tools", "hoststub"),
-                           "-I" + os.path.join(ROOT, "oracle"), "-o", exe, os.path.join(ROOT, "tests", "tools", "islands_check.cpp"),
-                           "-x", "c", os.path.join(ROOT, "oracle", "vxo_trace.c"), os.path.join(ROOT, "oracle", "vxo_world.c"),
-                           os.path.join(ROOT, "oracle", "vxo_render.c"), "-lm", "-lpthread", "-w"])
-    return exe
+    return build_harness(tmp_path_factory, "islands_check")
 
 
 def _run_harness(harness, tmp_path, world, factor, origin, dims, anchors, max_islands=1 << 20):
     from oracle import vxo
     X, Y, Z = world.shape
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.asarray([factor, X, Y, Z, *origin, *dims, anchors, max_islands], np.int32).tobytes())
-        f.write(vxo.dense_from_voxels(world).tobytes())
-    out = subprocess.run([harness, str(inp), str(outp)], capture_output=True, text=True)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
-    raw = np.fromfile(outp, np.uint32)
+    raw, _ = run_harness_files(harness, tmp_path, [factor, X, Y, Z, *origin, *dims, anchors, max_islands],
+                               vxo.dense_from_voxels(world))
+    raw = raw.view(np.uint32)
     n = dims[0] * dims[1] * dims[2]
     wpr = (dims[0] + 31) // 32
     nb = wpr * dims[1] * dims[2]

@@ -3,15 +3,13 @@ tests/ref_nav.py against each other and on hand-derived cases, and the kernels' 
 the host (tests/tools/nav_check.cpp) against them -- walkable bits, dist, next, summary and paths bit-equal, every index
 checked."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import ref_nav as R
+from tests.helpers import build_harness, run_harness_files
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = R.UNREACHED
 AGENTS = [(1, 2, 1, 3), (2, 3, 0, 1), (1, 1, 2, 8), (3, 2, 1, 2), (8, 32, 8, 32)]
 
@@ -164,12 +162,7 @@ def test_paths_decode():
 # ---- the kernels' nav code on the host ----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("nav") / "nav_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "tools", "hoststub"),
-                           "-I" + os.path.join(ROOT, "oracle"), "-o", exe, os.path.join(ROOT, "tests", "tools", "nav_check.cpp"),
-                           "-x", "c", os.path.join(ROOT, "oracle", "vxo_trace.c"), os.path.join(ROOT, "oracle", "vxo_world.c"),
-                           os.path.join(ROOT, "oracle", "vxo_render.c"), "-lm", "-lpthread", "-w"])
-    return exe
+    return build_harness(tmp_path_factory, "nav_check")
 
 
 def _run_harness(harness, tmp_path, world, factor, origin, dims, agent, goals, max_dist, starts, max_steps):
@@ -177,15 +170,8 @@ def _run_harness(harness, tmp_path, world, factor, origin, dims, agent, goals, m
     X, Y, Z = world.shape
     goals = np.asarray(goals, np.int32).reshape(-1, 3)
     starts = np.asarray(starts, np.int32).reshape(-1, 3)
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.asarray([factor, X, Y, Z, *origin, *dims, *agent, max_dist, len(goals), len(starts), max_steps], np.int32).tobytes())
-        f.write(goals.tobytes())
-        f.write(starts.tobytes())
-        f.write(vxo.dense_from_voxels(world).tobytes())
-    out = subprocess.run([harness, str(inp), str(outp)], capture_output=True, text=True)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
-    raw = np.fromfile(outp, np.uint8)
+    header = [factor, X, Y, Z, *origin, *dims, *agent, max_dist, len(goals), len(starts), max_steps]
+    raw, _ = run_harness_files(harness, tmp_path, header, goals, starts, vxo.dense_from_voxels(world))
     n = dims[0] * dims[1] * dims[2]
     nb = (dims[0] + 31) // 32 * dims[1] * dims[2]
     u32 = lambda a, k: np.frombuffer(raw[a:a + 4 * k].tobytes(), np.uint32)

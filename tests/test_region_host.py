@@ -2,13 +2,12 @@
 restatements (C: oracle/vxo_region.c; numpy: oracle/ref_region.py) on hand-derived cases and against each other, the
 region word layout (voxelengine_amd.pack_region / unpack_region), the row logic of the library
 (voxelengine_amd/csrc/vxrt_region.hpp) compiled for the host and held against the oracle, and the new ABI symbols."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import build_harness, run_harness
+
 REPLACE, UNION, SUBTRACT = 0, 1, 2
 
 
@@ -167,24 +166,12 @@ def test_copy_paste_and_undo_on_the_oracle(vxo):
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("region") / "region_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "tools", "hoststub"),
-                           "-I" + os.path.join(ROOT, "oracle"), "-o", exe, os.path.join(ROOT, "tests", "tools", "region_check.cpp"),
-                           "-x", "c", os.path.join(ROOT, "oracle", "vxo_trace.c"), os.path.join(ROOT, "oracle", "vxo_world.c"),
-                           os.path.join(ROOT, "oracle", "vxo_render.c"), os.path.join(ROOT, "oracle", "vxo_region.c"), "-lm",
-                           "-lpthread", "-w"])
-    return exe
-
-
-def _run(harness, *args):
-    out = subprocess.run([harness, *[str(a) for a in args]], capture_output=True, text=True)
-    assert out.returncode == 0 and "ALL OK" in out.stdout, out.stdout[-3000:]
-    return out.stdout
+    return build_harness(tmp_path_factory, "region_check", "vxo_region.c")
 
 
 def test_host_row_helpers_and_validation(harness):
     """row gather, funnel placement, coverage masks, region_words and stamp validation / clipping on hand-derived cases"""
-    _run(harness, "units")
+    run_harness(harness, "units")
 
 
 @pytest.mark.parametrize("factor,X,Y,Z,rounds", [(8, 64, 64, 64, 6), (16, 128, 128, 128, 3), (32, 256, 256, 256, 2),
@@ -192,7 +179,7 @@ def test_host_row_helpers_and_validation(harness):
 def test_host_read_logic_equals_the_oracle(harness, factor, X, Y, Z, rounds):
     """k_read_region's word (clipping, the bricks a word crosses, funnel shifts, padding) for random boxes, including
     boxes across every face, wholly outside and a single voxel, on random worlds; the last case is a wide grid"""
-    out = _run(harness, "read", factor, X, Y, Z, rounds)
+    out = run_harness(harness, "read", factor, X, Y, Z, rounds)
     assert int(out.split(" voxels set")[0].split()[-1]) > 0
 
 
@@ -202,7 +189,7 @@ def test_host_stamp_logic_equals_the_oracle(harness, factor, X, Y, Z, rounds):
     """k_stamp_bricks' functions (filter from the last covering replace stamp, row gather, coverage, the three modes,
     extents from the rows) brick by brick: images and packed extents equal the oracle's rebuilt brickmap of the stamped
     dense grid, for every brick of random worlds"""
-    out = _run(harness, "stamp", factor, X, Y, Z, rounds)
+    out = run_harness(harness, "stamp", factor, X, Y, Z, rounds)
     assert int(out.split(" changed")[0].split()[-1]) > 0
 
 

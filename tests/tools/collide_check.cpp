@@ -18,26 +18,14 @@ static void check_row(const vxrt::CollideWorld& W, int64_t x0, int y, int z);
 #define VXRT_COLLIDE_CHECK_ROW(W, x0, y, z) check_row(W, x0, y, z)
 
 #include "../../voxelengine_amd/csrc/vxrt_collide.hpp"
-extern "C" {
-#include "vxo.h"
-}
+#include "hbm_world.h"
 #include <cstdlib>
 #include <vector>
 using namespace vxrt;
 
-static int fails = 0;
 static uint64_t rows = 0;
 static int g_cy = 0;
 static uint64_t g_ncells = 0, g_pool_words = 0;
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            if (fails < 20)                                           \
-                printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);   \
-            ++fails;                                                  \
-        }                                                             \
-    } while (0)
-
 // the table indices region_row_word forms for this row, each checked against the tables' sizes
 static void check_row(const CollideWorld& W, int64_t x0, int y, int z)
 {
@@ -79,32 +67,13 @@ int main(int argc, char** argv)
         return 2;
     fclose(in);
 
-    // the oracle's brickmap in HBM order: cell records in HBM cell order, bricks in HBM bit order
+    // the oracle's brickmap in HBM order
     vxo_world* w = vxo_build_brickmap(dense.data(), X, Y, Z, f);
-    const int cx = w->cdims[0], cy = w->cdims[1], cz = w->cdims[2];
-    const uint32_t bw = (uint32_t)(f * f * f / 32);
-    std::vector<uint2> meta((size_t)w->ncells, make_uint2(kEmptySlot, 0u));
-    std::vector<uint32_t> pool((size_t)w->nslots * bw, 0u);
-    for (int bz = 0; bz < cz; ++bz) for (int by = 0; by < cy; ++by) for (int bx = 0; bx < cx; ++bx)
-        meta[hbm_index(bx, by, bz, cx, cz)].x = w->brick_slot[ref_tiled_index(bx, by, bz, cx / 8, cy / 8)];
-    for (uint64_t s = 0; s < w->nslots; ++s)
-        for (int z = 0; z < f; ++z) for (int y = 0; y < f; ++y) for (int x = 0; x < f; ++x) {
-            const uint32_t t = ref_tiled_index(x, y, z, f / 8, f / 8), i = (uint32_t)hbm_index(x, y, z, f, f);
-            if ((w->pool[s * bw + (t >> 5)] >> (t & 31)) & 1u) pool[s * bw + (i >> 5)] |= 1u << (i & 31);
-        }
-    g_cy = cy;
-    g_ncells = meta.size();
-    g_pool_words = pool.size();
-    CollideWorld W{};
-    W.meta = meta.data();
-    W.pool = pool.data();
-    W.f = f;
-    W.lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
-    W.cx = cx;
-    W.cz = cz;
-    W.dim[0] = X;
-    W.dim[1] = Y;
-    W.dim[2] = Z;
+    const HbmWorld h = to_hbm(w);
+    g_cy = h.cd[1];
+    g_ncells = h.meta.size();
+    g_pool_words = h.pool.size();
+    const CollideWorld W = h.world();
 
     std::vector<float> lohi((size_t)n * 6);
     std::vector<uint32_t> mflags((size_t)n), counts((size_t)n), oflags((size_t)n);

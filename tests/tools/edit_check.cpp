@@ -9,34 +9,12 @@ extern "C" {
 #include "vxo.h"
 #include "vxo_edit.h"
 }
+#include "hbm_world.h"
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
 using namespace vxrt;
-
-static int fails = 0;
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);       \
-            ++fails;                                                  \
-        }                                                             \
-    } while (0)
-
-// brick `slot` of an oracle world (tiled bits) in the HBM order of the library (x, z, y)
-static std::vector<uint32_t> hbm_brick(const vxo_world* w, uint32_t slot, int f)
-{
-    const uint32_t bw = f * f * f / 32;
-    std::vector<uint32_t> out(bw, 0u);
-    if (slot == VXO_EMPTY_SLOT)
-        return out;
-    for (int z = 0; z < f; ++z) for (int y = 0; y < f; ++y) for (int x = 0; x < f; ++x) {
-        const uint32_t t = ref_tiled_index(x, y, z, f / 8, f / 8), i = (uint32_t)hbm_index(x, y, z, f, f);
-        if ((w->pool[(size_t)slot * bw + (t >> 5)] >> (t & 31)) & 1u) out[i >> 5] |= 1u << (i & 31);
-    }
-    return out;
-}
 
 // what k_edit_bricks computes for the brick at cell (bx, by, bz), one voxel at a time
 static void edit_brick_host(const std::vector<EditOpDev>& ops, const std::vector<uint32_t>& old, int bx, int by, int bz, int f,
@@ -51,7 +29,7 @@ static void edit_brick_host(const std::vector<EditOpDev>& ops, const std::vector
     for (size_t k = first; k < ops.size(); ++k)
         if (edit_meets_brick(ops[k], b0, f))
             list.push_back(k);
-    const int fshift = f == 32 ? 5 : (f == 16 ? 4 : 3);
+    const int fshift = brick_shift(f);
     img.assign(old.size(), 0u);
     int mn[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, mx[3] = {-1, -1, -1};
     for (uint32_t o = 0; o < (uint32_t)(f * f * f); ++o) {

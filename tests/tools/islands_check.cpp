@@ -17,35 +17,10 @@ static void check_index(int array, uint64_t index);
 #define VXRT_ISL_CHECK(array, index) check_index(array, (uint64_t)(index))
 
 #include "../../voxelengine_amd/csrc/vxrt_islands.hpp"
-#include "../../voxelengine_amd/csrc/vxrt_region.hpp"
-extern "C" {
-#include "vxo.h"
-}
+#include "hbm_world.h"
 #include <cstdlib>
 #include <vector>
 using namespace vxrt;
-
-static int fails = 0;
-static uint64_t checked = 0;
-static uint64_t g_size[kIslTile + 1];
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            if (fails < 20)                                           \
-                printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);   \
-            ++fails;                                                  \
-        }                                                             \
-    } while (0)
-
-static void check_index(int array, uint64_t index)
-{
-    ++checked;
-    if (index >= g_size[array]) {
-        if (fails < 20)
-            printf("FAIL: index %llu of array %d (size %llu)\n", (unsigned long long)index, array, (unsigned long long)g_size[array]);
-        ++fails;
-    }
-}
 
 int main(int argc, char** argv)
 {
@@ -65,19 +40,9 @@ int main(int argc, char** argv)
         return 2;
     fclose(in);
 
-    // the oracle's brickmap in HBM order (as tests/tools/collide_check.cpp builds it)
+    // the oracle's brickmap in HBM order
     vxo_world* w = vxo_build_brickmap(dense.data(), X, Y, Z, f);
-    const int cx = w->cdims[0], cz = w->cdims[2];
-    const uint32_t bw = (uint32_t)(f * f * f / 32);
-    std::vector<uint2> meta((size_t)w->ncells, make_uint2(kEmptySlot, 0u));
-    std::vector<uint32_t> pool((size_t)w->nslots * bw, 0u);
-    for (int bz = 0; bz < cz; ++bz) for (int by = 0; by < w->cdims[1]; ++by) for (int bx = 0; bx < cx; ++bx)
-        meta[hbm_index(bx, by, bz, cx, cz)].x = w->brick_slot[ref_tiled_index(bx, by, bz, cx / 8, w->cdims[1] / 8)];
-    for (uint64_t s = 0; s < w->nslots; ++s)
-        for (int z = 0; z < f; ++z) for (int y = 0; y < f; ++y) for (int x = 0; x < f; ++x) {
-            const uint32_t t = ref_tiled_index(x, y, z, f / 8, f / 8), i = (uint32_t)hbm_index(x, y, z, f, f);
-            if ((w->pool[s * bw + (t >> 5)] >> (t & 31)) & 1u) pool[s * bw + (i >> 5)] |= 1u << (i & 31);
-        }
+    const HbmWorld h = to_hbm(w);
     vxo_world_free(w);
 
     IslandsLayout L;
@@ -125,17 +90,8 @@ int main(int argc, char** argv)
         A.anchor[k] = 0u;  // the memset
 
     // k_read_region: the box's words, clipped to the world before any load
-    const int lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
-    uint32_t* bits = ws + L.bits;
-    for (int z = 0; z < d[2]; ++z) for (int y = 0; y < d[1]; ++y) for (uint32_t xw = 0; xw < L.wpr; ++xw) {
-        const int64_t x0 = (int64_t)o[0] + 32 * (int64_t)xw, wy = (int64_t)o[1] + y, wz = (int64_t)o[2] + z;
-        uint32_t v = 0;
-        if (wy >= 0 && wy < Y && wz >= 0 && wz < Z && x0 + 31 >= 0 && x0 < X)
-            v = region_row_word(meta.data(), pool.data(), f, lgf, cx, cz, x0, (int)wy, (int)wz);
-        if (xw == L.wpr - 1 && (d[0] & 31))
-            v &= (1u << (d[0] & 31)) - 1u;
-        bits[xw + (uint64_t)L.wpr * (y + (uint64_t)d[1] * z)] = v;
-    }
+    const std::vector<uint32_t> box = read_host(h.world(), o, d);
+    std::copy(box.begin(), box.end(), ws + L.bits);
 
     // k_isl_local, tile by tile: the three phases of the workgroup, lane by lane
     const uint32_t ntx = L.wpr, nty = (d[1] + kIslTileY - 1) / kIslTileY, ntz = (d[2] + kIslTileZ - 1) / kIslTileZ;

@@ -17,34 +17,10 @@ static void check_index(int array, uint64_t index);
 #define VXRT_NAV_CHECK(array, index) check_index(array, (uint64_t)(index))
 
 #include "../../voxelengine_amd/csrc/vxrt_nav.hpp"
-extern "C" {
-#include "vxo.h"
-}
+#include "hbm_world.h"
 #include <cstdlib>
 #include <vector>
 using namespace vxrt;
-
-static int fails = 0;
-static uint64_t checked = 0;
-static uint64_t g_size[kNavLengths + 1];
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            if (fails < 20)                                           \
-                printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);   \
-            ++fails;                                                  \
-        }                                                             \
-    } while (0)
-
-static void check_index(int array, uint64_t index)
-{
-    ++checked;
-    if (index >= g_size[array]) {
-        if (fails < 20)
-            printf("FAIL: index %llu of array %d (size %llu)\n", (unsigned long long)index, array, (unsigned long long)g_size[array]);
-        ++fails;
-    }
-}
 
 int main(int argc, char** argv)
 {
@@ -67,19 +43,9 @@ int main(int argc, char** argv)
         return 2;
     fclose(in);
 
-    // the oracle's brickmap in HBM order (as tests/tools/islands_check.cpp builds it)
+    // the oracle's brickmap in HBM order
     vxo_world* w = vxo_build_brickmap(dense.data(), X, Y, Z, f);
-    const int cx = w->cdims[0], cz = w->cdims[2];
-    const uint32_t bw = (uint32_t)(f * f * f / 32);
-    std::vector<uint2> meta((size_t)w->ncells, make_uint2(kEmptySlot, 0u));
-    std::vector<uint32_t> pool((size_t)w->nslots * bw, 0u);
-    for (int bz = 0; bz < cz; ++bz) for (int by = 0; by < w->cdims[1]; ++by) for (int bx = 0; bx < cx; ++bx)
-        meta[hbm_index(bx, by, bz, cx, cz)].x = w->brick_slot[ref_tiled_index(bx, by, bz, cx / 8, w->cdims[1] / 8)];
-    for (uint64_t s = 0; s < w->nslots; ++s)
-        for (int z = 0; z < f; ++z) for (int y = 0; y < f; ++y) for (int x = 0; x < f; ++x) {
-            const uint32_t t = ref_tiled_index(x, y, z, f / 8, f / 8), i = (uint32_t)hbm_index(x, y, z, f, f);
-            if ((w->pool[s * bw + (t >> 5)] >> (t & 31)) & 1u) pool[s * bw + (i >> 5)] |= 1u << (i & 31);
-        }
+    const HbmWorld h = to_hbm(w);
     vxo_world_free(w);
 
     NavLayout L;
@@ -152,18 +118,11 @@ int main(int argc, char** argv)
     for (uint32_t k = 0; k < L.nvox; ++k) A.dist[k] = kNavUnreached;
 
     // k_read_region of the halo: clipped to the world before any load
-    const int lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
-    const int32_t ho[3] = {o[0], o[1] - 1, o[2]}, hx = d[0] + aw - 1;
-    uint32_t* halo = ws + L.halo;
-    for (uint32_t z = 0; z < L.hz; ++z) for (uint32_t y = 0; y < L.hy; ++y) for (uint32_t xw = 0; xw < L.wh; ++xw) {
-        const int64_t x0 = (int64_t)ho[0] + 32 * (int64_t)xw, wy = (int64_t)ho[1] + y, wz = (int64_t)ho[2] + z;
-        uint32_t v = 0;
-        if (wy >= 0 && wy < Y && wz >= 0 && wz < Z && x0 + 31 >= 0 && x0 < X)
-            v = region_row_word(meta.data(), pool.data(), f, lgf, cx, cz, x0, (int)wy, (int)wz);
-        if (xw == L.wh - 1 && (hx & 31))
-            v &= (1u << (hx & 31)) - 1u;
-        check_index(kNavHalo, xw + (uint64_t)L.wh * (y + (uint64_t)L.hy * z));
-        halo[xw + (uint64_t)L.wh * (y + (uint64_t)L.hy * z)] = v;
+    const int32_t ho[3] = {o[0], o[1] - 1, o[2]}, hdim[3] = {d[0] + aw - 1, (int32_t)L.hy, (int32_t)L.hz};
+    const std::vector<uint32_t> halo = read_host(h.world(), ho, hdim);
+    for (uint64_t i = 0; i < halo.size(); ++i) {
+        check_index(kNavHalo, i);
+        ws[L.halo + i] = halo[i];
     }
 
     // k_nav_xpass, k_nav_ypass, k_nav_zpass

@@ -11,82 +11,12 @@ extern "C" {
 #include "vxo.h"
 #include "vxo_region.h"
 }
+#include "hbm_world.h"
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
 using namespace vxrt;
-
-static int fails = 0;
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);       \
-            ++fails;                                                  \
-        }                                                             \
-    } while (0)
-
-// an oracle world (tiled tables) as the library holds it in HBM: cell records in HBM cell order, bricks in HBM bit order
-struct HbmWorld {
-    int f, cx, cy, cz;
-    std::vector<uint2> meta;
-    std::vector<uint32_t> pool;
-};
-
-static HbmWorld to_hbm(const vxo_world* w)
-{
-    HbmWorld h;
-    h.f = w->factor;
-    h.cx = w->cdims[0];
-    h.cy = w->cdims[1];
-    h.cz = w->cdims[2];
-    const int f = h.f;
-    const uint32_t bw = f * f * f / 32;
-    h.meta.assign((size_t)w->ncells, make_uint2(kEmptySlot, 0u));
-    h.pool.assign((size_t)w->nslots * bw, 0u);
-    for (int bz = 0; bz < h.cz; ++bz) for (int by = 0; by < h.cy; ++by) for (int bx = 0; bx < h.cx; ++bx) {
-        const uint32_t t = ref_tiled_index(bx, by, bz, h.cx / 8, h.cy / 8);
-        h.meta[hbm_index(bx, by, bz, h.cx, h.cz)].x = w->brick_slot[t];
-    }
-    for (uint64_t s = 0; s < w->nslots; ++s)
-        for (int z = 0; z < f; ++z) for (int y = 0; y < f; ++y) for (int x = 0; x < f; ++x) {
-            const uint32_t t = ref_tiled_index(x, y, z, f / 8, f / 8), i = (uint32_t)hbm_index(x, y, z, f, f);
-            if ((w->pool[s * bw + (t >> 5)] >> (t & 31)) & 1u) h.pool[s * bw + (i >> 5)] |= 1u << (i & 31);
-        }
-    return h;
-}
-
-// brick `slot` of an oracle world in HBM bit order (zeros for an empty cell)
-static std::vector<uint32_t> hbm_brick(const vxo_world* w, uint32_t slot, int f)
-{
-    const uint32_t bw = f * f * f / 32;
-    std::vector<uint32_t> out(bw, 0u);
-    if (slot == VXO_EMPTY_SLOT)
-        return out;
-    for (int z = 0; z < f; ++z) for (int y = 0; y < f; ++y) for (int x = 0; x < f; ++x) {
-        const uint32_t t = ref_tiled_index(x, y, z, f / 8, f / 8), i = (uint32_t)hbm_index(x, y, z, f, f);
-        if ((w->pool[(size_t)slot * bw + (t >> 5)] >> (t & 31)) & 1u) out[i >> 5] |= 1u << (i & 31);
-    }
-    return out;
-}
-
-// what k_read_region computes for every word of the region (the kernel's clipping, then region_row_word and the pad mask)
-static std::vector<uint32_t> read_host(const HbmWorld& h, const int32_t o[3], const int32_t d[3])
-{
-    const int f = h.f, lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
-    const int64_t X = (int64_t)h.cx * f, Y = (int64_t)h.cy * f, Z = (int64_t)h.cz * f;
-    const uint64_t wpr = region_words_per_row(d[0]);
-    const uint32_t pad = (d[0] & 31) ? (1u << (d[0] & 31)) - 1u : 0xFFFFFFFFu;
-    std::vector<uint32_t> out(region_words(d), 0xDEADBEEFu);
-    for (int64_t zl = 0; zl < d[2]; ++zl) for (int64_t yl = 0; yl < d[1]; ++yl) for (uint64_t xw = 0; xw < wpr; ++xw) {
-        const int64_t x0 = (int64_t)o[0] + 32 * (int64_t)xw, wy = (int64_t)o[1] + yl, wz = (int64_t)o[2] + zl;
-        uint32_t w = 0u;
-        if (wy >= 0 && wy < Y && wz >= 0 && wz < Z && x0 + 31 >= 0 && x0 < X)
-            w = region_row_word(h.meta.data(), h.pool.data(), f, lgf, h.cx, h.cz, x0, (int)wy, (int)wz);
-        out[((uint64_t)yl + (uint64_t)d[1] * zl) * wpr + xw] = w & (xw == wpr - 1 ? pad : 0xFFFFFFFFu);
-    }
-    return out;
-}
 
 // what k_stamp_bricks computes for the brick at cell (bx, by, bz): the filter, one word of rows per lane, the extents
 static void stamp_brick_host(const std::vector<StampDev>& st, const std::vector<uint32_t>& old, int bx, int by, int bz, int f,
@@ -101,7 +31,7 @@ static void stamp_brick_host(const std::vector<StampDev>& st, const std::vector<
     for (size_t k = first; k < st.size(); ++k)
         if (stamp_meets_brick(st[k], b0, f))
             list.push_back(k);
-    const int lgf = f == 32 ? 5 : (f == 16 ? 4 : 3), rpw = 32 >> lgf;
+    const int lgf = brick_shift(f), rpw = 32 >> lgf;
     const uint32_t fmask = f == 32 ? 0xFFFFFFFFu : (1u << f) - 1u;
     img.assign(old.size(), 0u);
     int mn[2] = {0x7FFFFFFF, 0x7FFFFFFF}, mx[2] = {-1, -1};
@@ -165,7 +95,7 @@ static void check_read(int f, int X, int Y, int Z, int rounds, unsigned seed)
             if (q == 0) { o[0] = -5; o[1] = -7; o[2] = -9; d[0] = X + 10; d[1] = std::min(Y + 14, 40); d[2] = 3; }  // every face
             if (q == 1) { o[0] = X; o[1] = 0; o[2] = 0; d[0] = 40; d[1] = 3; d[2] = 3; }                           // wholly outside
             if (q == 2) { o[0] = X / 2; o[1] = Y / 2; o[2] = Z / 2; d[0] = d[1] = d[2] = 1; }                    // one voxel
-            const std::vector<uint32_t> got = read_host(h, o, d);
+            const std::vector<uint32_t> got = read_host(h.world(), o, d);
             std::vector<uint32_t> want(got.size(), 0u);
             CHECK(vxo_read_region(dense.data(), X, Y, Z, o, d, want.data()) == 0);
             CHECK(got == want);

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <new>
 #include <set>
@@ -40,24 +41,22 @@ hipError_t edit_bricks(const uint32_t* cells, uint32_t n, const EditOpDev* ops, 
 hipError_t edit_commit(const uint32_t* cells, const uint32_t* new_slot, uint32_t n, const uint32_t* zero, uint32_t nzero,
                        const uint32_t* scratch, const uint32_t* ext, uint32_t* pool, uint2* meta, uint32_t* coarse, int f);
 hipError_t gather_bricks(const uint32_t* pool, const uint32_t* idx, uint32_t n, uint32_t* dst, int f);
-// region readback and voxel stamps (vxrt_region.hip)
-hipError_t read_region(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                       uint32_t* out, hipStream_t stream);
+// voxel stamps (vxrt_region.hip; read_region: vxrt_region.hpp)
 hipError_t stamp_bricks(const uint32_t* cells, uint32_t n, const StampDev* stamps, uint32_t nst, const uint2* meta,
                         const uint32_t* pool, uint32_t* scratch, uint32_t* ext, uint2* info, int f, int cx, int cz);
 // box collision queries (vxrt_collide.hip)
-hipError_t move_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
-                      const int order[3], float* lohi, uint32_t* flags, hipStream_t stream);
-hipError_t overlap_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
-                         uint32_t* counts, uint32_t* flags, hipStream_t stream);
+hipError_t move_boxes(const CollideWorld& W, const float* bodies, uint64_t n, const int order[3], float* lohi, uint32_t* flags,
+                      hipStream_t stream);
+hipError_t overlap_boxes(const CollideWorld& W, const float* bodies, uint64_t n, uint32_t* counts, uint32_t* flags,
+                         hipStream_t stream);
 // floating islands (vxrt_islands.hip)
-hipError_t find_islands(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                        uint32_t anchors, void* work, uint32_t* floating, uint32_t* labels, vxrt_island* table,
-                        uint32_t max_islands, vxrt_island_summary* summary, hipStream_t stream);
+hipError_t find_islands(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t anchors, void* work,
+                        uint32_t* floating, uint32_t* labels, vxrt_island* table, uint32_t max_islands,
+                        vxrt_island_summary* summary, hipStream_t stream);
 // navigation fields (vxrt_nav.hip)
-hipError_t nav_field(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                     const vxrt_nav_agent& ag, const int32_t* goals, uint32_t ngoals, uint32_t max_dist, void* work,
-                     uint32_t* walkable, uint8_t* next, uint32_t* dist, vxrt_nav_summary* summary, hipStream_t stream);
+hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], const vxrt_nav_agent& ag, const int32_t* goals,
+                     uint32_t ngoals, uint32_t max_dist, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
+                     vxrt_nav_summary* summary, hipStream_t stream);
 hipError_t nav_paths(const NavPathArgs& P, hipStream_t stream);
 }  // namespace vxrt
 
@@ -1782,6 +1781,57 @@ static int edit_run(vxrt_ctx* c, const std::vector<Op>& ops, Launch launch, vxrt
     return finish();
 }
 
+// ---- what the calls on the resident world share (edits, stamps, reads, collision, islands, navigation) -----------------
+
+// the checks every call on the resident world makes after its argument checks, in the order of include/vxrt.h: a world
+// resident, and not a streamed one (`verb`: what the call would do to it)
+static int world_ready(const vxrt_ctx* c, const char* verb)
+{
+    if (!c->has_world)
+        return fail(VXRT_ERR_NO_WORLD, "no world resident");
+    if (c->stream)
+        return fail(VXRT_ERR_INVALID, std::string("a streamed world (vxrt_stream_open) is a cache: it is not ") + verb);
+    return VXRT_OK;
+}
+
+// origin + dims of a box within int32 on every axis (`what`: the message's subject)
+static int box_in_range(const int32_t origin[3], const int32_t dims[3], const char* what)
+{
+    for (int k = 0; k < 3; ++k)
+        if ((int64_t)origin[k] + dims[k] > INT32_MAX)
+            return fail(VXRT_ERR_INVALID, std::string(what) + ": origin + dims beyond 2^31 - 1");
+    return VXRT_OK;
+}
+
+// the resident world as the query kernels read it
+static CollideWorld query_world(const vxrt_ctx* c)
+{
+    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
+    return query_world(c->d_meta, c->d_pool, c->view.f, cd);
+}
+
+// the device memory of a _host call: one allocation, cut into sections that start on 256-byte boundaries, freed on every path
+struct HostScratch {
+    char* base = nullptr;
+    size_t off[8] = {};
+    ~HostScratch() { (void)hipFree(base); }
+    // sections of these sizes in bytes (at most 8); the allocation's error is also cleared from hipGetLastError
+    hipError_t alloc(std::initializer_list<size_t> bytes)
+    {
+        size_t total = 0, k = 0;
+        for (size_t b : bytes) {
+            off[k++] = total;
+            total += section_up(b);
+        }
+        const hipError_t e = hipMalloc((void**)&base, total);
+        if (e != hipSuccess)
+            (void)hipGetLastError();
+        return e;
+    }
+    template <class T>
+    T* at(int k) const { return reinterpret_cast<T*>(base + off[k]); }
+};
+
 }  // namespace vxrt
 
 extern "C" {
@@ -1808,10 +1858,8 @@ int vxrt_edit_voxels(vxrt_ctx* c, const vxrt_edit_op* ops, uint32_t n_ops, vxrt_
         if (!noop)
             dev.push_back(d);
     }
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
+    if (int rc = vxrt::world_ready(c, "edited"))
+        return rc;
     auto launch = [&](const uint32_t* d_cells, uint32_t n, const EditOpDev* d_ops, uint32_t nops, uint32_t* d_img,
                       uint32_t* d_ext, uint2* d_info) {
         return vxrt::edit_bricks(d_cells, n, d_ops, nops, c->d_meta, c->d_pool, d_img, d_ext, d_info, f, c->view.cx, c->view.cz);
@@ -1830,13 +1878,10 @@ int vxrt_read_region(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3]
         return fail(VXRT_ERR_INVALID, "NULL argument");
     if (vxrt::region_words(dims) == 0)
         return fail(VXRT_ERR_INVALID, "region dims: each at least 1, at most 2^36 voxels");
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not read");
+    if (int rc = vxrt::world_ready(c, "read"))
+        return rc;
     VX_HIP(hipSetDevice(c->device));
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::read_region(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, d_bits, (hipStream_t)stream));
+    VX_HIP(vxrt::read_region(vxrt::query_world(c), origin, dims, d_bits, (hipStream_t)stream));
     return VXRT_OK;
 }
 
@@ -1847,23 +1892,15 @@ int vxrt_read_region_host(vxrt_ctx* c, const int32_t origin[3], const int32_t di
     const uint64_t words = vxrt::region_words(dims);
     if (words == 0)
         return fail(VXRT_ERR_INVALID, "region dims: each at least 1, at most 2^36 voxels");
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not read");
+    if (int rc = vxrt::world_ready(c, "read"))
+        return rc;
     VX_HIP(hipSetDevice(c->device));
-    struct Temp {
-        uint32_t* p = nullptr;
-        ~Temp() { (void)hipFree(p); }
-    } T;
-    hipError_t e = hipMalloc((void**)&T.p, words * 4);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({words * 4}))
         return fail(VXRT_ERR_NOMEM, std::string("region read of ") + std::to_string(words) + " words: " + hipGetErrorString(e));
-    }
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::read_region(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, T.p, nullptr));
-    VX_HIP(hipMemcpy(bits, T.p, words * 4, hipMemcpyDeviceToHost));
+    uint32_t* d_bits = T.at<uint32_t>(0);
+    VX_HIP(vxrt::read_region(vxrt::query_world(c), origin, dims, d_bits, nullptr));
+    VX_HIP(hipMemcpy(bits, d_bits, words * 4, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }
@@ -1891,10 +1928,8 @@ int vxrt_edit_stamps(vxrt_ctx* c, const vxrt_stamp* stamps, uint32_t n_stamps, v
         if (!noop)
             dev.push_back(d);
     }
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
+    if (int rc = vxrt::world_ready(c, "edited"))
+        return rc;
     auto launch = [&](const uint32_t* d_cells, uint32_t n, const StampDev* d_st, uint32_t nst, uint32_t* d_img,
                       uint32_t* d_ext, uint2* d_info) {
         return vxrt::stamp_bricks(d_cells, n, d_st, nst, c->d_meta, c->d_pool, d_img, d_ext, d_info, f, c->view.cx, c->view.cz);
@@ -1917,16 +1952,6 @@ static bool collide_order(const int32_t* order, int out[3])
     return seen == 7u;
 }
 
-// the checks every collision call makes after ctx / order / n, in the order of include/vxrt.h
-static int collide_ready(vxrt_ctx* c)
-{
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not queried");
-    return VXRT_OK;
-}
-
 int vxrt_move_boxes(vxrt_ctx* c, const vxrt_body* d_bodies, uint64_t n, const int32_t order[3], float* d_lohi_out,
                     uint32_t* d_flags_or_null, void* stream)
 {
@@ -1939,11 +1964,10 @@ int vxrt_move_boxes(vxrt_ctx* c, const vxrt_body* d_bodies, uint64_t n, const in
         return VXRT_OK;
     if (!d_bodies || !d_lohi_out)
         return fail(VXRT_ERR_INVALID, "NULL argument");
-    if (int rc = collide_ready(c))
+    if (int rc = vxrt::world_ready(c, "queried"))
         return rc;
     VX_HIP(hipSetDevice(c->device));
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::move_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)d_bodies, n, ord, d_lohi_out, d_flags_or_null,
+    VX_HIP(vxrt::move_boxes(vxrt::query_world(c), (const float*)d_bodies, n, ord, d_lohi_out, d_flags_or_null,
                             (hipStream_t)stream));
     return VXRT_OK;
 }
@@ -1957,20 +1981,12 @@ int vxrt_overlap_boxes(vxrt_ctx* c, const vxrt_body* d_bodies, uint64_t n, uint3
         return VXRT_OK;
     if (!d_bodies || !d_counts)
         return fail(VXRT_ERR_INVALID, "NULL argument");
-    if (int rc = collide_ready(c))
+    if (int rc = vxrt::world_ready(c, "queried"))
         return rc;
     VX_HIP(hipSetDevice(c->device));
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::overlap_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)d_bodies, n, d_counts, d_flags_or_null,
-                               (hipStream_t)stream));
+    VX_HIP(vxrt::overlap_boxes(vxrt::query_world(c), (const float*)d_bodies, n, d_counts, d_flags_or_null, (hipStream_t)stream));
     return VXRT_OK;
 }
-
-// device copies of the bodies and the results of a host call, freed on every path
-struct CollideTemp {
-    void* p = nullptr;
-    ~CollideTemp() { (void)hipFree(p); }
-};
 
 int vxrt_move_boxes_host(vxrt_ctx* c, const vxrt_body* bodies, uint64_t n, const int32_t order[3], float* lohi_out,
                          uint32_t* flags_or_null)
@@ -1984,26 +2000,22 @@ int vxrt_move_boxes_host(vxrt_ctx* c, const vxrt_body* bodies, uint64_t n, const
         return VXRT_OK;
     if (!bodies || !lohi_out)
         return fail(VXRT_ERR_INVALID, "NULL argument");
-    if (int rc = collide_ready(c))
+    if (int rc = vxrt::world_ready(c, "queried"))
         return rc;
     if (n > (1ull << 36))
         return fail(VXRT_ERR_INVALID, "too many bodies for one host call");
     VX_HIP(hipSetDevice(c->device));
-    CollideTemp T;
+    vxrt::HostScratch T;
     const size_t bb = (size_t)n * sizeof(vxrt_body), ob = (size_t)n * 24, fb = (size_t)n * 4;
-    hipError_t e = hipMalloc(&T.p, bb + ob + fb);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    if (hipError_t e = T.alloc({bb, ob, fb}))
         return fail(VXRT_ERR_NOMEM, std::string("move_boxes_host: ") + hipGetErrorString(e));
-    }
-    char* base = (char*)T.p;
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(hipMemcpy(base, bodies, bb, hipMemcpyHostToDevice));
-    VX_HIP(vxrt::move_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)base, n, ord, (float*)(base + bb),
-                            (uint32_t*)(base + bb + ob), nullptr));
-    VX_HIP(hipMemcpy(lohi_out, base + bb, ob, hipMemcpyDeviceToHost));
+    float *d_bodies = T.at<float>(0), *d_lohi = T.at<float>(1);
+    uint32_t* d_flags = T.at<uint32_t>(2);
+    VX_HIP(hipMemcpy(d_bodies, bodies, bb, hipMemcpyHostToDevice));
+    VX_HIP(vxrt::move_boxes(vxrt::query_world(c), d_bodies, n, ord, d_lohi, d_flags, nullptr));
+    VX_HIP(hipMemcpy(lohi_out, d_lohi, ob, hipMemcpyDeviceToHost));
     if (flags_or_null)
-        VX_HIP(hipMemcpy(flags_or_null, base + bb + ob, fb, hipMemcpyDeviceToHost));
+        VX_HIP(hipMemcpy(flags_or_null, d_flags, fb, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }
@@ -2016,26 +2028,22 @@ int vxrt_overlap_boxes_host(vxrt_ctx* c, const vxrt_body* bodies, uint64_t n, ui
         return VXRT_OK;
     if (!bodies || !counts)
         return fail(VXRT_ERR_INVALID, "NULL argument");
-    if (int rc = collide_ready(c))
+    if (int rc = vxrt::world_ready(c, "queried"))
         return rc;
     if (n > (1ull << 36))
         return fail(VXRT_ERR_INVALID, "too many bodies for one host call");
     VX_HIP(hipSetDevice(c->device));
-    CollideTemp T;
+    vxrt::HostScratch T;
     const size_t bb = (size_t)n * sizeof(vxrt_body), cb = (size_t)n * 4;
-    hipError_t e = hipMalloc(&T.p, bb + 2 * cb);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    if (hipError_t e = T.alloc({bb, cb, cb}))
         return fail(VXRT_ERR_NOMEM, std::string("overlap_boxes_host: ") + hipGetErrorString(e));
-    }
-    char* base = (char*)T.p;
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(hipMemcpy(base, bodies, bb, hipMemcpyHostToDevice));
-    VX_HIP(vxrt::overlap_boxes(c->d_meta, c->d_pool, c->view.f, cd, (const float*)base, n, (uint32_t*)(base + bb),
-                               (uint32_t*)(base + bb + cb), nullptr));
-    VX_HIP(hipMemcpy(counts, base + bb, cb, hipMemcpyDeviceToHost));
+    float* d_bodies = T.at<float>(0);
+    uint32_t *d_counts = T.at<uint32_t>(1), *d_flags = T.at<uint32_t>(2);
+    VX_HIP(hipMemcpy(d_bodies, bodies, bb, hipMemcpyHostToDevice));
+    VX_HIP(vxrt::overlap_boxes(vxrt::query_world(c), d_bodies, n, d_counts, d_flags, nullptr));
+    VX_HIP(hipMemcpy(counts, d_counts, cb, hipMemcpyDeviceToHost));
     if (flags_or_null)
-        VX_HIP(hipMemcpy(flags_or_null, base + bb + cb, cb, hipMemcpyDeviceToHost));
+        VX_HIP(hipMemcpy(flags_or_null, d_flags, cb, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }
@@ -2053,16 +2061,11 @@ static int islands_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dim
     vxrt::IslandsLayout L;
     if (!vxrt::islands_layout(dims, L))
         return fail(VXRT_ERR_INVALID, "island box dims: each at least 1, at most 2^28 voxels");
-    for (int k = 0; k < 3; ++k)
-        if ((int64_t)origin[k] + dims[k] > INT32_MAX)
-            return fail(VXRT_ERR_INVALID, "island box: origin + dims beyond 2^31 - 1");
+    if (int rc = vxrt::box_in_range(origin, dims, "island box"))
+        return rc;
     if (anchors & ~vxrt::kIslAnchorMask)
         return fail(VXRT_ERR_INVALID, "anchors: only VXRT_ISLAND_ANCHOR_* bits");
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not queried");
-    return VXRT_OK;
+    return vxrt::world_ready(c, "queried");
 }
 
 int vxrt_find_islands(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t anchors, void* d_work,
@@ -2074,9 +2077,8 @@ int vxrt_find_islands(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3
     if (int rc = islands_ready(c, origin, dims, anchors))
         return rc;
     VX_HIP(hipSetDevice(c->device));
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::find_islands(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, anchors, d_work, d_floating, d_labels_or_null,
-                              d_islands_or_null, max_islands, d_summary, (hipStream_t)stream));
+    VX_HIP(vxrt::find_islands(vxrt::query_world(c), origin, dims, anchors, d_work, d_floating, d_labels_or_null, d_islands_or_null,
+                              max_islands, d_summary, (hipStream_t)stream));
     return VXRT_OK;
 }
 
@@ -2093,22 +2095,14 @@ int vxrt_find_islands_host(vxrt_ctx* c, const int32_t origin[3], const int32_t d
     vxrt::islands_layout(dims, L);
     const size_t fb = (size_t)vxrt::region_words(dims) * 4u, lb = labels_or_null ? (size_t)L.nvox * 4u : 0;
     const size_t tb = islands_or_null ? (size_t)max_islands * sizeof(vxrt_island) : 0;
-    auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
-    CollideTemp T;
-    hipError_t e = hipMalloc(&T.p, up(L.total_bytes) + up(fb) + up(lb) + up(tb) + sizeof(vxrt_island_summary));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, fb, lb, tb, sizeof(vxrt_island_summary)}))
         return fail(VXRT_ERR_NOMEM, std::string("find_islands_host: ") + hipGetErrorString(e));
-    }
-    char* base = (char*)T.p;
-    char* d_float = base + up(L.total_bytes);
-    char* d_lab = d_float + up(fb);
-    char* d_tab = d_lab + up(lb);
-    char* d_sum = d_tab + up(tb);
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::find_islands(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, anchors, base, (uint32_t*)d_float,
-                              labels_or_null ? (uint32_t*)d_lab : nullptr, islands_or_null ? (vxrt_island*)d_tab : nullptr,
-                              islands_or_null ? max_islands : 0u, (vxrt_island_summary*)d_sum, nullptr));
+    uint32_t *d_float = T.at<uint32_t>(1), *d_lab = T.at<uint32_t>(2);
+    vxrt_island* d_tab = T.at<vxrt_island>(3);
+    vxrt_island_summary* d_sum = T.at<vxrt_island_summary>(4);
+    VX_HIP(vxrt::find_islands(vxrt::query_world(c), origin, dims, anchors, T.base, d_float, labels_or_null ? d_lab : nullptr,
+                              islands_or_null ? d_tab : nullptr, islands_or_null ? max_islands : 0u, d_sum, nullptr));
     VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_island_summary), hipMemcpyDeviceToHost));
     VX_HIP(hipMemcpy(floating, d_float, fb, hipMemcpyDeviceToHost));
     if (labels_or_null)
@@ -2138,18 +2132,13 @@ static int nav_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3]
         return fail(VXRT_ERR_INVALID, "nav agent: 1 <= width <= 8, 1 <= height <= 32, 0 <= climb <= 8, 0 <= drop <= 32");
     if (!vxrt::nav_layout(dims, ag->width, ag->height, ag->climb, ag->drop, L))
         return fail(VXRT_ERR_INVALID, "nav box dims: each at least 1, at most 2^28 cells");
-    for (int k = 0; k < 3; ++k)
-        if ((int64_t)origin[k] + dims[k] > INT32_MAX)
-            return fail(VXRT_ERR_INVALID, "nav box: origin + dims beyond 2^31 - 1");
+    if (int rc = vxrt::box_in_range(origin, dims, "nav box"))
+        return rc;
     if (max_dist < 1 || max_dist > vxrt::kNavMaxDist)
         return fail(VXRT_ERR_INVALID, "nav max_dist: 1 .. 2^24");
     if (n_goals > vxrt::kNavMaxGoals)
         return fail(VXRT_ERR_INVALID, "nav goals: at most VXRT_NAV_MAX_GOALS");
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not queried");
-    return VXRT_OK;
+    return vxrt::world_ready(c, "queried");
 }
 
 int vxrt_nav_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent* agent,
@@ -2161,9 +2150,8 @@ int vxrt_nav_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], 
     if (int rc = nav_ready(c, origin, dims, agent, n_goals, max_dist))
         return rc;
     VX_HIP(hipSetDevice(c->device));
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::nav_field(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, *agent, d_goals, n_goals, max_dist, d_work,
-                           d_walkable, d_next, d_dist_or_null, d_summary, (hipStream_t)stream));
+    VX_HIP(vxrt::nav_field(vxrt::query_world(c), origin, dims, *agent, d_goals, n_goals, max_dist, d_work, d_walkable, d_next,
+                           d_dist_or_null, d_summary, (hipStream_t)stream));
     return VXRT_OK;
 }
 
@@ -2179,25 +2167,17 @@ int vxrt_nav_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims
     vxrt::NavLayout L;
     vxrt::nav_layout(dims, agent->width, agent->height, agent->climb, agent->drop, L);
     const size_t wb = (size_t)L.nb * 4u, nb = L.nvox, db = dist_or_null ? (size_t)L.nvox * 4u : 0, gb = (size_t)n_goals * 12u;
-    auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
-    CollideTemp T;
-    hipError_t e = hipMalloc(&T.p, up(L.total_bytes) + up(wb) + up(nb) + up(db) + up(gb) + sizeof(vxrt_nav_summary));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, wb, nb, db, gb, sizeof(vxrt_nav_summary)}))
         return fail(VXRT_ERR_NOMEM, std::string("nav_field_host: ") + hipGetErrorString(e));
-    }
-    char* base = (char*)T.p;
-    char* d_walk = base + up(L.total_bytes);
-    char* d_next = d_walk + up(wb);
-    char* d_dist = d_next + up(nb);
-    char* d_goals = d_dist + up(db);
-    char* d_sum = d_goals + up(gb);
+    uint32_t *d_walk = T.at<uint32_t>(1), *d_dist = T.at<uint32_t>(3);
+    uint8_t* d_next = T.at<uint8_t>(2);
+    int32_t* d_goals = T.at<int32_t>(4);
+    vxrt_nav_summary* d_sum = T.at<vxrt_nav_summary>(5);
     if (n_goals)
         VX_HIP(hipMemcpy(d_goals, goals, gb, hipMemcpyHostToDevice));
-    const int cd[3] = {c->view.cx, c->view.cy, c->view.cz};
-    VX_HIP(vxrt::nav_field(c->d_meta, c->d_pool, c->view.f, cd, origin, dims, *agent, (const int32_t*)d_goals, n_goals, max_dist,
-                           base, (uint32_t*)d_walk, (uint8_t*)d_next, dist_or_null ? (uint32_t*)d_dist : nullptr,
-                           (vxrt_nav_summary*)d_sum, nullptr));
+    VX_HIP(vxrt::nav_field(vxrt::query_world(c), origin, dims, *agent, d_goals, n_goals, max_dist, T.base, d_walk, d_next,
+                           dist_or_null ? d_dist : nullptr, d_sum, nullptr));
     VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_nav_summary), hipMemcpyDeviceToHost));
     VX_HIP(hipMemcpy(walkable, d_walk, wb, hipMemcpyDeviceToHost));
     VX_HIP(hipMemcpy(next, d_next, nb, hipMemcpyDeviceToHost));
@@ -2216,9 +2196,8 @@ int vxrt_nav_paths(vxrt_ctx* c, const vxrt_nav_field_desc* field, const int32_t*
     const vxrt_nav_agent& ag = field->agent;
     if (!vxrt::nav_layout(field->dims, ag.width, ag.height, ag.climb, ag.drop, L))
         return fail(VXRT_ERR_INVALID, "nav field: bad dims or agent");
-    for (int k = 0; k < 3; ++k)
-        if ((int64_t)field->origin[k] + field->dims[k] > INT32_MAX)
-            return fail(VXRT_ERR_INVALID, "nav field: origin + dims beyond 2^31 - 1");
+    if (int rc = vxrt::box_in_range(field->origin, field->dims, "nav field"))
+        return rc;
     if (max_steps > vxrt::kNavMaxSteps)
         return fail(VXRT_ERR_INVALID, "nav paths: max_steps above 65535");
     if (n == 0)
@@ -2246,10 +2225,8 @@ int vxrt_edit_reserve(vxrt_ctx* c, uint64_t capacity_bricks)
 {
     if (!c)
         return fail(VXRT_ERR_INVALID, "ctx is NULL");
-    if (!c->has_world)
-        return fail(VXRT_ERR_NO_WORLD, "no world resident");
-    if (c->stream)
-        return fail(VXRT_ERR_INVALID, "a streamed world (vxrt_stream_open) is a cache: it is not edited");
+    if (int rc = vxrt::world_ready(c, "edited"))
+        return rc;
     if (capacity_bricks >= (1ull << 32) - 2)
         return fail(VXRT_ERR_INVALID, "capacity beyond 32-bit slot numbers");
     if (capacity_bricks <= c->pool_capacity_slots)

@@ -48,20 +48,6 @@ __global__ __launch_bounds__(256) void k_overlap_boxes(const CollideWorld W, con
     }
 }
 
-static CollideWorld collide_world(const uint2* meta, const uint32_t* pool, int f, const int cd[3])
-{
-    CollideWorld W{};
-    W.meta = meta;
-    W.pool = pool;
-    W.f = f;
-    W.lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
-    W.cx = cd[0];
-    W.cz = cd[2];
-    for (int k = 0; k < 3; ++k)
-        W.dim[k] = cd[k] * f;
-    return W;
-}
-
 // up to 64 K workgroups of 256 lanes; a grid-stride loop covers larger batches
 static unsigned collide_blocks(uint64_t n)
 {
@@ -69,20 +55,19 @@ static unsigned collide_blocks(uint64_t n)
     return (unsigned)(b > 65536 ? 65536 : (b ? b : 1));
 }
 
-// host entry points (vxrt_api.hip): the world is f, cd (cells per axis), meta / pool in HBM order; n > 0
-hipError_t move_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
-                      const int order[3], float* lohi, uint32_t* flags, hipStream_t stream)
+// host entry points (vxrt_api.hip); n > 0
+hipError_t move_boxes(const CollideWorld& W, const float* bodies, uint64_t n, const int order[3], float* lohi, uint32_t* flags,
+                      hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_move_boxes, dim3(collide_blocks(n)), dim3(256), 0, stream, collide_world(meta, pool, f, cd), bodies,
-                       n, order[0], order[1], order[2], lohi, flags);
+    hipLaunchKernelGGL(k_move_boxes, dim3(collide_blocks(n)), dim3(256), 0, stream, W, bodies, n, order[0], order[1], order[2],
+                       lohi, flags);
     return hipGetLastError();
 }
 
-hipError_t overlap_boxes(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const float* bodies, uint64_t n,
-                         uint32_t* counts, uint32_t* flags, hipStream_t stream)
+hipError_t overlap_boxes(const CollideWorld& W, const float* bodies, uint64_t n, uint32_t* counts, uint32_t* flags,
+                         hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_overlap_boxes, dim3(collide_blocks(n)), dim3(256), 0, stream, collide_world(meta, pool, f, cd), bodies,
-                       n, counts, flags);
+    hipLaunchKernelGGL(k_overlap_boxes, dim3(collide_blocks(n)), dim3(256), 0, stream, W, bodies, n, counts, flags);
     return hipGetLastError();
 }
 

@@ -29,14 +29,6 @@ constexpr int kBodyMaxDelta = 64;       // VXRT_BODY_MAX_DELTA
 constexpr float kBodyMaxCoord = 16777216.0f;  // 2^24: |lo|, |hi| stay below it
 constexpr uint32_t kBodyInvalid = 8u;   // VXRT_BODY_INVALID
 
-// the resident world as the collision code reads it (HBM order, vxrt_device.hpp)
-struct CollideWorld {
-    const uint2* meta;
-    const uint32_t* pool;
-    int f, lgf, cx, cz;
-    int dim[3];  // voxels per axis
-};
-
 // the body rule of include/vxrt.h: finite, lo < hi, hi - lo <= 64, |delta| <= 64, |lo|, |hi| < 2^24 on every axis
 __host__ __device__ inline bool body_valid(const float b[9])
 {

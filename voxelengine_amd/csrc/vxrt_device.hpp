@@ -304,6 +304,8 @@ __host__ __device__ inline void hbm_cell(uint64_t i, int dx, int dz, int& x, int
     z = (int)((i / (uint64_t)dx) % (uint64_t)dz);
     y = (int)(i / ((uint64_t)dx * (uint64_t)dz));
 }
+// log2 of the brick edge f (8, 16, 32)
+__host__ __device__ inline int brick_shift(int f) { return f == 32 ? 5 : (f == 16 ? 4 : 3); }
 
 // The reference's bit order (GetSampleIndex / GetPositionFromSampleIndex, VolumeRaytracer.cuh:107-171): 8x8x8 tiles,
 // tiles x-fastest, cells x-fastest inside a tile.  Only the re-ordering kernels and the builders use it (cold code).

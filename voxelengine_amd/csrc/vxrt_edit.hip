@@ -13,6 +13,7 @@
 #include "../../include/vxrt.h"
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
+#include "vxrt_region.hpp"
 
 namespace vxrt {
 
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(256) void k_edit_bricks(const uint32_t* __restrict_
     int bx, by, bz;
     hbm_cell(cell, cx, cz, bx, by, bz);
     const int b0[3] = {bx * f, by * f, bz * f};
-    const int fshift = f == 32 ? 5 : (f == 16 ? 4 : 3);
+    const int fshift = brick_shift(f);
     const uint32_t words = (uint32_t)(f * f * f) >> 5, vecs = words >> 2, nbits = words << 5;
     const uint32_t slot = meta[cell].x;
     for (uint32_t v = threadIdx.x; v < vecs; v += blockDim.x)
@@ -160,12 +161,6 @@ __global__ __launch_bounds__(256) void k_gather_bricks(const uint4* __restrict__
     uint4* out = dst + (size_t)blockIdx.x * vecs;
     for (uint32_t v = threadIdx.x; v < vecs; v += blockDim.x)
         out[v] = src[v];
-}
-
-static dim3 grid_2d(uint64_t blocks)
-{
-    const unsigned gx = blocks > (1u << 20) ? (1u << 20) : (unsigned)(blocks ? blocks : 1);
-    return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
 }
 
 // host entry points (vxrt_api.hip)

@@ -25,9 +25,6 @@ namespace vxrt {
 static_assert(sizeof(vxrt_island) == 32, "island row layout");
 static_assert(sizeof(vxrt_island_summary) == 12, "island summary layout");
 
-hipError_t read_region(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                       uint32_t* out, hipStream_t stream);
-
 __global__ __launch_bounds__(256) void k_isl_local(const IslandsArgs A, uint32_t ntiles, uint32_t ntx, uint32_t nty)
 {
     __shared__ uint32_t lp[kIslTileVoxels];
@@ -62,12 +59,6 @@ __global__ __launch_bounds__(256) void k_isl_merge(const IslandsArgs A)
     isl_merge_word(A, xw, row % (uint32_t)A.d[1], row / (uint32_t)A.d[1]);
 }
 
-__device__ inline uint32_t wave_sum(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1)
-        v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
 __device__ inline int32_t wave_min(int32_t v)
 {
     for (int m = 32; m; m >>= 1)
@@ -263,16 +254,10 @@ __global__ __launch_bounds__(256) void k_isl_output(const IslandsArgs A, uint32_
         atomicAdd(A.summary + 2, n);
 }
 
-static dim3 isl_grid(uint64_t blocks)
-{
-    const unsigned gx = blocks > (1u << 20) ? (1u << 20) : (unsigned)(blocks ? blocks : 1);
-    return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
-}
-
-// host entry point (vxrt_api.hip): arguments validated there; the world is f, cd (cells per axis), meta / pool in HBM order
-hipError_t find_islands(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                        uint32_t anchors, void* work, uint32_t* floating, uint32_t* labels, vxrt_island* table,
-                        uint32_t max_islands, vxrt_island_summary* summary, hipStream_t stream)
+// host entry point (vxrt_api.hip): arguments validated there
+hipError_t find_islands(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t anchors, void* work,
+                        uint32_t* floating, uint32_t* labels, vxrt_island* table, uint32_t max_islands,
+                        vxrt_island_summary* summary, hipStream_t stream)
 {
     IslandsLayout L;
     if (!islands_layout(d, L))
@@ -306,12 +291,12 @@ hipError_t find_islands(const uint2* meta, const uint32_t* pool, int f, const in
         return e;
     if ((e = hipMemsetAsync(summary, 0, sizeof(vxrt_island_summary), stream)) != hipSuccess)
         return e;
-    if ((e = read_region(meta, pool, f, cd, o, d, ws + L.bits, stream)) != hipSuccess)
+    if ((e = read_region(W, o, d, ws + L.bits, stream)) != hipSuccess)
         return e;
     const uint32_t ntx = L.wpr, nty = ((uint32_t)d[1] + kIslTileY - 1) / kIslTileY, ntz = ((uint32_t)d[2] + kIslTileZ - 1) / kIslTileZ;
     const uint64_t ntiles = (uint64_t)ntx * nty * ntz;  // <= 2^28
-    hipLaunchKernelGGL(k_isl_local, isl_grid(ntiles), dim3(256), 0, stream, A, (uint32_t)ntiles, ntx, nty);
-    hipLaunchKernelGGL(k_isl_merge, isl_grid((L.nbits + 255u) / 256u), dim3(256), 0, stream, A);
+    hipLaunchKernelGGL(k_isl_local, grid_2d(ntiles), dim3(256), 0, stream, A, (uint32_t)ntiles, ntx, nty);
+    hipLaunchKernelGGL(k_isl_merge, grid_2d((L.nbits + 255u) / 256u), dim3(256), 0, stream, A);
     const uint32_t fw = (L.nwords / 2u + 3u) / 4u;
     hipLaunchKernelGGL(k_isl_flatten, dim3(fw > 65536u ? 65536u : fw), dim3(256), 0, stream, A);
     hipLaunchKernelGGL(k_isl_scan_blocks, dim3(L.nblocks), dim3(256), 0, stream, A);

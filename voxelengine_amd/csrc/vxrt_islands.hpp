@@ -7,11 +7,13 @@
 // halving of a find lowers a parent to its grandparent with atomicMin too.  Every tree's root is therefore the minimum index
 // of its component, whatever order the races resolve in, and the flattened parent is the component id minus 1.  A union
 // whose atomicMin finds the larger root already linked elsewhere goes on with that parent, so no link is lost.
-// On the host every "atomic" is a plain read-modify-write: the harness runs one lane at a time.
+// The atomics are vxrt_region.hpp's (plain read-modify-writes on the host).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "vxrt_region.hpp"
 
 // The harness defines this to check every index the code forms into an array of the workspace, the LDS tile or the
 // outputs against that array's size (array: one of the kIsl* ids below).  The kernels leave it empty.
@@ -53,14 +55,13 @@ inline bool islands_layout(const int32_t d[3], IslandsLayout& L)
     L.nbits = (uint64_t)L.wpr * (uint64_t)d[1] * (uint64_t)d[2];
     L.nwords = (uint32_t)((((uint64_t)L.nvox + 63u) >> 6) << 1);
     L.nblocks = (L.nwords + kIslScanBlock - 1) / kIslScanBlock;
-    auto up = [](uint64_t w) { return (w + 63u) & ~(uint64_t)63u; };
     L.bits = 0;
-    L.parent = up(L.nbits);
-    L.roots = L.parent + up(L.nvox);
-    L.anchor = L.roots + up(L.nwords);
-    L.prefix = L.anchor + up(L.nwords);
-    L.blocks = L.prefix + up(L.nwords);
-    L.total_bytes = 4u * (L.blocks + up(L.nblocks));
+    L.parent = section_up(L.nbits, 4);
+    L.roots = L.parent + section_up(L.nvox, 4);
+    L.anchor = L.roots + section_up(L.nwords, 4);
+    L.prefix = L.anchor + section_up(L.nwords, 4);
+    L.blocks = L.prefix + section_up(L.nwords, 4);
+    L.total_bytes = 4u * (L.blocks + section_up(L.nblocks, 4));
     return true;
 }
 
@@ -83,29 +84,6 @@ struct IslandsArgs {
     uint64_t nbits;
 };
 
-#if defined(__HIP_DEVICE_COMPILE__)
-// agent-scope loads: another CU's atomicMin is seen, not a stale line of this CU's L1
-__device__ inline uint32_t isl_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline uint32_t isl_min(uint32_t* p, uint32_t v) { return atomicMin(p, v); }
-__device__ inline void isl_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
-__device__ inline void isl_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-__device__ inline void isl_min_i(int32_t* p, int32_t v) { atomicMin(p, v); }
-__device__ inline void isl_max_i(int32_t* p, int32_t v) { atomicMax(p, v); }
-#else
-inline uint32_t isl_load(const uint32_t* p) { return *p; }
-inline uint32_t isl_min(uint32_t* p, uint32_t v)
-{
-    const uint32_t o = *p;
-    if (v < o)
-        *p = v;
-    return o;
-}
-inline void isl_or(uint32_t* p, uint32_t v) { *p |= v; }
-inline void isl_add(uint32_t* p, uint32_t v) { *p += v; }
-inline void isl_min_i(int32_t* p, int32_t v) { *p = v < *p ? v : *p; }
-inline void isl_max_i(int32_t* p, int32_t v) { *p = v > *p ? v : *p; }
-#endif
-
 // the first bit of the run of set bits of w that holds bit b (bit b set): one past the highest clear bit below b
 __host__ __device__ inline int isl_run_start(uint32_t w, int b)
 {
@@ -126,14 +104,14 @@ __host__ __device__ inline uint32_t isl_find(uint32_t* P, uint32_t x)
 {
     for (;;) {
         VXRT_ISL_CHECK(kArray, x);
-        const uint32_t p = isl_load(P + x);
+        const uint32_t p = atom_load(P + x);
         if (p == x)
             return x;
         VXRT_ISL_CHECK(kArray, p);
-        const uint32_t g = isl_load(P + p);
+        const uint32_t g = atom_load(P + p);
         if (g == p)
             return p;
-        isl_min(P + x, g);
+        atom_min(P + x, g);
         x = g;
     }
 }
@@ -153,7 +131,7 @@ __host__ __device__ inline void isl_union(uint32_t* P, uint32_t a, uint32_t b)
             b = t;
         }
         VXRT_ISL_CHECK(kArray, b);
-        const uint32_t old = isl_min(P + b, a);
+        const uint32_t old = atom_min(P + b, a);
         if (old == b)
             return;
         b = old;  // b had been linked meanwhile: unite a with what it now hangs under
@@ -295,8 +273,8 @@ __host__ __device__ inline void isl_mark_anchor(const IslandsArgs& A, uint32_t r
 {
     VXRT_ISL_CHECK(kIslAnchor, root >> 5);
     const uint32_t bit = 1u << (root & 31u);
-    if (!(isl_load(A.anchor + (root >> 5)) & bit))
-        isl_or(A.anchor + (root >> 5), bit);
+    if (!(atom_load(A.anchor + (root >> 5)) & bit))
+        atom_or(A.anchor + (root >> 5), bit);
 }
 
 // ---- islands: after the scan, roots word w holds the island roots, prefix[w] the island roots before w in its block and
@@ -363,10 +341,10 @@ __host__ __device__ inline void isl_add_to_row(const IslandsArgs& A, uint32_t ra
 {
     VXRT_ISL_CHECK(kIslTable, rank);
     int32_t* row = A.table + 8u * (uint64_t)rank;
-    isl_add((uint32_t*)row + 1, n);
+    atom_add((uint32_t*)row + 1, n);
     for (int k = 0; k < 3; ++k) {
-        isl_min_i(row + 2 + k, lo[k]);
-        isl_max_i(row + 5 + k, hi[k] + 1);
+        atom_min(row + 2 + k, lo[k]);
+        atom_max(row + 5 + k, hi[k] + 1);
     }
 }
 

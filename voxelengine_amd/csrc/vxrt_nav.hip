@@ -23,18 +23,8 @@ namespace vxrt {
 static_assert(sizeof(vxrt_nav_agent) == 16, "nav agent layout");
 static_assert(sizeof(vxrt_nav_summary) == 32, "nav summary layout");
 
-hipError_t read_region(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                       uint32_t* out, hipStream_t stream);
-
 constexpr uint32_t kNavSyncLevels = 16;  // levels launched between two reads of the termination flag
 constexpr uint32_t kNavLevelGroups = 512;
-
-__device__ inline uint32_t nav_wave_sum(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1)
-        v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
 
 // i = x + a (y + b z): 32-bit divisions when i fits (always but for halo boxes of more than 2^32 words)
 __device__ inline void nav_split(uint64_t i, uint32_t a, uint32_t b, uint32_t& x, uint32_t& y, uint32_t& z)
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(256) void k_nav_zpass(const NavArgs A)
         nav_split(i, A.wb, (uint32_t)A.d[1], xw, y, z);
         c += nav_zpass_word(A, xw, y, z);
     }
-    c = nav_wave_sum(c);
+    c = wave_sum(c);
     if ((threadIdx.x & 63u) == 0)
         part[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -176,17 +166,11 @@ __global__ __launch_bounds__(256) void k_nav_paths(const NavPathArgs P)
         nav_path(P, i);
 }
 
-static dim3 nav_grid(uint64_t blocks)
-{
-    const unsigned gx = blocks > (1u << 20) ? (1u << 20) : (unsigned)(blocks ? blocks : 1);
-    return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
-}
-
-// host entry point (vxrt_api.hip): arguments validated there; the world is f, cd (cells per axis), meta / pool in HBM order.
-// Returns when the field is complete (the stream is synchronised every kNavSyncLevels levels).
-hipError_t nav_field(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                     const vxrt_nav_agent& ag, const int32_t* goals, uint32_t ngoals, uint32_t max_dist, void* work,
-                     uint32_t* walkable, uint8_t* next, uint32_t* dist, vxrt_nav_summary* summary, hipStream_t stream)
+// host entry point (vxrt_api.hip): arguments validated there.  Returns when the field is complete (the stream is
+// synchronised every kNavSyncLevels levels).
+hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], const vxrt_nav_agent& ag, const int32_t* goals,
+                     uint32_t ngoals, uint32_t max_dist, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
+                     vxrt_nav_summary* summary, hipStream_t stream)
 {
     NavLayout L;
     if (!nav_layout(d, ag.width, ag.height, ag.climb, ag.drop, L))
@@ -247,12 +231,12 @@ hipError_t nav_field(const uint2* meta, const uint32_t* pool, int f, const int c
     } else {
         const int32_t ho[3] = {o[0], (int32_t)hlo, o[2]};
         const int32_t hd[3] = {d[0] + ag.width - 1, (int32_t)L.hy, (int32_t)L.hz};
-        if ((e = read_region(meta, pool, f, cd, ho, hd, ws + L.halo, stream)) != hipSuccess)
+        if ((e = read_region(W, ho, hd, ws + L.halo, stream)) != hipSuccess)
             return e;
     }
     const uint64_t nx = (uint64_t)L.wb * L.hy * L.hz, ny = (uint64_t)L.wb * (uint64_t)d[1] * L.hz;
-    hipLaunchKernelGGL(k_nav_xpass, nav_grid((nx + 255u) / 256u), dim3(256), 0, stream, A, nx);
-    hipLaunchKernelGGL(k_nav_ypass, nav_grid((ny + 255u) / 256u), dim3(256), 0, stream, A, ny);
+    hipLaunchKernelGGL(k_nav_xpass, grid_2d((nx + 255u) / 256u), dim3(256), 0, stream, A, nx);
+    hipLaunchKernelGGL(k_nav_ypass, grid_2d((ny + 255u) / 256u), dim3(256), 0, stream, A, ny);
     const uint64_t zb = (L.nb + 255u) / 256u;
     hipLaunchKernelGGL(k_nav_zpass, dim3(zb < kNavZpassGroups ? (unsigned)zb : kNavZpassGroups), dim3(256), 0, stream, A);
     if (ngoals)
@@ -271,7 +255,7 @@ hipError_t nav_field(const uint2* meta, const uint32_t* pool, int f, const int c
         if (!pending)
             break;
     }
-    hipLaunchKernelGGL(k_nav_next, nav_grid(((uint64_t)L.nvox + 255u) / 256u), dim3(256), 0, stream, A);
+    hipLaunchKernelGGL(k_nav_next, grid_2d(((uint64_t)L.nvox + 255u) / 256u), dim3(256), 0, stream, A);
     hipLaunchKernelGGL(k_nav_finish, dim3(1), dim3(1), 0, stream, A);
     if ((e = hipGetLastError()) != hipSuccess)
         return e;

@@ -17,7 +17,7 @@
 // marks the tiles that can hold their predecessors (x +-1 word when bit 0 / 31 is set, y - climb .. y + drop, z +-1) for
 // level L + 1: an atomicMax of the level into the tile's mark appends the tile to the next list once.  Lists rotate over
 // three slots (level L reads L % 3, appends to (L + 1) % 3, clears (L + 2) % 3), so no level sweeps all of B.
-// On the host every "atomic" is a plain read-modify-write: the harness runs one lane at a time.
+// The atomics are vxrt_region.hpp's (plain read-modify-writes on the host).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,20 +78,19 @@ inline bool nav_layout(const int32_t d[3], int32_t w, int32_t h, int32_t climb, 
     L.nty = ((uint32_t)d[1] + kNavTileY - 1) / kNavTileY;
     L.ntz = ((uint32_t)d[2] + kNavTileZ - 1) / kNavTileZ;
     L.ntiles = L.wb * L.nty * L.ntz;  // <= 2^23
-    auto up = [](uint64_t n) { return (n + 63u) & ~(uint64_t)63u; };
     L.halo = 0;
-    L.ex = up((uint64_t)L.wh * L.hy * L.hz);
-    L.dx = L.ex + up((uint64_t)L.wb * L.hy * L.hz);
-    L.fy = L.dx + up((uint64_t)L.wb * (uint64_t)d[1] * L.hz);
-    L.free = L.fy + up((uint64_t)L.wb * (uint64_t)d[1] * L.hz);
-    L.vis = L.free + up(L.nb);
-    L.front[0] = L.vis + up(L.nb);
-    L.front[1] = L.front[0] + up(L.nb);
-    L.dist = L.front[1] + up(L.nb);
-    L.stamp = L.dist + up(L.nvox);
+    L.ex = section_up((uint64_t)L.wh * L.hy * L.hz, 4);
+    L.dx = L.ex + section_up((uint64_t)L.wb * L.hy * L.hz, 4);
+    L.fy = L.dx + section_up((uint64_t)L.wb * (uint64_t)d[1] * L.hz, 4);
+    L.free = L.fy + section_up((uint64_t)L.wb * (uint64_t)d[1] * L.hz, 4);
+    L.vis = L.free + section_up(L.nb, 4);
+    L.front[0] = L.vis + section_up(L.nb, 4);
+    L.front[1] = L.front[0] + section_up(L.nb, 4);
+    L.dist = L.front[1] + section_up(L.nb, 4);
+    L.stamp = L.dist + section_up(L.nvox, 4);
     L.mark = L.stamp + 2u * (uint64_t)L.ntiles;
     L.list = L.mark + L.ntiles;
-    L.ctrl = L.stamp + up(6u * (uint64_t)L.ntiles);
+    L.ctrl = L.stamp + section_up(6u * (uint64_t)L.ntiles, 4);
     L.total_bytes = 4u * (L.ctrl + kNavCtrlWords);
     return true;
 }
@@ -120,29 +119,6 @@ struct NavArgs {
     uint32_t wb, wh, hy, hz, nvox, nty, ntz, ntiles;
     uint64_t nb;
 };
-
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ inline uint32_t nav_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
-__device__ inline void nav_add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-__device__ inline uint32_t nav_max(uint32_t* p, uint32_t v) { return atomicMax(p, v); }
-__device__ inline uint32_t nav_inc(uint32_t* p) { return atomicAdd(p, 1u); }
-#else
-inline uint32_t nav_or(uint32_t* p, uint32_t v)
-{
-    const uint32_t o = *p;
-    *p = o | v;
-    return o;
-}
-inline void nav_add(uint32_t* p, uint32_t v) { *p += v; }
-inline uint32_t nav_max(uint32_t* p, uint32_t v)
-{
-    const uint32_t o = *p;
-    if (v > o)
-        *p = v;
-    return o;
-}
-inline uint32_t nav_inc(uint32_t* p) { return (*p)++; }
-#endif
 
 __host__ __device__ inline uint64_t nav_word(const NavArgs& A, uint32_t xw, uint32_t y, uint32_t z)
 {
@@ -229,9 +205,9 @@ __host__ __device__ inline uint32_t nav_zpass_word(const NavArgs& A, uint32_t xw
 __host__ __device__ inline void nav_mark_tile(const NavArgs& A, uint32_t lv, uint32_t t)
 {
     VXRT_NAV_CHECK(kNavMark, t);
-    if (nav_max(A.mark + t, lv + 1u) < lv + 1u) {
+    if (atom_max(A.mark + t, lv + 1u) < lv + 1u) {
         VXRT_NAV_CHECK(kNavCtrl, lv % kNavSlots);
-        const uint32_t k = nav_inc(A.ctrl + lv % kNavSlots);
+        const uint32_t k = atom_add(A.ctrl + lv % kNavSlots, 1u);
         VXRT_NAV_CHECK(kNavList, (uint64_t)(lv % kNavSlots) * A.ntiles + k);
         A.list[(uint64_t)(lv % kNavSlots) * A.ntiles + k] = t;
     }
@@ -272,8 +248,8 @@ __host__ __device__ inline int nav_goal(const NavArgs& A, uint32_t g)
         return 0;
     VXRT_NAV_CHECK(kNavFront, w);
     VXRT_NAV_CHECK(kNavVis, w);
-    nav_or(A.front[0] + w, bit);
-    const bool fresh = !(nav_or(A.vis + w, bit) & bit);
+    atom_or(A.front[0] + w, bit);
+    const bool fresh = !(atom_or(A.vis + w, bit) & bit);
     const uint32_t t = nav_tile(A, xw, (uint32_t)y, (uint32_t)z);
     VXRT_NAV_CHECK(kNavStamp, t);
     A.stamp[t] = 0u;

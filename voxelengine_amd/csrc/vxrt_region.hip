@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_stamp_bricks(const uint32_t* __restrict
     int bx, by, bz;
     hbm_cell(cell, cx, cz, bx, by, bz);
     const int b0[3] = {bx * f, by * f, bz * f};
-    const int lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
+    const int lgf = brick_shift(f);
     const uint32_t words = (uint32_t)(f * f * f) >> 5, vecs = words >> 2;
     const uint32_t slot = meta[cell].x;
     for (uint32_t v = threadIdx.x; v < vecs; v += blockDim.x)
@@ -169,27 +169,20 @@ __global__ __launch_bounds__(256) void k_stamp_bricks(const uint32_t* __restrict
     }
 }
 
-static dim3 grid_2d(uint64_t blocks)
-{
-    const unsigned gx = blocks > (1u << 20) ? (1u << 20) : (unsigned)(blocks ? blocks : 1);
-    return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
-}
-
-// host entry points (vxrt_api.hip).  read_region: the world is f, cd (cells per axis), meta / pool in HBM order.
-hipError_t read_region(const uint2* meta, const uint32_t* pool, int f, const int cd[3], const int32_t o[3], const int32_t d[3],
-                       uint32_t* out, hipStream_t stream)
+// host entry points (vxrt_api.hip)
+hipError_t read_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t* out, hipStream_t stream)
 {
     ReadArgs A{};
-    A.meta = meta;
-    A.pool = pool;
+    A.meta = W.meta;
+    A.pool = W.pool;
     A.out = out;
-    A.f = f;
-    A.lgf = f == 32 ? 5 : (f == 16 ? 4 : 3);
-    A.cx = cd[0];
-    A.cz = cd[2];
-    A.X = cd[0] * f;
-    A.Y = cd[1] * f;
-    A.Z = cd[2] * f;
+    A.f = W.f;
+    A.lgf = W.lgf;
+    A.cx = W.cx;
+    A.cz = W.cz;
+    A.X = W.dim[0];
+    A.Y = W.dim[1];
+    A.Z = W.dim[2];
     for (int k = 0; k < 3; ++k) {
         A.o[k] = o[k];
         A.d[k] = d[k];

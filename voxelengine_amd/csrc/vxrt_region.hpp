@@ -1,7 +1,9 @@
 // vxrt_region.hpp -- region readback and voxel stamps (include/vxrt.h, vxrt_read_region / vxrt_edit_stamps): the pieces
-// shared by the kernels of vxrt_region.hip, the host side in vxrt_api.hip and the host harness of the tests
-// (tests/tools/region_check.cpp, through tests/tools/hoststub): the brick row, the 32-voxel row gather of a read, the
+// shared by the kernels of vxrt_region.hip, the host side in vxrt_api.hip and the host harnesses of the tests
+// (tests/tools/*_check.cpp, through tests/tools/hoststub): the brick row, the 32-voxel row gather of a read, the
 // funnel-shifted gather of a stamp's bits, the per-row stamp step, the per-brick stamp filter and stamp validation.
+// Every world query (edits, reads, collision, islands, navigation) reads the world through this layer, so it also holds
+// what they share: the world as a query reads it, the 2-D launch grid, workspace sections, the wave sum and the atomics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +14,100 @@
 namespace vxrt {
 
 constexpr uint64_t kRegionMaxVoxels = 1ull << 36;
+
+// the resident world as a query reads it (HBM order, vxrt_device.hpp).  Named after its first user, the collision
+// queries: the name is part of the collision kernels' symbols and of what the collision harness declares.
+struct CollideWorld {
+    const uint2* meta;
+    const uint32_t* pool;
+    int f, lgf, cx, cz;
+    int dim[3];  // voxels per axis
+};
+
+// the world of f-voxel bricks, cd cells per axis
+inline CollideWorld query_world(const uint2* meta, const uint32_t* pool, int f, const int cd[3])
+{
+    CollideWorld W{};
+    W.meta = meta;
+    W.pool = pool;
+    W.f = f;
+    W.lgf = brick_shift(f);
+    W.cx = cd[0];
+    W.cz = cd[2];
+    for (int k = 0; k < 3; ++k)
+        W.dim[k] = cd[k] * f;
+    return W;
+}
+
+// n rounded up to a multiple of 256 bytes, n counted in units of `unit` bytes: workspace and scratch sections start on
+// 256-byte boundaries
+inline uint64_t section_up(uint64_t n, uint64_t unit = 1)
+{
+    const uint64_t a = 256u / unit;
+    return (n + a - 1u) / a * a;
+}
+
+#ifndef VXRT_HOST_CHECK
+// more workgroups than one grid axis holds: x up to 2^20, the rest in y (the kernels flatten blockIdx.x + blockIdx.y * gridDim.x)
+inline dim3 grid_2d(uint64_t blocks)
+{
+    const unsigned gx = blocks > (1u << 20) ? (1u << 20) : (unsigned)(blocks ? blocks : 1);
+    return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
+}
+
+// k_read_region of the box o, d into `out` (region layout); vxrt_region.hip
+hipError_t read_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t* out, hipStream_t stream);
+
+__device__ inline uint32_t wave_sum(uint32_t v)
+{
+    for (int m = 32; m; m >>= 1)
+        v += (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+#endif
+
+// Atomics of the query kernels, each returning the old value.  On the host every "atomic" is a plain read-modify-write: the
+// harnesses run one lane at a time.
+#if defined(__HIP_DEVICE_COMPILE__)
+// agent-scope loads: another CU's atomic is seen, not a stale line of this CU's L1
+__device__ inline uint32_t atom_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T>
+__device__ inline T atom_min(T* p, T v) { return atomicMin(p, v); }
+template <class T>
+__device__ inline T atom_max(T* p, T v) { return atomicMax(p, v); }
+__device__ inline uint32_t atom_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
+__device__ inline uint32_t atom_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+#else
+inline uint32_t atom_load(const uint32_t* p) { return *p; }
+template <class T>
+inline T atom_min(T* p, T v)
+{
+    const T o = *p;
+    if (v < o)
+        *p = v;
+    return o;
+}
+template <class T>
+inline T atom_max(T* p, T v)
+{
+    const T o = *p;
+    if (v > o)
+        *p = v;
+    return o;
+}
+inline uint32_t atom_or(uint32_t* p, uint32_t v)
+{
+    const uint32_t o = *p;
+    *p = o | v;
+    return o;
+}
+inline uint32_t atom_add(uint32_t* p, uint32_t v)
+{
+    const uint32_t o = *p;
+    *p = o + v;
+    return o;
+}
+#endif
 
 // a stamp as the kernels read it: validated, its voxel box clipped to the world (lo > hi on some axis: a no-op)
 struct StampDev {

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_fill_bricks(uint32_t* __restrict__ scra
     // One voxel per lane: a wave's 64 consecutive bits are 64 / f whole x-rows of the brick (HBM order: x, then z, then y), and the ballot mask IS
     // that uint64 of the bit image.  Every lane is busy for every brick edge (f = 8: 512 voxels on 256 threads; the
     // earlier one-word-per-lane form left 240 of them idle there).
-    const int fshift = f == 32 ? 5 : (f == 16 ? 4 : 3);
+    const int fshift = brick_shift(f);
     const uint32_t words = (uint32_t)(f * f * f) >> 5, nbits = words << 5;
     int mnx = 0x7FFFFFFF, mny = 0x7FFFFFFF, mnz = 0x7FFFFFFF, mxx = -1, mxy = -1, mxz = -1;
     unsigned long long* dst = reinterpret_cast<unsigned long long*>(scratch + (size_t)cell * words);
