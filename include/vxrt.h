@@ -557,7 +557,10 @@ int vxrt_deinterleave_views(vxrt_ctx *ctx, uint32_t width, uint32_t height, int3
  * direction, and directions so short or long that the squared length leaves the binary32 range make Raytrace's prologue
  * (VolumeRaytracer.cu:359-367) produce NaN, which the reference then casts to int (undefined).  An INVALID ray of a batch
  * is not traced: its result is a miss with 0 steps (point = +inf, normal = 0, d_hit = 0, d_voxel = -1); it is counted as
- * a ray.  vxrt_render / vxrt_render_views return VXRT_ERR_INVALID for a camera with a non-finite component. */
+ * a ray.  vxrt_render / vxrt_render_views return VXRT_ERR_INVALID for a camera with a non-finite component.
+ * vxrt_set_environment returns VXRT_ERR_INVALID, and keeps the context's environment, for a light_dir with a non-finite
+ * component or whose squared length, evaluated in binary32, is 0 or not finite: its unit vector -- the direction of every
+ * shadow ray -- would not be a finite vector.  Any other light_dir, light colour and ambient is accepted. */
 int vxrt_trace_batch(vxrt_ctx *ctx, const float *d_origins, const float *d_dirs, uint64_t n, float *d_pos,
                      float *d_normal, int32_t *d_steps, uint8_t *d_hit, int64_t *d_voxel,
                      vxrt_frame_stats *stats_or_null, void *stream);

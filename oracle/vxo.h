@@ -28,6 +28,7 @@ extern "C" {
 
 #define VXO_MAX_STEPS 2048          /* VoxelRT/VolumeRaytracer.cuh:235 */
 #define VXO_EMPTY_SLOT 0xFFFFFFFFu
+#define VXO_EPS_DDA 1e-6            /* a DOUBLE in the reference, VolumeRaytracer.cuh:20 */
 
 /* ---- layout (VoxelRT/VolumeRaytracer.cuh:107-171, VolumeRaytracer.cu:61-68) */
 uint32_t vxo_sample_index(uint32_t x, uint32_t y, uint32_t z, uint32_t width, uint32_t height);
@@ -184,6 +185,22 @@ void vxo_render(const vxo_world *w, const vxo_render_params *p, uint8_t *fb, flo
  * pre-tonemap colour, frames in the history}; shaded hit pixels only */
 void vxo_render_accum(const vxo_world *w, const vxo_render_params *p, uint8_t *fb, float *color_aov,
                       int64_t *hit_aov, float *accum, int accum_reset, vxo_frame_stats *stats, int nthreads);
+/* the same with a branch census: `census` (optional, width*height bytes) receives, for every pixel the launch computes,
+ * the VXO_CEN_* conditions its computation met (bookkeeping for the edge-case tests; it changes no result).  "Not ordinary" is the HIP kernel's test of the operands of its short division and square root
+ * (vxrt_device.hpp): exponent outside [-100, 100], zero, infinite or NaN. */
+enum {
+    VXO_CEN_CAM_LEN = 1,          /* perspective camera ray: squared length not ordinary */
+    VXO_CEN_VIEW = 2,             /* view vector (hit point - ray origin): squared length not ordinary */
+    VXO_CEN_TONEMAP = 4,          /* tonemap c / (c + 1): a non-zero c or a c + 1 not ordinary */
+    VXO_CEN_BOUNCE_DIR = 8,       /* bounce sample direction: squared length not ordinary */
+    VXO_CEN_SPECIAL_PRIMARY = 16, /* primary / shadow / bounce ray whose set-up leaves a direction component 0 or below */
+    VXO_CEN_SPECIAL_SHADOW = 32,  /* 2^-40, or a start component -0.0 */
+    VXO_CEN_SPECIAL_BOUNCE = 64,
+    VXO_CEN_INVALID = 128         /* a ray that is not valid (include/vxrt.h, ray validity) was traced */
+};
+void vxo_render_census(const vxo_world *w, const vxo_render_params *p, uint8_t *fb, float *color_aov,
+                       int64_t *hit_aov, float *accum, int accum_reset, uint8_t *census, vxo_frame_stats *stats,
+                       int nthreads);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,9 @@ EMPTY_SLOT = 0xFFFFFFFF
 MAX_STEPS = 2048
 GEN_HASH_HEIGHTFIELD, GEN_PERLIN_REF, GEN_INT_TERRAIN = 0, 1, 2
 MODE_SHADED, MODE_DEBUG = 0, 1
+# per-pixel census bits of World.render(want_census=True) (oracle/vxo.h VXO_CEN_*)
+CEN_CAM_LEN, CEN_VIEW, CEN_TONEMAP, CEN_BOUNCE_DIR = 1, 2, 4, 8
+CEN_SPECIAL_PRIMARY, CEN_SPECIAL_SHADOW, CEN_SPECIAL_BOUNCE, CEN_INVALID = 16, 32, 64, 128
 
 
 class _World(C.Structure):
@@ -133,6 +136,8 @@ def lib() -> C.CDLL:
                                  C.c_void_p, C.POINTER(FrameStats), C.c_int]
         L.vxo_render_accum.argtypes = [C.POINTER(_World), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.POINTER(FrameStats), C.c_int]
+        L.vxo_render_census.argtypes = [C.POINTER(_World), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FrameStats), C.c_int]
         L.free = C.CDLL(None).free
         L.free.argtypes = [C.c_void_p]
         _LIB = L
@@ -259,7 +264,7 @@ class World:
         return dict(pos=pos, normal=nrm, steps=steps, hit=hit, voxel=vox, stats=st)
 
     def render(self, params: RenderParams, fb: np.ndarray | None = None, want_color=False, want_hit=False,
-               nthreads: int = 8, accum: np.ndarray | None = None, accum_reset: bool = False):
+               nthreads: int = 8, accum: np.ndarray | None = None, accum_reset: bool = False, want_census=False):
         W, H = params.width, params.height
         if params.row_end == 0:
             params.row_end = H
@@ -267,13 +272,14 @@ class World:
             fb = np.full((H, W, 4), 255, np.uint8)
         col = np.zeros((H, W, 3), np.float32) if want_color else None
         hit = np.full((H, W), -1, np.int64) if want_hit else None
+        cen = np.zeros((H, W), np.uint8) if want_census else None
         st = FrameStats()
         if accum is not None:
             assert accum.dtype == np.float32 and accum.shape == (H, W, 4) and accum.flags.c_contiguous
-        lib().vxo_render_accum(self._p, C.byref(params), fb.ctypes.data, col.ctypes.data if want_color else None,
+        lib().vxo_render_census(self._p, C.byref(params), fb.ctypes.data, col.ctypes.data if want_color else None,
                                hit.ctypes.data if want_hit else None, accum.ctypes.data if accum is not None else None,
-                               int(bool(accum_reset)), C.byref(st), nthreads)
-        return dict(fb=fb, color=col, hit=hit, stats=st)
+                               int(bool(accum_reset)), cen.ctypes.data if want_census else None, C.byref(st), nthreads)
+        return dict(fb=fb, color=col, hit=hit, stats=st, census=cen)
 
 
 def dense_from_voxels(vox: np.ndarray) -> np.ndarray:

@@ -66,6 +66,8 @@ typedef struct frame_ctx {
     int64_t *hit_aov;
     float *accum;       /* temporal accumulation (this build's extension): W*H*4 floats {sum r,g,b, frames}, or NULL */
     int accum_reset;
+    uint8_t *census;    /* per pixel VXO_CEN_* bits, or NULL */
+    uint8_t cen;        /* the bits of the pixel being computed */
     uint32_t first_chunk, chunk_stride, rows; /* launch-grid rows for this worker, in chunks of ROW_CHUNK */
     uint32_t grid_w;
     vxo_frame_stats stats;
@@ -95,6 +97,55 @@ static void put_pixel(frame_ctx *c, int x, int y, v3 col)
     c->stats.pixels_written += 1;
 }
 
+/* the kernel's `ordinary` (vxrt_device.hpp): exponent in [-100, 100], not zero, infinite or NaN */
+static inline int ordinary(float x)
+{
+    uint32_t b;
+    memcpy(&b, &x, 4);
+    return (uint32_t)((b & 0x7FFFFFFFu) - 0x0D800000u) < (0x72000000u - 0x0D800000u);
+}
+
+static inline int neg_zero(float x)
+{
+    uint32_t b;
+    memcpy(&b, &x, 4);
+    return b == 0x80000000u;
+}
+
+/* census of one ray about to be traced (no effect on results): INVALID by include/vxrt.h's ray validity; `special_bit` when
+ * the tracer's set-up (vxo_raytrace's prologue, restated) leaves a direction component that is 0 or below 2^-40, or a start
+ * component -0.0 -- the `special` lanes of vxrt_wave2.hpp */
+static void census_ray(frame_ctx *c, v3 o, v3 d, uint8_t special_bit)
+{
+    if (!c->census)
+        return;
+    const float osum = fabsf(o.x) + fabsf(o.y) + fabsf(o.z), dd = dot3(d, d);
+    if (!isfinite(osum) || !(dd > 0) || !isfinite(dd)) {
+        c->cen |= VXO_CEN_INVALID;
+        return;
+    }
+    const vxo_world *w = c->w;
+    const float ff = (float)w->factor;
+    v3 dir = scl(d, 1.0f / sqrtf(dd));
+    float s[3] = {o.x / ff, o.y / ff, o.z / ff}, df[3] = {dir.x, dir.y, dir.z};
+    int inside = 1;
+    for (int a = 0; a < 3; ++a)
+        inside = inside && s[a] >= 0 && s[a] < (float)w->cdims[a];
+    if (!inside) {
+        float bmin[3], bmax[3], entry[3], en[3];
+        for (int a = 0; a < 3; ++a) {
+            bmin[a] = (float)VXO_EPS_DDA;
+            bmax[a] = (float)((double)w->cdims[a] - VXO_EPS_DDA);
+        }
+        if (vxo_ray_aabb(s, df, bmin, bmax, entry, en))
+            memcpy(s, entry, sizeof(entry));
+    }
+    const float tiny = 9.094947017729282e-13f; /* 2^-40 */
+    if (!(fabsf(dir.x) >= tiny && fabsf(dir.y) >= tiny && fabsf(dir.z) >= tiny) || neg_zero(s[0]) || neg_zero(s[1]) ||
+        neg_zero(s[2]))
+        c->cen |= special_bit;
+}
+
 static int trace(frame_ctx *c, int max_steps, v3 o, v3 d, int *steps, v3 *n, v3 *pos, int vox[3])
 {
     float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z}, nf[3], pf[3] = {pos->x, pos->y, pos->z};
@@ -121,6 +172,7 @@ static v3 shade(frame_ctx *c, uint32_t tx, uint32_t ty, v3 cam, v3 normal, v3 po
         int st;
         v3 sn;
         c->stats.shadow_rays += 1;
+        census_ray(c, spos, sray, VXO_CEN_SPECIAL_SHADOW);
         shadowed = trace(c, VXO_MAX_STEPS, spos, sray, &st, &sn, &spos, NULL);
     }
     float l_dot = hi(dot3(normal, L), 0) * (float)(shadowed ? 0 : 1);
@@ -132,7 +184,10 @@ static v3 shade(frame_ctx *c, uint32_t tx, uint32_t ty, v3 cam, v3 normal, v3 po
     v3 color = add(diffuse, scl(Amb, 0.25f + t * (1.0f - 0.25f)));
 
     if (!shadowed) {
-        v3 view = unit(sub(position, cam));
+        v3 to_hit = sub(position, cam);
+        if (!ordinary(dot3(to_hit, to_hit)))
+            c->cen |= VXO_CEN_VIEW;
+        v3 view = unit(to_hit);
         v3 refl = bounce_dir(L, normal);
         float spec = pow32(hi(dot3(view, refl), 0));
         color.x += spec * Lc.x;
@@ -149,12 +204,15 @@ static v3 shade(frame_ctx *c, uint32_t tx, uint32_t ty, v3 cam, v3 normal, v3 po
             uint32_t si = seed + (uint32_t)i * 1000u + (p->frame_number + 1u) * 1000u;
             v3 sd = mk(vxo_random_float(si) * 2 - 1, vxo_random_float(si * 10u) * 2 - 1,
                        vxo_random_float(si * 100u) * 2 - 1);
+            if (!ordinary(dot3(sd, sd)))
+                c->cen |= VXO_CEN_BOUNCE_DIR;
             sd = unit(sd);
             if (dot3(sd, normal) < 0)
                 sd = bounce_dir(sd, normal);
             v3 sp = add(position, scl(normal, 0.01f)), sn;
             int st;
             c->stats.bounce_rays += 1;
+            census_ray(c, sp, sd, VXO_CEN_SPECIAL_BOUNCE);
             if (!trace(c, 8, sp, sd, &st, &sn, &sp, NULL)) {
                 occl += 1.0f;
             } else if (p->bounce_depth >= 2) {
@@ -164,11 +222,14 @@ static v3 shade(frame_ctx *c, uint32_t tx, uint32_t ty, v3 cam, v3 normal, v3 po
                 uint32_t s2 = si + 500u;
                 v3 d2 = mk(vxo_random_float(s2) * 2 - 1, vxo_random_float(s2 * 10u) * 2 - 1,
                            vxo_random_float(s2 * 100u) * 2 - 1);
+                if (!ordinary(dot3(d2, d2)))
+                    c->cen |= VXO_CEN_BOUNCE_DIR;
                 d2 = unit(d2);
                 if (dot3(d2, n2) < 0)
                     d2 = bounce_dir(d2, n2);
                 v3 o2 = add(sp, scl(n2, 0.01f)), sn2;
                 c->stats.bounce_rays += 1;
+                census_ray(c, o2, d2, VXO_CEN_SPECIAL_BOUNCE);
                 if (!trace(c, 8, o2, d2, &st, &sn2, &o2, NULL))
                     occl += 0.5f;
             }
@@ -221,6 +282,7 @@ static void pixel_thread(frame_ctx *c, uint32_t tx, uint32_t ty)
     if ((uint32_t)y < p->row_begin || (uint32_t)y >= p->row_end)
         return;                                  /* strip sharding (this build) */
     const int W = (int)p->width, H = (int)p->height;
+    c->cen = 0;
     float u = (float)x / (float)W, v = (float)y / (float)H;
     v3 origin = from(p->origin), fwd = from(p->fwd), up = from(p->up), right = from(p->right);
     v3 ray;
@@ -237,12 +299,15 @@ static void pixel_thread(frame_ctx *c, uint32_t tx, uint32_t ty)
         ray.x = fwd.x + su * kx * right.x + sv * ky * up.x;
         ray.y = fwd.y + su * kx * right.y + sv * ky * up.y;
         ray.z = fwd.z + su * kx * right.z + sv * ky * up.z;
+        if (!ordinary(dot3(ray, ray)))
+            c->cen |= VXO_CEN_CAM_LEN;
         ray = unit(ray);
     }
 
     int steps = 0, vox[3] = {0, 0, 0};
     v3 normal, pos = mk(0, 0, 0);
     c->stats.primary_rays += 1;
+    census_ray(c, origin, ray, VXO_CEN_SPECIAL_PRIMARY);
     int hit = trace(c, VXO_MAX_STEPS, origin, ray, &steps, &normal, &pos, vox);
     normal = mk(-normal.x, -normal.y, -normal.z);
     if (c->hit_aov) {
@@ -268,6 +333,10 @@ static void pixel_thread(frame_ctx *c, uint32_t tx, uint32_t ty)
             v3 col = shade(c, tx, ty, origin, normal, pos);
             if (c->accum)
                 col = accumulate(c, x, y, col);
+            /* the operands the kernel's short division takes (vxrt_persist2.hpp, store_pixel) */
+            if (!((col.x == 0 || ordinary(col.x)) && (col.y == 0 || ordinary(col.y)) && (col.z == 0 || ordinary(col.z)) &&
+                  ordinary(col.x + 1.0f) && ordinary(col.y + 1.0f) && ordinary(col.z + 1.0f)))
+                c->cen |= VXO_CEN_TONEMAP;
             put_pixel(c, x, y, tonemap(col));
         }
     } else {
@@ -278,6 +347,8 @@ static void pixel_thread(frame_ctx *c, uint32_t tx, uint32_t ty)
         put_pixel(c, x, y, mk(10, 10, 10));
     if (p->mode == VXO_MODE_DEBUG && x < (W >> 1) && y > (H >> 1))   /* :270-275 */
         put_pixel(c, x, y, mk((float)steps / 256.0f, 0, 0));
+    if (c->census)
+        c->census[(size_t)y * p->width + (size_t)x] = c->cen;
 }
 
 #define ROW_CHUNK 4u
@@ -312,11 +383,18 @@ static void stats_add(vxo_frame_stats *a, const vxo_frame_stats *b)
 void vxo_render(const vxo_world *w, const vxo_render_params *p, uint8_t *fb, float *color_aov,
                 int64_t *hit_aov, vxo_frame_stats *stats, int nthreads)
 {
-    vxo_render_accum(w, p, fb, color_aov, hit_aov, NULL, 0, stats, nthreads);
+    vxo_render_census(w, p, fb, color_aov, hit_aov, NULL, 0, NULL, stats, nthreads);
 }
 
 void vxo_render_accum(const vxo_world *w, const vxo_render_params *p, uint8_t *fb, float *color_aov,
                       int64_t *hit_aov, float *accum, int accum_reset, vxo_frame_stats *stats, int nthreads)
+{
+    vxo_render_census(w, p, fb, color_aov, hit_aov, accum, accum_reset, NULL, stats, nthreads);
+}
+
+void vxo_render_census(const vxo_world *w, const vxo_render_params *p, uint8_t *fb, float *color_aov,
+                       int64_t *hit_aov, float *accum, int accum_reset, uint8_t *census, vxo_frame_stats *stats,
+                       int nthreads)
 {
     uint32_t rows = p->checkerboard ? (p->height >> 1) : p->height;
     uint32_t grid_w = ((p->width + 31u) / 32u) * 32u;
@@ -337,6 +415,7 @@ void vxo_render_accum(const vxo_world *w, const vxo_render_params *p, uint8_t *f
         c->hit_aov = hit_aov;
         c->accum = accum;
         c->accum_reset = accum_reset;
+        c->census = census;
         c->grid_w = grid_w;
         c->rows = rows;
         c->first_chunk = (uint32_t)i;

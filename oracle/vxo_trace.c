@@ -13,7 +13,6 @@
 
 #define VXO_INF ((float)INFINITY)
 #define VXO_FLT_EPS 1.1920928955078125e-7f /* std::numeric_limits<float>::epsilon, VolumeRaytracer.cuh:22 */
-#define VXO_EPS_DDA 1e-6                   /* a DOUBLE in the reference, VolumeRaytracer.cuh:20 */
 
 /* ------------------------------------------------------------------ layout */
 

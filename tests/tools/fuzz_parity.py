@@ -1,7 +1,10 @@
 """Randomised parity run (development; not part of the test suite): random worlds, random ray batches and random
 render configurations through the HIP path (the product kernels -- queue and one-ray-per-lane batch kernels, the persistent
 render kernel, timed and probe-counting instantiations -- and the straightforward cross-check) against the CPU oracle, for a
-time budget.  One round in six uses a WIDE grid (1024 or 2048 coarse cells along x: the re-armed step counters).
+time budget.  One round in six uses a WIDE grid (1024 or 2048 coarse cells along x: the re-armed step counters).  One frame
+in three comes from the edge-case generator of tests/render_edge_cases.py instead of the cameras A-D: a random axis-aligned
+view (special lanes: zero direction components, origins on grid lines or -0.0) with a random environment and FOV (axis and
+non-unit lights, colours far from 1, negative ambient).
 Prints one summary line per round and a final tally; exits non-zero at the first mismatch after dumping the seed.
 
 usage: fuzz_parity.py [seconds=120] [first_seed=1000]
@@ -17,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import voxelengine_amd as vx  # noqa: E402
 from oracle import vxo  # noqa: E402
 from tests import helpers  # noqa: E402
+from tests import render_edge_cases  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
@@ -77,13 +81,22 @@ while time.time() < t_end:
     rays_checked += 3 * n
     # one random frame configuration, all three render kernels
     W, H = int(rng.integers(40, 400)), int(rng.integers(30, 260))
-    cam = str(rng.choice(["A", "B", "C", "D"]))
-    pos, f, u, r = helpers.camera(cam, w.dims, vxo)
+    edge = seed % 3 == 1
+    env, fov = render_edge_cases.DEFAULT_ENV, 90.0
+    if edge:
+        cam = "axis-aligned"
+        pos, f, u, r = render_edge_cases.random_axis_camera(rng, w.dims)
+        env, fov = render_edge_cases.random_environment(rng)
+    else:
+        cam = str(rng.choice(["A", "B", "C", "D"]))
+        pos, f, u, r = helpers.camera(cam, w.dims, vxo)
     kw = dict(frame_number=int(rng.integers(0, 9)), mode=int(rng.integers(0, 2)), checkerboard=int(rng.integers(0, 2)),
               shadow=int(rng.integers(0, 2)), bounce_samples=int(rng.integers(0, 3)), bounce_all_hits=int(rng.integers(0, 2)),
               bounce_depth=int(rng.integers(1, 3)), ortho=int(rng.integers(0, 4) == 0))
     size = float(rng.choice([10.0, 40.0, 120.0]))
-    p = vxo.make_params(W, H, pos, f, u, r, ortho_size=(size, size), **kw)
+    if edge and kw["ortho"]:
+        W, H, size = 64, 64, 32.0   # pixel origins on integer grid lines
+    p = vxo.make_params(W, H, pos, f, u, r, ortho_size=(size, size), fov=fov, **env, **kw)
     fb0 = rng.integers(0, 255, size=(H, W, 4), dtype=np.uint8)
     want = w.render(p, fb=fb0.copy(), want_hit=True)
     ctx.SetEnvironment(list(p.env.light_dir), list(p.env.light_color), list(p.env.ambient))
@@ -114,10 +127,10 @@ while time.time() < t_end:
     ctx.set_kernel_variant(4)
     views, wants = [], []
     for j in range(3):
-        cj = cam if j == 0 else str(rng.choice(["A", "B", "C", "D"]))
-        pj, fj, uj, rj = helpers.camera(cj, w.dims, vxo)
+        pj, fj, uj, rj = (pos, f, u, r) if j == 0 else helpers.camera(str(rng.choice(["A", "B", "C", "D"])), w.dims, vxo)
         kwj = dict(kw, frame_number=kw["frame_number"] + j)
-        wants.append(want["fb"] if j == 0 else w.render(vxo.make_params(W, H, pj, fj, uj, rj, ortho_size=(size, size), **kwj),
+        wants.append(want["fb"] if j == 0 else w.render(vxo.make_params(W, H, pj, fj, uj, rj, ortho_size=(size, size), fov=fov,
+                                                                        **env, **kwj),
                                                          fb=fb0.copy())["fb"])
         views.append(dict(fb=torch.from_numpy(fb0.copy()).cuda(), origin=pj, fwd=fj, up=uj, right=rj,
                           frame_number=kwj["frame_number"]))

@@ -618,6 +618,13 @@ int vxrt_set_environment(vxrt_ctx* c, const float light_dir[3], const float ligh
 {
     if (!c || !light_dir || !light_color || !ambient)
         return fail(VXRT_ERR_INVALID, "NULL argument");
+    {   // a light whose unit vector (the shadow rays' direction, unit3 of the launch set-up) is not a finite vector: every
+        // shadow ray would be invalid (include/vxrt.h)
+        const float lx = light_dir[0], ly = light_dir[1], lz = light_dir[2];
+        const float dd = lx * lx + ly * ly + lz * lz;
+        if (!std::isfinite(lx) || !std::isfinite(ly) || !std::isfinite(lz) || !(dd > 0.0f) || !std::isfinite(dd))
+            return fail(VXRT_ERR_INVALID, "light_dir must be finite with a binary32 squared length that is positive and finite");
+    }
     memcpy(c->light_dir, light_dir, sizeof(c->light_dir));
     memcpy(c->light_color, light_color, sizeof(c->light_color));
     memcpy(c->ambient, ambient, sizeof(c->ambient));
