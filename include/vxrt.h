@@ -140,11 +140,32 @@ int vxrt_world_file_info(const char *path, vxrt_world_info *out);
  * chunk arrives with one read, two copies and two small re-ordering launches.  A chunk that is not resident reads as EMPTY space: the kernels do not
  * change, and every frame equals the frame of the world with exactly the resident chunks' bricks (tests hold the HIP
  * frames equal to the oracle on that truncated world).
- *   vxrt_stream_open: replaces the context's world by the (so far empty) streamed world of `path`.
+ *   vxrt_stream_open: replaces the context's world by the (so far empty) streamed world of `path`.  A NULL argument, a
+ *     pool_capacity_bricks of 0 or above 0xFFFFFFFF (slots are 32 bits and VXRT_EMPTY_SLOT is none) and a file that
+ *     cannot be opened or validated give VXRT_ERR_INVALID before anything changes: the previous world stays.
  *   vxrt_stream_focus: makes every chunk whose box lies within `radius` voxels of `focus` resident, nearest first;
  *     when the pool is full, resident chunks OUTSIDE the radius are evicted, farthest first; chunks inside the radius
- *     that still do not fit stay absent (stats.chunks_missing).  Synchronises the device before it touches the tables.
- *   vxrt_stream_resident: one byte per chunk (chunk = tile index of the coarse grid), 1 = resident.
+ *     that still do not fit stay absent (stats.chunks_missing).  Precisely, in binary32 throughout:
+ *     - chunk t = (tx, ty, tz) (index tx + tw * (ty + th * tz), tw = cdims[0] / 8, th = cdims[1] / 8) has the closed box
+ *       [8f t, 8f (t + 1)] per axis (f = factor); d^2 = gx^2 + gy^2 + gz^2 summed in that order, g = the focus's gap to
+ *       the box on that axis (0 inside); "within the radius" is d^2 <= radius * radius;
+ *     - only occupied chunks (those with at least one brick) are considered, in ascending d^2, ties to the lower index;
+ *     - a chunk within the radius that is not resident takes the lowest-addressed run of free pool bricks long enough
+ *       for it (first fit; bricks freed by evictions are merged with the free runs next to them);
+ *     - while no run fits, resident chunks outside the radius are evicted from the far end of the order; each is
+ *       scanned at most once per call (the scan does not restart for the next chunk);
+ *     - a chunk that still does not fit counts in chunks_missing, and the next chunk is tried;
+ *     - a chunk whose read from the file fails (e.g. the file was cut short) ends the call with VXRT_ERR_INVALID at that
+ *       chunk: the loads and evictions made before it stay, it is not resident, and stats are not written.  A HIP error
+ *       (VXRT_ERR_HIP) ends the call the same way; a chunk whose eviction it interrupts stays resident, and the device
+ *       tables of the chunk it stopped at are undefined;
+ *     - bytes_read = f^3 / 8 per loaded brick; chunks_loaded / evicted / missing count this call's events.
+ *     A NULL ctx or focus, a focus with a non-finite component, or a radius that is negative or NaN give VXRT_ERR_INVALID
+ *     and change nothing (radius = +inf is allowed: every occupied chunk is within it).  The call synchronises the device
+ *     before it touches the tables, and again before it returns -- on success and on every failure after that point --
+ *     so a launch issued after the call on any stream, non-blocking ones included, sees the tables the call left.
+ *   vxrt_stream_resident: one byte per chunk (chunk = tile index of the coarse grid), 1 = resident; n_chunks must be the
+ *     number of chunks (VXRT_ERR_INVALID otherwise).
  * The coarse tables are validated at open exactly as vxrt_load_world validates them (sizes, position-sensitive sums, slots
  * in cell order, brick extents); brick data read per chunk is NOT checksummed (the file's pool sum covers the whole
  * stream, not its chunks).  vxrt_download_world / vxrt_save_world on a streamed world give the CACHE as it stands: the

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import helpers
+from tests import ref_stream as R
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -56,6 +57,7 @@ def test_streamed_frames_equal_the_oracle_on_the_resident_world(vxo, tmp_path):
         full.save_world(path)
         nbricks = w.pool.size // (F ** 3 // 32)
         info = ctx.stream_open(path, nbricks)            # room for everything
+        model = R.StreamModelA(R.Tables.of(w), nbricks)
         assert (info.factor, tuple(info.cdims)) == (F, tuple(w.cdims))
         nchunks = int(np.prod(w.cdims)) // 512
         assert ctx.stream_resident().sum() == 0
@@ -67,6 +69,8 @@ def test_streamed_frames_equal_the_oracle_on_the_resident_world(vxo, tmp_path):
         pos = helpers.camera("A", dims, vxo)[0]
         st = ctx.stream_focus(pos, 120.0)
         flags = ctx.stream_resident()
+        want = model.focus(pos, 120.0)
+        assert tuple(int(getattr(st, k)) for k in R.STAT_FIELDS) == want["stats"] and np.array_equal(flags, want["flags"])
         assert 0 < st.chunks_resident == flags.sum() < st.chunks_occupied and st.chunks_loaded == st.chunks_resident
         assert st.bytes_read == st.bricks_resident * (F ** 3 // 8) and st.chunks_missing == 0
         for cam in ("A", "B"):
@@ -77,6 +81,7 @@ def test_streamed_frames_equal_the_oracle_on_the_resident_world(vxo, tmp_path):
 
         # everything within reach: the streamed world IS the world
         st = ctx.stream_focus(pos, 1.0e6)
+        assert tuple(int(getattr(st, k)) for k in R.STAT_FIELDS) == model.focus(pos, 1.0e6)["stats"]
         assert st.chunks_resident == st.chunks_occupied and st.bricks_resident == nbricks and st.chunks_evicted == 0
         for cam in ("A", "D"):
             fb, hit = _render(vx, ctx, torch, cam, dims, vxo)
@@ -112,6 +117,7 @@ def test_a_small_pool_evicts_the_farthest_chunks_as_the_focus_moves(vxo, tmp_pat
         ctx.save_world(path)
         nbricks = w.pool.size // (F ** 3 // 32)
         ctx.stream_open(path, nbricks // 3)               # a third of the world fits
+        model = R.StreamModelA(R.Tables.of(w), nbricks // 3)
         evicted = 0
         for step, fx in enumerate((0.1, 0.3, 0.5, 0.7, 0.9, 0.5)):    # fly across the world and back
             focus = (fx * X, 0.5 * Y, 0.5 * Z)
@@ -119,7 +125,10 @@ def test_a_small_pool_evicts_the_farthest_chunks_as_the_focus_moves(vxo, tmp_pat
             evicted += int(st.chunks_evicted)
             flags = ctx.stream_resident()
             assert st.bricks_resident <= nbricks // 3 and st.chunks_resident == flags.sum()
-            # every chunk inside the radius is resident unless the call says it could not fit
+            # which chunks load, are evicted or do not fit: the model of the policy (tests/ref_stream.py), call by call
+            want = model.focus(focus, 150.0)
+            assert tuple(int(getattr(st, k)) for k in R.STAT_FIELDS) == want["stats"], step
+            assert np.array_equal(flags, want["flags"]), step
             pos = (focus[0], 0.9 * Y, focus[2])
             f, u, r = vx.GetDirections((-0.9, 0.3 * step, 0.0))
             fb = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")

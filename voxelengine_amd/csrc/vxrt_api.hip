@@ -7,6 +7,7 @@
 #include "vxrt_islands.hpp"
 #include "vxrt_nav.hpp"
 #include "vxrt_region.hpp"
+#include "vxrt_stream.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1097,20 +1098,6 @@ struct FileCloser {
     ~FileCloser() { if (f) fclose(f); }
 };
 
-// tight extents of an occupied cell's record: six 5-bit fields {min x,y,z, max x,y,z}, each inside the brick, min <= max,
-// nothing above them (shared by vxrt_load_world and vxrt_stream_open)
-bool extents_valid(uint32_t packed, int factor)
-{
-    if ((packed >> 30) != 0u)
-        return false;
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t lo = (packed >> (5 * a)) & 31u, hi = (packed >> (5 * (a + 3))) & 31u;
-        if (hi >= (uint32_t)factor || lo > hi)
-            return false;
-    }
-    return true;
-}
-
 int read_header(FILE* f, const char* path, FileHeader& h)
 {
     if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, kFileMagic, 8) != 0)
@@ -1298,7 +1285,7 @@ int vxrt_load_world(vxrt_ctx* c, const char* path)
                     const bool bit = (coarse[cell >> 5] >> (cell & 31)) & 1u;
                     if (bit ? m[i].x >= h.nslots : m[i].x != VXRT_EMPTY_SLOT)
                         return bad("cell table does not match the coarse bits / pool size");
-                    if (bit && !extents_valid(m[i].y, h.factor))
+                    if (bit && !vxrt::extents_valid(m[i].y, h.factor))
                         return bad("brick extents outside the brick");
                 }
             }
@@ -1329,53 +1316,62 @@ int vxrt_load_world(vxrt_ctx* c, const char* path)
 }  // extern "C"
 
 // ---- chunk streaming (include/vxrt.h): coarse tables of the whole world resident, brick data only near the focus --------
+// The bookkeeping -- chunk table, order, radius test, eviction scan, pool allocator -- is vxrt::StreamPolicy
+// (vxrt_stream.hpp, host only); this file adds the file, the device tables and the pool.
 struct StreamState {
     FILE* f = nullptr;
     FileHeader h{};
-    uint64_t pool_off = 0, brick_bytes = 0, nchunks = 0;
-    std::vector<uint32_t> coarse;   // the whole world's coarse bits
-    std::vector<uint2> meta;        // ... and cell records, with the FILE's slot numbers
-    struct Chunk {
-        uint32_t first_slot = 0, nbricks = 0;   // its run of bricks in the file
-        int64_t base = -1;                      // first brick of its range in the device pool, or -1 = not resident
-        float lo[3], hi[3];                     // its box in voxels
-    };
-    std::vector<Chunk> chunks;
-    std::map<uint64_t, uint64_t> free_ranges;   // device pool: start -> length, in bricks
-    uint2* d_chunk_meta = nullptr;              // device staging for one chunk's 512 cell records
-    uint64_t capacity = 0, bricks_resident = 0, chunks_resident = 0, chunks_occupied = 0;
+    uint64_t pool_off = 0, brick_bytes = 0;
+    std::vector<uint32_t> coarse;             // the whole world's coarse bits
+    std::vector<vxrt::StreamCell> meta;       // ... and cell records, with the FILE's slot numbers
+    vxrt::StreamPolicy P;
+    uint2* d_chunk_meta = nullptr;            // device staging for one chunk's 512 cell records
+};
+static_assert(sizeof(vxrt::StreamCell) == sizeof(uint2), "a cell record is 8 bytes in the file and on the device");
 
-    bool alloc(uint64_t n, uint64_t& start)
+namespace {
+// the loads and evictions of vxrt_stream_focus: file reads, copies into the pool and the two re-ordering launches
+struct StreamDeviceIO final : vxrt::StreamIO {
+    vxrt_ctx* c;
+    StreamState* S;
+    std::vector<unsigned char> stage;
+    std::vector<uint2> meta = std::vector<uint2>(512);
+    StreamDeviceIO(vxrt_ctx* c_, StreamState* S_) : c(c_), S(S_) {}
+
+    int load(uint32_t, uint32_t first_slot, uint32_t nbricks, uint64_t start) override
     {
-        for (auto it = free_ranges.begin(); it != free_ranges.end(); ++it)
-            if (it->second >= n) {  // first fit
-                start = it->first;
-                const uint64_t rest = it->second - n, at = it->first + n;
-                free_ranges.erase(it);
-                if (rest)
-                    free_ranges[at] = rest;
-                return true;
-            }
-        return false;
+        const uint64_t nbytes = (uint64_t)nbricks * S->brick_bytes;
+        stage.resize(nbytes);
+        if (fseek(S->f, (long)(S->pool_off + (uint64_t)first_slot * S->brick_bytes), SEEK_SET) != 0 ||
+            fread(stage.data(), 1, nbytes, S->f) != nbytes)
+            return fail(VXRT_ERR_INVALID, "brickmap file: chunk read failed");
+        hipError_t e = hipMemcpy(reinterpret_cast<unsigned char*>(c->d_pool) + start * S->brick_bytes, stage.data(), nbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {  // the file's bricks are in the reference's tiled bit order: into the HBM order, in place
+            uint32_t* at = c->d_pool + start * (S->brick_bytes / 4);
+            e = vxrt::layout_bricks(at, at, nbricks, S->h.factor, true);
+        }
+        if (e != hipSuccess)
+            return fail(VXRT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+        return VXRT_OK;
     }
-    void release(uint64_t start, uint64_t n)
+
+    int tables(uint32_t ch, bool resident, int64_t base) override
     {
-        auto next = free_ranges.lower_bound(start);
-        if (next != free_ranges.begin()) {  // merge with the range that ends where this one starts
-            auto prev = std::prev(next);
-            if (prev->first + prev->second == start) {
-                start = prev->first;
-                n += prev->second;
-                free_ranges.erase(prev);
-            }
+        uint32_t k = 0;
+        for (uint64_t i = 0; i < 512; ++i) {
+            const vxrt::StreamCell m = S->meta[(uint64_t)ch * 512 + i];
+            meta[i] = (resident && m.slot != VXRT_EMPTY_SLOT) ? make_uint2((uint32_t)(base + k++), m.extents) : make_uint2(VXRT_EMPTY_SLOT, 0u);
         }
-        if (next != free_ranges.end() && start + n == next->first) {
-            n += next->second;
-            free_ranges.erase(next);
-        }
-        free_ranges[start] = n;
+        // the chunk's 512 records (file order: the reference's tiled order, one chunk = one tile) go to their places in
+        // the HBM tables -- 64 rows of 8 cells -- with their coarse bits
+        VX_HIP(hipMemcpy(S->d_chunk_meta, meta.data(), 512 * sizeof(uint2), hipMemcpyHostToDevice));
+        const int tw = S->h.cdims[0] / 8, th = S->h.cdims[1] / 8;
+        VX_HIP(vxrt::chunk_tables(c->d_meta, c->d_coarse, S->d_chunk_meta, (int)(ch % (uint32_t)tw), (int)((ch / (uint32_t)tw) % (uint32_t)th),
+                                  (int)(ch / ((uint32_t)tw * (uint32_t)th)), S->h.cdims[0], S->h.cdims[2]));
+        return VXRT_OK;
     }
 };
+}  // namespace
 
 namespace vxrt {
 void stream_drop(vxrt_ctx* c)
@@ -1396,6 +1392,8 @@ int vxrt_stream_open(vxrt_ctx* c, const char* path, uint64_t pool_capacity_brick
 {
     if (!c || !path || pool_capacity_bricks == 0)
         return fail(VXRT_ERR_INVALID, "NULL argument or empty pool");
+    if (pool_capacity_bricks > (uint64_t)VXRT_EMPTY_SLOT)  // slot numbers are 32 bits, and VXRT_EMPTY_SLOT is none
+        return fail(VXRT_ERR_INVALID, "pool capacity above 0xFFFFFFFF bricks");
     FILE* f = fopen(path, "rb");
     if (!f)
         return fail(VXRT_ERR_INVALID, std::string(path) + ": cannot open");
@@ -1430,37 +1428,10 @@ int vxrt_stream_open(vxrt_ctx* c, const char* path, uint64_t pool_capacity_brick
     }
     S->pool_off = sizeof(FileHeader) + h.coarse_bytes + h.meta_bytes;
     S->brick_bytes = (uint64_t)h.factor * h.factor * h.factor / 8;
-    S->nchunks = h.ncells / 512;
-    S->chunks.resize(S->nchunks);
-    const int tw = h.cdims[0] / 8, th = h.cdims[1] / 8;
-    uint32_t next_slot = 0;
-    for (uint64_t ch = 0; ch < S->nchunks; ++ch) {
-        StreamState::Chunk& C = S->chunks[ch];
-        C.first_slot = next_slot;
-        for (uint64_t i = ch * 512; i < ch * 512 + 512; ++i) {
-            const bool bit = (S->coarse[i >> 5] >> (i & 31)) & 1u;
-            // slots run through the file in cell order (vxrt_save_world writes what the builders produce): a chunk's
-            // bricks are ONE contiguous run
-            if (bit ? S->meta[i].x != next_slot : S->meta[i].x != VXRT_EMPTY_SLOT)
-                return bad(VXRT_ERR_INVALID, std::string(path) + ": brick slots are not in cell order");
-            if (bit && !extents_valid(S->meta[i].y, h.factor))  // (what vxrt_load_world checks of a cell record)
-                return bad(VXRT_ERR_INVALID, std::string(path) + ": brick extents outside the brick");
-            if (bit) {
-                ++next_slot;
-                ++C.nbricks;
-            }
-        }
-        const int tx = (int)(ch % tw), ty = (int)((ch / tw) % th), tz = (int)(ch / ((uint64_t)tw * th));
-        const float e = 8.0f * (float)h.factor;
-        C.lo[0] = tx * e; C.lo[1] = ty * e; C.lo[2] = tz * e;
-        C.hi[0] = C.lo[0] + e; C.hi[1] = C.lo[1] + e; C.hi[2] = C.lo[2] + e;
-        if (C.nbricks)
-            S->chunks_occupied += 1;
-    }
-    if (next_slot != h.nslots)
-        return bad(VXRT_ERR_INVALID, std::string(path) + ": brick count does not match the coarse bits");
-    // device: the whole world's tables (all empty for now) + a pool of the requested capacity
     int cd[3] = {h.cdims[0], h.cdims[1], h.cdims[2]};
+    if (const char* why = S->P.init(h.factor, cd, S->coarse.data(), S->meta.data(), h.nslots, pool_capacity_bricks))
+        return bad(VXRT_ERR_INVALID, std::string(path) + ": " + why);
+    // device: the whole world's tables (all empty for now) + a pool of the requested capacity
     if (hipSetDevice(c->device) != hipSuccess)
         return bad(VXRT_ERR_HIP, "hipSetDevice");
     (void)hipDeviceSynchronize();
@@ -1482,8 +1453,6 @@ int vxrt_stream_open(vxrt_ctx* c, const char* path, uint64_t pool_capacity_brick
         vxrt::free_world(c);
         return bad(VXRT_ERR_HIP, std::string("stream tables: ") + hipGetErrorString(e));
     }
-    S->capacity = pool_capacity_bricks;
-    S->free_ranges[0] = pool_capacity_bricks;
     c->nslots = pool_capacity_bricks;
     vxrt::fill_view(c, h.factor, cd);
     c->has_world = true;
@@ -1493,108 +1462,32 @@ int vxrt_stream_open(vxrt_ctx* c, const char* path, uint64_t pool_capacity_brick
 
 int vxrt_stream_focus(vxrt_ctx* c, const float focus[3], float radius, vxrt_stream_stats* out)
 {
-    if (!c || !focus || !(radius >= 0.0f))
-        return fail(VXRT_ERR_INVALID, "NULL argument or negative radius");
+    if (!c || !focus || !vxrt::StreamPolicy::focus_valid(focus, radius))
+        return fail(VXRT_ERR_INVALID, "NULL argument, non-finite focus, or negative or NaN radius");
     StreamState* S = c->stream;
     if (!S)
         return fail(VXRT_ERR_NO_WORLD, "no streamed world (vxrt_stream_open)");
     VX_HIP(hipSetDevice(c->device));
     VX_HIP(hipDeviceSynchronize());  // no launch may read the tables while chunks come and go
-    // squared distance of the focus to every occupied chunk's box
-    std::vector<std::pair<float, uint32_t>> order;
-    order.reserve(S->chunks_occupied);
-    for (uint64_t ch = 0; ch < S->nchunks; ++ch) {
-        const StreamState::Chunk& C = S->chunks[ch];
-        if (!C.nbricks)
-            continue;
-        float d2 = 0.0f;
-        for (int a = 0; a < 3; ++a) {
-            const float d = focus[a] < C.lo[a] ? C.lo[a] - focus[a] : (focus[a] > C.hi[a] ? focus[a] - C.hi[a] : 0.0f);
-            d2 += d * d;
-        }
-        order.emplace_back(d2, (uint32_t)ch);
-    }
-    std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    const float r2 = radius * radius;
-    uint64_t loaded = 0, evicted = 0, missing = 0, bytes = 0;
-    size_t far = order.size();  // eviction candidates: from the far end of the order, outside the radius only
-    std::vector<unsigned char> stage;
-    std::vector<uint2> meta(512);
-    auto write_tables = [&](uint32_t ch, bool resident) -> hipError_t {
-        const StreamState::Chunk& C = S->chunks[ch];
-        uint32_t k = 0;
-        for (uint64_t i = 0; i < 512; ++i) {
-            const uint2 m = S->meta[(uint64_t)ch * 512 + i];
-            meta[i] = (resident && m.x != VXRT_EMPTY_SLOT) ? make_uint2((uint32_t)(C.base + k++), m.y) : make_uint2(VXRT_EMPTY_SLOT, 0u);
-        }
-        // the chunk's 512 records (file order: the reference's tiled order, one chunk = one tile) go to their places in
-        // the HBM tables -- 64 rows of 8 cells -- with their coarse bits
-        hipError_t e = hipMemcpy(S->d_chunk_meta, meta.data(), 512 * sizeof(uint2), hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return e;
-        const int tw = S->h.cdims[0] / 8, th = S->h.cdims[1] / 8;
-        return vxrt::chunk_tables(c->d_meta, c->d_coarse, S->d_chunk_meta, (int)(ch % (uint32_t)tw), (int)((ch / (uint32_t)tw) % (uint32_t)th),
-                                  (int)(ch / ((uint32_t)tw * (uint32_t)th)), S->h.cdims[0], S->h.cdims[2]);
-    };
-    for (size_t k = 0; k < order.size() && order[k].first <= r2; ++k) {
-        const uint32_t ch = order[k].second;
-        StreamState::Chunk& C = S->chunks[ch];
-        if (C.base >= 0)
-            continue;
-        uint64_t start = 0;
-        bool ok = S->alloc(C.nbricks, start);
-        while (!ok && far > 0) {  // make room: the farthest resident chunk outside the radius goes
-            --far;
-            if (order[far].first <= r2)
-                break;
-            StreamState::Chunk& V = S->chunks[order[far].second];
-            if (V.base < 0)
-                continue;
-            VX_HIP(write_tables(order[far].second, false));
-            S->release((uint64_t)V.base, V.nbricks);
-            S->bricks_resident -= V.nbricks;
-            S->chunks_resident -= 1;
-            V.base = -1;
-            evicted += 1;
-            ok = S->alloc(C.nbricks, start);
-        }
-        if (!ok) {
-            missing += 1;
-            continue;
-        }
-        const uint64_t nbytes = (uint64_t)C.nbricks * S->brick_bytes;
-        stage.resize(nbytes);
-        if (fseek(S->f, (long)(S->pool_off + (uint64_t)C.first_slot * S->brick_bytes), SEEK_SET) != 0 ||
-            fread(stage.data(), 1, nbytes, S->f) != nbytes) {
-            S->release(start, C.nbricks);
-            return fail(VXRT_ERR_INVALID, "brickmap file: chunk read failed");
-        }
-        bytes += nbytes;
-        hipError_t e = hipMemcpy(reinterpret_cast<unsigned char*>(c->d_pool) + start * S->brick_bytes, stage.data(), nbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {  // the file's bricks are in the reference's tiled bit order: into the HBM order, in place
-            uint32_t* at = c->d_pool + start * (S->brick_bytes / 4);
-            e = vxrt::layout_bricks(at, at, C.nbricks, S->h.factor, true);
-        }
-        if (e != hipSuccess) {
-            S->release(start, C.nbricks);
-            return fail(VXRT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-        }
-        C.base = (int64_t)start;
-        VX_HIP(write_tables(ch, true));
-        S->bricks_resident += C.nbricks;
-        S->chunks_resident += 1;
-        loaded += 1;
-    }
-    VX_HIP(hipDeviceSynchronize());  // the table updates and re-ordered bricks are in place before any launch reads them
+    StreamDeviceIO io(c, S);
+    vxrt::StreamPolicy::Result r;
+    const int rc = S->P.focus(focus, radius, S->brick_bytes, io, r);
+    // whether or not the call got through: the table updates and re-ordered bricks made so far are in place before any
+    // launch -- on any stream -- reads them
+    const hipError_t e = hipDeviceSynchronize();
+    if (rc)
+        return rc;
+    if (e != hipSuccess)
+        return fail(VXRT_ERR_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
     if (out) {
-        out->chunks_total = S->nchunks;
-        out->chunks_occupied = S->chunks_occupied;
-        out->chunks_resident = S->chunks_resident;
-        out->bricks_resident = S->bricks_resident;
-        out->chunks_loaded = loaded;
-        out->chunks_evicted = evicted;
-        out->chunks_missing = missing;
-        out->bytes_read = bytes;
+        out->chunks_total = S->P.nchunks;
+        out->chunks_occupied = S->P.chunks_occupied;
+        out->chunks_resident = S->P.chunks_resident;
+        out->bricks_resident = S->P.bricks_resident;
+        out->chunks_loaded = r.loaded;
+        out->chunks_evicted = r.evicted;
+        out->chunks_missing = r.missing;
+        out->bytes_read = r.bytes;
     }
     return VXRT_OK;
 }
@@ -1605,10 +1498,10 @@ int vxrt_stream_resident(vxrt_ctx* c, uint8_t* flags, uint64_t n_chunks)
         return fail(VXRT_ERR_INVALID, "NULL argument");
     if (!c->stream)
         return fail(VXRT_ERR_NO_WORLD, "no streamed world (vxrt_stream_open)");
-    if (n_chunks != c->stream->nchunks)
+    if (n_chunks != c->stream->P.nchunks)
         return fail(VXRT_ERR_INVALID, "one flag per 8x8x8 tile of the coarse grid");
     for (uint64_t ch = 0; ch < n_chunks; ++ch)
-        flags[ch] = c->stream->chunks[ch].base >= 0 ? 1 : 0;
+        flags[ch] = c->stream->P.chunks[ch].base >= 0 ? 1 : 0;
     return VXRT_OK;
 }
 

@@ -152,10 +152,11 @@ class Context:
         N.check(self._L.vxrt_stream_focus(self._h, _f3(focus), float(radius), C.byref(st)))
         return st
 
-    def stream_resident(self) -> np.ndarray:
-        """One flag per chunk (tile index of the coarse grid): 1 = its bricks are resident."""
+    def stream_resident(self, n_chunks: int | None = None) -> np.ndarray:
+        """One flag per chunk (tile index of the coarse grid): 1 = its bricks are resident.  ``n_chunks``: the number of
+        flags to ask for (default: the world's chunk count; the library refuses any other)."""
         info = self.world_info()
-        flags = np.zeros(int(info.ncells) // 512, np.uint8)
+        flags = np.zeros(int(info.ncells) // 512 if n_chunks is None else int(n_chunks), np.uint8)
         N.check(self._L.vxrt_stream_resident(self._h, flags.ctypes.data, flags.size))
         return flags
 
