@@ -30,7 +30,9 @@
 // stamp's brick counts.  A dig that severs an overhang, then a collapse around it, removes the overhang.  Kind 5 computes a
 // navigation field over the box of origin a and dims b (VoxelRaytracer3D::NavField, the default agent width 1, height 2,
 // climb 1, drop 3) with one goal, the cell that holds frame N's camera position (floor of each coordinate), and prints one
-// line "nav frame N nodes .. reached .. levels .. max_dist ..".
+// line "nav frame N nodes .. reached .. levels .. max_dist ..".  Kind 6 computes the exact distance field of the box of
+// origin a and dims b (VoxelRaytracer3D::DistanceField) within the radius |value|, to the nearest solid voxel when value > 0
+// and to the nearest empty voxel when value < 0, and prints one line "dist frame N zero .. near .. far .. max_d2 .. sum_d2 ..".
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -237,6 +239,18 @@ int main(int argc, char** argv)
                 }
                 std::printf("nav frame %d nodes %u reached %u levels %u max_dist %u\n", from, sum.nodes, sum.reached, sum.levels,
                             sum.max_dist_found);
+            } else if (e.op.kind == 6) {  // distance field
+                flush_ops();
+                std::vector<uint16_t> dist2;
+                vxrt_distance_summary sum{};
+                const uint32_t radius = (uint32_t)std::abs((long long)e.op.value);
+                if (raytracer->DistanceField(e.op.a, e.op.b, radius, e.op.value < 0 ? VXRT_DIST_TO_EMPTY : VXRT_DIST_TO_SOLID, dist2,
+                                             sum) != VXRT_OK) {
+                    std::cerr << "dist before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("dist frame %d zero %u near %u far %u max_d2 %u sum_d2 %llu\n", from, sum.zero, sum.near, sum.far,
+                            sum.max_d2, (unsigned long long)sum.sum_d2);
             } else if (e.op.kind == 3) {  // paste
                 flush_ops();
                 const auto it = clipboard.find(e.op.value);

@@ -28,6 +28,7 @@ struct vxrt_island;
 struct vxrt_island_summary;
 struct vxrt_nav_agent;
 struct vxrt_nav_summary;
+struct vxrt_distance_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -169,6 +170,12 @@ public:
     int NavPaths(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent, const std::vector<uint8_t>& next,
                  const int32_t* starts, size_t n, uint32_t max_steps, std::vector<uint32_t>& lengths,
                  std::vector<uint32_t>& status, std::vector<int32_t>* cells = nullptr);
+    // exact distance fields (extension, include/vxrt.h, vxrt_distance_field_host): the squared distance of every voxel of
+    // the box origin .. origin + dims - 1 to the nearest VXRT_DIST_TO_SOLID / VXRT_DIST_TO_EMPTY voxel of the world within
+    // `radius`, VXRT_DIST_FAR beyond it (one uint16 per voxel in region order), and the summary.  Pending uploads are flushed
+    // first.  Returns the vxrt_status.
+    int DistanceField(const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode, std::vector<uint16_t>& dist2,
+                      vxrt_distance_summary& summary);
 
 private:
     void Flush();

@@ -453,6 +453,53 @@ int vxrt_nav_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t di
                         const int32_t *goals, uint32_t n_goals, uint32_t max_dist, uint32_t *walkable, uint8_t *next,
                         uint32_t *dist_or_null, vxrt_nav_summary *summary);
 
+/* ---- exact distance fields -- an EXTENSION (with the editing above: how far the nearest surface is, recomputed on the
+ * device after every edit).  A call looks at one box B = [origin, origin + dims) of world voxels and a radius R.
+ *   Targets.  VXRT_DIST_TO_SOLID: the solid voxels of the world.  VXRT_DIST_TO_EMPTY: the empty voxels; voxels outside the
+ *     world are empty (as for vxrt_read_region), so they are targets too.  Targets are voxels of the WHOLE world, not only
+ *     of B: the call reads the halo [origin - R, origin + dims + R).
+ *   Value.  For voxel v of B, d2(v) = min over targets t of (vx-tx)^2 + (vy-ty)^2 + (vz-tz)^2: the squared Euclidean
+ *     distance between voxel indices, an integer; 0 for a target.  The output is d2(v) when d2(v) <= R^2 and VXRT_DIST_FAR
+ *     otherwise.  The field is exact, not a chamfer or jump-flood approximation: a target with d2 <= R^2 is at most R away
+ *     on every axis, so it lies in the halo, and the three separable sweeps (x, then y, then z, each over offsets -R .. R)
+ *     take the minimum over every target of the halo; a partial sum above R^2 can only end above R^2.  The value does not
+ *     depend on the algorithm or the scheduling.
+ *   Limits.  1 <= R <= VXRT_DIST_MAX_RADIUS (R^2 = 65025 < VXRT_DIST_FAR, so the field is one uint16_t per voxel);
+ *     1 <= dims[k]; dims[0] * dims[1] * dims[2] <= 2^28; the halo box (dims[k] + 2R per axis) within vxrt_read_region's
+ *     2^36 voxels; origin[k] - R >= -2^31 and origin[k] + dims[k] + R <= 2^31 - 1.
+ * Outputs:
+ *   d_dist2: one uint16_t per voxel in region order (x fastest, then y, then z, no padding, as d_labels of
+ *     vxrt_find_islands).
+ *   d_summary: zero (voxels of B that are targets), near (values 1 .. R^2), far (VXRT_DIST_FAR), max_d2 (the largest value
+ *     that is not FAR, 0 when there is none), sum_d2 (the sum of the values that are not FAR: a checksum for callers that
+ *     do not want the whole field back).
+ * Workspace.  d_work holds vxrt_distance_workspace_bytes(dims, radius) bytes, 0 outside the limits on dims and radius.  With
+ *   r(n) = n rounded up to a multiple of 256, h[k] = dims[k] + 2R, wh = ceil(h[0] / 32) and T[k] = ceil(dims[k] / 64):
+ *     bytes = r(4 * wh * h[1] * h[2]) + r(2 * dims[0] * dims[1] * h[2]) + r(wh * ceil(h[1] / 8) * ceil(h[2] / 8))
+ *             + r(T[0] * T[1] * T[2])
+ *   (the halo's bits, the uint16 field after the y sweep over every halo slice, one occupancy byte per 32 x 8 x 8 halo
+ *   voxels, one byte per 64^3 tile of B): 2 * (1 + 2R / dims[2]) bytes per voxel and the halo's bits.  The caller owns it; the
+ *   library allocates nothing per call.
+ * Call rules (as vxrt_find_islands): asynchronous on `stream`.  Checked in this order: a NULL ctx, origin, dims, d_work,
+ *   d_dist2 or d_summary; the radius; the dims and the halo box; the origin; the mode -- each VXRT_ERR_INVALID; then no
+ *   world VXRT_ERR_NO_WORLD; a streamed world VXRT_ERR_INVALID (a cache is not queried).  A refused call writes nothing.
+ *   The call never loads outside the tables.  Results are bit-identical from call to call.
+ * vxrt_distance_field_host copies the outputs to host buffers (the same sizes), allocates its own workspace and is
+ *   synchronous. */
+#define VXRT_DIST_MAX_RADIUS 255
+#define VXRT_DIST_FAR 0xFFFFu
+typedef enum vxrt_dist_mode { VXRT_DIST_TO_SOLID = 0, VXRT_DIST_TO_EMPTY = 1 } vxrt_dist_mode;
+typedef struct vxrt_distance_summary {
+    uint32_t zero, near, far, max_d2;
+    uint64_t sum_d2;
+} vxrt_distance_summary;
+uint64_t vxrt_distance_workspace_bytes(const int32_t dims[3], uint32_t radius); /* 0 outside the contract */
+int vxrt_distance_field(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode,
+                        void *d_work, uint16_t *d_dist2, vxrt_distance_summary *d_summary, void *stream);
+/* the same on host buffers, synchronous; allocates its own workspace */
+int vxrt_distance_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode,
+                             uint16_t *dist2, vxrt_distance_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

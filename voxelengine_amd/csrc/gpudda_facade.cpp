@@ -297,6 +297,16 @@ int VoxelRaytracer3D::NavField(const int32_t origin[3], const int32_t dims[3], c
                                dist ? dist->data() : nullptr, &summary);
 }
 
+int VoxelRaytracer3D::DistanceField(const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode,
+                                    std::vector<uint16_t>& dist2, vxrt_distance_summary& summary)
+{
+    Flush();
+    if (vxrt_distance_workspace_bytes(dims, radius) == 0)
+        return VXRT_ERR_INVALID;
+    dist2.assign((size_t)dims[0] * dims[1] * dims[2], 0u);
+    return vxrt_distance_field_host(ctx, origin, dims, radius, mode, dist2.data(), &summary);
+}
+
 int VoxelRaytracer3D::NavPaths(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent,
                                const std::vector<uint8_t>& next, const int32_t* starts, size_t n, uint32_t max_steps,
                                std::vector<uint32_t>& lengths, std::vector<uint32_t>& status, std::vector<int32_t>* cells)

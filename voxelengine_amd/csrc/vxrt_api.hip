@@ -2,6 +2,7 @@
 // Owns the HBM-resident world tables, the camera/lighting state the reference keeps in
 // process globals (hFrameInfo / g_env, VoxelRT/Renderer.cu:24-25,89) and the launches.
 #include "../../include/vxrt.h"
+#include "vxrt_dist.hpp"
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
 #include "vxrt_islands.hpp"
@@ -59,6 +60,9 @@ hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[
                      uint32_t ngoals, uint32_t max_dist, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
                      vxrt_nav_summary* summary, hipStream_t stream);
 hipError_t nav_paths(const NavPathArgs& P, hipStream_t stream);
+// distance fields (vxrt_dist.hip)
+hipError_t distance_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t radius, uint32_t mode, void* work,
+                          uint16_t* dist2, vxrt_distance_summary* summary, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -1681,7 +1685,7 @@ static int edit_run(vxrt_ctx* c, const std::vector<Op>& ops, Launch launch, vxrt
     return finish();
 }
 
-// ---- what the calls on the resident world share (edits, stamps, reads, collision, islands, navigation) -----------------
+// ---- what the calls on the resident world share (edits, stamps, reads, collision, islands, navigation, distance) -------
 
 // the checks every call on the resident world makes after its argument checks, in the order of include/vxrt.h: a world
 // resident, and not a streamed one (`verb`: what the call would do to it)
@@ -2118,6 +2122,64 @@ int vxrt_nav_paths(vxrt_ctx* c, const vxrt_nav_field_desc* field, const int32_t*
     P.climb = ag.climb;
     P.drop = ag.drop;
     VX_HIP(vxrt::nav_paths(P, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+// ---- distance fields -------------------------------------------------------------------------------------------------
+uint64_t vxrt_distance_workspace_bytes(const int32_t dims[3], uint32_t radius)
+{
+    vxrt::DistLayout L;
+    return dims && vxrt::dist_layout(nullptr, dims, radius, L) ? L.total_bytes : 0;
+}
+
+// the checks both distance calls make after their NULL checks, in the order of include/vxrt.h
+static int distance_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode)
+{
+    vxrt::DistLayout L;
+    if (radius < 1 || radius > vxrt::kDistMaxRadius)
+        return fail(VXRT_ERR_INVALID, "distance radius: 1 .. VXRT_DIST_MAX_RADIUS");
+    if (!vxrt::dist_layout(nullptr, dims, radius, L))
+        return fail(VXRT_ERR_INVALID, "distance box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36");
+    if (!vxrt::dist_layout(origin, dims, radius, L))
+        return fail(VXRT_ERR_INVALID, "distance box: origin - radius or origin + dims + radius beyond int32");
+    if (mode != VXRT_DIST_TO_SOLID && mode != VXRT_DIST_TO_EMPTY)
+        return fail(VXRT_ERR_INVALID, "distance mode: VXRT_DIST_TO_SOLID or VXRT_DIST_TO_EMPTY");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_distance_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode, void* d_work,
+                        uint16_t* d_dist2, vxrt_distance_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !d_work || !d_dist2 || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = distance_ready(c, origin, dims, radius, mode))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::distance_field(vxrt::query_world(c), origin, dims, radius, (uint32_t)mode, d_work, d_dist2, d_summary,
+                                (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_distance_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode,
+                             uint16_t* dist2, vxrt_distance_summary* summary)
+{
+    if (!c || !origin || !dims || !dist2 || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = distance_ready(c, origin, dims, radius, mode))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::DistLayout L;
+    vxrt::dist_layout(origin, dims, radius, L);
+    const size_t ob = (size_t)L.nvox * 2u;
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, ob, sizeof(vxrt_distance_summary)}))
+        return fail(VXRT_ERR_NOMEM, std::string("distance_field_host: ") + hipGetErrorString(e));
+    uint16_t* d_out = T.at<uint16_t>(1);
+    vxrt_distance_summary* d_sum = T.at<vxrt_distance_summary>(2);
+    VX_HIP(vxrt::distance_field(vxrt::query_world(c), origin, dims, radius, (uint32_t)mode, T.base, d_out, d_sum, nullptr));
+    VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_distance_summary), hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(dist2, d_out, ob, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }
 

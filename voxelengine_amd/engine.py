@@ -370,6 +370,48 @@ class Context:
         return NavField(origin=tuple(int(v) for v in origin), dims=dims, agent=agent, walkable=unpack_region(walk, dims),
                         next=grid(nxt), dist=grid(dst), summary=NavSummary(*(int(v) for v in summary)), ctx=self)
 
+    # ---- exact distance fields (extension, include/vxrt.h) -----------------------------------------------------------
+    def distance_workspace_bytes(self, dims, radius: int) -> int:
+        """vxrt_distance_workspace_bytes: the workspace of one distance_field call, 0 outside the contract"""
+        return int(self._L.vxrt_distance_workspace_bytes(_i3(dims), int(radius)))
+
+    def distance_field(self, origin, dims, radius: int, mode: int = N.DIST_TO_SOLID, out=None,
+                       stream: int | None = None) -> "DistanceField":
+        """The exact squared distance from every voxel of the box ``origin`` .. ``origin + dims - 1`` to the nearest solid
+        (``DIST_TO_SOLID``) or empty (``DIST_TO_EMPTY``) voxel of the world within ``radius`` voxels, ``DIST_FAR`` beyond it:
+        include/vxrt.h, vxrt_distance_field.  Asynchronous on ``stream`` (default: torch's current stream).  ``out``: a
+        device tensor of two-byte elements to write the field to (one per voxel; default: a new one).  Returns a
+        DistanceField; reading its ``summary`` waits for the call."""
+        import torch
+        dims = tuple(int(v) for v in dims)
+        ws = self.distance_workspace_bytes(dims, radius)
+        dev = "cuda:%d" % self.device
+        nvox = dims[0] * dims[1] * dims[2] if ws else 0
+        work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(max(nvox, 1), dtype=torch.int16, device=dev)
+        elif out.element_size() != 2 or out.numel() < nvox or not out.is_contiguous():
+            raise ValueError("out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] two-byte elements")
+        summary = torch.zeros(6, dtype=torch.int32, device=dev)
+        s = _stream(stream)
+        N.check(self._L.vxrt_distance_field(self._h, _i3(origin), _i3(dims), int(radius), int(mode), _ptr(work), _ptr(out),
+                                            _ptr(summary), s))
+        work.record_stream(torch.cuda.ExternalStream(s, device=dev))  # freed here, still in use on the call's stream
+        return DistanceField(origin=tuple(int(v) for v in origin), dims=dims, radius=int(radius), mode=int(mode),
+                             dist2=out.view(-1)[:nvox], _summary=summary, _stream=s)
+
+    def distance_field_host(self, origin, dims, radius: int, mode: int = N.DIST_TO_SOLID) -> "DistanceField":
+        """distance_field through the synchronous host call (vxrt_distance_field_host): ``dist2`` is a numpy uint16
+        [x, y, z] grid."""
+        dims = tuple(int(v) for v in dims)
+        nvox = dims[0] * dims[1] * dims[2] if self.distance_workspace_bytes(dims, radius) else 0
+        out = np.zeros(max(nvox, 1), np.uint16)
+        summary = np.zeros(6, np.uint32)
+        N.check(self._L.vxrt_distance_field_host(self._h, _i3(origin), _i3(dims), int(radius), int(mode), out.ctypes.data,
+                                                 summary.ctypes.data))
+        return DistanceField(origin=tuple(int(v) for v in origin), dims=dims, radius=int(radius), mode=int(mode),
+                             dist2=out[:nvox].reshape(dims[::-1]).transpose(2, 1, 0), _summary=summary, _stream=None)
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -602,6 +644,47 @@ class Islands:
         """One Body per table row -- the island's box, displaced by ``delta`` -- for move_boxes (falling debris).  A box
         wider than BODY_MAX_EXTENT on some axis is an invalid body there: move_boxes returns it unchanged with BODY_INVALID."""
         return [Body(tuple(float(v) for v in r["lo"]), tuple(float(v) for v in r["hi"]), tuple(delta)) for r in self.table]
+
+
+class DistanceSummary(NamedTuple):
+    """vxrt_distance_summary: voxels of the box that are targets, values 1 .. radius^2, DIST_FAR values, the largest value
+    that is not DIST_FAR, the sum of the values that are not DIST_FAR"""
+    zero: int
+    near: int
+    far: int
+    max_d2: int
+    sum_d2: int
+
+
+@dataclass
+class DistanceField:
+    """The result of Context.distance_field: ``dist2`` one two-byte value per voxel in region order on the device (a numpy
+    uint16 [x, y, z] grid from distance_field_host), ``summary`` a DistanceSummary."""
+    origin: tuple
+    dims: tuple
+    radius: int
+    mode: int
+    dist2: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> DistanceSummary:
+        """the summary; for a device field this waits for the call's stream"""
+        w = self._summary
+        if not isinstance(w, np.ndarray):
+            import torch
+            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
+            w = self._summary = w.cpu().numpy().view(np.uint32)
+        return DistanceSummary(int(w[0]), int(w[1]), int(w[2]), int(w[3]), int(w[4]) | int(w[5]) << 32)
+
+    def grid(self) -> np.ndarray:
+        """the field as a numpy uint16 [x, y, z] grid (a device field is copied to the host)"""
+        if isinstance(self.dist2, np.ndarray):
+            return self.dist2
+        import torch
+        torch.cuda.ExternalStream(self._stream, device=self.dist2.device).synchronize()
+        return self.dist2.cpu().numpy().view(np.uint16).reshape(self.dims[::-1]).transpose(2, 1, 0)
 
 
 class NavAgent(NamedTuple):
