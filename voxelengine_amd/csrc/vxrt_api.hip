@@ -926,6 +926,11 @@ int vxrt_frame_stats_get(vxrt_ctx* c, vxrt_frame_stats* out)
     out->dbg[11] = h[vxrt::kStatDbgParkTicks];
     out->guard_slack_loads = h[vxrt::kStatGuardSlack];
     out->guard_stray_loads = h[vxrt::kStatGuardStray];
+#ifdef VXRT_EXPERIMENTS  // (vxrt_frame_stats has no field for them: a development print of the A/B build)
+    if (getenv("VXRT_PRINT_COSTART"))
+        fprintf(stderr, "vxrt: rounds with the end-of-walk and the ray-finished phase %llu, with walk starts from both %llu, of %llu rounds\n",
+                h[vxrt::kStatDbgCoRuns], h[vxrt::kStatDbgCoStarts], h[vxrt::kStatDbgIters]);
+#endif
     return VXRT_OK;
 }
 

@@ -75,9 +75,9 @@ __global__ __launch_bounds__(64, VXRT_BATCH_OCC) void k_trace_batch_persist(Batc
             c_end = __popcll(__ballot(waits_for_end(T.st)));
         }
         if (vote_run(c_end, c_walk + c_box, VXRT_BATCH_VOTE_END)) {
-            T.template phase_end<STATS>(W);
+            T.template phase_end_deferred<STATS>(W);
             c_end = 0;
-            c_walk = __popcll(__ballot(T.st == ST_WALK));
+            c_walk = __popcll(__ballot(T.st == ST_WALK));  // (a restarted coarse walk is set up below, before the probes)
             c_next = __popcll(__ballot(T.st == ST_DONE));
         }
         // ---- parked phase: a ray finished -> write its result, take the next ray of the ticket --------------------
@@ -152,13 +152,15 @@ __global__ __launch_bounds__(64, VXRT_BATCH_OCC) void k_trace_batch_persist(Batc
                 }
             }
             if (launch)
-                T.begin_ray(W, o, d, B.max_steps);
-            T.after_begin_ray(launch);
+                T.begin_ray_deferred(W, o, d, B.max_steps);
+            T.after_begin_ray_deferred(launch);
             if (drained && T.st == ST_DONE && my_ray == kNone)
                 T.st = ST_IDLE;
             n_rays += (uint32_t)__popcll(__ballot(got));
             n_hits += (uint32_t)__popcll(__ballot(c_hit));
         }
+        // the coarse walks the end-of-walk and ray-finished phases of this round recorded, set up in one execution
+        T.start_pending(W);
         T.template probe_pairs<VXRT_BATCH_PAIRS, STATS, VXRT_BATCH_MASKED != 0>(W);
     }
 

@@ -28,6 +28,8 @@ enum StatSlot {
     kStatDbgParkTicks,  // ... inside the box and end-of-walk phases
     kStatGuardSlack,    // load guard (probe-counting launches): occupancy loads beyond a table, inside the allocator's slack
     kStatGuardStray,    // ... and outside everything addressable (must stay 0)
+    kStatDbgCoRuns,     // persistent render kernel: rounds in which both the end-of-walk and the ray-finished phase ran
+    kStatDbgCoStarts,   // ... and in which the first restarted a coarse walk and the second launched a ray (one shared set-up)
     kStatCount
 };
 

@@ -246,6 +246,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     unsigned int dg_runs[3] = {0, 0, 0}, dg_lanes[3] = {0, 0, 0};  // next / end / box phase executions, lanes served
     const unsigned long long dg_t0 = STATS ? wall_clock64() : 0ull;
     unsigned long long dg_next_ticks = 0, dg_park_ticks = 0;
+    unsigned long long dg_co_runs = 0, dg_co_starts = 0;  // rounds in which the end-of-walk AND the ray-finished phase ran / started walks
 #ifdef VXRT_TAIL_DEBUG
     unsigned long long px_t0 = 0;
 #endif
@@ -313,6 +314,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
         // hits can enter its brick, and a lane whose ray ends can start its next ray, in the same round instead of
         // waiting for the next round's vote (+4 % with several probes per round; with one probe per round it was +-0)
         int c_walk = n_walk, c_box = n_box, c_end = n_end, c_next = n_next;
+        bool dg_end_ran = false, dg_end_restarted = false;  // STATS only: this round's end-of-walk phase ran / restarted a lane
         if (vote2(c_box, c_walk, VXRT_VOTE2_BOX, VXRT_VOTE2_ABS_BOX)) {
             if (STATS) {
                 dg_runs[2] += 1u;
@@ -332,11 +334,16 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 dg_lanes[1] += (unsigned)c_end;
                 dg_park_ticks -= wall_clock64();
             }
-            T.template phase_end<STATS>(W);
+            T.template phase_end_deferred<STATS>(W);
             if (STATS)
                 dg_park_ticks += wall_clock64();
             c_end = 0;
+            // (lanes whose coarse walk restarts are ST_WALK already, set up by start_pending below: walkers for the vote that follows)
             c_walk = __popcll(__ballot(T.st == ST_WALK));
+            if (STATS) {
+                dg_end_ran = true;
+                dg_end_restarted = T.pend_m != 0ull;
+            }
             c_next = __popcll(__ballot(T.st == ST_DONE));
         }
         // ---- parked phase: a ray finished -> continue the pixel's chain, store, take the next pixel ------------
@@ -463,7 +470,9 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                                       bounce2 ? -r.normal.z : normal.z);
                     const f3 bo = mk3(bounce2 ? r.pos.x : position.x, bounce2 ? r.pos.y : position.y,
                                       bounce2 ? r.pos.z : position.z);
-                    f3 sd = mk3(random_float(si) * 2 - 1, random_float(si * 10u) * 2 - 1, random_float(si * 100u) * 2 - 1);
+                    float two = 2.0f;
+                    pin(two);  // (materialised here, as `ten` in store_pixel: hoisted to the top of the kernel it is spilled)
+                    f3 sd = mk3(random_float(si) * two - 1, random_float(si * 10u) * two - 1, random_float(si * 100u) * two - 1);
                     {
                         const float sdd = dot3(sd, sd);
                         const f3 raw = sd;
@@ -500,7 +509,10 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 }
             }
             // hand out pixels of the wave's tile(s) to the lanes that are free
+            // (the new pixel in variables of its own, stored by the lanes that got one: the old pixel's coordinates are dead
+            // once its chain has been continued, instead of being carried through the hand-out for the store below)
             bool got = false;
+            uint32_t new_tx = 0, new_row = 0;
             unsigned long long want = __ballot(T.st == ST_DONE && stage == PX_NONE);
             while (want != 0ull && !drained) {
                 if (tile_used >= 64u) {
@@ -532,19 +544,21 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(want >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)want, 0u));
                 if (wants && rank < avail) {
                     const uint32_t p = tile_used + rank;
-                    px_tx = (tile % ntx) * 8u + (p & 7u);
-                    px_row = (tile / ntx) * 8u + (p >> 3);
-                    got = pixel_coords(A, MULTI ? A.views[tile_view].frame_number : A.frame_number, px_tx, px_row).live;
+                    new_tx = (tile % ntx) * 8u + (p & 7u);
+                    new_row = (tile / ntx) * 8u + (p >> 3);
+                    got = pixel_coords(A, MULTI ? A.views[tile_view].frame_number : A.frame_number, new_tx, new_row).live;
                     if (MULTI)
-                        px_row |= tile_view << 16;
+                        new_row |= tile_view << 16;
                 }
                 const uint32_t asked = (uint32_t)__popcll(want);
                 tile_used += asked < avail ? asked : avail;
                 want = __ballot(T.st == ST_DONE && stage == PX_NONE && !got);
             }
             if (got) {
-                const LaneView V = lane_view(A, MULTI ? px_row >> 16 : 0u);
-                const PixelCoords pc = pixel_coords(A, V.frame_number, px_tx, MULTI ? px_row & 0xFFFFu : px_row);
+                PX_ST_U(PF_TX, new_tx);
+                PX_ST_U(PF_ROW, new_row);
+                const LaneView V = lane_view(A, MULTI ? new_row >> 16 : 0u);
+                const PixelCoords pc = pixel_coords(A, V.frame_number, new_tx, MULTI ? new_row & 0xFFFFu : new_row);
                 camera_ray(A, V, pc.x, pc.y, l_origin, l_dir);
                 color = l_dir;  // the pixel's colour if the primary ray misses (Renderer.cu:254-258)
                 PX_ST_COL();
@@ -556,13 +570,15 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
 #endif
             }
             if (launch)
-                T.begin_ray(W, l_origin, l_dir, l_max);
-            T.after_begin_ray(launch);
+                T.begin_ray_deferred(W, l_origin, l_dir, l_max);
+            T.after_begin_ray_deferred(launch);
+            if (STATS) {
+                dg_co_runs += dg_end_ran ? 1ull : 0ull;
+                dg_co_starts += (dg_end_restarted && __ballot(launch) != 0ull) ? 1ull : 0ull;
+            }
             if (drained && T.st == ST_DONE && stage == PX_NONE)
                 T.st = ST_IDLE;
             PX_ST_U(PF_STAGE, stage);
-            PX_ST_U(PF_TX, px_tx);
-            PX_ST_U(PF_ROW, px_row);
             {   // ray counters: ballots here, where the whole wave is converged again; accumulated in LDS (as registers they
                 // are vector registers spilled around this phase: the scalar file is full)
                 const uint32_t d0 = (uint32_t)__popcll(__ballot(got)), d1 = (uint32_t)__popcll(__ballot(c_shadow)),
@@ -585,6 +601,11 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
         // (Measured and not kept, profiles/r04_tail.md: one or two pairs per round once the tile queue has run dry -- on the idea
         // that the tail is a latency problem -- 16 views per launch -2.3 %, one view per launch -5 %; leaving a burst as soon as
         // no lane walks any more: -0.8 % / +-0.)
+        // Before the probes, the coarse walks this round's phases recorded -- restarts after a brick miss (end-of-walk phase) and
+        // new rays (ray-finished phase) -- are set up in ONE execution of start_walk<false> over the union of their lanes: the
+        // two phases usually run in the same round (finished lanes come from the end-of-walk phase), and the kernel holds one
+        // inlined copy of the set-up instead of two (profiles/r10_coarse_start.md).
+        T.start_pending(W);
         T.template probe_pairs<VXRT_SUBROUNDS2, STATS>(W);
     }
 
@@ -624,6 +645,8 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             atomicAdd(&stats[kStatDbgDrained], dg_drain);
             atomicAdd(&stats[kStatDbgNextTicks], dg_next_ticks);
             atomicAdd(&stats[kStatDbgParkTicks], dg_park_ticks);
+            atomicAdd(&stats[kStatDbgCoRuns], dg_co_runs);
+            atomicAdd(&stats[kStatDbgCoStarts], dg_co_starts);
         }
     }
 }

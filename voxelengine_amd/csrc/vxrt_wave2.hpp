@@ -61,7 +61,11 @@ namespace vxrt {
 // lane states: walking; parked for the tight-box phase; parked for the end-of-walk phase (ST_END, and ST_ENDHIT after a brick
 // probe that found an occupied voxel: the two codes differ in bit 0 only, so "waits for the end-of-walk phase" is one OR and
 // one compare -- written as `a || b` the vote's ballot compiled to two compares, a select and a third compare); ray finished;
-// no work left
+// no work left.  A lane whose coarse walk is recorded (CF_START_*) but not yet set up is ST_WALK already and has its bit in the
+// wave mask pend_m until start_pending, which runs before the next probe: the votes between count it as the walker it is about
+// to be without a compare of their own.  (A state code for it -- one bit from ST_WALK, an AND before the votes' compare --
+// was compiled too: it needs no scalar pair, yet the timed render kernels came out with MORE spilled scalar registers, 6 to 8
+// against 4 to 6, and the second-bounce ones with spilled vector registers.)
 enum : uint32_t { ST_WALK = 0u, ST_BOX = 1u, ST_END = 2u, ST_ENDHIT = 3u, ST_DONE = 4u, ST_IDLE = 5u };
 __device__ __forceinline__ bool waits_for_end(uint32_t st) { return (st | 1u) == 3u; }
 // (Measured in round 4 and not kept, profiles/r04_finish_walks.md: the two common ends of a ray -- a brick probe that finds a
@@ -178,6 +182,7 @@ struct WaveTracerT {
     uint32_t dn;              // per ray: bit k set where the ray does not move up axis k (d_k <= 0)
     f3 point;                 // HitIntersectedPoint of the walk that ended (tight-box phase / end-of-walk phase)
     lanemask_t fine_m;        // wave mask: lanes walking inside a brick
+    lanemask_t pend_m;        // wave mask: lanes whose coarse walk is recorded but not set up
     uint32_t* cold;           // &block[lane]; field F of this lane is cold[F * 64]
     // Probe counters of SURVEY 8(d)'s algorithmic bytes (the STATS instantiations of the phases only; dead otherwise):
     // in-range coarse probes (:247-256), brick entries (:420), in-range brick probes (:276).  They fall out of the walk's
@@ -185,6 +190,14 @@ struct WaveTracerT {
     // themselves count nothing.
     RayCounters cnt;
 
+    __device__ __forceinline__ bool lane_pending() const
+    {
+#ifdef VXRT_HOST_CHECK
+        return (pend_m & 1ull) != 0ull;
+#else
+        return lane_test(pend_m);
+#endif
+    }
     __device__ __forceinline__ bool lane_fine() const
     {
 #ifdef VXRT_HOST_CHECK
@@ -213,6 +226,7 @@ struct WaveTracerT {
         ws = point = mk3(0, 0, 0);
         rem0 = 0u;
         fine_m = 0ull;
+        pend_m = 0ull;
         cnt = RayCounters{0u, 0u, 0u, 0u, 0u};
     }
 
@@ -381,9 +395,33 @@ struct WaveTracerT {
         st = inside ? (uint32_t)ST_WALK : (uint32_t)ST_END;
     }
 
+    // The coarse walks that the deferred forms below (begin_ray_deferred, phase_end_deferred) recorded, all set up at once:
+    // start_walk<false> from CF_START_* for every lane of pend_m, which leaves it ST_WALK, or ST_END for a start outside
+    // the grid.  Called by the whole wave once per round, after the parked phases and before the probes, so that a
+    // round in which the end-of-walk phase restarts lanes AND the caller's ray-finished phase launches rays executes the
+    // set-up once (the kernels hold one inlined copy of the coarse set-up instead of two).  fine_m is the callers' business,
+    // as with start_walk.  One scalar test when nothing is pending.
+    __device__ __forceinline__ void start_pending(const WorldView& W)
+    {
+        if (pend_m == 0ull)
+            return;
+        if (lane_pending())
+            start_walk<false>(W, mk3(__uint_as_float(cold[CF_START_X * 64]), __uint_as_float(cold[CF_START_Y * 64]),
+                                     __uint_as_float(cold[CF_START_Z * 64])));
+        pend_m = 0ull;
+    }
+
     // Raytrace's prologue (:359-384): per-ray constants, world entry, first coarse walk.  Per lane; the caller clears the
     // lanes' bits in fine_m afterwards (after_begin_ray), where the wave is converged again.
     __device__ __forceinline__ void begin_ray(const WorldView& W, f3 origin, f3 ray, int max_steps_)
+    {
+        begin_ray_deferred(W, origin, ray, max_steps_);
+        start_walk<false>(W, mk3(__uint_as_float(cold[CF_START_X * 64]), __uint_as_float(cold[CF_START_Y * 64]),
+                                 __uint_as_float(cold[CF_START_Z * 64])));
+    }
+    // ... without the walk's set-up: its start is in CF_START_*, and after_begin_ray_deferred, where the wave is converged
+    // again, puts the lane into pend_m (start_pending)
+    __device__ __forceinline__ void begin_ray_deferred(const WorldView& W, f3 origin, f3 ray, int max_steps_)
     {
         // normalize and the three reciprocals of the slab test (:127-129, :366): the short exact forms of vxrt_device.hpp where
         // every operand is of ordinary size, the plain operators for the wave if any lane's is not
@@ -419,9 +457,15 @@ struct WaveTracerT {
         special = !(fabsf(d.x) >= kMinFastDir && fabsf(d.y) >= kMinFastDir && fabsf(d.z) >= kMinFastDir) ||
                   __float_as_uint(s0.x) == 0x80000000u || __float_as_uint(s0.y) == 0x80000000u || __float_as_uint(s0.z) == 0x80000000u;
         dn = (d.x > 0 ? 0u : 1u) | (d.y > 0 ? 0u : 2u) | (d.z > 0 ? 0u : 4u);
-        start_walk<false>(W, s0);
+        st = ST_WALK;
     }
     __device__ __forceinline__ void after_begin_ray(bool launched) { fine_m &= ~__ballot(launched); }
+    __device__ __forceinline__ void after_begin_ray_deferred(bool launched)
+    {
+        const lanemask_t m = __ballot(launched);
+        fine_m &= ~m;
+        pend_m |= m;
+    }
 
     // The crossing point of the step that started from rem word `before` (the cell before the step) along the axis
     // whose field the step decremented by `dec`, at time t -- the reference's `cross` (:293-313).
@@ -461,6 +505,13 @@ struct WaveTracerT {
     // phase enters the brick itself.
     template <bool STATS = false>
     __device__ __forceinline__ void phase_end(const WorldView& W)
+    {
+        phase_end_deferred<STATS>(W);
+        start_pending(W);
+    }
+    // ... without the set-up of the coarse walks it restarts: those lanes are left in pend_m (start_pending)
+    template <bool STATS = false>
+    __device__ __forceinline__ void phase_end_deferred(const WorldView& W)
     {
         const bool me = waits_for_end(st);
         const bool is_fine = lane_fine();
@@ -606,7 +657,7 @@ struct WaveTracerT {
                     cold[CF_START_Z * 64] = __float_as_uint(sz);
                     const bool restart = total_ < (int)(cold[CF_RAY_CODES * 64] >> 7);  // the while condition (:386)
                     if (restart) {
-                        start_walk<false>(W, mk3(sx, sy, sz));
+                        st = ST_WALK;
                         go_coarse = true;
                     } else {
                         st = ST_DONE;
@@ -615,7 +666,9 @@ struct WaveTracerT {
             }
         }
         // the level mask, where the wave is converged again
-        fine_m &= ~__ballot(go_coarse);
+        const lanemask_t m = __ballot(go_coarse);
+        fine_m &= ~m;
+        pend_m |= m;
     }
 
     // parked phase: tight-box test of an occupied coarse cell (:248-273) and, on a hit, the end of the coarse walk with
@@ -908,9 +961,10 @@ __device__ inline void trace_wave2(const WorldView& W, const int max_steps, cons
     WaveTracerT<WIDE> T;
     T.init(W, cold_column);
     if (active)
-        T.begin_ray(W, origin, ray, max_steps);
-    T.after_begin_ray(active);
+        T.begin_ray_deferred(W, origin, ray, max_steps);
+    T.after_begin_ray_deferred(active);
     for (;;) {
+        // (the ray just begun walks from the first round on: start_pending below sets it up before the first probe)
         const unsigned long long m_walk = __ballot(T.st == ST_WALK);
         const unsigned long long m_box = __ballot(T.st == ST_BOX);
         const unsigned long long m_end = __ballot(waits_for_end(T.st));
@@ -918,9 +972,10 @@ __device__ inline void trace_wave2(const WorldView& W, const int max_steps, cons
             break;
         const int n_walk = __popcll(m_walk), n_box = __popcll(m_box), n_end = __popcll(m_end);
         if (vote_run(n_end, n_walk + n_box, VXRT_VOTE_END))
-            T.template phase_end<STATS>(W);
+            T.template phase_end_deferred<STATS>(W);
         if (vote_run(n_box, n_walk, VXRT_VOTE_BOX))
             T.template phase_box<STATS>(W);
+        T.start_pending(W);
         T.template probe_pairs<PAIRS, STATS, MASKED>(W);
     }
     if (active)
