@@ -33,6 +33,9 @@
 // line "nav frame N nodes .. reached .. levels .. max_dist ..".  Kind 6 computes the exact distance field of the box of
 // origin a and dims b (VoxelRaytracer3D::DistanceField) within the radius |value|, to the nearest solid voxel when value > 0
 // and to the nearest empty voxel when value < 0, and prints one line "dist frame N zero .. near .. far .. max_d2 .. sum_d2 ..".
+// Kind 7 stamps a built-in mesh (VoxelRaytracer3D::StampMesh, union): an octahedron generated here, its centre on the centre of
+// voxel a, its radius bx voxels (by = bz = 0), voxelized in the modes `value` (1 = surface, 2 = solid, 3 = both), and prints one
+// line "mesh before frame N: T triangles, S set voxels, ... bricks touched, ... created".
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -251,6 +254,20 @@ int main(int argc, char** argv)
                 }
                 std::printf("dist frame %d zero %u near %u far %u max_d2 %u sum_d2 %llu\n", from, sum.zero, sum.near, sum.far,
                             sum.max_d2, (unsigned long long)sum.sum_d2);
+            } else if (e.op.kind == 7) {  // stamp the built-in mesh
+                flush_ops();
+                const int32_t r = 256 * e.op.b[0], c = 128;  // mesh frame: the origin is the corner of voxel a
+                const std::vector<int32_t> verts = {c + r, c, c, c - r, c, c, c, c + r, c, c, c - r, c, c, c, c + r, c, c, c - r};
+                const std::vector<uint32_t> tris = {0, 2, 4, 2, 1, 4, 1, 3, 4, 3, 0, 4, 2, 0, 5, 1, 2, 5, 3, 1, 5, 0, 3, 5};
+                vxrt_edit_stats st{};
+                vxrt_voxelize_summary sum{};
+                if (e.op.b[0] < 1 || e.op.b[1] != 0 || e.op.b[2] != 0 ||
+                    raytracer->StampMesh(verts, tris, e.op.a, e.op.value, VXRT_STAMP_UNION, &st, &sum) != VXRT_OK) {
+                    std::cerr << "mesh before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("mesh before frame %d: %u triangles, %u set voxels, %llu bricks touched, %llu created\n", from, sum.triangles,
+                            sum.set, (unsigned long long)st.bricks_touched, (unsigned long long)st.bricks_created);
             } else if (e.op.kind == 3) {  // paste
                 flush_ops();
                 const auto it = clipboard.find(e.op.value);

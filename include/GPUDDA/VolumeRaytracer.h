@@ -29,6 +29,7 @@ struct vxrt_island_summary;
 struct vxrt_nav_agent;
 struct vxrt_nav_summary;
 struct vxrt_distance_summary;
+struct vxrt_voxelize_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -176,6 +177,16 @@ public:
     // first.  Returns the vxrt_status.
     int DistanceField(const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode, std::vector<uint16_t>& dist2,
                       vxrt_distance_summary& summary);
+    // mesh voxelization (extension, include/vxrt.h, vxrt_voxelize_mesh_host): `vertices` 3 int32 per vertex in units of
+    // 1 / 256 voxel in the frame of a region of `dims` voxels, `triangles` 3 vertex indices per triangle, `modes` a subset of
+    // VXRT_VOX_SURFACE | VXRT_VOX_SOLID; `bits` gets the region words (a StampVoxels argument as it is).  No world is needed.
+    int VoxelizeMesh(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles, const int32_t dims[3],
+                     int32_t modes, std::vector<uint32_t>& bits, vxrt_voxelize_summary& summary);
+    // VoxelizeMesh into the mesh's own bounding box (the voxels its valid triangles' vertices touch, at most
+    // VXRT_VOX_MAX_DIM per axis), then one StampVoxels of it in `stampMode`: mesh unit (0, 0, 0) lands on the corner of world
+    // voxel `origin`.  Returns the vxrt_status; VXRT_ERR_INVALID for a mesh without a triangle of valid indices.
+    int StampMesh(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles, const int32_t origin[3],
+                  int32_t modes, int stampMode, vxrt_edit_stats* stats = nullptr, vxrt_voxelize_summary* summary = nullptr);
 
 private:
     void Flush();

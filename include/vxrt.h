@@ -500,6 +500,69 @@ int vxrt_distance_field(vxrt_ctx *ctx, const int32_t origin[3], const int32_t di
 int vxrt_distance_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t radius, int32_t mode,
                              uint16_t *dist2, vxrt_distance_summary *summary);
 
+/* ---- mesh voxelization -- an EXTENSION (with the stamps above: a triangle mesh turned into a stamp on the device).  The
+ * call reads no world: it works with none resident and with a streamed one.
+ *   Coordinates.  Fixed point, VXRT_VOX_FRAC_BITS = 8: 256 units per voxel.  d_vertices is int32[n_vertices][3] in the frame
+ *     of the output region; region voxel (i, j, k) is the cube [256 i, 256 (i+1)] x [256 j, 256 (j+1)] x [256 k, 256 (k+1)]
+ *     and its centre is (256 i + 128, 256 j + 128, 256 k + 128).  d_triangles is uint32[n_triangles][3] vertex indices.  The
+ *     mesh may extend outside the region; it is clipped to it.
+ *   Limits.  1 <= dims[k] <= VXRT_VOX_MAX_DIM = 1024; every vertex coordinate that a triangle uses lies in
+ *     [-2^18, 2^18] (VXRT_VOX_MAX_COORD); n_triangles <= VXRT_VOX_MAX_TRIANGLES = 2^24.  Hence the arithmetic bound:
+ *     coordinate differences stay below 2^20, cross-product components below 2^40 and a plane value n . (p - v0) below
+ *     2^62, so every quantity below is exact in int64.
+ *   Validity (per triangle, like the body validity rule).  A triangle is INVALID when one of its indices is >= n_vertices
+ *     or one of its vertices has a coordinate outside the range; DEGENERATE when it is valid and its normal
+ *     n = (v1 - v0) x (v2 - v0) is the zero vector.  Both kinds contribute nothing and are counted.
+ *   VXRT_VOX_SURFACE.  Voxel (i, j, k) is set if and only if some valid, non-degenerate triangle, as a closed set,
+ *     intersects the voxel's closed cube; touching counts.  Decided exactly by the 13-axis separating-axis test in integers
+ *     (the 3 cube axes, the normal, the 9 products edge x cube axis); a pair is separated only on a strict inequality.
+ *   VXRT_VOX_SOLID.  Voxel (i, j, k) is set if and only if an odd number of valid, non-degenerate triangles are CROSSED by
+ *     the ray from its centre c toward +x.  Triangle T is crossed when
+ *     (a) T covers (cy, cz) in the yz projection: never when n.x == 0; otherwise T is oriented so that n.x > 0 (v1 and v2
+ *         swapped when n.x < 0), and for each directed edge a -> b, with the inward normal (ey, ez) = (-(b.z - a.z), b.y - a.y)
+ *         and E = ey (cy - a.y) + ez (cz - a.z): E > 0, or E == 0 and (ey > 0 or (ey == 0 and ez > 0)) -- the top-left rule;
+ *     (b) the plane meets the ray strictly beyond the centre: sign(n.x) * (n . (c - v0)) < 0.
+ *     This is the test of the point (cx + eta, cy + eps, cz + eps^2), 0 < eps << eta << 1: for a closed mesh the parity is
+ *     the inside test of a generic point; a shared edge or vertex is never counted twice or missed; a box mesh [a, b) fills
+ *     exactly the centres a <= c < b (voxel v occupies [v, v+1)).  Equivalent form per (T, j, k): with x* the plane's x at
+ *     (cy, cz), m = clamp(ceil((x* - 128) / 256), 0, dims[0]) and T toggles voxels 0 .. m-1 of row (j, k).  A triangle beyond
+ *     the region's +x face is crossed like any other (the part of a closed mesh that sticks out closes the parity).
+ *   The result does not depend on triangle order, vertex order within a triangle, winding or scheduling.
+ *   modes: a non-zero subset of {VXRT_VOX_SURFACE, VXRT_VOX_SOLID}; the output is the OR of the chosen fields.
+ * Outputs:
+ *   d_bits: vxrt_read_region's layout, vxrt_region_words(dims) words, padding bits 0: a vxrt_stamp's d_bits as it is.
+ *   d_summary: set (bits set in the output); surface, solid (bits of each chosen field, 0 for one not chosen); triangles
+ *     (n_triangles); invalid; degenerate; outside (valid triangles whose closed bounding box misses the closed region box
+ *     [0, 256 dims]).
+ * Workspace.  d_work holds vxrt_voxelize_workspace_bytes(dims, n_triangles) bytes, 0 outside the limits.  With r(n) = n
+ *   rounded up to a multiple of 256 and W = ceil(dims[0] / 32) * dims[1] * dims[2]:
+ *     bytes = r(4 * W) + r(4 * n_triangles) + r(8 * ceil(n_triangles / 256)) + 256
+ *   (the solid field's toggle bits, one item offset per triangle, one per group of 256 triangles, the counters).  The caller
+ *   owns it; the library allocates nothing per call and never synchronises with the host inside the call.
+ * Call rules (as vxrt_distance_field): asynchronous on `stream`.  Checked in this order: a NULL ctx, dims, d_work, d_bits
+ *   or d_summary; modes outside {1, 2, 3}; the dims; n_triangles above the limit; d_vertices or d_triangles NULL with
+ *   n_triangles > 0 -- each VXRT_ERR_INVALID.  n_triangles == 0 is valid: zeroed bits and summary.  A refused call writes
+ *   nothing.  Results are bit-identical from call to call.
+ * vxrt_voxelize_mesh_host takes host buffers, allocates its own workspace and is synchronous.
+ * The cost follows the voxels near the triangles (blocks of 64 x 8 x 8 voxels and their rows are culled by the same exact
+ * test before any voxel is tested), the yz area of the triangles (solid) and one pass over the output. */
+#define VXRT_VOX_FRAC_BITS 8
+#define VXRT_VOX_MAX_DIM 1024
+#define VXRT_VOX_MAX_COORD (1 << 18)
+#define VXRT_VOX_MAX_TRIANGLES (1u << 24)
+#define VXRT_VOX_SURFACE 1
+#define VXRT_VOX_SOLID 2
+typedef struct vxrt_voxelize_summary {
+    uint32_t set, surface, solid, triangles, invalid, degenerate, outside, reserved;
+} vxrt_voxelize_summary;
+uint64_t vxrt_voxelize_workspace_bytes(const int32_t dims[3], uint32_t n_triangles); /* 0 outside the contract */
+int vxrt_voxelize_mesh(vxrt_ctx *ctx, const int32_t *d_vertices, uint32_t n_vertices, const uint32_t *d_triangles,
+                       uint32_t n_triangles, const int32_t dims[3], int32_t modes, void *d_work, uint32_t *d_bits,
+                       vxrt_voxelize_summary *d_summary, void *stream);
+int vxrt_voxelize_mesh_host(vxrt_ctx *ctx, const int32_t *vertices, uint32_t n_vertices, const uint32_t *triangles,
+                            uint32_t n_triangles, const int32_t dims[3], int32_t modes, uint32_t *bits,
+                            vxrt_voxelize_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

@@ -4,6 +4,8 @@
 #include "../../include/GPUDDA/VoxelWorldBuilder.h"
 #include "../../include/vxrt.h"
 
+#include <climits>
+#include <cstdint>
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -305,6 +307,60 @@ int VoxelRaytracer3D::DistanceField(const int32_t origin[3], const int32_t dims[
         return VXRT_ERR_INVALID;
     dist2.assign((size_t)dims[0] * dims[1] * dims[2], 0u);
     return vxrt_distance_field_host(ctx, origin, dims, radius, mode, dist2.data(), &summary);
+}
+
+int VoxelRaytracer3D::VoxelizeMesh(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles,
+                                   const int32_t dims[3], int32_t modes, std::vector<uint32_t>& bits,
+                                   vxrt_voxelize_summary& summary)
+{
+    const uint32_t nv = (uint32_t)(vertices.size() / 3), nt = (uint32_t)(triangles.size() / 3);
+    if (vertices.size() / 3 > UINT32_MAX || triangles.size() / 3 > UINT32_MAX || vxrt_voxelize_workspace_bytes(dims, nt) == 0)
+        return VXRT_ERR_INVALID;
+    bits.assign((size_t)vxrt_region_words(dims), 0u);
+    return vxrt_voxelize_mesh_host(ctx, vertices.data(), nv, triangles.data(), nt, dims, modes, bits.data(), &summary);
+}
+
+int VoxelRaytracer3D::StampMesh(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles,
+                                const int32_t origin[3], int32_t modes, int stampMode, vxrt_edit_stats* stats,
+                                vxrt_voxelize_summary* summary)
+{
+    const size_t nv = vertices.size() / 3, nt = triangles.size() / 3;
+    int64_t mn[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, mx[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+    for (size_t t = 0; t < nt; ++t) {
+        const uint32_t* idx = &triangles[3 * t];
+        if (idx[0] >= nv || idx[1] >= nv || idx[2] >= nv)
+            continue;
+        for (int i = 0; i < 3; ++i)
+            for (int k = 0; k < 3; ++k) {
+                const int64_t c = vertices[3 * (size_t)idx[i] + k];
+                mn[k] = c < mn[k] ? c : mn[k];
+                mx[k] = c > mx[k] ? c : mx[k];
+            }
+    }
+    if (mn[0] > mx[0])
+        return VXRT_ERR_INVALID;
+    int32_t lo[3], dims[3], at[3];
+    for (int k = 0; k < 3; ++k) {  // the voxel cubes the bounding box touches
+        const int64_t l = (mn[k] - 1) >> 8, h = mx[k] >> 8;
+        if (h - l + 1 > VXRT_VOX_MAX_DIM || (int64_t)origin[k] + l < INT32_MIN || (int64_t)origin[k] + h > INT32_MAX - 1)
+            return VXRT_ERR_INVALID;
+        lo[k] = (int32_t)l;
+        dims[k] = (int32_t)(h - l + 1);
+        at[k] = origin[k] + lo[k];
+    }
+    std::vector<int32_t> local(vertices.size() - vertices.size() % 3);
+    for (size_t i = 0; i < local.size(); ++i) {  // a vertex no valid triangle uses may leave int32: the library never reads it
+        const int64_t c = (int64_t)vertices[i] - 256 * (int64_t)lo[i % 3];
+        local[i] = c < INT32_MIN ? INT32_MIN : (c > INT32_MAX ? INT32_MAX : (int32_t)c);
+    }
+    std::vector<uint32_t> bits;
+    vxrt_voxelize_summary sum{};
+    int rc = VoxelizeMesh(local, triangles, dims, modes, bits, sum);
+    if (summary)
+        *summary = sum;
+    if (rc != VXRT_OK)
+        return rc;
+    return StampVoxels(at, dims, bits.data(), stampMode, stats);
 }
 
 int VoxelRaytracer3D::NavPaths(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent,

@@ -9,6 +9,7 @@
 #include "vxrt_nav.hpp"
 #include "vxrt_region.hpp"
 #include "vxrt_stream.hpp"
+#include "vxrt_voxelize.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -63,6 +64,9 @@ hipError_t nav_paths(const NavPathArgs& P, hipStream_t stream);
 // distance fields (vxrt_dist.hip)
 hipError_t distance_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t radius, uint32_t mode, void* work,
                           uint16_t* dist2, vxrt_distance_summary* summary, hipStream_t stream);
+// mesh voxelization (vxrt_voxelize.hip)
+hipError_t voxelize_mesh(const int32_t* verts, uint32_t nv, const uint32_t* tris, uint32_t nt, const int32_t d[3], uint32_t modes,
+                         void* work, uint32_t* bits, vxrt_voxelize_summary* summary, uint32_t work_waves, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -2184,6 +2188,71 @@ int vxrt_distance_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t
     VX_HIP(vxrt::distance_field(vxrt::query_world(c), origin, dims, radius, (uint32_t)mode, T.base, d_out, d_sum, nullptr));
     VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_distance_summary), hipMemcpyDeviceToHost));
     VX_HIP(hipMemcpy(dist2, d_out, ob, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- mesh voxelization -------------------------------------------------------------------------------------------------
+uint64_t vxrt_voxelize_workspace_bytes(const int32_t dims[3], uint32_t n_triangles)
+{
+    vxrt::VoxLayout L;
+    return dims && vxrt::vox_layout(dims, n_triangles, L) ? L.total_bytes : 0;
+}
+
+// the checks both voxelize calls make after their NULL checks, in the order of include/vxrt.h
+static int voxelize_ready(const int32_t dims[3], uint32_t n_triangles, int32_t modes, const void* vertices, const void* triangles)
+{
+    vxrt::VoxLayout L;
+    if (modes < 1 || modes > 3)
+        return fail(VXRT_ERR_INVALID, "voxelize modes: VXRT_VOX_SURFACE, VXRT_VOX_SOLID or both");
+    if (!vxrt::vox_layout(dims, 0, L))
+        return fail(VXRT_ERR_INVALID, "voxelize dims: each 1 .. VXRT_VOX_MAX_DIM");
+    if (n_triangles > vxrt::kVoxMaxTriangles)
+        return fail(VXRT_ERR_INVALID, "voxelize: more than 2^24 triangles");
+    if (n_triangles && (!vertices || !triangles))
+        return fail(VXRT_ERR_INVALID, "voxelize: vertices or triangles NULL with n_triangles > 0");
+    return VXRT_OK;
+}
+
+int vxrt_voxelize_mesh(vxrt_ctx* c, const int32_t* d_vertices, uint32_t n_vertices, const uint32_t* d_triangles, uint32_t n_triangles,
+                       const int32_t dims[3], int32_t modes, void* d_work, uint32_t* d_bits, vxrt_voxelize_summary* d_summary,
+                       void* stream)
+{
+    if (!c || !dims || !d_work || !d_bits || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = voxelize_ready(dims, n_triangles, modes, d_vertices, d_triangles))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::voxelize_mesh(d_vertices, n_vertices, d_triangles, n_triangles, dims, (uint32_t)modes, d_work, d_bits, d_summary,
+                               c->cus * 8u, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_voxelize_mesh_host(vxrt_ctx* c, const int32_t* vertices, uint32_t n_vertices, const uint32_t* triangles,
+                            uint32_t n_triangles, const int32_t dims[3], int32_t modes, uint32_t* bits,
+                            vxrt_voxelize_summary* summary)
+{
+    if (!c || !dims || !bits || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = voxelize_ready(dims, n_triangles, modes, vertices, triangles))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::VoxLayout L;
+    vxrt::vox_layout(dims, n_triangles, L);
+    const size_t vb = n_triangles ? (size_t)n_vertices * 12u : 0, tb = (size_t)n_triangles * 12u, ob = (size_t)L.words * 4u;
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, ob, sizeof(vxrt_voxelize_summary), vb, tb}))
+        return fail(VXRT_ERR_NOMEM, std::string("voxelize_mesh_host: ") + hipGetErrorString(e));
+    uint32_t* d_out = T.at<uint32_t>(1);
+    vxrt_voxelize_summary* d_sum = T.at<vxrt_voxelize_summary>(2);
+    if (vb)
+        VX_HIP(hipMemcpy(T.at<int32_t>(3), vertices, vb, hipMemcpyHostToDevice));
+    if (tb)
+        VX_HIP(hipMemcpy(T.at<uint32_t>(4), triangles, tb, hipMemcpyHostToDevice));
+    VX_HIP(vxrt::voxelize_mesh(T.at<int32_t>(3), n_vertices, T.at<uint32_t>(4), n_triangles, dims, (uint32_t)modes, T.base, d_out,
+                               d_sum, c->cus * 8u, nullptr));
+    VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_voxelize_summary), hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(bits, d_out, ob, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }

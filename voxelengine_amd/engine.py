@@ -412,6 +412,86 @@ class Context:
         return DistanceField(origin=tuple(int(v) for v in origin), dims=dims, radius=int(radius), mode=int(mode),
                              dist2=out[:nvox].reshape(dims[::-1]).transpose(2, 1, 0), _summary=summary, _stream=None)
 
+    # ---- mesh voxelization (extension, include/vxrt.h) ----------------------------------------------------------------
+    def voxelize_workspace_bytes(self, dims, n_triangles: int) -> int:
+        """vxrt_voxelize_workspace_bytes: the workspace of one voxelize_mesh call, 0 outside the contract"""
+        n = int(n_triangles)
+        return int(self._L.vxrt_voxelize_workspace_bytes(_i3(dims), n)) if 0 <= n < 1 << 32 else 0
+
+    def voxelize_mesh(self, vertices, triangles, dims, modes: int = N.VOX_SURFACE | N.VOX_SOLID, stream: int | None = None,
+                      work=None, out=None) -> "VoxelizedMesh":
+        """A triangle mesh as region bits of ``dims`` voxels (include/vxrt.h, vxrt_voxelize_mesh): ``vertices`` (n, 3) int32
+        in units of 1 / 256 voxel in the region's frame (``quantize_vertices`` makes them from floats), ``triangles``
+        (m, 3) vertex indices; numpy arrays or device tensors.  ``modes``: VOX_SURFACE, VOX_SOLID or both.  Asynchronous on
+        ``stream`` (default: torch's current stream).  ``work`` / ``out``: device tensors to reuse as the workspace and the
+        output words.  Returns a VoxelizedMesh; ``.bits`` is a stamp's device words as it is."""
+        import torch
+        dev = "cuda:%d" % self.device
+        dims = tuple(int(v) for v in dims)
+        copied = False
+
+        def on_device(a, np_dtype):
+            nonlocal copied
+            if isinstance(a, torch.Tensor):
+                if a.dtype not in (torch.int32, torch.uint32) or not a.is_contiguous() or a.numel() % 3 or not a.is_cuda:
+                    raise ValueError("mesh tensors: contiguous device tensors of int32, 3 per row")
+                return a
+            a = _mesh_array(a, np_dtype)
+            copied = copied or a.size > 0
+            return torch.from_numpy(a.view(np.int32)).to(dev) if a.size else torch.empty((0, 3), dtype=torch.int32, device=dev)
+
+        v, t = on_device(vertices, np.int32), on_device(triangles, np.uint32)
+        nv, nt = v.numel() // 3, t.numel() // 3
+        ws = self.voxelize_workspace_bytes(dims, nt)
+        nw = region_words(dims) if ws else 0
+        if work is None:
+            work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
+        elif work.numel() * work.element_size() < ws:
+            raise ValueError("work holds fewer than voxelize_workspace_bytes(dims, n_triangles) bytes")
+        if out is None:
+            out = torch.empty(max(nw, 1), dtype=torch.int32, device=dev)
+        elif out.numel() * out.element_size() < 4 * nw:
+            raise ValueError("out holds fewer than region_words(dims) words")
+        summary = torch.zeros(8, dtype=torch.int32, device=dev)
+        s = _stream(stream)
+        if copied:  # the mesh's copy is on torch's current stream: order it before the call's stream
+            torch.cuda.current_stream(dev).synchronize()
+        N.check(self._L.vxrt_voxelize_mesh(self._h, _ptr(v) if nt else None, nv, _ptr(t) if nt else None, nt, _i3(dims), int(modes),
+                                           _ptr(work), _ptr(out), _ptr(summary), s))
+        es = torch.cuda.ExternalStream(s, device=dev)
+        for a in (work, v, t):
+            a.record_stream(es)
+        return VoxelizedMesh(dims=dims, modes=int(modes), bits=out.view(-1)[:nw] if out.element_size() == 4 else out,
+                             _summary=summary, _stream=s)
+
+    def voxelize_mesh_host(self, vertices, triangles, dims, modes: int = N.VOX_SURFACE | N.VOX_SOLID) -> "VoxelizedMesh":
+        """voxelize_mesh through the synchronous host call (vxrt_voxelize_mesh_host): ``bits`` is a bool [x, y, z] grid."""
+        dims = tuple(int(v) for v in dims)
+        v, t = _mesh_array(vertices, np.int32), _mesh_array(triangles, np.uint32)
+        nw = region_words(dims) if self.voxelize_workspace_bytes(dims, len(t)) else 0
+        words = np.zeros(max(nw, 1), np.uint32)
+        summary = np.zeros(8, np.uint32)
+        N.check(self._L.vxrt_voxelize_mesh_host(self._h, v.ctypes.data if len(t) else None, len(v), t.ctypes.data if len(t) else None,
+                                                len(t), _i3(dims), int(modes), words.ctypes.data, summary.ctypes.data))
+        return VoxelizedMesh(dims=dims, modes=int(modes), bits=unpack_region(words, dims), _summary=summary, _stream=None)
+
+    def stamp_mesh(self, vertices, triangles, origin, modes: int = N.VOX_SURFACE | N.VOX_SOLID, stamp_mode: int = N.STAMP_UNION):
+        """Voxelize a mesh given in WORLD units of 1 / 256 voxel into its own bounding box and write it into the resident
+        world with one stamp: the box is the voxels the mesh's bounding box touches, moved by ``origin`` (world voxels).
+        Returns (VoxelizedMesh, EditStats, the stamp's origin)."""
+        v = np.asarray(vertices).reshape(-1, 3).astype(np.int64)
+        t = np.asarray(triangles).reshape(-1, 3)
+        used = v[t[t.max(axis=1) < len(v)].reshape(-1)] if len(t) else v[:0]
+        if not len(used):
+            raise ValueError("stamp_mesh: no triangle with valid indices")
+        lo = (used.min(axis=0) - 1) >> 8  # the voxel cubes the bounding box touches
+        hi = used.max(axis=0) >> 8
+        dims = tuple(int(x) for x in hi - lo + 1)
+        m = self.voxelize_mesh((v - 256 * lo).astype(np.int32), t, dims, modes)
+        at = tuple(int(a) + int(b) for a, b in zip(origin, lo))
+        st = self.edit_stamps([Stamp(at, m.bits, stamp_mode, dims)])
+        return m, st, at
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -644,6 +724,67 @@ class Islands:
         """One Body per table row -- the island's box, displaced by ``delta`` -- for move_boxes (falling debris).  A box
         wider than BODY_MAX_EXTENT on some axis is an invalid body there: move_boxes returns it unchanged with BODY_INVALID."""
         return [Body(tuple(float(v) for v in r["lo"]), tuple(float(v) for v in r["hi"]), tuple(delta)) for r in self.table]
+
+
+def _mesh_array(a, np_dtype) -> np.ndarray:
+    """integer vertices (int32) or triangle indices (uint32) as a contiguous (n, 3) array: any integer input whose values fit"""
+    a = np.asarray(a)
+    if a.size == 0:
+        return np.zeros((0, 3), np_dtype)
+    if a.dtype.kind not in "iu":
+        raise TypeError("mesh arrays hold integers (quantize_vertices makes vertices from floats)")
+    if a.size % 3:
+        raise ValueError("mesh arrays: 3 values per row")
+    info = np.iinfo(np_dtype)
+    if int(a.min()) < info.min or int(a.max()) > info.max:
+        raise ValueError("mesh array values outside %s" % np.dtype(np_dtype).name)
+    return np.ascontiguousarray(a.reshape(-1, 3).astype(np_dtype))
+
+
+def quantize_vertices(xyz) -> np.ndarray:
+    """float voxel coordinates -> the int32 fixed point of voxelize_mesh: x * 256 rounded half to even"""
+    return np.rint(np.asarray(xyz, np.float64) * 256.0).astype(np.int32).reshape(-1, 3)
+
+
+class VoxelizeSummary(NamedTuple):
+    """vxrt_voxelize_summary: bits set in the output, in the surface field and in the solid field (0 for a field not chosen);
+    the triangles given, and those invalid, degenerate and with a bounding box that misses the region"""
+    set: int
+    surface: int
+    solid: int
+    triangles: int
+    invalid: int
+    degenerate: int
+    outside: int
+
+
+@dataclass
+class VoxelizedMesh:
+    """The result of Context.voxelize_mesh: ``bits`` the region words on the device (a bool [x, y, z] grid from
+    voxelize_mesh_host), ``summary`` a VoxelizeSummary."""
+    dims: tuple
+    modes: int
+    bits: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> VoxelizeSummary:
+        """the summary; for a device result this waits for the call's stream"""
+        w = self._summary
+        if not isinstance(w, np.ndarray):
+            import torch
+            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
+            w = self._summary = w.cpu().numpy().view(np.uint32)
+        return VoxelizeSummary(*(int(x) for x in w[:7]))
+
+    def grid(self) -> np.ndarray:
+        """the voxels as a bool [x, y, z] numpy grid (device words are copied to the host)"""
+        if isinstance(self.bits, np.ndarray):
+            return self.bits
+        import torch
+        torch.cuda.ExternalStream(self._stream, device=self.bits.device).synchronize()
+        return unpack_region(self.bits.cpu().numpy().view(np.uint32), self.dims)
 
 
 class DistanceSummary(NamedTuple):
