@@ -4,6 +4,7 @@
   distance_field_scipy  scipy.ndimage.distance_transform_edt(..., return_indices=True) on the halo (used when scipy imports);
                         d2 is recomputed in int64 from the returned indices, never taken from the float distances.
   distance_field_brute  O(voxels x targets), for tiny grids.
+  distance_field_points the definition on a world given as a short list of voxels (no halo is built), for large radii.
 Each returns {"dist2": uint16 [x, y, z] (FAR above R^2), "summary": (zero, near, far, max_d2, sum_d2)}.
 TEST INFRASTRUCTURE ONLY: imported by tests/ and tools/ alone."""
 from __future__ import annotations
@@ -94,6 +95,28 @@ def distance_field_brute(world, origin, dims, radius: int, mode: int = TO_SOLID)
         diff = v[:, None, :] - t[None, a:a + 512, :]
         d2 = np.minimum(d2, (diff * diff).sum(-1).min(1))
     return _result(d2.reshape(dims), R)
+
+
+def distance_field_points(world_shape, targets, origin, dims, radius: int, mode: int = TO_SOLID) -> dict:
+    """The definition itself on a world given by a short list of voxels, for radii at which the halo forms are slow.
+    TO_SOLID: `targets` are the solid voxels of an otherwise empty world of `world_shape`; d2 = min over them of |p - s|^2.
+    TO_EMPTY: they are the empty voxels of an otherwise solid world, and every voxel outside the world is empty too: the
+    nearest of those is straight across the nearest face, so its distance is the least over the six faces.  A target with
+    d2 <= R^2 is within R on every axis, so no halo is built.  O(voxels x targets)."""
+    R = int(radius)
+    shape = np.asarray(world_shape, np.int64)
+    dims = tuple(int(d) for d in dims)
+    ax = [np.arange(d, dtype=np.int64) + int(o) for o, d in zip(origin, dims)]  # world coordinates of the box
+    t = np.asarray(targets, np.int64).reshape(-1, 3)
+    d2 = np.full(dims, _INF)
+    for s in t[((t >= 0) & (t < shape)).all(1)]:  # a listed voxel outside the world changes nothing in either mode
+        sq = [(a - c) ** 2 for a, c in zip(ax, s)]
+        np.minimum(d2, sq[0][:, None, None] + sq[1][None, :, None] + sq[2][None, None, :], out=d2)
+    if mode == TO_EMPTY:
+        steps = [np.where((a < 0) | (a >= n), 0, np.minimum(a + 1, n - a)) for a, n in zip(ax, shape)]  # 0: outside already
+        out = np.minimum(np.minimum(steps[0][:, None, None], steps[1][None, :, None]), steps[2][None, None, :])
+        np.minimum(d2, out * out, out=d2)
+    return _result(d2, R)
 
 
 def have_scipy() -> bool:

@@ -12,6 +12,7 @@ import pytest
 
 from tests import ref_voxelize as R
 from tests.helpers import ROOT, run_harness_files
+from tests.launch_limit_cases import coordinate_limit_dims, coordinate_limit_meshes
 
 MODES = (R.SURFACE, R.SOLID, R.SURFACE | R.SOLID)
 U = R.UNIT
@@ -318,16 +319,11 @@ def test_the_cull_follows_the_triangle_not_its_bounding_box(harness, tmp_path):
 def test_coordinate_limits(harness, tmp_path, axis):
     """vertices at +-2^18 and 1024 voxels on one axis, under the overflow trap: the closed box over the whole coordinate range
     fills every voxel, and two triangles between extreme corners equal the reference"""
-    M = 1 << 18
-    dims = [3, 2, 3]
-    dims[axis] = 1024
-    dims = tuple(dims)
-    box = R.box_mesh((-M, -M, -M), (M, M, M))
+    dims = coordinate_limit_dims(axis)
+    box, tri = coordinate_limit_meshes()
     want = R.voxelize(*box, dims, 3)
     assert want["grid"].all()
     _assert_harness(harness, tmp_path, box, dims, 3, want)
-    v = np.array([[-M, -M, -M], [M, M, M - 1], [M, -M, M], [-M, M, -M + 3], [M - 5, M, -M], [-M, -M + 7, M]], np.int32)
-    tri = (v, np.array([[0, 1, 2], [3, 4, 5], [0, 4, 5], [1, 3, 2]], np.uint32))
     for modes in MODES:
         got = _assert_harness(harness, tmp_path, tri, dims, modes, R.voxelize(*tri, dims, modes))
         assert got["summary"][0] > 0
