@@ -36,6 +36,9 @@
 // Kind 7 stamps a built-in mesh (VoxelRaytracer3D::StampMesh, union): an octahedron generated here, its centre on the centre of
 // voxel a, its radius bx voxels (by = bz = 0), voxelized in the modes `value` (1 = surface, 2 = solid, 3 = both), and prints one
 // line "mesh before frame N: T triangles, S set voxels, ... bricks touched, ... created".
+// Kind 8 extracts the surface of the box of origin a and dims b (VoxelRaytracer3D::ExtractSurface, with triangles) in the mode
+// `value` (0 = VXRT_SURF_CAP, 1 = VXRT_SURF_OPEN) and prints one line "surface frame N solid .. faces .. quads .. tris ..",
+// then one line "surface hash frame N quads .. vertices .. triangles .." with the 64-bit FNV-1a hash of each array's bytes.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -254,6 +257,27 @@ int main(int argc, char** argv)
                 }
                 std::printf("dist frame %d zero %u near %u far %u max_d2 %u sum_d2 %llu\n", from, sum.zero, sum.near, sum.far,
                             sum.max_d2, (unsigned long long)sum.sum_d2);
+            } else if (e.op.kind == 8) {  // surface extraction
+                flush_ops();
+                std::vector<vxrt_quad> quads;
+                std::vector<int32_t> verts;
+                std::vector<uint32_t> tris;
+                vxrt_surface_summary sum{};
+                if (raytracer->ExtractSurface(e.op.a, e.op.b, e.op.value, quads, &sum, &verts, &tris) != VXRT_OK) {
+                    std::cerr << "surface before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("surface frame %d solid %u faces %u quads %u tris %zu\n", from, sum.solid, sum.faces, sum.quads,
+                            tris.size() / 3);
+                auto fnv = [](const void* p, size_t n) {
+                    uint64_t h = 0xcbf29ce484222325ull;
+                    for (size_t i = 0; i < n; ++i)
+                        h = (h ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+                    return (unsigned long long)h;
+                };
+                std::printf("surface hash frame %d quads %016llx vertices %016llx triangles %016llx\n", from,
+                            fnv(quads.data(), quads.size() * sizeof(vxrt_quad)), fnv(verts.data(), verts.size() * 4),
+                            fnv(tris.data(), tris.size() * 4));
             } else if (e.op.kind == 7) {  // stamp the built-in mesh
                 flush_ops();
                 const int32_t r = 256 * e.op.b[0], c = 128;  // mesh frame: the origin is the corner of voxel a

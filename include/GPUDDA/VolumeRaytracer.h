@@ -30,6 +30,8 @@ struct vxrt_nav_agent;
 struct vxrt_nav_summary;
 struct vxrt_distance_summary;
 struct vxrt_voxelize_summary;
+struct vxrt_quad;
+struct vxrt_surface_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -187,6 +189,13 @@ public:
     // voxel `origin`.  Returns the vxrt_status; VXRT_ERR_INVALID for a mesh without a triangle of valid indices.
     int StampMesh(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles, const int32_t origin[3],
                   int32_t modes, int stampMode, vxrt_edit_stats* stats = nullptr, vxrt_voxelize_summary* summary = nullptr);
+    // surface extraction (extension, include/vxrt.h, vxrt_extract_surface_host): the surface of the box `origin`, `dims` of
+    // the resident world as merged quads in canonical order, `mode` VXRT_SURF_CAP or VXRT_SURF_OPEN; with `vertices` and
+    // `triangles` (both or neither) also as a mesh in VoxelizeMesh's input format.  A counting call sizes the vectors, a
+    // second call fills them.  Flushes queued edits first.  Returns the vxrt_status.
+    int ExtractSurface(const int32_t origin[3], const int32_t dims[3], int32_t mode, std::vector<vxrt_quad>& quads,
+                       vxrt_surface_summary* summary = nullptr, std::vector<int32_t>* vertices = nullptr,
+                       std::vector<uint32_t>* triangles = nullptr);
 
 private:
     void Flush();

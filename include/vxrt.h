@@ -563,6 +563,68 @@ int vxrt_voxelize_mesh_host(vxrt_ctx *ctx, const int32_t *vertices, uint32_t n_v
                             uint32_t n_triangles, const int32_t dims[3], int32_t modes, uint32_t *bits,
                             vxrt_voxelize_summary *summary);
 
+/* ---- surface extraction -- an EXTENSION (the opposite direction of mesh voxelization: the surface of a box of the
+ * resident world as quads and, optionally, triangles in vxrt_voxelize_mesh's input format).
+ *   Box.  One call looks at one box B = [origin, origin + dims) of world voxels; voxels outside the world are empty, as for
+ *     vxrt_read_region.
+ *   Limits.  1 <= dims[k] <= VXRT_SURF_MAX_DIM = 1024 (output coordinates at 256 units per voxel stay within
+ *     VXRT_VOX_MAX_COORD); dims[0] * dims[1] * dims[2] <= 2^28; origin[k] - 1 >= -2^31 and origin[k] + dims[k] + 1 <= 2^31 - 1.
+ *   Directions.  d = 0 .. 5 means -x, +x, -y, +y, -z, +z; the axis of d is a = d / 2; the in-plane axes (u, v) are the other
+ *     two in ascending order: (y, z) for x, (x, z) for y, (x, y) for z.
+ *   Faces.  Voxel p of B has a face in direction d when p is solid and its neighbour p + d is empty.
+ *   mode.  VXRT_SURF_CAP (0): neighbours outside B count as empty; the mesh is a closed surface.  VXRT_SURF_OPEN (1):
+ *     neighbours outside B are the world's own voxels, so that chunk meshes tile without interior walls.  Outside the world
+ *     is empty in both modes.
+ *   Quads ("run-stack" merging).  For direction d and slice s (the coordinate of p along a, in box coordinates) the faces
+ *     form a 2-D mask over (u, v).  A RUN of row v is a maximal interval [u, u + w) of set bits of that row.  A QUAD
+ *     (u, v, w, h) is a maximal set of consecutive rows v .. v + h - 1 that each have [u, u + w) as a run: row v - 1 and row
+ *     v + h do not have that run.  Every face lies in exactly one quad.  Whether a quad exists is a local property of the
+ *     mask: the result does not depend on a scan order or on scheduling.
+ *   Output order.  Ascending (d, s, v, u).
+ *   Quad record.  vxrt_quad, 8 bytes: pos = x | y << 10 | z << 20, the lowest box-relative voxel of the quad;
+ *     ext = (w - 1) | (h - 1) << 10 | d << 20.
+ *   Triangles (optional; d_vertices and d_triangles both NULL or both given).  Quad i yields vertices 4 i .. 4 i + 3 (int32
+ *     xyz, 256 units per voxel, in the box's frame): the corners (u, v), (u + w, v), (u + w, v + h), (u, v + h) on the plane
+ *     a = 256 (s + (d & 1)); and triangles 2 i and 2 i + 1 (uint32 indices), split along the diagonal from corner 0 to
+ *     corner 2 and wound so that (v1 - v0) x (v2 - v0) is a positive multiple of the outward direction d: (0, 1, 2), (0, 2, 3)
+ *     for d = 1, 2, 5 and (0, 2, 1), (0, 3, 2) for d = 0, 3, 4.  Vertices are not welded.  The CAP mesh voxelized with
+ *     VXRT_VOX_SOLID into `dims` gives B's bits again.  With triangles at most 2^30 quads are written (their indices fit
+ *     uint32): a larger capacity_quads counts as 2^30.
+ *   Capacity.  Only the first min(quads, capacity_quads) records in the output order are written, with their vertices and
+ *     triangles; nothing past them is touched.  capacity_quads == 0 with NULL outputs is a valid counting call.
+ * Outputs:
+ *   d_quads: capacity_quads records; d_vertices: 12 int32 per quad; d_triangles: 6 uint32 per quad.
+ *   d_summary: solid (solid voxels of B); faces; quads (the full count, whatever the capacity); written; faces_dir[6];
+ *     quads_dir[6].
+ * Workspace.  d_work holds vxrt_surface_workspace_bytes(dims) bytes, 0 outside the limits.  With r(n) = n rounded up to a
+ *   multiple of 256, H = ceil((dims[0] + 2) / 32) * (dims[1] + 2) * (dims[2] + 2) and R = 2 * dims[2] * (dims[0] + 2 * dims[1]):
+ *     bytes = r(4 * H) + r(4 * R) + r(4 * ceil(R / 256))
+ *   (the bits of B grown by one voxel, one count per row of a mask, one per group of 256 rows).  The caller owns it; the
+ *   library allocates nothing per call and never synchronises with the host inside the call.
+ * Call rules (as vxrt_distance_field): asynchronous on `stream`.  Checked in this order: a NULL ctx, origin, dims, d_work or
+ *   d_summary; the mode; the dims; the origin; d_quads NULL with capacity_quads > 0; only one of d_vertices and d_triangles
+ *   given -- each VXRT_ERR_INVALID; then no world: VXRT_ERR_NO_WORLD; then a streamed world: VXRT_ERR_INVALID.  A refused call
+ *   writes nothing.  The call never loads outside the tables.  Results are bit-identical from call to call.
+ * vxrt_extract_surface_host takes host buffers, allocates its own workspace and is synchronous.
+ * The cost is one region read of the grown box, two passes over its face bits (a count and an emit, a scan of the row
+ * counts between them) and the records written. */
+#define VXRT_SURF_MAX_DIM 1024
+#define VXRT_SURF_CAP 0
+#define VXRT_SURF_OPEN 1
+typedef struct vxrt_quad {
+    uint32_t pos, ext;
+} vxrt_quad;
+typedef struct vxrt_surface_summary {
+    uint32_t solid, faces, quads, written;
+    uint32_t faces_dir[6], quads_dir[6];
+} vxrt_surface_summary;
+uint64_t vxrt_surface_workspace_bytes(const int32_t dims[3]); /* 0 outside the contract */
+int vxrt_extract_surface(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], int32_t mode, void *d_work,
+                         vxrt_quad *d_quads, uint32_t capacity_quads, int32_t *d_vertices, uint32_t *d_triangles,
+                         vxrt_surface_summary *d_summary, void *stream);
+int vxrt_extract_surface_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], int32_t mode, vxrt_quad *quads,
+                              uint32_t capacity_quads, int32_t *vertices, uint32_t *triangles, vxrt_surface_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

@@ -309,6 +309,30 @@ int VoxelRaytracer3D::DistanceField(const int32_t origin[3], const int32_t dims[
     return vxrt_distance_field_host(ctx, origin, dims, radius, mode, dist2.data(), &summary);
 }
 
+int VoxelRaytracer3D::ExtractSurface(const int32_t origin[3], const int32_t dims[3], int32_t mode, std::vector<vxrt_quad>& quads,
+                                     vxrt_surface_summary* summary, std::vector<int32_t>* vertices, std::vector<uint32_t>* triangles)
+{
+    Flush();
+    if (!vertices != !triangles)
+        return VXRT_ERR_INVALID;
+    vxrt_surface_summary sum{};
+    int rc = vxrt_extract_surface_host(ctx, origin, dims, mode, nullptr, 0, nullptr, nullptr, &sum);  // the counting call
+    if (rc != VXRT_OK)
+        return rc;
+    const size_t n = vertices && sum.quads > (1u << 30) ? (size_t)1 << 30 : sum.quads;  // vertex indices are uint32
+    quads.assign(n, vxrt_quad{});
+    if (vertices) {
+        vertices->assign(12 * n, 0);
+        triangles->assign(6 * n, 0u);
+    }
+    if (n)
+        rc = vxrt_extract_surface_host(ctx, origin, dims, mode, quads.data(), (uint32_t)n, vertices ? vertices->data() : nullptr,
+                                       triangles ? triangles->data() : nullptr, &sum);
+    if (summary)
+        *summary = sum;
+    return rc;
+}
+
 int VoxelRaytracer3D::VoxelizeMesh(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles,
                                    const int32_t dims[3], int32_t modes, std::vector<uint32_t>& bits,
                                    vxrt_voxelize_summary& summary)

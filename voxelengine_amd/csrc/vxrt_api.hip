@@ -9,6 +9,7 @@
 #include "vxrt_nav.hpp"
 #include "vxrt_region.hpp"
 #include "vxrt_stream.hpp"
+#include "vxrt_surface.hpp"
 #include "vxrt_voxelize.hpp"
 
 #include <algorithm>
@@ -67,6 +68,9 @@ hipError_t distance_field(const CollideWorld& W, const int32_t o[3], const int32
 // mesh voxelization (vxrt_voxelize.hip)
 hipError_t voxelize_mesh(const int32_t* verts, uint32_t nv, const uint32_t* tris, uint32_t nt, const int32_t d[3], uint32_t modes,
                          void* work, uint32_t* bits, vxrt_voxelize_summary* summary, uint32_t work_waves, hipStream_t stream);
+// surface extraction (vxrt_surface.hip)
+hipError_t extract_surface(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t mode, void* work, vxrt_quad* quads,
+                           uint32_t capacity, int32_t* verts, uint32_t* tris, vxrt_surface_summary* summary, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -2253,6 +2257,75 @@ int vxrt_voxelize_mesh_host(vxrt_ctx* c, const int32_t* vertices, uint32_t n_ver
                                d_sum, c->cus * 8u, nullptr));
     VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_voxelize_summary), hipMemcpyDeviceToHost));
     VX_HIP(hipMemcpy(bits, d_out, ob, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- surface extraction --------------------------------------------------------------------------------------------------
+uint64_t vxrt_surface_workspace_bytes(const int32_t dims[3])
+{
+    vxrt::SurfLayout L;
+    return dims && vxrt::surf_layout(nullptr, dims, L) ? L.total_bytes : 0;
+}
+
+// the checks both surface calls make after their NULL checks, in the order of include/vxrt.h
+static int surface_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], int32_t mode, const void* quads,
+                         uint32_t capacity, const void* vertices, const void* triangles)
+{
+    vxrt::SurfLayout L;
+    if (mode != VXRT_SURF_CAP && mode != VXRT_SURF_OPEN)
+        return fail(VXRT_ERR_INVALID, "surface mode: VXRT_SURF_CAP or VXRT_SURF_OPEN");
+    if (!vxrt::surf_layout(nullptr, dims, L))
+        return fail(VXRT_ERR_INVALID, "surface box dims: each 1 .. VXRT_SURF_MAX_DIM, at most 2^28 voxels");
+    if (!vxrt::surf_layout(origin, dims, L))
+        return fail(VXRT_ERR_INVALID, "surface box: origin - 1 or origin + dims + 1 beyond int32");
+    if (!quads && capacity)
+        return fail(VXRT_ERR_INVALID, "surface: quads NULL with capacity_quads > 0");
+    if (!vertices != !triangles)
+        return fail(VXRT_ERR_INVALID, "surface: vertices and triangles are both NULL or both given");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_extract_surface(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], int32_t mode, void* d_work, vxrt_quad* d_quads,
+                         uint32_t capacity_quads, int32_t* d_vertices, uint32_t* d_triangles, vxrt_surface_summary* d_summary,
+                         void* stream)
+{
+    if (!c || !origin || !dims || !d_work || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = surface_ready(c, origin, dims, mode, d_quads, capacity_quads, d_vertices, d_triangles))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::extract_surface(vxrt::query_world(c), origin, dims, (uint32_t)mode, d_work, d_quads, capacity_quads, d_vertices,
+                                 d_triangles, d_summary, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_extract_surface_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], int32_t mode, vxrt_quad* quads,
+                              uint32_t capacity_quads, int32_t* vertices, uint32_t* triangles, vxrt_surface_summary* summary)
+{
+    if (!c || !origin || !dims || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = surface_ready(c, origin, dims, mode, quads, capacity_quads, vertices, triangles))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::SurfLayout L;
+    vxrt::surf_layout(origin, dims, L);
+    const size_t cap = vertices && capacity_quads > vxrt::kSurfMaxIndexed ? vxrt::kSurfMaxIndexed : capacity_quads;
+    const size_t qb = cap * sizeof(vxrt_quad), vb = vertices ? cap * 48u : 0, tb = vertices ? cap * 24u : 0;
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, sizeof(vxrt_surface_summary), qb, vb, tb}))
+        return fail(VXRT_ERR_NOMEM, std::string("extract_surface_host: ") + hipGetErrorString(e));
+    vxrt_surface_summary* d_sum = T.at<vxrt_surface_summary>(1);
+    VX_HIP(vxrt::extract_surface(vxrt::query_world(c), origin, dims, (uint32_t)mode, T.base, cap ? T.at<vxrt_quad>(2) : nullptr,
+                                 (uint32_t)cap, vb ? T.at<int32_t>(3) : nullptr, tb ? T.at<uint32_t>(4) : nullptr, d_sum, nullptr));
+    VX_HIP(hipMemcpy(summary, d_sum, sizeof(vxrt_surface_summary), hipMemcpyDeviceToHost));
+    const size_t n = summary->written;  // only the records written come back: nothing past them is touched
+    if (n)
+        VX_HIP(hipMemcpy(quads, T.at<vxrt_quad>(2), n * sizeof(vxrt_quad), hipMemcpyDeviceToHost));
+    if (n && vertices) {
+        VX_HIP(hipMemcpy(vertices, T.at<int32_t>(3), n * 48u, hipMemcpyDeviceToHost));
+        VX_HIP(hipMemcpy(triangles, T.at<uint32_t>(4), n * 24u, hipMemcpyDeviceToHost));
+    }
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }

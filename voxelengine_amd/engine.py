@@ -492,6 +492,73 @@ class Context:
         st = self.edit_stamps([Stamp(at, m.bits, stamp_mode, dims)])
         return m, st, at
 
+    # ---- surface extraction (extension, include/vxrt.h) ---------------------------------------------------------------
+    def surface_workspace_bytes(self, dims) -> int:
+        """vxrt_surface_workspace_bytes: the workspace of one extract_surface call, 0 outside the contract"""
+        return int(self._L.vxrt_surface_workspace_bytes(_i3(dims)))
+
+    def extract_surface(self, origin, dims, mode: int = N.SURF_CAP, triangles: bool = False, capacity: int | None = None,
+                        stream: int | None = None) -> "ExtractedSurface":
+        """The surface of the box ``origin`` .. ``origin + dims - 1`` of the resident world as merged quads in canonical
+        order (include/vxrt.h, vxrt_extract_surface), with ``triangles`` also as vertices and triangles in voxelize_mesh's
+        input format.  ``mode``: SURF_CAP (neighbours outside the box are empty: a closed surface) or SURF_OPEN (they are the
+        world's voxels).  ``capacity``: quads to make room for; None counts first (one more call, and a wait for it) and
+        makes room for all.  Asynchronous on ``stream`` (default: torch's current stream).  Returns an ExtractedSurface of
+        device tensors sized to the capacity; its ``summary`` tells how many records were written."""
+        import torch
+        dev = "cuda:%d" % self.device
+        dims = tuple(int(v) for v in dims)
+        work = torch.empty(max(self.surface_workspace_bytes(dims), 4), dtype=torch.uint8, device=dev)
+        s = _stream(stream)
+        es = torch.cuda.ExternalStream(s, device=dev)
+
+        def call(cap, quads, verts, tris):
+            summary = torch.zeros(16, dtype=torch.int32, device=dev)
+            N.check(self._L.vxrt_extract_surface(self._h, _i3(origin), _i3(dims), int(mode), _ptr(work), _ptr(quads), cap,
+                                                 _ptr(verts), _ptr(tris), _ptr(summary), s))
+            return summary
+
+        if capacity is None:
+            counted = call(0, None, None, None)
+            es.synchronize()
+            capacity = int(counted.cpu().numpy().view(np.uint32)[2])
+        capacity = int(capacity)
+        if not 0 <= capacity < 1 << 32:
+            raise ValueError("capacity: 0 .. 2^32 - 1 quads")
+        quads = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+        verts = torch.empty((4 * capacity, 3), dtype=torch.int32, device=dev) if triangles else None
+        tris = torch.empty((2 * capacity, 3), dtype=torch.int32, device=dev) if triangles else None
+        summary = call(capacity, quads if capacity else None, verts, tris)
+        work.record_stream(es)  # freed here, still in use on the call's stream
+        return ExtractedSurface(origin=tuple(int(v) for v in origin), dims=dims, mode=int(mode), quads=quads, vertices=verts,
+                                triangles=tris, _summary=summary, _stream=s)
+
+    def extract_surface_host(self, origin, dims, mode: int = N.SURF_CAP, triangles: bool = False,
+                             capacity: int | None = None) -> "ExtractedSurface":
+        """extract_surface through the synchronous host call (vxrt_extract_surface_host): numpy arrays, cut to the records
+        written."""
+        dims = tuple(int(v) for v in dims)
+
+        def call(cap, quads, verts, tris):
+            summary = np.zeros(16, np.uint32)
+            N.check(self._L.vxrt_extract_surface_host(self._h, _i3(origin), _i3(dims), int(mode), quads.ctypes.data if cap else None,
+                                                      cap, verts.ctypes.data if triangles and quads is not None else None,
+                                                      tris.ctypes.data if triangles and quads is not None else None,
+                                                      summary.ctypes.data))
+            return summary
+
+        if capacity is None:
+            capacity = int(call(0, None, None, None)[2])
+        capacity = int(capacity)
+        quads = np.zeros((capacity, 2), np.uint32)
+        verts = np.zeros((4 * capacity, 3), np.int32)
+        tris = np.zeros((2 * capacity, 3), np.uint32)
+        summary = call(capacity, quads, verts, tris)
+        n = int(summary[3])
+        return ExtractedSurface(origin=tuple(int(v) for v in origin), dims=dims, mode=int(mode), quads=quads[:n],
+                                vertices=verts[:4 * n] if triangles else None, triangles=tris[:2 * n] if triangles else None,
+                                _summary=summary, _stream=None)
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -785,6 +852,53 @@ class VoxelizedMesh:
         import torch
         torch.cuda.ExternalStream(self._stream, device=self.bits.device).synchronize()
         return unpack_region(self.bits.cpu().numpy().view(np.uint32), self.dims)
+
+
+class SurfaceSummary(NamedTuple):
+    """vxrt_surface_summary: solid voxels of the box, faces, quads (the full count), quads written, faces and quads by
+    direction (-x, +x, -y, +y, -z, +z)"""
+    solid: int
+    faces: int
+    quads: int
+    written: int
+    faces_dir: tuple
+    quads_dir: tuple
+
+
+@dataclass
+class ExtractedSurface:
+    """The result of Context.extract_surface: ``quads`` (capacity, 2) words pos, ext; ``vertices`` (4 * capacity, 3) int32 at
+    256 units per voxel in the box's frame and ``triangles`` (2 * capacity, 3) indices, or None; device tensors (numpy arrays
+    cut to the records written from extract_surface_host).  Only the first ``summary.written`` quads hold records."""
+    origin: tuple
+    dims: tuple
+    mode: int
+    quads: object
+    vertices: object
+    triangles: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> SurfaceSummary:
+        """the summary; for a device result this waits for the call's stream"""
+        w = self._summary
+        if not isinstance(w, np.ndarray):
+            import torch
+            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
+            w = self._summary = w.cpu().numpy().view(np.uint32)
+        return SurfaceSummary(int(w[0]), int(w[1]), int(w[2]), int(w[3]), tuple(int(x) for x in w[4:10]),
+                              tuple(int(x) for x in w[10:16]))
+
+    def decode(self):
+        """the written quads as numpy arrays (d, x, y, z, w, h): direction, lowest box-relative voxel, extent along u and v"""
+        n = self.summary.written
+        q = self.quads
+        if not isinstance(q, np.ndarray):
+            q = q[:n].cpu().numpy()
+        q = np.ascontiguousarray(q[:n]).view(np.uint32).reshape(-1, 2)
+        pos, ext = q[:, 0], q[:, 1]
+        return (ext >> 20, pos & 1023, pos >> 10 & 1023, pos >> 20 & 1023, (ext & 1023) + 1, (ext >> 10 & 1023) + 1)
 
 
 class DistanceSummary(NamedTuple):
