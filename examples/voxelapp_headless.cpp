@@ -39,6 +39,9 @@
 // Kind 8 extracts the surface of the box of origin a and dims b (VoxelRaytracer3D::ExtractSurface, with triangles) in the mode
 // `value` (0 = VXRT_SURF_CAP, 1 = VXRT_SURF_OPEN) and prints one line "surface frame N solid .. faces .. quads .. tris ..",
 // then one line "surface hash frame N quads .. vertices .. triangles .." with the 64-bit FNV-1a hash of each array's bytes.
+// Kind 9 downsamples the box of origin a and cell dims b (VoxelRaytracer3D::DownsampleRegion, with counts) at shift
+// `value & 7` and threshold `value >> 3` and prints one line "lod frame N shift .. threshold .. set .. empty .. full .. mixed ..
+// max .. solid ..", then one line "lod hash frame N bits .. counts .." with the 64-bit FNV-1a hash of each array's bytes.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -278,6 +281,26 @@ int main(int argc, char** argv)
                 std::printf("surface hash frame %d quads %016llx vertices %016llx triangles %016llx\n", from,
                             fnv(quads.data(), quads.size() * sizeof(vxrt_quad)), fnv(verts.data(), verts.size() * 4),
                             fnv(tris.data(), tris.size() * 4));
+            } else if (e.op.kind == 9) {  // occupancy LOD
+                flush_ops();
+                std::vector<uint32_t> bits;
+                std::vector<uint16_t> counts;
+                vxrt_lod_summary sum{};
+                const uint32_t shift = (uint32_t)e.op.value & 7u, threshold = (uint32_t)e.op.value >> 3;
+                if (raytracer->DownsampleRegion(e.op.a, e.op.b, shift, threshold, bits, sum, &counts) != VXRT_OK) {
+                    std::cerr << "lod before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("lod frame %d shift %u threshold %u set %u empty %u full %u mixed %u max %u solid %llu\n", from, shift,
+                            threshold, sum.set, sum.empty, sum.full, sum.mixed, sum.max_count, (unsigned long long)sum.solid);
+                auto fnv = [](const void* p, size_t n) {
+                    uint64_t h = 0xcbf29ce484222325ull;
+                    for (size_t i = 0; i < n; ++i)
+                        h = (h ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+                    return (unsigned long long)h;
+                };
+                std::printf("lod hash frame %d bits %016llx counts %016llx\n", from, fnv(bits.data(), bits.size() * 4),
+                            fnv(counts.data(), counts.size() * 2));
             } else if (e.op.kind == 7) {  // stamp the built-in mesh
                 flush_ops();
                 const int32_t r = 256 * e.op.b[0], c = 128;  // mesh frame: the origin is the corner of voxel a

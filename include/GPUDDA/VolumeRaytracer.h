@@ -32,6 +32,7 @@ struct vxrt_distance_summary;
 struct vxrt_voxelize_summary;
 struct vxrt_quad;
 struct vxrt_surface_summary;
+struct vxrt_lod_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -196,6 +197,13 @@ public:
     int ExtractSurface(const int32_t origin[3], const int32_t dims[3], int32_t mode, std::vector<vxrt_quad>& quads,
                        vxrt_surface_summary* summary = nullptr, std::vector<int32_t>* vertices = nullptr,
                        std::vector<uint32_t>* triangles = nullptr);
+
+    // occupancy LOD (extension, include/vxrt.h, vxrt_downsample_region_host): the box of `dims` cells of (1 << shift)^3 voxels
+    // at world voxel `origin` reduced to one bit per cell, set when the cell holds at least `threshold` solid voxels (1 = any),
+    // as region words (a stamp's bits for a coarser world); with `counts` also one uint16 per cell in region order.  Flushes
+    // queued edits first.  Returns the vxrt_status.
+    int DownsampleRegion(const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
+                         std::vector<uint32_t>& bits, vxrt_lod_summary& summary, std::vector<uint16_t>* counts = nullptr);
 
 private:
     void Flush();

@@ -625,6 +625,51 @@ int vxrt_extract_surface(vxrt_ctx *ctx, const int32_t origin[3], const int32_t d
 int vxrt_extract_surface_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], int32_t mode, vxrt_quad *quads,
                               uint32_t capacity_quads, int32_t *vertices, uint32_t *triangles, vxrt_surface_summary *summary);
 
+/* ---- occupancy LOD -- an EXTENSION (the reference's to-do item "LOD, further chunks with lower voxel resolution": a box
+ * of the resident world reduced by 2^shift per axis on the device, as bits and as counts).  One call looks at one box of
+ * CELLS, with f = 1 << shift and 1 <= shift <= VXRT_LOD_MAX_SHIFT = 5.
+ *   Cell.  Cell C = (X, Y, Z), 0 <= C[k] < dims[k], covers the f^3 world voxels origin + f * C + [0, f)^3.  `origin` is any
+ *     int32 triple: it need not be a multiple of f, and may be negative or beyond the world.  Voxels outside the world are
+ *     empty, as for vxrt_read_region.
+ *   Count.  c(C) is the number of solid voxels of the cell, 0 .. f^3.  f^3 <= 32768, so a count is one uint16_t.
+ *   Bit.  c(C) >= threshold, with 1 <= threshold <= f^3.  threshold = 1 is ANY: it is conservative (nothing thin
+ *     disappears, a ray that misses the coarse world misses the fine one), the choice for ray tracing and collision
+ *     proxies.  threshold = f^3 is ALL; threshold = f^3 / 2 is the majority.
+ *   Limits.  dims[k] >= 1.  The source box S[k] = f * dims[k] has S[0] * S[1] * S[2] <= 2^32 voxels: every S[k] stays within
+ *     int32 and the workspace at most 512 MiB; a larger volume is tiled by the caller, in z slabs for instance.
+ *     origin[k] >= -2^31 and origin[k] + S[k] <= 2^31 - 1.
+ * Outputs:
+ *   d_bits: the cell bits in vxrt_read_region's layout for `dims` (vxrt_region_words(dims) words, padding bits 0): a
+ *     vxrt_stamp's d_bits as it is.
+ *   d_counts_or_null: one uint16_t per cell in region order (x fastest, then y, then z, no padding, as d_dist2).
+ *   d_summary: solid (the sum of all counts: the solid voxels of the source box), set (cells with c >= threshold), empty
+ *     (c == 0), full (c == f^3), mixed (the rest), max_count, reserved (0).
+ *   The result does not depend on the scheduling: two calls are bit-identical.
+ * Workspace.  d_work holds vxrt_lod_workspace_bytes(dims, shift) bytes, 0 outside the limits on dims and shift.  With
+ *   r(n) = n rounded up to a multiple of 256 and S[k] = dims[k] << shift:
+ *     bytes = r(4 * ceil(S[0] / 32) * S[1] * S[2])
+ *   (the bits of the source box, vxrt_region_words(S) words; the reduction needs no further section).  The caller owns it;
+ *   the library allocates nothing per call and never synchronises with the host inside the call.
+ * Call rules (as vxrt_distance_field): asynchronous on `stream`.  Checked in this order: a NULL ctx, origin, dims, d_work,
+ *   d_bits or d_summary; the shift; the threshold; the dims and the source box; the origin -- each VXRT_ERR_INVALID; then no
+ *   world: VXRT_ERR_NO_WORLD; then a streamed world: VXRT_ERR_INVALID (a cache is not queried).  A refused call writes
+ *   nothing.  The call never loads outside the tables.
+ * vxrt_downsample_region_host takes host buffers (the same sizes; counts_or_null may be NULL), allocates its own workspace
+ *   and is synchronous.
+ * The cost is one region read of the source box and one pass over its words: every source word is loaded once and counted
+ *   with word operations, never voxel by voxel. */
+#define VXRT_LOD_MAX_SHIFT 5
+typedef struct vxrt_lod_summary {
+    uint64_t solid;
+    uint32_t set, empty, full, mixed, max_count, reserved;
+} vxrt_lod_summary;
+uint64_t vxrt_lod_workspace_bytes(const int32_t dims[3], uint32_t shift); /* 0 outside the contract */
+int vxrt_downsample_region(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
+                           void *d_work, uint32_t *d_bits, uint16_t *d_counts_or_null, vxrt_lod_summary *d_summary,
+                           void *stream);
+int vxrt_downsample_region_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t shift,
+                                uint32_t threshold, uint32_t *bits, uint16_t *counts_or_null, vxrt_lod_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

@@ -309,6 +309,18 @@ int VoxelRaytracer3D::DistanceField(const int32_t origin[3], const int32_t dims[
     return vxrt_distance_field_host(ctx, origin, dims, radius, mode, dist2.data(), &summary);
 }
 
+int VoxelRaytracer3D::DownsampleRegion(const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
+                                       std::vector<uint32_t>& bits, vxrt_lod_summary& summary, std::vector<uint16_t>* counts)
+{
+    Flush();
+    // the vectors are sized only for a box within the limits; the call itself refuses anything else, in its own order
+    const bool sized = vxrt_lod_workspace_bytes(dims, shift) != 0;
+    bits.assign(sized ? (size_t)vxrt_region_words(dims) : 1u, 0u);
+    if (counts)
+        counts->assign(sized ? (size_t)dims[0] * dims[1] * dims[2] : 1u, 0u);
+    return vxrt_downsample_region_host(ctx, origin, dims, shift, threshold, bits.data(), counts ? counts->data() : nullptr, &summary);
+}
+
 int VoxelRaytracer3D::ExtractSurface(const int32_t origin[3], const int32_t dims[3], int32_t mode, std::vector<vxrt_quad>& quads,
                                      vxrt_surface_summary* summary, std::vector<int32_t>* vertices, std::vector<uint32_t>* triangles)
 {

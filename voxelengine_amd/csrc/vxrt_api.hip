@@ -6,6 +6,7 @@
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
 #include "vxrt_islands.hpp"
+#include "vxrt_lod.hpp"
 #include "vxrt_nav.hpp"
 #include "vxrt_region.hpp"
 #include "vxrt_stream.hpp"
@@ -71,6 +72,9 @@ hipError_t voxelize_mesh(const int32_t* verts, uint32_t nv, const uint32_t* tris
 // surface extraction (vxrt_surface.hip)
 hipError_t extract_surface(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t mode, void* work, vxrt_quad* quads,
                            uint32_t capacity, int32_t* verts, uint32_t* tris, vxrt_surface_summary* summary, hipStream_t stream);
+// occupancy LOD (vxrt_lod.hip)
+hipError_t downsample_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t shift, uint32_t threshold,
+                             void* work, uint32_t* bits, uint16_t* counts, vxrt_lod_summary* summary, hipStream_t stream);
 }  // namespace vxrt
 
 static thread_local std::string g_last_error = "";
@@ -2326,6 +2330,65 @@ int vxrt_extract_surface_host(vxrt_ctx* c, const int32_t origin[3], const int32_
         VX_HIP(hipMemcpy(vertices, T.at<int32_t>(3), n * 48u, hipMemcpyDeviceToHost));
         VX_HIP(hipMemcpy(triangles, T.at<uint32_t>(4), n * 24u, hipMemcpyDeviceToHost));
     }
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- occupancy LOD ----------------------------------------------------------------------------------------------------------
+uint64_t vxrt_lod_workspace_bytes(const int32_t dims[3], uint32_t shift)
+{
+    vxrt::LodLayout L;
+    return dims && vxrt::lod_layout(nullptr, dims, shift, L) ? L.total_bytes : 0;
+}
+
+// the checks both LOD calls make after their NULL checks, in the order of include/vxrt.h
+static int lod_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold)
+{
+    vxrt::LodLayout L;
+    if (shift < 1u || shift > VXRT_LOD_MAX_SHIFT)
+        return fail(VXRT_ERR_INVALID, "lod shift: 1 .. VXRT_LOD_MAX_SHIFT");
+    if (!vxrt::lod_threshold_ok(shift, threshold))
+        return fail(VXRT_ERR_INVALID, "lod threshold: 1 .. f^3 with f = 1 << shift");
+    if (!vxrt::lod_layout(nullptr, dims, shift, L))
+        return fail(VXRT_ERR_INVALID, "lod dims: each at least 1, the source box dims << shift at most 2^32 voxels");
+    if (!vxrt::lod_layout(origin, dims, shift, L))
+        return fail(VXRT_ERR_INVALID, "lod box: origin + (dims << shift) beyond 2^31 - 1");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_downsample_region(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
+                           void* d_work, uint32_t* d_bits, uint16_t* d_counts_or_null, vxrt_lod_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !d_work || !d_bits || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = lod_ready(c, origin, dims, shift, threshold))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::downsample_region(vxrt::query_world(c), origin, dims, shift, threshold, d_work, d_bits, d_counts_or_null, d_summary,
+                                   (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_downsample_region_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
+                                uint32_t* bits, uint16_t* counts_or_null, vxrt_lod_summary* summary)
+{
+    if (!c || !origin || !dims || !bits || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = lod_ready(c, origin, dims, shift, threshold))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::LodLayout L;
+    vxrt::lod_layout(origin, dims, shift, L);
+    const size_t bb = 4u * (size_t)vxrt::region_words(dims), cells = (size_t)dims[0] * L.rows, cb = counts_or_null ? 2u * cells : 0;
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, sizeof(vxrt_lod_summary), bb, cb}))
+        return fail(VXRT_ERR_NOMEM, std::string("downsample_region_host: ") + hipGetErrorString(e));
+    VX_HIP(vxrt::downsample_region(vxrt::query_world(c), origin, dims, shift, threshold, T.base, T.at<uint32_t>(2),
+                                   cb ? T.at<uint16_t>(3) : nullptr, T.at<vxrt_lod_summary>(1), nullptr));
+    VX_HIP(hipMemcpy(summary, T.at<vxrt_lod_summary>(1), sizeof(vxrt_lod_summary), hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(bits, T.at<uint32_t>(2), bb, hipMemcpyDeviceToHost));
+    if (cb)
+        VX_HIP(hipMemcpy(counts_or_null, T.at<uint16_t>(3), cb, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }

@@ -559,6 +559,136 @@ class Context:
                                 vertices=verts[:4 * n] if triangles else None, triangles=tris[:2 * n] if triangles else None,
                                 _summary=summary, _stream=None)
 
+    # ---- occupancy LOD (extension, include/vxrt.h) ----------------------------------------------------------------------
+    def lod_workspace_bytes(self, dims, shift: int) -> int:
+        """vxrt_lod_workspace_bytes: the workspace of one downsample call, 0 outside the contract"""
+        shift = int(shift)
+        return int(self._L.vxrt_lod_workspace_bytes(_i3(dims), shift)) if 0 <= shift < 1 << 32 else 0
+
+    def downsample(self, origin, dims, shift: int, threshold: int = 1, counts: bool = False, out=None, work=None,
+                   stream: int | None = None) -> "Downsampled":
+        """The box of ``dims`` cells of (1 << shift)^3 voxels at world voxel ``origin`` reduced to one bit per cell: set when
+        the cell holds at least ``threshold`` solid voxels (1: any, the conservative choice; f^3: all), as region words of
+        ``dims`` -- a Stamp's bits for a coarser world -- and with ``counts`` one two-byte count per cell in region order
+        (include/vxrt.h, vxrt_downsample_region).  Asynchronous on ``stream`` (default: torch's current stream); the tensors
+        this method allocates are torch's, made on torch's current stream, so a ``stream`` other than that one must already be
+        ordered after it (as for the other queries).  ``out``: a
+        device tensor of region_words(dims) four-byte elements for the bits; ``work``: a device tensor of at least
+        lod_workspace_bytes(dims, shift) bytes (default: new ones).  Returns a Downsampled; reading its ``summary`` waits for
+        the call."""
+        import torch
+        dims = tuple(int(v) for v in dims)
+        dev = "cuda:%d" % self.device
+        ws = self.lod_workspace_bytes(dims, shift)
+        n = region_words(dims) if ws else 0
+        ncell = dims[0] * dims[1] * dims[2] if ws else 0
+        own_work = work is None
+        if own_work:
+            work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
+        elif work.numel() * work.element_size() < ws or not work.is_contiguous():
+            raise ValueError("work: a contiguous device tensor of at least lod_workspace_bytes(dims, shift) bytes")
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        elif out.element_size() != 4 or out.numel() < n or not out.is_contiguous():
+            raise ValueError("out: a contiguous device tensor of at least region_words(dims) four-byte elements")
+        cnt = torch.empty(max(ncell, 1), dtype=torch.int16, device=dev) if counts else None
+        summary = torch.zeros(8, dtype=torch.int32, device=dev)
+        s = _stream(stream)
+        N.check(self._L.vxrt_downsample_region(self._h, _i3(origin), _i3(dims), _u32(shift), _u32(threshold), _ptr(work), _ptr(out),
+                                               _ptr(cnt), _ptr(summary), s))
+        if own_work:
+            work.record_stream(torch.cuda.ExternalStream(s, device=dev))  # freed here, still in use on the call's stream
+        return Downsampled(origin=tuple(int(v) for v in origin), dims=dims, shift=int(shift), threshold=int(threshold),
+                           bits=out.view(-1)[:n], counts=cnt[:ncell] if counts else None, _summary=summary, _stream=s)
+
+    def downsample_host(self, origin, dims, shift: int, threshold: int = 1, counts: bool = True) -> "Downsampled":
+        """downsample through the synchronous host call (vxrt_downsample_region_host): ``bits`` is a numpy bool [x, y, z] grid
+        and ``counts`` a numpy uint16 [x, y, z] grid (None without ``counts``)."""
+        dims = tuple(int(v) for v in dims)
+        ok = self.lod_workspace_bytes(dims, shift) != 0
+        words = np.zeros(max(region_words(dims) if ok else 0, 1), np.uint32)
+        ncell = dims[0] * dims[1] * dims[2] if ok else 0
+        cnt = np.zeros(max(ncell, 1), np.uint16)
+        summary = np.zeros(8, np.uint32)
+        N.check(self._L.vxrt_downsample_region_host(self._h, _i3(origin), _i3(dims), _u32(shift), _u32(threshold), words.ctypes.data,
+                                                    cnt.ctypes.data if counts else None, summary.ctypes.data))
+        return Downsampled(origin=tuple(int(v) for v in origin), dims=dims, shift=int(shift), threshold=int(threshold),
+                           bits=unpack_region(words, dims), counts=cnt[:ncell].reshape(dims[::-1]).transpose(2, 1, 0) if counts else None,
+                           _summary=summary, _stream=None)
+
+    def lod_world(self, shift: int, threshold: int = 1, into: "Context | None" = None, box=None,
+                  slab_cells: int | None = None) -> "Context":
+        """A coarser copy of the resident world in a Context of its own: voxel C of it is the bit of cell C of
+        ``downsample((0, 0, 0), ..., shift, threshold)``, so it is rendered by the unchanged tracer with the camera scaled by
+        1 / f, f = 1 << shift.
+
+        ``into=None`` opens a second Context on this device, uploads an empty world of ceil(world / f) voxels per axis
+        (rounded up to whole bricks and to 8 bricks per axis, the shape rule of upload_world) with the same brick factor and
+        fills it.  ``into`` with ``box = (lo, hi)``, a box of world voxels with inclusive corners such as an edit's bounding
+        box, refreshes an existing LOD world of this shift: the box grows outwards to multiples of f and only those cells are
+        written again (``box=None``: all of them).  ``into`` must have the brick factor and the size that ``into=None`` gives for
+        this shift, and a world that lod_world made must have been made at this shift (ValueError otherwise): a world of
+        another shift would be stamped in the wrong places.
+
+        The cells are filled in z slabs of ``slab_cells`` cells (default: as many as the 2^32-voxel source limit of one
+        downsample allows), each one downsample followed by one STAMP_REPLACE stamp into the LOD world; the bits never leave
+        the device.  The stamp's cost rules and its synchronisation are vxrt_edit_stamps' own: each stamp synchronises the
+        device before and after, and costs in proportion to the LOD bricks its box touches.  Returns the LOD Context."""
+        shift, f = int(shift), 1 << int(shift)
+        if not 1 <= shift <= N.LOD_MAX_SHIFT:
+            raise ValueError("shift: 1 .. LOD_MAX_SHIFT")
+        info = self.world_info()
+        F = int(info.factor)
+        cells = [-(-int(c) * F // f) for c in info.cdims]  # cells that meet the world, per axis
+        if into is None:
+            if box is not None:
+                raise ValueError("box refreshes an existing LOD world: give into")
+            cd = [max(-(-(-(-n // F)) // 8) * 8, 8) for n in cells]
+            ncells = cd[0] * cd[1] * cd[2]
+            into = Context(self.device)
+            try:
+                into.upload_world(F, cd, np.zeros((ncells + 31) // 32, np.uint32), np.full(ncells, N.EMPTY_SLOT, np.uint32),
+                                  np.zeros(6 * ncells, np.float32), np.zeros(0, np.uint32))
+                into._lod_shift = shift  # a later refresh at another shift is refused
+                return self._lod_fill(into, shift, threshold, cells, None, slab_cells)
+            except BaseException:
+                into.close()  # the context opened here does not outlive a failure
+                raise
+        have = into.world_info()
+        if int(have.factor) != F or [int(c) for c in have.cdims] != [max(-(-(-(-n // F)) // 8) * 8, 8) for n in cells]:
+            raise ValueError("into: not an LOD world of this world at this shift (brick factor or size differ)")
+        if getattr(into, "_lod_shift", shift) != shift:
+            raise ValueError("into: an LOD world of shift %d, not %d" % (into._lod_shift, shift))
+        return self._lod_fill(into, shift, threshold, cells, box, slab_cells)
+
+    def _lod_fill(self, into: "Context", shift: int, threshold: int, cells, box, slab_cells) -> "Context":
+        """lod_world's slabs: the cells of ``box`` (all of ``cells`` when None) downsampled and stamped into ``into``"""
+        import torch
+        f = 1 << shift
+        lo, hi = [0, 0, 0], list(cells)  # the cell box [lo, hi)
+        if box is not None:
+            lo = [max(int(a) // f, 0) for a in box[0]]
+            hi = [min(int(b) // f + 1, n) for b, n in zip(box[1], cells)]
+        d = [b - a for a, b in zip(lo, hi)]
+        if min(d) < 1:
+            return into
+        per_slab = f ** 3 * d[0] * d[1]
+        if per_slab > 1 << 32:
+            raise ValueError("one z slab of the cell box exceeds the 2^32-voxel source limit of a downsample")
+        most = (1 << 32) // per_slab
+        slab = most if slab_cells is None else int(slab_cells)
+        if not 1 <= slab <= most:
+            raise ValueError("slab_cells: 1 .. %d for this box and shift" % most)
+        slab = min(slab, d[2])
+        dev = "cuda:%d" % self.device
+        work = torch.empty(max(self.lod_workspace_bytes((d[0], d[1], slab), shift), 4), dtype=torch.uint8, device=dev)
+        bits = torch.empty(region_words((d[0], d[1], slab)), dtype=torch.int32, device=dev)
+        for z in range(lo[2], hi[2], slab):
+            dz = (d[0], d[1], min(slab, hi[2] - z))
+            got = self.downsample((lo[0] * f, lo[1] * f, z * f), dz, shift, threshold, out=bits, work=work)
+            into.edit_stamps([Stamp((lo[0], lo[1], z), got.bits, N.STAMP_REPLACE, dz)])
+        return into
+
     def download_world(self, with_pool: bool = True):
         info = self.world_info()
         n = int(info.ncells)
@@ -901,6 +1031,60 @@ class ExtractedSurface:
         return (ext >> 20, pos & 1023, pos >> 10 & 1023, pos >> 20 & 1023, (ext & 1023) + 1, (ext >> 10 & 1023) + 1)
 
 
+class LodSummary(NamedTuple):
+    """vxrt_lod_summary: the solid voxels of the source box (the sum of all counts), the cells at or above the threshold, the
+    cells with no solid voxel, with f^3 and with something between, the largest count"""
+    solid: int
+    set: int
+    empty: int
+    full: int
+    mixed: int
+    max_count: int
+
+
+@dataclass
+class Downsampled:
+    """The result of Context.downsample: ``bits`` the cell bits as region words of ``dims`` on the device (a Stamp's bits),
+    ``counts`` one two-byte count per cell in region order or None; from downsample_host a numpy bool [x, y, z] grid and a
+    numpy uint16 [x, y, z] grid.  ``summary`` is a LodSummary."""
+    origin: tuple
+    dims: tuple
+    shift: int
+    threshold: int
+    bits: object
+    counts: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> LodSummary:
+        """the summary; for a device result this waits for the call's stream"""
+        w = self._summary
+        if not isinstance(w, np.ndarray):
+            import torch
+            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
+            w = self._summary = w.cpu().numpy().view(np.uint32)
+        return LodSummary(int(w[0]) | int(w[1]) << 32, int(w[2]), int(w[3]), int(w[4]), int(w[5]), int(w[6]))
+
+    def grid(self) -> np.ndarray:
+        """the cell bits as a numpy bool [x, y, z] grid (a device result is copied to the host)"""
+        if isinstance(self.bits, np.ndarray):
+            return self.bits
+        import torch
+        torch.cuda.ExternalStream(self._stream, device=self.bits.device).synchronize()
+        return unpack_region(self.bits, self.dims)
+
+    def count_grid(self) -> np.ndarray:
+        """the counts as a numpy uint16 [x, y, z] grid (a device result is copied to the host)"""
+        if self.counts is None:
+            raise ValueError("the call asked for no counts")
+        if isinstance(self.counts, np.ndarray):
+            return self.counts
+        import torch
+        torch.cuda.ExternalStream(self._stream, device=self.counts.device).synchronize()
+        return self.counts.cpu().numpy().view(np.uint16).reshape(self.dims[::-1]).transpose(2, 1, 0)
+
+
 class DistanceSummary(NamedTuple):
     """vxrt_distance_summary: voxels of the box that are targets, values 1 .. radius^2, DIST_FAR values, the largest value
     that is not DIST_FAR, the sum of the values that are not DIST_FAR"""
@@ -1044,6 +1228,12 @@ def _bodies_dev(bodies):
 
 def _i3(v):
     return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def _u32(v) -> int:
+    """an argument of a uint32 parameter: a value outside it is the library's to refuse, not ctypes' to wrap"""
+    v = int(v)
+    return v if 0 <= v < 1 << 32 else 0xFFFFFFFF
 
 
 def region_words(dims) -> int:
