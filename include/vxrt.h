@@ -688,11 +688,12 @@ typedef struct vxrt_frame_stats {
     uint64_t coarse_probes; /* Nc: in-range coarse cell probes */
     uint64_t brick_entries; /* Nb */
     uint64_t fine_probes;   /* Nf: in-range brick cell probes */
-    uint64_t dbg[12];       /* wave-loop diagnostics of collect_stats launches, summed over waves: [0] iterations,
+    uint64_t dbg[13];       /* wave-loop diagnostics of collect_stats launches, summed over waves: [0] iterations,
                                [1] walking lanes over those iterations, [2] end-of-walk / [3] tight-box / [4] ray-finished
                                phase executions, [5..7] lanes those executions served (same order); persistent kernel
                                only: [8] wave lifetime in 100 MHz ticks, [9] iterations after the tile queue ran dry, [10] ticks inside
-                               the ray-finished phase, [11] ticks inside the box and end-of-walk phases */
+                               the ray-finished phase, [11] ticks inside the box and end-of-walk phases, [12] shadow rays launched
+                               from the end-of-walk phase (primary hits that went on without parking) */
     /* Load guard of collect_stats launches (product kernels).  The tracer lets a lane that has just stepped out of a grid
      * issue one more occupancy load before it stops; the library allocates slack around both bit tables for it.  Counted
      * per load: beyond a table but inside its allocation (expected, > 0 on ordinary frames), and outside everything

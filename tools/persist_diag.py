@@ -51,3 +51,5 @@ for cname, frac, euler in bench.CAMERAS:
         100.0 * box_r / max(iters, 1), box_l / max(box_r, 1)), flush=True)
     print("    share of wave time: ray-finished phase %.1f%%  box+end phases %.1f%%  (rest: probes, votes, queue)" % (
         100.0 * int(st.dbg[10]) / max(life, 1), 100.0 * int(st.dbg[11]) / max(life, 1)), flush=True)
+    print("    shadow rays launched from the end-of-walk phase: %d of %d (%.1f%%)" % (
+        int(st.dbg[12]), int(st.shadow_rays), 100.0 * int(st.dbg[12]) / max(int(st.shadow_rays), 1)), flush=True)

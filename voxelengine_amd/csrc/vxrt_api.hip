@@ -936,6 +936,7 @@ int vxrt_frame_stats_get(vxrt_ctx* c, vxrt_frame_stats* out)
     out->dbg[9] = h[vxrt::kStatDbgDrained];
     out->dbg[10] = h[vxrt::kStatDbgNextTicks];
     out->dbg[11] = h[vxrt::kStatDbgParkTicks];
+    out->dbg[12] = h[vxrt::kStatDbgEndShadow];
     out->guard_slack_loads = h[vxrt::kStatGuardSlack];
     out->guard_stray_loads = h[vxrt::kStatGuardStray];
 #ifdef VXRT_EXPERIMENTS  // (vxrt_frame_stats has no field for them: a development print of the A/B build)

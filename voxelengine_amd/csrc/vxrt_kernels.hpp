@@ -30,6 +30,7 @@ enum StatSlot {
     kStatGuardStray,    // ... and outside everything addressable (must stay 0)
     kStatDbgCoRuns,     // persistent render kernel: rounds in which both the end-of-walk and the ray-finished phase ran
     kStatDbgCoStarts,   // ... and in which the first restarted a coarse walk and the second launched a ray (one shared set-up)
+    kStatDbgEndShadow,  // persistent render kernel: shadow rays launched from the end-of-walk phase (primary hits that never parked)
     kStatCount
 };
 

@@ -125,6 +125,11 @@ __device__ __forceinline__ f3 camera_origin(const RenderArgs& A, const LaneView&
 
 enum : int { PF_STAGE = 0, PF_TX, PF_ROW, PF_POS_X, PF_POS_Y, PF_POS_Z, PF_COL_X, PF_COL_Y, PF_COL_Z, PF_PCODE, PF_PSTEPS, PF_OCCL,
              PF_SAMPLE, PF_PIXEL_FIELDS };
+// The words of the wave's LDS block behind the lanes' columns: the four ray counters, then what the shadow ray has in common
+// for every pixel of the launch (written once per wave, read by the end-of-walk phase's continuation): the tracer's per-ray
+// invariants of the light's direction, the ray's offset from the hit, and whether the launch takes that path at all.
+enum : int { WV_COUNTERS = 0, WV_LIGHT_DX = 4, WV_LIGHT_DY, WV_LIGHT_DZ, WV_LIGHT_IVX, WV_LIGHT_IVY, WV_LIGHT_IVZ, WV_LIGHT_DN,
+             WV_LIGHT_STEP_X, WV_LIGHT_STEP_Y, WV_LIGHT_STEP_Z, WV_SHADOW_FROM_END, WV_WORDS = 16 };
 // The launch's arguments as the ray-finished phase reads them.  The ~50 frame arguments (camera, light, mode words, strips,
 // buffers) are used by that phase only, but as kernel arguments the compiler loads them once, before the loop, and keeps
 // them in scalar registers for the kernel's lifetime -- beside the probe loop's wave masks they do not fit (74 spilled
@@ -207,7 +212,10 @@ template <bool STATS, bool BOUNCE2, bool MULTI, bool WIDE>
 __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(RenderArgs A_kern)
 {
     constexpr bool LDS = true;  // (the PX_* macros and the tracer's LDS_COLD parameter)
-    __shared__ uint32_t cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64 + 4];  // + the wave's four ray counters
+    // shadow rays are launched from the end-of-walk phase (shadow_from_end below).  Not in the multi-view second-bounce
+    // instantiations: with the continuation they spill 8 vector registers, so they keep the ray-finished phase's path.
+    constexpr bool END_SHADOW = !(BOUNCE2 && MULTI);
+    __shared__ uint32_t cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64 + WV_WORDS];  // + the wave's own words (WV_*)
     const WorldView& W = A_kern.W;
     const int lane = threadIdx.x & 63;
     uint32_t* const PX = &cold_block[CF_TRACER_FIELDS * 64 + lane];  // this lane's column of the pixel fields
@@ -232,8 +240,41 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     int sample = 0;
     uint32_t n_primary = 0, n_shadow = 0, n_bounce = 0, n_hits = 0;  // wave-uniform (ballot counts): scalar registers
     PX_ST_U(PF_STAGE, stage);  // (the other fields are written before they are read: a pixel starts with its primary ray)
+    uint32_t* const WV = &cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64];
     if (lane < 4)
-        cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64 + lane] = 0u;
+        WV[WV_COUNTERS + lane] = 0u;
+    {
+        // The shadow ray's direction is the launch's light: its per-ray invariants, by the operations of begin_ray_deferred
+        // on A.light_unit (the direction that phase passes for a shadow ray), once per wave.  A light with a component that is
+        // zero or below 2^-40 (`special` for every start) keeps the ray-finished phase's path for the whole launch, and so does
+        // a launch that writes a hit-index AOV for any of its views (the index is stored by that phase).
+        const f3 lu = A_kern.light_unit;
+        const float dd = dot3(lu, lu);
+        f3 ld = unit3_ordinary(lu, dd);
+        const float ex = ld.x == 0 ? kFltEps : ld.x, ey = ld.y == 0 ? kFltEps : ld.y, ez = ld.z == 0 ? kFltEps : ld.z;
+        float lix = rcp_rn(ex), liy = rcp_rn(ey), liz = rcp_rn(ez);
+        if (!(ordinary(dd) & ordinary(ex) & ordinary(ey) & ordinary(ez))) {  // (wave-uniform)
+            ld = unit3(lu);
+            lix = 1.0f / (ld.x == 0 ? kFltEps : ld.x);
+            liy = 1.0f / (ld.y == 0 ? kFltEps : ld.y);
+            liz = 1.0f / (ld.z == 0 ? kFltEps : ld.z);
+        }
+        const bool light_special = !(fabsf(ld.x) >= kMinFastDir && fabsf(ld.y) >= kMinFastDir && fabsf(ld.z) >= kMinFastDir);
+        const bool aov = MULTI ? A_kern.want_hit_aov != 0 : A_kern.hit_aov != nullptr;
+        if (lane == 0) {
+            WV[WV_LIGHT_DX] = __float_as_uint(ld.x);
+            WV[WV_LIGHT_DY] = __float_as_uint(ld.y);
+            WV[WV_LIGHT_DZ] = __float_as_uint(ld.z);
+            WV[WV_LIGHT_IVX] = __float_as_uint(lix);
+            WV[WV_LIGHT_IVY] = __float_as_uint(liy);
+            WV[WV_LIGHT_IVZ] = __float_as_uint(liz);
+            WV[WV_LIGHT_DN] = (ld.x > 0 ? 0u : 1u) | (ld.y > 0 ? 0u : 2u) | (ld.z > 0 ? 0u : 4u);
+            WV[WV_LIGHT_STEP_X] = __float_as_uint(A_kern.light_step.x);
+            WV[WV_LIGHT_STEP_Y] = __float_as_uint(A_kern.light_step.y);
+            WV[WV_LIGHT_STEP_Z] = __float_as_uint(A_kern.light_step.z);
+            WV[WV_SHADOW_FROM_END] = (END_SHADOW && A_kern.mode == 0 && A_kern.shadow && !light_special && !aov) ? 1u : 0u;
+        }
+    }
 
     // the wave's share of the tile queue (wave-uniform)
     // Whole tiles per ticket: one same-address atomic per 64 pixels.  A finer queue is limited by the atomic rate
@@ -247,6 +288,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     const unsigned long long dg_t0 = STATS ? wall_clock64() : 0ull;
     unsigned long long dg_next_ticks = 0, dg_park_ticks = 0;
     unsigned long long dg_co_runs = 0, dg_co_starts = 0;  // rounds in which the end-of-walk AND the ray-finished phase ran / started walks
+    unsigned long long dg_end_shadow = 0;  // shadow rays launched from the end-of-walk phase
 #ifdef VXRT_TAIL_DEBUG
     unsigned long long px_t0 = 0;
 #endif
@@ -296,6 +338,64 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             sink.put(pc.x, pc.y, mk3((float)p_steps / 256.0f, 0, 0));
     };
 
+    // The end-of-walk phase's continuation (WaveTracerT::phase_end_deferred): a PRIMARY ray that has just ended on a voxel
+    // becomes its pixel's shadow ray there and then -- what the ray-finished phase's PX_PRIMARY branch does for such a lane
+    // (result(), the pixel's fields, the counters, the ray from position + light_step along the light), with the light's
+    // invariants from the wave's words instead of begin_ray_deferred's normalisation and reciprocals, and without the world-entry
+    // test: only a start inside the coarse grid takes this path, and only one without a -0.0 component (`special`).  Every other
+    // lane stays ST_DONE with its fields untouched, for the ray-finished phase.
+    auto shadow_from_end = [&](WaveTracerT<WIDE>& Tr, const lanemask_t ended) -> lanemask_t {
+        if (ended == 0ull)
+            return 0ull;
+        bool go = false;
+        if (lane_test(ended)) {
+            if (PX[PF_STAGE * 64] == PX_PRIMARY && WV[WV_SHADOW_FROM_END] != 0u) {
+                TraceResult r;
+                Tr.result(W, r);
+                const f3 at = r.pos;
+                const f3 from = at + mk3(__uint_as_float(WV[WV_LIGHT_STEP_X]), __uint_as_float(WV[WV_LIGHT_STEP_Y]),
+                                         __uint_as_float(WV[WV_LIGHT_STEP_Z]));
+                const f3 s0 = mk3(from.x * W.inv_f, from.y * W.inv_f, from.z * W.inv_f);
+                // inside the coarse grid (begin_ray_deferred's test) and no -0.0: no sign bit, and below the far faces
+                const uint32_t signs = __float_as_uint(s0.x) | __float_as_uint(s0.y) | __float_as_uint(s0.z);
+                if ((int32_t)signs >= 0 && s0.x < (float)W.cx && s0.y < (float)W.cy && s0.z < (float)W.cz) {
+                    PX[PF_PCODE * 64] = r.ncode;
+                    PX[PF_PSTEPS * 64] = (uint32_t)r.steps;
+                    PX[PF_POS_X * 64] = __float_as_uint(at.x);
+                    PX[PF_POS_Y * 64] = __float_as_uint(at.y);
+                    PX[PF_POS_Z * 64] = __float_as_uint(at.z);
+                    PX[PF_COL_X * 64] = 0u;  // (a hit pixel's colour starts from zero)
+                    PX[PF_COL_Y * 64] = 0u;
+                    PX[PF_COL_Z * 64] = 0u;
+                    PX[PF_STAGE * 64] = PX_SHADOW;
+                    Tr.cold[CF_RAY_CODES * 64] = (uint32_t)kMaxSteps << 7;
+                    Tr.cold[CF_START_X * 64] = __float_as_uint(s0.x);
+                    Tr.cold[CF_START_Y * 64] = __float_as_uint(s0.y);
+                    Tr.cold[CF_START_Z * 64] = __float_as_uint(s0.z);
+                    Tr.cold[CF_LAST_CI * 64] = 0xFFFFFFFFu;
+                    Tr.cold[CF_TOTAL * 64] = 0u;
+                    Tr.d = mk3(__uint_as_float(WV[WV_LIGHT_DX]), __uint_as_float(WV[WV_LIGHT_DY]), __uint_as_float(WV[WV_LIGHT_DZ]));
+                    Tr.ivx = __uint_as_float(WV[WV_LIGHT_IVX]);
+                    Tr.ivy = __uint_as_float(WV[WV_LIGHT_IVY]);
+                    Tr.ivz = __uint_as_float(WV[WV_LIGHT_IVZ]);
+                    Tr.dn = WV[WV_LIGHT_DN];
+                    Tr.special = false;
+                    Tr.st = ST_WALK;
+                    go = true;
+                }
+            }
+        }
+        const lanemask_t launched = __ballot(go);
+        const uint32_t n = (uint32_t)__popcll(launched);
+        if (lane == 0) {  // one primary hit and one shadow ray each
+            WV[WV_COUNTERS + 1] += n;
+            WV[WV_COUNTERS + 3] += n;
+        }
+        if (STATS)
+            dg_end_shadow += n;
+        return launched;
+    };
+
     for (;;) {
         const unsigned long long m_walk = __ballot(T.st == ST_WALK);
         const unsigned long long m_box = __ballot(T.st == ST_BOX);
@@ -334,11 +434,15 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 dg_lanes[1] += (unsigned)c_end;
                 dg_park_ticks -= wall_clock64();
             }
-            T.template phase_end_deferred<STATS>(W);
+            if constexpr (END_SHADOW)
+                T.template phase_end_deferred<STATS>(W, shadow_from_end);
+            else
+                T.template phase_end_deferred<STATS>(W);
             if (STATS)
                 dg_park_ticks += wall_clock64();
             c_end = 0;
-            // (lanes whose coarse walk restarts are ST_WALK already, set up by start_pending below: walkers for the vote that follows)
+            // (lanes whose coarse walk restarts, and primary hits that went on as shadow rays, are ST_WALK already, set up by
+            // start_pending below: walkers for the vote that follows)
             c_walk = __popcll(__ballot(T.st == ST_WALK));
             if (STATS) {
                 dg_end_ran = true;
@@ -584,7 +688,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 const uint32_t d0 = (uint32_t)__popcll(__ballot(got)), d1 = (uint32_t)__popcll(__ballot(c_shadow)),
                                d2 = (uint32_t)__popcll(__ballot(c_bounce)), d3 = (uint32_t)__popcll(__ballot(c_hit));
                 if (lane == 0) {
-                    uint32_t* const C = &cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64];
+                    uint32_t* const C = &WV[WV_COUNTERS];
                     C[0] += d0;
                     C[1] += d1;
                     C[2] += d2;
@@ -610,7 +714,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     }
 
     if (lane == 0) {
-        const uint32_t* const C = &cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64];
+        const uint32_t* const C = &WV[WV_COUNTERS];
         n_primary = C[0];
         n_shadow = C[1];
         n_bounce = C[2];
@@ -647,6 +751,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             atomicAdd(&stats[kStatDbgParkTicks], dg_park_ticks);
             atomicAdd(&stats[kStatDbgCoRuns], dg_co_runs);
             atomicAdd(&stats[kStatDbgCoStarts], dg_co_starts);
+            atomicAdd(&stats[kStatDbgEndShadow], dg_end_shadow);
         }
     }
 }

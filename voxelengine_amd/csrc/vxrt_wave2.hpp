@@ -51,6 +51,7 @@
 #pragma once
 
 #include "vxrt_device.hpp"
+#include <type_traits>
 #ifdef VXRT_HOST_DEBUG
 #include <cstdio>
 #include <cstdlib>
@@ -510,12 +511,21 @@ struct WaveTracerT {
         start_pending(W);
     }
     // ... without the set-up of the coarse walks it restarts: those lanes are left in pend_m (start_pending)
-    template <bool STATS = false>
-    __device__ __forceinline__ void phase_end_deferred(const WorldView& W)
+    // HOOK: an optional continuation of the caller's, `lanemask_t hook(tracer, ended)`.  It is called once per execution, where
+    // the wave is converged again, with the mask of the lanes this execution turned from ST_ENDHIT into ST_DONE (a ray that
+    // ended on a voxel: result() is valid for them), and may launch the NEXT ray of any of those lanes as a coarse walk right
+    // here instead of in a phase of its own: it writes the per-ray state (d, ivx / ivy / ivz, dn, special, st = ST_WALK) and
+    // the cold fields as begin_ray_deferred does (CF_RAY_CODES, CF_START_*, CF_LAST_CI, CF_TOTAL) and returns the mask of the
+    // lanes it launched, which join the restarted lanes in pend_m.  Without one (NoEndHook) nothing of it is compiled.
+    struct NoEndHook {};
+    template <bool STATS = false, class HOOK = NoEndHook>
+    __device__ __forceinline__ void phase_end_deferred(const WorldView& W, HOOK hook = HOOK())
     {
+        constexpr bool HOOKED = !std::is_same<HOOK, NoEndHook>::value;
         const bool me = waits_for_end(st);
         const bool is_fine = lane_fine();
         bool go_coarse = false;  // this lane restarts the coarse walk
+        bool ended_hit = false;  // (HOOKED) this lane's ray has just ended on a voxel
         if (me) {
             // ---- what the walk that just ended did.  ST_ENDHIT: the probe of the cell `rp` found it occupied; the advance
             // after it (rp -> rem) is the reference's exit advance.  ST_END: validate the last advance (rp -> rem, at time
@@ -603,6 +613,8 @@ struct WaveTracerT {
                     const uint32_t hit_code = steps == 0u ? (box_codes & 7u) : (axis1 + (up_last ? 0u : 4u));
                     cold[CF_RAY_CODES * 64] = (ray_codes & ~0x78u) | (hit_code << 3) | 0x40u;
                     st = ST_DONE;
+                    if constexpr (HOOKED)
+                        ended_hit = true;
                 } else if (!is_fine) {
                     st = ST_DONE;  // the coarse walk left the world (:399-401)
                 } else {
@@ -669,6 +681,11 @@ struct WaveTracerT {
         const lanemask_t m = __ballot(go_coarse);
         fine_m &= ~m;
         pend_m |= m;
+        if constexpr (HOOKED) {
+            const lanemask_t launched = hook(*this, (lanemask_t)__ballot(ended_hit));
+            fine_m &= ~launched;
+            pend_m |= launched;
+        }
     }
 
     // parked phase: tight-box test of an occupied coarse cell (:248-273) and, on a hit, the end of the coarse walk with
