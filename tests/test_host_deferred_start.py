@@ -10,6 +10,8 @@ import subprocess
 
 import pytest
 
+from tests import grid_shape_cases as G
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -34,13 +36,17 @@ def harness_small_caps(tmp_path_factory):
     return _build(tmp_path_factory.mktemp("hdc_cap"), "host_defer_check_caps", ("-DVXRT_FIELD_CAP_XZ=3u", "-DVXRT_FIELD_CAP_Y=2u"))
 
 
-def _run(exe, *args):
+def _run_out(exe, *args):
     out = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:]
     assert "mismatches 0 of %d" % args[3] in out.stdout, out.stdout[-2000:]
     assert "outside it 0)" in out.stdout, out.stdout[-2000:]  # zero stray loads
     m = re.search(r"new rays (\d+), restarts (\d+), outside the grid (\d+); rounds with nothing pending (\d+)", out.stdout)
-    return [int(v) for v in m.groups()]
+    return [int(v) for v in m.groups()], out.stdout
+
+
+def _run(exe, *args):
+    return _run_out(exe, *args)[0]
 
 
 @pytest.mark.parametrize("factor,edge,density,n", [(8, 64, 0.01, 20000), (8, 64, 0.3, 10000), (16, 128, 0.002, 10000),
@@ -63,3 +69,21 @@ def test_deferred_starts_on_wide_grids(harness, harness_small_caps, factor, sx, 
 def test_deferred_starts_with_wide_grid_code_on_ordinary_grids(harness_small_caps, factor, edge, density, n):
     new_rays, restarts, outside, idle = _run(harness_small_caps, factor, edge, density, n, edge, edge, 1)
     assert new_rays == n and restarts > n // 20
+
+
+@pytest.mark.parametrize("name", ["O1", "O2", "O3", "W2", "W3", "W5", "W6"])
+def test_deferred_starts_on_grids_long_in_y_and_z(harness, harness_small_caps, name):
+    """The shapes of tests/grid_shape_cases.py that a dense voxel array holds (f = 8), long walks along whichever axis is long
+    included, with the product's caps and re-armed every 3 / 2 steps."""
+    case = G.BY_NAME[name]
+    assert case.factor == 8
+    sx, sy, sz = case.dims
+    for exe in (harness, harness_small_caps):
+        counts, out = _run_out(exe, 8, sx, G.density(case), 20000, sy, sz)
+        assert counts[0] == 20000 and "UNSUSPECTED EXITS" not in out, out[-2000:]
+        long_walks = int(re.search(r"rays of more than 1024 steps (\d+)", out).group(1))
+        exhausted = int(re.search(r"without a hit (\d+)", out).group(1))
+        if max(case.cells) >= 1024:
+            assert long_walks > 100, out
+        if max(case.cells) >= 2048:
+            assert exhausted > 100, out

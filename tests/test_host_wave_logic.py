@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+from tests import grid_shape_cases as G
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -63,3 +65,23 @@ def test_wide_grid_code_on_ordinary_grids(harness_small_caps, factor, edge, dens
     """The wide-grid path forced on small cubic grids, re-arming every 3 / 2 steps: the adversarial ray families (far-face
     starts, exact ties, denormal directions, single-step mode) through the re-armed history."""
     _run(harness_small_caps, factor, edge, density, n, edge, edge, 1)
+
+
+@pytest.mark.parametrize("name", ["O1", "O2", "O3", "W2", "W3", "W5", "W6"])
+def test_grids_long_in_y_and_z(harness, harness_small_caps, name):
+    """The shapes of tests/grid_shape_cases.py that a dense voxel array holds (f = 8), with the family of long walks along
+    whichever axis is long: the 9-bit y field and the c_slice stride, the z field under the sign bit, CF_OFF_Y and the high
+    half of CF_OFF_XZ, with the product's caps and re-armed every 3 / 2 steps.  No mismatch, no load outside the tables'
+    slack, no lane that leaves an ordinary grid unseen by its time threshold; and the run does contain the walks it is for."""
+    case = G.BY_NAME[name]
+    assert case.factor == 8
+    sx, sy, sz = case.dims
+    for exe in (harness, harness_small_caps):
+        out = _run(exe, 8, sx, G.density(case), 20000, sy, sz)
+        assert "outside it 0)" in out and "UNSUSPECTED EXITS" not in out, out[-2000:]
+        long_walks = int(re.search(r"rays of more than 1024 steps (\d+)", out).group(1))
+        exhausted = int(re.search(r"without a hit (\d+)", out).group(1))
+        if max(case.cells) >= 1024:
+            assert long_walks > 100, out
+        if max(case.cells) >= 2048:
+            assert exhausted > 100, out

@@ -16,7 +16,7 @@ struct Ray { float o[3], d[3]; };
 
 // the adversarial ray families of host_wave_check.cpp: zero, tiny and denormal direction components, starts exactly on the far
 // faces (edge rule), origins outside and far outside the grid, exact ties through corners, long and axis-parallel walks
-static Ray make_ray(int i, const float ext[3], int S, int Sy)
+static Ray make_ray(int i, const float ext[3], int Sy)
 {
     Ray r;
     float* o = r.o;
@@ -30,7 +30,14 @@ static Ray make_ray(int i, const float ext[3], int S, int Sy)
     if (i % 23 == 0) { for (int a = 0; a < 3; ++a) { o[a] = o[a] * 1000.0f; d[a] = ext[a] * 0.5f - o[a]; } }
     if (i % 31 == 0) { o[0] = o[1] = Sy * (1.5f + (i % 7)); d[0] = d[1] = -fabsf(d[0]) - 0.1f; }
     if (i % 37 == 0) { o[1] = o[2] = -Sy * 0.5f; d[1] = d[2] = fabsf(d[1]) + 0.1f; }
-    if (i % 5 == 0 && S > 4 * Sy) { d[0] = (i & 8) ? 1.0f : -1.0f; d[1] *= 0.002f; d[2] *= 0.002f; if (i % 10 == 0) o[0] = d[0] > 0 ? -3.0f : S + 3.0f; }
+    // long walks along whichever axes are more than 4 x the shortest, in turn (a grid long in x only: every such ray along x)
+    int long_axes[3], n_long_axes = 0;
+    for (int a = 0; a < 3; ++a) if (ext[a] > 4 * fminf(ext[0], fminf(ext[1], ext[2]))) long_axes[n_long_axes++] = a;
+    if (i % 5 == 0 && n_long_axes) {
+        const int a = long_axes[(i / 5) % n_long_axes];
+        d[a] = (i & 8) ? 1.0f : -1.0f; d[(a + 1) % 3] *= 0.002f; d[(a + 2) % 3] *= 0.002f;
+        if (i % 10 == 0) o[a] = d[a] > 0 ? -3.0f : ext[a] + 3.0f;
+    }
     if (i % 29 == 0) { d[0] = (i & 1) ? 1.0f : -1.0f; d[1] = d[2] = 0; o[1] = floorf(o[1]); o[2] = floorf(o[2]); }
     if (i % 41 == 0) { int a = (i / 41) % 3; d[a] = (i & 2) ? 1.0f : -1.0f; d[(a + 1) % 3] *= 1e-4f; d[(a + 2) % 3] *= 1e-5f; o[a] = d[a] > 0 ? 0.0f : ext[a]; }
     // rays that miss the world altogether: the deferred start lands outside the grid and the lane meets the end-of-walk phase
@@ -85,9 +92,9 @@ int main(int argc, char** argv)
     const float ext[3] = {(float)S, (float)Sy, (float)Sz};
 
     std::vector<Ray> rays(n);
-    for (int i = 0; i < n; ++i) rays[i] = make_ray(i, ext, S, Sy);
+    for (int i = 0; i < n; ++i) rays[i] = make_ray(i, ext, Sy);
 
-    int bad = 0, n_hits = 0;
+    int bad = 0, n_hits = 0, n_long = 0, n_exhausted = 0;  // coverage: hits, walks beyond 1024 steps, rays that ran into MAX_STEPS
     unsigned long long stray = 0, slack = 0;
     // coverage: walks set up by start_pending for a new ray / for a restart after a brick miss, rounds in which it had nothing
     // to do, deferred starts that landed outside the grid
@@ -112,7 +119,7 @@ int main(int argc, char** argv)
                     const Ray& r = rays[cur];
                     int steps; float nn[3], pp[3] = {0, 0, 0}; int vox[3] = {0, 0, 0}; vxo_ray_stats st{};
                     const int h = vxo_raytrace(w, 2048, r.o, r.d, &steps, nn, pp, vox, &st);
-                    n_hits += h != 0;
+                    n_hits += h != 0; n_long += steps > 1024; n_exhausted += steps >= 2048 && !h;
                     bool ok = (t.hit == (h != 0)) && t.steps == steps && T.cnt.coarse_probes == st.coarse_probes &&
                               T.cnt.brick_entries == st.brick_entries && T.cnt.fine_probes == st.fine_probes && T.cnt.stray_loads == 0;
                     if (h) ok = ok && memcmp(&t.pos, pp, 12) == 0 && t.normal.x == nn[0] && t.normal.y == nn[1] && t.normal.z == nn[2] &&
@@ -151,7 +158,7 @@ int main(int argc, char** argv)
         printf("UNSUSPECTED EXITS: %llu\n", host_unsuspected_exits());
         bad += 1;
     }
-    printf("mismatches %d of %d  (hits %d; deferred starts: new rays %llu, restarts %llu, outside the grid %llu; rounds with nothing pending %llu; "
-           "loads in the tables' slack %llu, outside it %llu)\n", bad, n, n_hits, starts_ray, starts_restart, starts_outside, idle_calls, slack, stray);
+    printf("mismatches %d of %d  (hits %d, rays of more than 1024 steps %d, of 2048 or more without a hit %d; deferred starts: new rays %llu, restarts %llu, "
+           "outside the grid %llu; rounds with nothing pending %llu; loads in the tables' slack %llu, outside it %llu)\n", bad, n, n_hits, n_long, n_exhausted, starts_ray, starts_restart, starts_outside, idle_calls, slack, stray);
     return bad != 0;
 }

@@ -5,6 +5,7 @@ extern "C" {
 #include "vxo.h"
 }
 #include <cstdio>
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 using namespace vxrt;
@@ -12,16 +13,42 @@ int main(int argc, char** argv)
 {
     // usage: host_wave_check f S density n [Sy Sz [wide]]   (S = voxels along x; Sy, Sz default to S; wide = 1 forces the
     // wide-grid code of vxrt_wave2.hpp on a grid that would not need it)
-    int f = argc > 1 ? atoi(argv[1]) : 8, S = argc > 2 ? atoi(argv[2]) : 64;
-    double dens = argc > 3 ? atof(argv[3]) : 0.01;
-    int n = argc > 4 ? atoi(argv[4]) : 30000;
-    const int Sy = argc > 5 ? atoi(argv[5]) : S, Sz = argc > 6 ? atoi(argv[6]) : S;
-    const int force_wide = argc > 7 ? atoi(argv[7]) : 0;
-    std::vector<uint32_t> dense((size_t)S * Sy * Sz / 32, 0);
-    srand(1);
-    for (int z = 0; z < Sz; ++z) for (int y = 0; y < Sy; ++y) for (int x = 0; x < S; ++x)
-        if (rand() / (double)RAND_MAX < dens) { uint64_t i = vxo_sample_index64(x, y, z, S, Sy); dense[i >> 5] |= 1u << (i & 31); }
-    vxo_world* w = vxo_build_brickmap(dense.data(), S, Sy, Sz, f);
+    //    or: host_wave_check @FILE   -- the world's tables and the rays from FILE (tests/test_grid_shapes_host.py writes it):
+    //        int32 f, cx, cy, cz, nslots, n; then coarse_bits, brick_slot, bounds, pool in the oracle's layout; then n origins
+    //        and n directions (3 floats each)
+    int f = 8, S = 64, n = 30000, Sy = 64, Sz = 64, force_wide = 0;
+    std::vector<uint32_t> file_coarse, file_slot, file_pool;
+    std::vector<float> file_bounds, file_rays;
+    vxo_world* w = nullptr;
+    if (argc > 1 && argv[1][0] == '@') {
+        FILE* fi = fopen(argv[1] + 1, "rb");
+        int32_t h[6];
+        if (!fi || fread(h, 4, 6, fi) != 6) { printf("cannot read %s\n", argv[1] + 1); return 2; }
+        f = h[0]; n = h[5];
+        const int cd[3] = {h[1], h[2], h[3]};
+        const uint64_t ncells = (uint64_t)cd[0] * cd[1] * cd[2], nslots = (uint32_t)h[4];
+        file_coarse.resize((ncells + 31) / 32); file_slot.resize(ncells); file_bounds.resize(ncells * 6);
+        file_pool.resize(std::max<uint64_t>(nslots, 1) * ((uint64_t)f * f * f / 32)); file_rays.resize((size_t)n * 6);
+        bool ok = fread(file_coarse.data(), 4, file_coarse.size(), fi) == file_coarse.size() && fread(file_slot.data(), 4, ncells, fi) == ncells &&
+                  fread(file_bounds.data(), 4, ncells * 6, fi) == ncells * 6;
+        ok = ok && fread(file_pool.data(), 4, nslots * ((uint64_t)f * f * f / 32), fi) == nslots * ((uint64_t)f * f * f / 32) &&
+             fread(file_rays.data(), 4, file_rays.size(), fi) == file_rays.size();
+        fclose(fi);
+        if (!ok) { printf("%s is too short\n", argv[1] + 1); return 2; }
+        w = vxo_world_wrap(f, cd, file_coarse.data(), file_slot.data(), file_bounds.data(), nslots, file_pool.data());
+        S = cd[0] * f; Sy = cd[1] * f; Sz = cd[2] * f;
+    } else {
+        f = argc > 1 ? atoi(argv[1]) : 8; S = argc > 2 ? atoi(argv[2]) : 64;
+        const double dens = argc > 3 ? atof(argv[3]) : 0.01;
+        n = argc > 4 ? atoi(argv[4]) : 30000;
+        Sy = argc > 5 ? atoi(argv[5]) : S; Sz = argc > 6 ? atoi(argv[6]) : S;
+        force_wide = argc > 7 ? atoi(argv[7]) : 0;
+        std::vector<uint32_t> dense((size_t)S * Sy * Sz / 32, 0);
+        srand(1);
+        for (int z = 0; z < Sz; ++z) for (int y = 0; y < Sy; ++y) for (int x = 0; x < S; ++x)
+            if (rand() / (double)RAND_MAX < dens) { uint64_t i = vxo_sample_index64(x, y, z, S, Sy); dense[i >> 5] |= 1u << (i & 31); }
+        w = vxo_build_brickmap(dense.data(), S, Sy, Sz, f);
+    }
     // the oracle's tables are in the reference's tiled order; the tracer reads the HBM order (linear x, z, y on both
     // levels): re-order on the host what the library re-orders on the device (vxrt_worldgen.hip)
     const int cx = w->cdims[0], cy = w->cdims[1], cz = w->cdims[2];
@@ -81,25 +108,36 @@ int main(int argc, char** argv)
     auto trace_persistent = [&](const f3 o, const f3 d, TraceResult& out, RayCounters& c) {
         if (W.c_wide) trace_persistent_on(TPw, o, d, out, c); else trace_persistent_on(TPn, o, d, out, c);
     };
+    int long_axes[3], n_long_axes = 0;  // the axes more than 4 x the shortest one
+    for (int a = 0; a < 3; ++a) if (ext[a] > 4 * fminf(ext[0], fminf(ext[1], ext[2]))) long_axes[n_long_axes++] = a;
     int bad = 0, n_hits = 0, n_long = 0, n_exhausted = 0;  // coverage of the run: hits, walks beyond 1024 steps, rays that ran into MAX_STEPS
     for (int i = 0; i < n; ++i) {
         float o[3], d[3];
-        for (int a = 0; a < 3; ++a) { o[a] = (rand() / (float)RAND_MAX) * (i % 3 ? ext[a] : 3 * ext[a]) - (i % 3 ? 0 : ext[a]); d[a] = rand() / (float)RAND_MAX * 2 - 1; }
-        if (i % 7 == 0) d[i % 3] = 0;
-        if (i % 11 == 0) { o[0] = floorf(o[0]); o[1] = floorf(o[1]); }
-        // adversarial families: tiny / denormal direction components, starts exactly on the far faces (edge rule),
-        // far-away origins aimed at the grid, axis-aligned rays along cell boundaries
-        if (i % 13 == 0) d[(i / 13) % 3] *= 1e-30f;
-        if (i % 17 == 0) d[(i / 17) % 3] = 1e-42f;
-        if (i % 19 == 0) { o[(i / 19) % 3] = ext[(i / 19) % 3]; d[(i / 19) % 3] = -fabsf(d[(i / 19) % 3]) - 0.01f; }
-        if (i % 23 == 0) { for (int a = 0; a < 3; ++a) { o[a] = o[a] * 1000.0f; d[a] = ext[a] * 0.5f - o[a]; } }
-        if (i % 31 == 0) { o[0] = o[1] = Sy * (1.5f + (i % 7)); d[0] = d[1] = -fabsf(d[0]) - 0.1f; }  // exact x/y ties through a grid corner
-        if (i % 37 == 0) { o[1] = o[2] = -Sy * 0.5f; d[1] = d[2] = fabsf(d[1]) + 0.1f; }
-        // long walks along the long axis (wide grids: the packed counters are re-armed, a walk of MAX_STEPS steps ends the ray)
-        if (i % 5 == 0 && S > 4 * Sy) { d[0] = (i & 8) ? 1.0f : -1.0f; d[1] *= 0.002f; d[2] *= 0.002f; if (i % 10 == 0) o[0] = d[0] > 0 ? -3.0f : S + 3.0f; }
-        if (i % 29 == 0) { d[0] = (i & 1) ? 1.0f : -1.0f; d[1] = d[2] = 0; o[1] = floorf(o[1]); o[2] = floorf(o[2]); }
-        // nearly axis-parallel rays from a face: the longest accumulation of one axis' tMax (the exit threshold's margin)
-        if (i % 41 == 0) { int a = (i / 41) % 3; d[a] = (i & 2) ? 1.0f : -1.0f; d[(a + 1) % 3] *= 1e-4f; d[(a + 2) % 3] *= 1e-5f; o[a] = d[a] > 0 ? 0.0f : ext[a]; }
+        if (!file_rays.empty()) {
+            for (int a = 0; a < 3; ++a) { o[a] = file_rays[(size_t)i * 3 + a]; d[a] = file_rays[((size_t)n + i) * 3 + a]; }
+        } else {
+            for (int a = 0; a < 3; ++a) { o[a] = (rand() / (float)RAND_MAX) * (i % 3 ? ext[a] : 3 * ext[a]) - (i % 3 ? 0 : ext[a]); d[a] = rand() / (float)RAND_MAX * 2 - 1; }
+            if (i % 7 == 0) d[i % 3] = 0;
+            if (i % 11 == 0) { o[0] = floorf(o[0]); o[1] = floorf(o[1]); }
+            // adversarial families: tiny / denormal direction components, starts exactly on the far faces (edge rule),
+            // far-away origins aimed at the grid, axis-aligned rays along cell boundaries
+            if (i % 13 == 0) d[(i / 13) % 3] *= 1e-30f;
+            if (i % 17 == 0) d[(i / 17) % 3] = 1e-42f;
+            if (i % 19 == 0) { o[(i / 19) % 3] = ext[(i / 19) % 3]; d[(i / 19) % 3] = -fabsf(d[(i / 19) % 3]) - 0.01f; }
+            if (i % 23 == 0) { for (int a = 0; a < 3; ++a) { o[a] = o[a] * 1000.0f; d[a] = ext[a] * 0.5f - o[a]; } }
+            if (i % 31 == 0) { o[0] = o[1] = Sy * (1.5f + (i % 7)); d[0] = d[1] = -fabsf(d[0]) - 0.1f; }  // exact x/y ties through a grid corner
+            if (i % 37 == 0) { o[1] = o[2] = -Sy * 0.5f; d[1] = d[2] = fabsf(d[1]) + 0.1f; }
+            // long walks along the long axes (wide grids: the packed counters are re-armed, a walk of MAX_STEPS steps ends the ray):
+            // along whichever axes are more than 4 x the shortest, in turn (a grid long in x only: every such ray along x)
+            if (i % 5 == 0 && n_long_axes) {
+                const int a = long_axes[(i / 5) % n_long_axes];
+                d[a] = (i & 8) ? 1.0f : -1.0f; d[(a + 1) % 3] *= 0.002f; d[(a + 2) % 3] *= 0.002f;
+                if (i % 10 == 0) o[a] = d[a] > 0 ? -3.0f : ext[a] + 3.0f;
+            }
+            if (i % 29 == 0) { d[0] = (i & 1) ? 1.0f : -1.0f; d[1] = d[2] = 0; o[1] = floorf(o[1]); o[2] = floorf(o[2]); }
+            // nearly axis-parallel rays from a face: the longest accumulation of one axis' tMax (the exit threshold's margin)
+            if (i % 41 == 0) { int a = (i / 41) % 3; d[a] = (i & 2) ? 1.0f : -1.0f; d[(a + 1) % 3] *= 1e-4f; d[(a + 2) % 3] *= 1e-5f; o[a] = d[a] > 0 ? 0.0f : ext[a]; }
+        }
         int steps; float nn[3], pp[3] = {0, 0, 0}; int vox[3] = {0, 0, 0}; vxo_ray_stats st{};
         int h = vxo_raytrace(w, 2048, o, d, &steps, nn, pp, vox, &st);
         n_hits += h != 0; n_long += steps > 1024; n_exhausted += steps >= 2048 && !h;
