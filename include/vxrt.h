@@ -718,7 +718,14 @@ typedef struct vxrt_render_flags {
     /* multi-GPU strip sharding: rows are cut into strips of `strip_rows`; strip s belongs to
      * shard s % strip_count.  strip_count <= 1 renders the whole frame. */
     int32_t strip_rows, strip_count, strip_index;
-    int32_t compact;         /* 1: d_fb (and AOVs) hold only this shard's strips, packed in order */
+    int32_t compact;         /* 1: d_fb (and AOVs) hold only this shard's strips, packed in order: frame row y is row
+                                (y / strip_rows / strip_count) * strip_rows + y % strip_rows of vxrt_compact_rows rows;
+                                0: the buffers are full-size and the shard's rows sit at their frame rows.  Either way a
+                                launch writes the shard's pixels only (under checkerboard: those the frame's launch
+                                writes) and every other entry of d_fb, the AOVs and d_accum keeps its contents; a shard
+                                that owns no strip writes nothing, counts nothing and succeeds.  Bad strip arguments with
+                                strip_count > 1 (strip_rows <= 0, strip_index outside 0 .. strip_count - 1) and frames of
+                                more than 65535 rows are refused with VXRT_ERR_INVALID before anything is written */
     int32_t collect_stats;   /* 1: also count probes (the STATS instantiation of the same kernel); rays are always counted */
     int32_t tile_schedule;   /* persistent kernel: 1 (default) = hand out the rows of 8x8 pixel tiles expected-longest
                                 first (ranked per frame on the host by the elevation of the row's centre ray in a

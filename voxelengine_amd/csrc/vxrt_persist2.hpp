@@ -24,57 +24,12 @@
 #pragma once
 
 #include "vxrt_kernels.hpp"
+#include "vxrt_pixel_map.hpp"
 #include "vxrt_wave2.hpp"
 
 namespace vxrt {
 
 enum : uint32_t { PX_NONE = 0u, PX_PRIMARY = 1u, PX_SHADOW = 2u, PX_BOUNCE = 3u, PX_BOUNCE2 = 4u };
-
-struct PixelCoords {
-    uint32_t tx, ty;  // launch coordinates of the reference's thread (crosshair, RNG seed)
-    int x, y;         // frame pixel
-    int out_row;      // row in the destination buffers
-    bool live;
-};
-
-// launch (tx,row) -> pixel (Renderer.cu:183-196 + this build's strip sharding)
-__device__ __forceinline__ PixelCoords pixel_coords(const RenderArgs& A, uint32_t frame_number, uint32_t tx, uint32_t row)
-{
-    PixelCoords c;
-    c.tx = tx;
-    c.ty = row;
-    c.x = (int)tx;
-    const bool sharded = A.strip_count > 1;
-    if (sharded && !A.checkerboard) {
-        // A shard's launch rows are its own frame rows in order: launch row = packed row, the frame row follows from
-        // the strip arithmetic, and ownership holds by construction -- no division by the strip count, and none by the
-        // strip height when it is a power of two (strip_shift >= 0; the default 16 is).
-        const uint32_t sr = (uint32_t)A.strip_rows;
-        const uint32_t q = A.strip_shift >= 0 ? row >> A.strip_shift : row / sr;
-        c.ty = (q * (uint32_t)A.strip_count + (uint32_t)A.strip_index) * sr + (row - q * sr);
-        c.y = (int)c.ty;
-        c.live = row < A.launch_rows && (uint32_t)c.x < A.width && (uint32_t)c.y < A.height;
-        c.out_row = A.compact ? (int)row : c.y;
-        return c;
-    }
-    c.live = row < A.launch_rows;
-    c.y = (int)c.ty;
-    if (A.checkerboard) {
-        c.y *= 2;
-        if ((c.x % 2) == 0)
-            c.y += 1;
-        if (frame_number % 2 == 0)
-            c.y += 1;
-    }
-    c.live = c.live && (uint32_t)c.x < A.width && (uint32_t)c.y < A.height;
-    if (c.live && sharded && ((uint32_t)c.y / (uint32_t)A.strip_rows) % (uint32_t)A.strip_count != (uint32_t)A.strip_index)
-        c.live = false;
-    c.out_row = c.y;
-    if (A.compact && sharded)
-        c.out_row = (int)((((uint32_t)c.y / (uint32_t)A.strip_rows) / (uint32_t)A.strip_count) * (uint32_t)A.strip_rows +
-                          (uint32_t)c.y % (uint32_t)A.strip_rows);
-    return c;
-}
 
 // the per-view inputs of one lane's pixel: kernel arguments for a single-view launch, loaded from the launch's
 // ViewArgs array for a multi-view one
