@@ -76,6 +76,11 @@ uint32_t *vxo_gen_dense(int g, int X, int Y, int Z, int nthreads);
 /* brickmap built brick by brick without the dense intermediate (same result
  * as vxo_build_brickmap(vxo_gen_dense(...))) */
 vxo_world *vxo_gen_brickmap(int g, int X, int Y, int Z, int factor, int nthreads);
+/* chosen cells of that world (tiled cell indices; any order, repeats allowed), each straight from
+ * vxo_gen_solid: per entry f^3/32 image words, 6 bounds floats and one any byte.  0, or -1 for a shape
+ * vxo_gen_brickmap refuses or a cell index outside the world */
+int vxo_gen_bricks(int g, int X, int Y, int Z, int factor, const uint32_t *cells, uint64_t n, uint32_t *pool_out,
+                   float *bounds_out, uint8_t *any_out, int nthreads);
 /* cuda_noise.cuh:44-54 / :66-71 */
 uint32_t vxo_hash32(uint32_t seed);
 float vxo_random_float(uint32_t seed);

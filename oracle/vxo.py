@@ -118,6 +118,8 @@ def lib() -> C.CDLL:
         L.vxo_build_brickmap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.vxo_gen_brickmap.restype = C.POINTER(_World)
         L.vxo_gen_brickmap.argtypes = [C.c_int] * 6
+        L.vxo_gen_bricks.restype = C.c_int
+        L.vxo_gen_bricks.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.vxo_world_wrap.restype = C.POINTER(_World)
         L.vxo_world_wrap.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_uint64, C.c_void_p]
@@ -176,6 +178,24 @@ def ray_aabb(start, d, bmin, bmax):
     p, n = (C.c_float * 3)(), (C.c_float * 3)()
     h = lib().vxo_ray_aabb(_f3(start), _f3(d), _f3(bmin), _f3(bmax), p, n)
     return bool(h), np.array(p[:], np.float32), np.array(n[:], np.float32)
+
+
+def gen_bricks(gen: int, X: int, Y: int, Z: int, factor: int, cells, nthreads: int = 8):
+    """The cells ``cells`` (tiled cell indices; any order, repeats allowed) of World.generate(gen, X, Y, Z, factor),
+    each evaluated straight from the generator: dict(pool=(n, f^3/32) uint32 bit images, zero where empty,
+    bounds=(n, 6) float32, any=(n,) bool)."""
+    cells = np.asarray(cells).reshape(-1)
+    if cells.size and (cells.dtype.kind not in "iu" or int(cells.min()) < 0 or int(cells.max()) > 0xFFFFFFFF):
+        raise ValueError("cells must be integers that fit 32 bits")     # (the cast below would wrap them into the world)
+    cells = np.ascontiguousarray(cells, np.uint32)
+    n = cells.size
+    pool = np.zeros((n, factor ** 3 // 32), np.uint32)
+    bounds = np.zeros((n, 6), np.float32)
+    any_ = np.zeros(n, np.uint8)
+    if lib().vxo_gen_bricks(gen, X, Y, Z, factor, cells.ctypes.data, n, pool.ctypes.data, bounds.ctypes.data,
+                            any_.ctypes.data, nthreads) != 0:
+        raise ValueError("invalid world shape for the tiled-linear layout, or a cell outside the world")
+    return dict(pool=pool, bounds=bounds, any=any_.astype(bool))
 
 
 class World:

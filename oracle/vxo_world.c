@@ -400,3 +400,67 @@ vxo_world *vxo_gen_brickmap(int g, int X, int Y, int Z, int factor, int nthreads
 {
     return build_common(NULL, g, X, Y, Z, factor, nthreads);
 }
+
+/* ---------------------------------------------------------- sampled bricks */
+
+typedef struct cells_job {
+    int g, X, Y, Z, factor;
+    const uint32_t *cells;
+    uint64_t begin, end;
+    uint32_t *pool_out;
+    float *bounds_out;
+    uint8_t *any_out;
+} cells_job;
+
+static void *cells_worker(void *arg)
+{
+    cells_job *j = (cells_job *)arg;
+    const int f = j->factor;
+    const uint64_t bw = (uint64_t)f * f * f / 32u;
+    for (uint64_t i = j->begin; i < j->end; ++i) {
+        uint32_t x, y, z;
+        vxo_position_from_index(j->cells[i], (uint32_t)(j->X / f), (uint32_t)(j->Y / f), &x, &y, &z);
+        j->any_out[i] = (uint8_t)fill_brick(f, x, y, z, NULL, j->X, j->Y, j->Z, j->g, j->pool_out + i * bw,
+                                            j->bounds_out + i * 6);
+    }
+    return NULL;
+}
+
+/* The cells `cells[0..n)` (tiled cell indices, in any order, repeats allowed) of the world that
+ * vxo_gen_brickmap(g, X, Y, Z, factor) builds, straight from vxo_gen_solid: entry i gets its bit image
+ * (f^3/32 words, all zero when empty), its bounds and any_out[i] = 1 iff a voxel is solid. */
+int vxo_gen_bricks(int g, int X, int Y, int Z, int factor, const uint32_t *cells, uint64_t n, uint32_t *pool_out,
+                   float *bounds_out, uint8_t *any_out, int nthreads)
+{
+    if (factor <= 0 || factor % 8 || X <= 0 || Y <= 0 || Z <= 0 || X % factor || Y % factor || Z % factor)
+        return -1;
+    const int cd[3] = {X / factor, Y / factor, Z / factor};
+    if (cd[0] % 8 || cd[1] % 8 || cd[2] % 8)
+        return -1;
+    const uint64_t ncells = (uint64_t)cd[0] * cd[1] * cd[2];
+    for (uint64_t i = 0; i < n; ++i)
+        if (cells[i] >= ncells)
+            return -1;
+    if (n == 0)
+        return 0;
+    if (nthreads < 1)
+        nthreads = 1;
+    if ((uint64_t)nthreads > n)
+        nthreads = (int)n;
+    cells_job *jobs = (cells_job *)calloc((size_t)nthreads, sizeof(cells_job));
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nthreads);
+    for (int i = 0; i < nthreads; ++i) {
+        cells_job *j = &jobs[i];
+        j->g = g; j->X = X; j->Y = Y; j->Z = Z; j->factor = factor;
+        j->cells = cells;
+        j->begin = n * (uint64_t)i / (uint64_t)nthreads;
+        j->end = n * (uint64_t)(i + 1) / (uint64_t)nthreads;
+        j->pool_out = pool_out; j->bounds_out = bounds_out; j->any_out = any_out;
+        pthread_create(&th[i], NULL, cells_worker, j);
+    }
+    for (int i = 0; i < nthreads; ++i)
+        pthread_join(th[i], NULL);
+    free(th);
+    free(jobs);
+    return 0;
+}

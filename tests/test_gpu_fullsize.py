@@ -7,11 +7,14 @@ the oracle cannot render whole frames in test time: size-independent properties 
   * the separately written kernels (variants 1, 2, 5, 6) produce the same frame
   * 8 interleaved strip shards reassemble into the single-GPU frame
   * ray accounting: shadow rays == primary hits; rays <= 3 * pixels
+  * the world itself against the generator: whole cell columns evaluated by the oracle straight from PERLIN_REF, and the
+    consistency of the whole download
 """
 import numpy as np
 import pytest
 
 from tests import helpers
+from tests import ref_worldgen as rw
 
 pytestmark = pytest.mark.gpu
 
@@ -175,3 +178,23 @@ def test_idempotence_variants_and_strip_shards(big):
     torch.cuda.synchronize()
     assert torch.equal(out, a)
     ctx.frame_stats()
+
+
+def test_bench_world_against_the_generator(big, vxo):
+    """The world every reported number is measured on, against the oracle's generator (the other tests of this file wrap
+    what the device built): the full height of 16 cell columns -- the four world corners, one more on the faces x = 8191
+    and z = 8191 each, ten seeded -- cell by cell against vxo.gen_bricks (256 bricks of 32^3 voxels: 3.5 s of oracle time
+    on 16 CPU threads when measured), and over the whole download the slot numbering, coarse bits, brick emptiness and nslots."""
+    vx, ctx, torch, info = big
+    cx, cy, cz = X // F, Y // F, Z // F
+    rng = np.random.default_rng(3)
+    cols = [(0, 0), (cx - 1, 0), (0, cz - 1), (cx - 1, cz - 1), (cx - 1, int(rng.integers(1, cz - 1))), (int(rng.integers(1, cx - 1)), cz - 1)]
+    cols += [(int(a), int(b)) for a, b in rng.integers(0, cx, (10, 2))]
+    assert len(set(cols)) == 16
+    bx, bz = np.repeat([c[0] for c in cols], cy), np.repeat([c[1] for c in cols], cy)
+    cells = rw.tiled_index(bx, np.tile(np.arange(cy), len(cols)), bz, cx, cy)
+    g = vxo.gen_bricks(vxo.GEN_PERLIN_REF, X, Y, Z, F, cells, nthreads=16)
+    d = ctx.download_world()
+    assert tuple(d["cdims"]) == (cx, cy, cz) and d["factor"] == F and tuple(info.cdims) == (cx, cy, cz)
+    rw.assert_cells_match_generator(d, cells, g)      # (asserts that the sample holds surface, solid and empty bricks)
+    rw.assert_consistent(d, int(info.nslots))
