@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY (like the rest of oracle/): imported by tests/ alone.  It exists for two reasons:
   * two separately written restatements (this one, and the C one in vxo_trace.c) agreeing ray for ray is a stronger pin
-    than either alone -- the reference holds no vectors and cannot be built here (parity with it: UNPINNED);
+    than either alone -- the reference holds no vectors (both are pinned to its source by tests/test_reference_pin.py);
   * it records WHICH of the reference's quirks a ray exercised (edge padding, exact ties, region check, previous_cell
     break, ulp nudge, NextCell snap and its branch), so that the known-answer tests can prove that their cases do
     reach the lines they are named for.

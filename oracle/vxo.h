@@ -5,13 +5,14 @@
  * `cpu_baseline` leg and __graft_entry__.smoke() may load it; the shipped
  * library (voxelengine_amd/csrc) never links, imports or calls anything here.
  *
- * PARITY UNPINNED: the reference (JoshuaLim007/VoxelEngine) holds no tests,
- * golden vectors or fixtures for this path, and its sources are CUDA (.cu,
- * need nvcc + libcudart) so they cannot be built in this image without
- * writing stand-ins for the CUDA toolchain.  This file set is therefore a
- * hand restatement of the reference algorithm in plain C, executed with IEEE
- * float semantics (-ffp-contract=off, no fast-math), checked only by
- * hand-derived known-answer tests (tests/test_oracle_*.py).
+ * PARITY: the reference (JoshuaLim007/VoxelEngine) holds no tests, golden
+ * vectors or fixtures for this path.  This file set is a hand restatement of
+ * the reference algorithm in plain C, executed with IEEE float semantics
+ * (-ffp-contract=off, no fast-math).  It is pinned, bit for bit, to the
+ * reference's own sources compiled as host C++ (oracle/ref_build.py,
+ * tests/test_reference_pin.py) and checked by hand-derived known-answer
+ * tests (tests/test_oracle_*.py).  What stays unpinned is CUDA's own code
+ * generation and this build's extensions.
  *
  * Every function cites the reference file:line it restates (paths relative
  * to the reference checkout).
@@ -84,6 +85,8 @@ int vxo_gen_bricks(int g, int X, int Y, int Z, int factor, const uint32_t *cells
 /* cuda_noise.cuh:44-54 / :66-71 */
 uint32_t vxo_hash32(uint32_t seed);
 float vxo_random_float(uint32_t seed);
+/* both over n seeds */
+void vxo_hash_batch(size_t n, const uint32_t *seeds, uint32_t *hashes, float *randoms);
 /* cuda_noise.cuh:565-628 with the a12 parameters (VoxelWorldBuilder.cu:4-8) */
 float vxo_fbm_perlin(float x, float y, float z);
 
@@ -119,6 +122,9 @@ typedef struct vxo_dda_result {     /* DDARayResults, VolumeRaytracer.cuh:266-27
 
 /* DDARayTraversal (VolumeRaytracer.cu:176-352) */
 void vxo_dda(const vxo_dda_params *p, vxo_dda_result *r);
+/* the same over n rays (3 floats each); `p` gives everything but start and dir; vector outputs are n * 3 floats */
+void vxo_dda_batch(const vxo_dda_params *p, size_t n, const float *starts, const float *dirs, uint8_t *hit, uint8_t *out_of_bounds,
+                   int32_t *steps, float *hit_cell, float *point, float *next_cell, float *normal);
 
 typedef struct vxo_ray_stats {      /* bookkeeping for SURVEY 8(d) byte accounting */
     uint64_t coarse_probes;         /* Nc */
@@ -139,6 +145,10 @@ int vxo_raytrace(const vxo_world *w, int max_steps, const float origin[3], const
 void vxo_trace_batch(const vxo_world *w, const float *origins, const float *dirs, size_t n,
                      float *out_pos, float *out_normal, int32_t *out_steps, uint8_t *out_hit,
                      int64_t *out_voxel, vxo_ray_stats *stats_sum, int nthreads);
+/* the same with the step budget of Raytrace's first argument (the bounce rays run with 8, Renderer.cu:141) */
+void vxo_trace_batch_steps(const vxo_world *w, int max_steps, const float *origins, const float *dirs, size_t n,
+                           float *out_pos, float *out_normal, int32_t *out_steps, uint8_t *out_hit,
+                           int64_t *out_voxel, vxo_ray_stats *stats_sum, int nthreads);
 
 /* ---- renderer */
 typedef struct vxo_env {            /* Graphics::Environment, Renderer.cuh:33-37 */

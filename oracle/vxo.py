@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE ONLY -- see oracle/vxo.h.  Importers: tests/, bench.py's
 cpu_baseline leg, __graft_entry__.smoke().  Never imported by voxelengine_amd.
-Parity status: UNPINNED (no reference fixtures exist; reference not buildable here).
+Parity status: pinned to the reference's source, built as host C++ (oracle/vxref.py, tests/test_reference_pin.py;
+DESIGN.md section 2 says what stays unpinned).
 """
 from __future__ import annotations
 
@@ -108,6 +109,7 @@ def lib() -> C.CDLL:
         L.vxo_hash32.argtypes = [C.c_uint32]
         L.vxo_random_float.restype = C.c_float
         L.vxo_random_float.argtypes = [C.c_uint32]
+        L.vxo_hash_batch.argtypes = [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vxo_fbm_perlin.restype = C.c_float
         L.vxo_fbm_perlin.argtypes = [C.c_float] * 3
         L.vxo_gen_solid.restype = C.c_int
@@ -127,12 +129,15 @@ def lib() -> C.CDLL:
         L.vxo_ray_aabb.restype = C.c_int
         L.vxo_ray_aabb.argtypes = [f32p] * 6
         L.vxo_dda.argtypes = [C.POINTER(DDAParams), C.POINTER(DDAResult)]
+        L.vxo_dda_batch.argtypes = [C.POINTER(DDAParams), C.c_size_t] + [C.c_void_p] * 9
         L.vxo_raytrace.restype = C.c_int
         L.vxo_raytrace.argtypes = [C.POINTER(_World), C.c_int, f32p, f32p, C.POINTER(C.c_int), f32p, f32p,
                                    C.POINTER(C.c_int), C.POINTER(RayStats)]
         L.vxo_trace_batch.argtypes = [C.POINTER(_World), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RayStats),
                                       C.c_int]
+        L.vxo_trace_batch_steps.argtypes = [C.POINTER(_World), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RayStats), C.c_int]
         L.vxo_get_directions.argtypes = [f32p] * 4
         L.vxo_render.argtypes = [C.POINTER(_World), C.POINTER(RenderParams), C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.POINTER(FrameStats), C.c_int]
@@ -268,7 +273,7 @@ class World:
                     pos=np.array(pos[:], np.float32), voxel=tuple(vox[:]) if h else None,
                     stats=(st.coarse_probes, st.brick_entries, st.fine_probes))
 
-    def trace_batch(self, origins, dirs, nthreads: int = 8):
+    def trace_batch(self, origins, dirs, nthreads: int = 8, max_steps: int = MAX_STEPS):
         origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         n = origins.shape[0]
@@ -278,9 +283,9 @@ class World:
         hit = np.empty(n, np.uint8)
         vox = np.empty(n, np.int64)
         st = RayStats()
-        lib().vxo_trace_batch(self._p, origins.ctypes.data, dirs.ctypes.data, n, pos.ctypes.data,
-                              nrm.ctypes.data, steps.ctypes.data, hit.ctypes.data, vox.ctypes.data,
-                              C.byref(st), nthreads)
+        lib().vxo_trace_batch_steps(self._p, max_steps, origins.ctypes.data, dirs.ctypes.data, n, pos.ctypes.data,
+                                    nrm.ctypes.data, steps.ctypes.data, hit.ctypes.data, vox.ctypes.data,
+                                    C.byref(st), nthreads)
         return dict(pos=pos, normal=nrm, steps=steps, hit=hit, voxel=vox, stats=st)
 
     def render(self, params: RenderParams, fb: np.ndarray | None = None, want_color=False, want_hit=False,

@@ -1,5 +1,5 @@
 /*
- * vxo_render.c -- ORACLE (test infrastructure; parity unpinned, see vxo.h).
+ * vxo_render.c -- ORACLE (test infrastructure; parity: see vxo.h).
  * Camera, per-pixel primary/secondary shading and the BGRA8 store, restated
  * from the reference's VoxelRT/Renderer.cu, plus the batch entry point
  * (VoxelRT/VolumeRaytracer.cu:95-117,574-618).  Threads split the launch grid's
@@ -443,6 +443,7 @@ typedef struct batch_ctx {
     uint8_t *out_hit;
     int64_t *out_voxel;
     vxo_ray_stats stats;
+    int max_steps;
 } batch_ctx;
 
 static void *batch_worker(void *arg)
@@ -452,7 +453,7 @@ static void *batch_worker(void *arg)
     for (size_t i = b->begin; i < b->end; ++i) {
         int steps = 0, vox[3] = {0, 0, 0};
         float n[3], pos[3] = {0, 0, 0};
-        int h = vxo_raytrace(b->w, VXO_MAX_STEPS, b->origins + 3 * i, b->dirs + 3 * i, &steps, n, pos, vox,
+        int h = vxo_raytrace(b->w, b->max_steps, b->origins + 3 * i, b->dirs + 3 * i, &steps, n, pos, vox,
                              &b->stats);
         for (int a = 0; a < 3; ++a) {
             b->out_pos[3 * i + a] = h ? pos[a] : (float)INFINITY; /* dispatch, VolumeRaytracer.cu:105-113 */
@@ -471,6 +472,14 @@ void vxo_trace_batch(const vxo_world *w, const float *origins, const float *dirs
                      float *out_normal, int32_t *out_steps, uint8_t *out_hit, int64_t *out_voxel,
                      vxo_ray_stats *stats_sum, int nthreads)
 {
+    vxo_trace_batch_steps(w, VXO_MAX_STEPS, origins, dirs, n, out_pos, out_normal, out_steps, out_hit, out_voxel, stats_sum,
+                          nthreads);
+}
+
+void vxo_trace_batch_steps(const vxo_world *w, int max_steps, const float *origins, const float *dirs, size_t n, float *out_pos,
+                           float *out_normal, int32_t *out_steps, uint8_t *out_hit, int64_t *out_voxel,
+                           vxo_ray_stats *stats_sum, int nthreads)
+{
     if (nthreads < 1)
         nthreads = 1;
     if ((size_t)nthreads > n)
@@ -479,6 +488,7 @@ void vxo_trace_batch(const vxo_world *w, const float *origins, const float *dirs
     pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nthreads);
     for (int i = 0; i < nthreads; ++i) {
         ctx[i].w = w;
+        ctx[i].max_steps = max_steps;
         ctx[i].origins = origins;
         ctx[i].dirs = dirs;
         ctx[i].begin = n * (size_t)i / (size_t)nthreads;

@@ -1,5 +1,5 @@
 /*
- * vxo_trace.c -- ORACLE (test infrastructure; parity unpinned, see vxo.h).
+ * vxo_trace.c -- ORACLE (test infrastructure; parity: see vxo.h).
  * Bit layout, slab test, single-level DDA and the two-level brickmap trace,
  * restated from the reference's VoxelRT/VolumeRaytracer.cu / .cuh.
  * Build with -ffp-contract=off and without fast-math: results are meant to be
@@ -245,6 +245,26 @@ void vxo_dda(const vxo_dda_params *p, vxo_dda_result *r)
         }
         r->steps += 1;
         memcpy(r->point, crossing, sizeof(crossing));
+    }
+}
+
+/* vxo_dda over n rays: `p` gives everything but start and dir */
+void vxo_dda_batch(const vxo_dda_params *p, size_t n, const float *starts, const float *dirs, uint8_t *hit, uint8_t *out_of_bounds,
+                   int32_t *steps, float *hit_cell, float *point, float *next_cell, float *normal)
+{
+    vxo_dda_params q = *p;
+    vxo_dda_result r;
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(q.start, starts + 3 * i, sizeof(q.start));
+        memcpy(q.dir, dirs + 3 * i, sizeof(q.dir));
+        vxo_dda(&q, &r);
+        hit[i] = (uint8_t)r.hit;
+        out_of_bounds[i] = (uint8_t)r.out_of_bounds;
+        steps[i] = r.steps;
+        memcpy(hit_cell + 3 * i, r.hit_cell, sizeof(r.hit_cell));
+        memcpy(point + 3 * i, r.point, sizeof(r.point));
+        memcpy(next_cell + 3 * i, r.next_cell, sizeof(r.next_cell));
+        memcpy(normal + 3 * i, r.normal, sizeof(r.normal));
     }
 }
 

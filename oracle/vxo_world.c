@@ -1,5 +1,5 @@
 /*
- * vxo_world.c -- ORACLE (test infrastructure; parity unpinned, see vxo.h).
+ * vxo_world.c -- ORACLE (test infrastructure; parity: see vxo.h).
  * Brickmap construction (VoxelRT/VolumeRaytracer.cuh:379-516) and the
  * procedural worlds used by tests and bench (VoxelRT/VoxelWorldBuilder.cu:4-35,
  * VoxelRT/cuda_noise.cuh:44-71,162-202,580-628).
@@ -60,6 +60,14 @@ uint32_t vxo_hash32(uint32_t seed)
 float vxo_random_float(uint32_t seed)
 {
     return (float)vxo_hash32(seed) / 4294967296.0f; /* (float)0xffffffff rounds to 2^32 */
+}
+
+void vxo_hash_batch(size_t n, const uint32_t *seeds, uint32_t *hashes, float *randoms)
+{
+    for (size_t i = 0; i < n; ++i) {
+        hashes[i] = vxo_hash32(seeds[i]);
+        randoms[i] = vxo_random_float(seeds[i]);
+    }
 }
 
 /* float -> unsigned conversion as AMD/NVIDIA GPUs do it (saturating, NaN -> 0).

@@ -2,8 +2,8 @@
 oracle (oracle/, a restatement of the reference algorithm).
 
 What they pin: the oracle's behaviour (and with it the HIP path's) against drift between rounds -- any change to
-either must reproduce these vectors bit for bit.  What they do NOT pin: parity with the reference itself (the
-reference's CUDA sources cannot be built here and hold no fixtures of their own).
+either must reproduce these vectors bit for bit.  What they do NOT pin: parity with the reference itself
+(that is what tests/golden/make_ref_golden.py's fixtures, recorded from the reference's own code, are for).
 
     python tests/golden/make_golden.py        # rewrites the fixtures (only when a definition deliberately changes)
 

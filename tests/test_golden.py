@@ -1,7 +1,7 @@
 """Committed golden vectors (tests/golden/*.npz, generator: tests/golden/make_golden.py).
 
 They were produced by this repository's CPU oracle and pin the oracle AND the HIP path against drift between rounds:
-both must reproduce them bit for bit.  They do not pin parity with the reference itself."""
+both must reproduce them bit for bit.  They do not pin parity with the reference itself: tests/test_ref_golden.py does."""
 import importlib.util
 import os
 

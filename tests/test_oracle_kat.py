@@ -1,9 +1,9 @@
 """Hand-derived known-answer tests for the CPU oracle.
 
-The reference holds no tests or golden vectors for this path and
-cannot be built here, so the oracle's parity with it is UNPINNED; these cases were
-worked out by hand from the reference source (file:line in each docstring) and pin
-the restatement against transcription slips.
+The reference holds no tests or golden vectors for this path; these
+cases were worked out by hand from the reference source (file:line in each docstring) and
+pin the restatement against transcription slips.  (tests/test_reference_pin.py compares the
+oracle with the reference's own code, compiled as host C++, on far more inputs.)
 """
 import numpy as np
 

@@ -7,8 +7,8 @@ the previous_cell break (:402-407) and the NextCell snap with its <,< / else ord
 Every case in tests/quirk_cases.py was stepped through the reference's text by hand; the derivations are the docstrings
 below.  Each is checked against BOTH restatements (the C oracle and the event-tracing Python one, oracle/ref_py.py), and the
 events prove that the ray reaches the lines the case is named for.  The same cases run on the GPU in
-tests/test_gpu_parity.py::test_quirk_cases_on_gpu.  The reference itself holds no vectors and cannot be built here: parity
-with it stays "partial" by construction.
+tests/test_gpu_parity.py::test_quirk_cases_on_gpu.  The reference itself holds no vectors; the same cases also run
+through its own code, compiled as host C++ (tests/test_reference_pin.py).
 """
 import ctypes as C
 
