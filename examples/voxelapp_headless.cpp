@@ -42,6 +42,10 @@
 // Kind 9 downsamples the box of origin a and cell dims b (VoxelRaytracer3D::DownsampleRegion, with counts) at shift
 // `value & 7` and threshold `value >> 3` and prints one line "lod frame N shift .. threshold .. set .. empty .. full .. mixed ..
 // max .. solid ..", then one line "lod hash frame N bits .. counts .." with the 64-bit FNV-1a hash of each array's bytes.
+// Kind 10 computes the light field of the box of origin a and dims b (VoxelRaytracer3D::LightField) in the channels
+// `value & 3` (1 = sky, 2 = block), with one emitter of level 15 in the cell that holds frame N's camera position when the
+// block channel is set, and prints one line "light frame N solid .. exposed .. sky_sum .. block_sum .. used ..", then one
+// line "light hash frame N levels .." with the 64-bit FNV-1a hash of the level bytes.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -301,6 +305,25 @@ int main(int argc, char** argv)
                 };
                 std::printf("lod hash frame %d bits %016llx counts %016llx\n", from, fnv(bits.data(), bits.size() * 4),
                             fnv(counts.data(), counts.size() * 2));
+            } else if (e.op.kind == 10) {  // light field, one emitter in the camera's cell
+                flush_ops();
+                const float3 cp = path.empty() ? cam_pos : path[(size_t)from].pos;
+                const uint32_t channels = (uint32_t)e.op.value & 3u;
+                std::vector<int32_t> emitters;
+                if (channels & VXRT_LIGHT_BLOCK)
+                    emitters = {(int32_t)std::floor(cp.x), (int32_t)std::floor(cp.y), (int32_t)std::floor(cp.z), VXRT_LIGHT_MAX};
+                std::vector<uint8_t> levels;
+                vxrt_light_summary sum{};
+                if (raytracer->LightField(e.op.a, e.op.b, emitters, channels, levels, sum) != VXRT_OK) {
+                    std::cerr << "light before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("light frame %d solid %u exposed %u sky_sum %llu block_sum %llu used %u\n", from, sum.solid, sum.exposed,
+                            (unsigned long long)sum.sum_sky, (unsigned long long)sum.sum_block, sum.emitters_used);
+                uint64_t h = 0xcbf29ce484222325ull;
+                for (size_t i = 0; i < levels.size(); ++i)
+                    h = (h ^ levels[i]) * 0x100000001b3ull;
+                std::printf("light hash frame %d levels %016llx\n", from, (unsigned long long)h);
             } else if (e.op.kind == 7) {  // stamp the built-in mesh
                 flush_ops();
                 const int32_t r = 256 * e.op.b[0], c = 128;  // mesh frame: the origin is the corner of voxel a

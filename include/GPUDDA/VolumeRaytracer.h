@@ -33,6 +33,7 @@ struct vxrt_voxelize_summary;
 struct vxrt_quad;
 struct vxrt_surface_summary;
 struct vxrt_lod_summary;
+struct vxrt_light_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -204,6 +205,13 @@ public:
     // queued edits first.  Returns the vxrt_status.
     int DownsampleRegion(const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
                          std::vector<uint32_t>& bits, vxrt_lod_summary& summary, std::vector<uint16_t>* counts = nullptr);
+
+    // voxel light fields (extension, include/vxrt.h, vxrt_light_field_host): the sky and block light levels of every voxel of
+    // the box origin .. origin + dims - 1, one byte (sky << 4) | block per voxel in region order, and the summary.
+    // `emitters`: 4 int32 (x, y, z, level) per entry; `channels` a subset of VXRT_LIGHT_SKY | VXRT_LIGHT_BLOCK.  Flushes
+    // queued edits first.  Returns the vxrt_status.
+    int LightField(const int32_t origin[3], const int32_t dims[3], const std::vector<int32_t>& emitters, uint32_t channels,
+                   std::vector<uint8_t>& levels, vxrt_light_summary& summary);
 
 private:
     void Flush();

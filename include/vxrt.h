@@ -670,6 +670,80 @@ int vxrt_downsample_region(vxrt_ctx *ctx, const int32_t origin[3], const int32_t
 int vxrt_downsample_region_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], uint32_t shift,
                                 uint32_t threshold, uint32_t *bits, uint16_t *counts_or_null, vxrt_lod_summary *summary);
 
+/* ---- voxel light fields -- an EXTENSION (the reference's to-do item "Proper indirect lighting" in its cheap, exact,
+ * edit-friendly form: flood-fill light, recomputed on the device for the box an edit touched).  A call looks at one box
+ * B = [origin, origin + dims) of world voxels.  +y is up, as for vxrt_nav_field.  Voxels outside the world are empty, as for
+ * vxrt_read_region.
+ *   Levels and channels.  A level is 0 .. VXRT_LIGHT_MAX = 15.  `channels` is a non-empty subset of VXRT_LIGHT_SKY = 1 and
+ *     VXRT_LIGHT_BLOCK = 2.
+ *   Transparent and solid.  An empty voxel carries light.  A solid voxel has level 0 in both channels and passes none on.
+ *   Sky sources.  Voxel v is EXPOSED when v is empty and every voxel (v.x, y', v.z) with y' > v.y is empty -- over the WHOLE
+ *     world, not only B or its halo: everything at or above the world's top is exposed, and so is everything beside the
+ *     world in x or z.  An exposed voxel is a sky source of level 15.
+ *   Block sources.  d_emitters is n_emitters x int32[4] (x, y, z, level), at most VXRT_LIGHT_MAX_EMITTERS = 65536 entries.
+ *     Every entry falls in exactly one class: INVALID (level outside 1 .. 15); FAR (valid level, the voxel outside the
+ *     halo box below: it cannot reach B, and its voxel is not looked at); SOLID (valid level, in the halo box, a solid voxel:
+ *     ignored); USED (valid level, in the halo box, an empty voxel: a block source of that level).  Several used entries on
+ *     one voxel give it the largest of their levels.
+ *   Value.  Per channel, with g(s, v) the length of the shortest 6-connected path from s to v through empty voxels
+ *     (infinite when there is none): level(v) = max(0, max over sources s of level(s) - g(s, v)) for an empty v, and 0 for
+ *     a solid v.  Equivalently the least fixed point of level(v) = max(source(v), max over the six neighbours n of
+ *     level(n) - 1) on the empty voxels.  The value is a function of the world, B and the emitters alone: it does not depend
+ *     on the algorithm or the scheduling.
+ *   Halo.  H = VXRT_LIGHT_MAX - 1 = 14.  A level >= 1 at v needs a source s with level(s) - g(s, v) >= 1, so g(s, v) <= 14:
+ *     s is at most 14 steps away, and every voxel of such a path is within 14 steps of v, so the path never leaves the box
+ *     of +-14 around v.  For v in B that box lies in the halo box [origin - 14, origin + dims + 14): the call reads the
+ *     halo box and, for the sky channel (whether a halo voxel is exposed depends on its whole column), the columns above
+ *     it up to the world's top.  The levels computed for halo voxels outside B may be too low; they are not output.
+ *   Limits.  1 <= dims[k]; dims[0] * dims[1] * dims[2] <= 2^28; the halo box (dims[k] + 28 per axis) within
+ *     vxrt_read_region's 2^36 voxels; origin[k] - 14 >= -2^31 and origin[k] + dims[k] + 14 <= 2^31 - 1;
+ *     n_emitters <= VXRT_LIGHT_MAX_EMITTERS.
+ * Outputs:
+ *   d_levels: one byte per voxel of B in region order (x fastest, then y, then z, no padding, as d_dist2):
+ *     (sky << 4) | block.  The nibble of a channel that is not requested is 0.
+ *   d_summary: solid (solid voxels of B); exposed (exposed voxels of B; 0 without the sky channel); hist_sky[16] and
+ *     hist_block[16] (the EMPTY voxels of B by level; a channel that is not requested has all of them in entry 0, so each
+ *     histogram always sums to the empty voxels of B); sum_sky and sum_block (the sum of the channel's levels over B: a
+ *     checksum for callers that do not want the whole field back); emitters_used, emitters_solid, emitters_far,
+ *     emitters_invalid (entries per class; they sum to n_emitters).  Without the block channel d_emitters is not read and
+ *     all four counts are 0, whatever n_emitters is (only the check n_emitters <= VXRT_LIGHT_MAX_EMITTERS is made).
+ * Workspace.  d_work holds vxrt_light_workspace_bytes(dims, channels) bytes, 0 outside the limits on dims and channels.  It
+ *   depends on dims and channels only, never on the world.  With r(n) = n rounded up to a multiple of 256,
+ *   h[k] = dims[k] + 28, wh = ceil(h[0] / 32), P = 4 * wh * h[1] * h[2] (one bit plane of the halo box), n = the number of
+ *   channels requested, s = 1 with the sky channel and b = 1 with the block channel (else 0):
+ *     bytes = r(P) * (1 + 6 * n) + s * r(4 * wh * h[2]) + b * 8 * VXRT_LIGHT_MAX_EMITTERS
+ *   (the halo's empty bits; per channel two planes for the level sets in turn and four for the bit-sliced level; the
+ *   "blocked above" bit per (x, z) of the halo, reduced from the columns above it in slabs of 8 rows straight from the
+ *   tables -- the columns are never materialised; one 8-byte record per emitter).  The caller owns it; the library
+ *   allocates nothing per call.
+ * Call rules (as vxrt_distance_field): asynchronous on `stream`; the launches follow from the arguments and the world's
+ *   height alone (14 rounds whatever the world holds), and the call never synchronises with the host.  Checked in this
+ *   order: a NULL ctx, origin, dims, d_work, d_levels or d_summary; the channels; n_emitters above the limit, or d_emitters
+ *   NULL with n_emitters > 0 and the block channel set; the dims and the halo box; the origin -- each VXRT_ERR_INVALID;
+ *   then no world: VXRT_ERR_NO_WORLD; then a streamed world: VXRT_ERR_INVALID (a cache is not queried).  A refused call
+ *   writes nothing.  The call never loads outside the tables.  Two calls are bit-identical.
+ * vxrt_light_field_host takes host buffers (emitters in; levels and summary out, the same sizes), allocates its own
+ *   workspace and is synchronous.
+ * The cost is one region read of the halo box, the columns above it for the sky channel, and 14 rounds of word
+ *   operations over six bit planes per channel; no voxel is visited on its own before the bytes are written.  After an
+ *   edit a caller relights the edit's box grown by 14 on every axis: no level outside it can have changed. */
+#define VXRT_LIGHT_MAX 15
+#define VXRT_LIGHT_SKY 1
+#define VXRT_LIGHT_BLOCK 2
+#define VXRT_LIGHT_MAX_EMITTERS 65536u
+typedef struct vxrt_light_summary {
+    uint32_t solid, exposed;
+    uint32_t hist_sky[16], hist_block[16];
+    uint64_t sum_sky, sum_block;
+    uint32_t emitters_used, emitters_solid, emitters_far, emitters_invalid;
+} vxrt_light_summary;
+uint64_t vxrt_light_workspace_bytes(const int32_t dims[3], uint32_t channels); /* 0 outside the contract */
+int vxrt_light_field(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const int32_t *d_emitters,
+                     uint32_t n_emitters, uint32_t channels, void *d_work, uint8_t *d_levels, vxrt_light_summary *d_summary,
+                     void *stream);
+int vxrt_light_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const int32_t *emitters,
+                          uint32_t n_emitters, uint32_t channels, uint8_t *levels, vxrt_light_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],

@@ -1,0 +1,183 @@
+// Host harness of voxel light fields (voxelengine_amd/csrc/vxrt_light.hpp: the blocked-above mask, the column pass, the
+// emitter records and their scatter, the dilation rounds with the bit-sliced level, the byte expansion and the tally of
+// the kernels of vxrt_light.hip), compiled for the CPU through tests/tools/hoststub and run one lane at a time, launch by
+// launch, in the order vxrt_light.hip launches them.  The world is the oracle's brickmap (oracle/vxo_world.c) of a dense
+// grid, laid out as the library holds it in HBM; the halo's bits come from region_row_word, clipped as k_read_region
+// clips.  Every index the code forms into the workspace, the emitters or the output is checked against that array's size.
+// Run by tests/test_light_host.py, which compares the outputs with tests/ref_light.py.
+//
+//   light_check in.bin out.bin
+//   in:  i32 op, f, X, Y, Z, origin[3], dims[3], channels, n_emitters; X * Y * Z / 32 u32 dense words (vxo_sample_index64);
+//        n_emitters x i32[4]
+//   op 0 (field): out: 42 u32 (vxrt_light_summary), nvox u8 levels
+//   op 1 (layout only; no world is built): out: u32 accepted by light_layout with the origin, u32 accepted without it,
+//        u64 total_bytes
+//   stdout: indices checked, "ALL OK" or "FAILED"
+#include <cstdint>
+#include <cstdio>
+
+static void check_index(int array, uint64_t index);
+#define VXRT_LIGHT_CHECK(array, index) check_index(array, (uint64_t)(index))
+
+#include "../../voxelengine_amd/csrc/vxrt_light.hpp"
+#include "hbm_world.h"
+#include <cstdlib>
+#include <vector>
+using namespace vxrt;
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) {
+        printf("usage: light_check in.bin out.bin\n");
+        return 2;
+    }
+    FILE* in = fopen(argv[1], "rb");
+    int32_t hd[13];
+    if (!in || fread(hd, 4, 13, in) != 13)
+        return 2;
+    const int op = hd[0], f = hd[1], X = hd[2], Y = hd[3], Z = hd[4];
+    const int32_t o[3] = {hd[5], hd[6], hd[7]}, d[3] = {hd[8], hd[9], hd[10]};
+    const uint32_t channels = (uint32_t)hd[11], n_emitters = (uint32_t)hd[12];
+    LightLayout L{};
+    if (op == 1) {
+        fclose(in);
+        const uint32_t with = light_layout(o, d, channels, L) ? 1u : 0u, without = light_layout(nullptr, d, channels, L) ? 1u : 0u;
+        const uint64_t bytes = without ? L.total_bytes : 0u;
+        FILE* out = fopen(argv[2], "wb");
+        if (!out)
+            return 2;
+        fwrite(&with, 4, 1, out);
+        fwrite(&without, 4, 1, out);
+        fwrite(&bytes, 8, 1, out);
+        fclose(out);
+        printf("layout %u %u\nALL OK\n", with, without);
+        return 0;
+    }
+    std::vector<uint32_t> dense((size_t)X * Y * Z / 32);
+    std::vector<int32_t> emitters((size_t)n_emitters * 4u + 1u, 0);
+    if (fread(dense.data(), 4, dense.size(), in) != dense.size() || n_emitters > kLightMaxEmitters ||
+        fread(emitters.data(), 16, n_emitters, in) != n_emitters)
+        return 2;
+    fclose(in);
+
+    // the oracle's brickmap in HBM order
+    vxo_world* w = vxo_build_brickmap(dense.data(), X, Y, Z, f);
+    const HbmWorld h = to_hbm(w);
+    vxo_world_free(w);
+    const CollideWorld W = h.world();
+
+    if (!light_layout(o, d, channels, L)) {
+        printf("outside the contract\n");
+        return 2;
+    }
+    const size_t guard = 64;
+    std::vector<uint8_t> work(L.total_bytes + guard, 0xA5);
+    std::vector<uint8_t> levels((size_t)L.nvox + guard, 0x5A);
+    uint32_t summary[kLightSumWords + 1] = {};
+    summary[kLightSumWords] = 0xC0FFEEu;
+    g_size[kLightPlane] = L.np;
+    g_size[kLightAbove] = L.nabove;
+    g_size[kLightRec] = n_emitters;
+    g_size[kLightEmit] = (uint64_t)n_emitters * 4u;
+    g_size[kLightOut] = L.nvox;
+    // the sections in order, each on a 256-byte boundary and as large as what it holds
+    const uint64_t pb = 4u * L.np;
+    CHECK(L.empty == 0 && L.above >= pb && L.above % 256u == 0 && L.rec % 256u == 0 && L.total_bytes >= L.rec);
+    CHECK(!(channels & kLightSky) || L.set[0][0] - L.above >= 4u * L.nabove);
+    CHECK(!(channels & kLightBlock) || L.total_bytes - L.rec >= 8u * (uint64_t)kLightMaxEmitters);
+    for (uint32_t c = 0; c < L.nch; ++c) {
+        CHECK(L.set[c][0] % 256u == 0 && L.set[c][1] - L.set[c][0] >= pb && L.level[c] - L.set[c][1] >= pb);
+        CHECK((c + 1u < L.nch ? L.set[c + 1u][0] : L.rec) - L.level[c] >= 4u * pb);
+    }
+    LightArgs A{};
+    light_args(A, L, o, d, channels, work.data(), emitters.data(), n_emitters, levels.data(), summary);
+    CHECK(A.wide == 1u || ((uintptr_t)levels.data() & 3u) != 0u);
+
+    // k_read_region of the halo: clipped to the world before any load
+    const int32_t H = (int32_t)kLightHalo;
+    const int32_t ho[3] = {o[0] - H, o[1] - H, o[2] - H}, hdim[3] = {d[0] + 2 * H, d[1] + 2 * H, d[2] + 2 * H};
+    const std::vector<uint32_t> halo = read_host(W, ho, hdim);
+    CHECK(halo.size() == L.np);
+    for (uint64_t i = 0; i < halo.size(); ++i)
+        A.empty[i] = halo[i];
+
+    // the memsets, k_light_above, k_light_columns
+    if (A.sky < 2u) {
+        for (uint64_t i = 0; i < L.nabove; ++i)
+            A.above[i] = 0u;
+        const uint64_t n = L.nabove * light_above_slabs(A, W);
+        for (uint64_t i = 0; i < n; ++i)
+            light_above_lane(A, W, light_above_first(A), i);
+    }
+    for (uint64_t i = 0; i < L.nabove; ++i)
+        summary[kLightSumExposed] += light_column_lane(A, i);
+
+    // k_light_classify, k_light_scatter of level 15
+    if (A.block < 2u) {
+        for (uint64_t i = 0; i < L.np; ++i)
+            A.set[A.block][0][i] = 0u;
+        for (uint32_t e = 0; e < A.n_emitters; ++e)
+            summary[kLightSumUsed + light_classify_lane(A, e)] += 1u;
+        for (uint32_t e = 0; e < A.n_emitters; ++e)
+            light_scatter_lane(A, A.set[A.block][0], kLightMax, e);
+    }
+
+    // 14 x (k_light_round, k_light_scatter)
+    for (uint32_t turn = 0; turn < kLightMax - 1u; ++turn) {
+        for (uint64_t i = 0; i < L.np * L.nch; ++i)
+            light_round_lane(A, turn, i);
+        for (uint32_t e = 0; e < A.n_emitters; ++e)
+            light_scatter_lane(A, A.set[A.block][~turn & 1u], kLightMax - 1u - turn, e);
+    }
+
+    // k_light_expand with dword stores and, into a second buffer off the dword grid, with byte stores; k_light_tally
+    for (uint64_t j = 0; j < ((uint64_t)L.nvox + 3u) / 4u; ++j)
+        light_expand_lane(A, j);
+    std::vector<uint8_t> bytes((size_t)L.nvox + guard, 0x5A);
+    LightArgs B = A;
+    B.out = bytes.data();
+    B.wide = 0u;
+    for (uint64_t j = 0; j < ((uint64_t)L.nvox + 3u) / 4u; ++j)
+        light_expand_lane(B, j);
+    for (uint64_t i = 0; i < (uint64_t)L.nvox + guard; ++i)
+        CHECK(bytes[i] == levels[i]);
+    const uint64_t nt = (uint64_t)light_box_words(A) * (uint32_t)d[1] * (uint32_t)d[2];
+    uint64_t sums[2] = {0u, 0u};
+    for (uint32_t ch = 0; ch < 2u; ++ch) {
+        LightTally t{};
+        for (uint64_t i = 0; i < nt; ++i)
+            light_tally_lane(A, ch, i, t);
+        if (ch == 0u)
+            summary[kLightSumSolid] = t.solid;
+        for (uint32_t k = 0; k < 16u; ++k) {
+            summary[kLightSumHist + 16u * ch + k] = t.hist[k];
+            sums[ch] += (uint64_t)t.hist[k] * k;
+        }
+    }
+    for (int c = 0; c < 2; ++c) {
+        summary[kLightSumSum + 2 * c] = (uint32_t)sums[c];
+        summary[kLightSumSum + 2 * c + 1] = (uint32_t)(sums[c] >> 32);
+    }
+
+    // nothing written behind the output, the workspace or the summary
+    for (size_t i = 0; i < guard; ++i) {
+        CHECK(levels[(size_t)L.nvox + i] == 0x5A);
+        CHECK(work[L.total_bytes + i] == 0xA5);
+    }
+    CHECK(summary[kLightSumWords] == 0xC0FFEEu);
+    uint64_t empties[2] = {0u, 0u};
+    for (uint32_t k = 0; k < 32u; ++k)
+        empties[k >> 4] += summary[kLightSumHist + k];
+    CHECK(empties[0] == empties[1] && empties[0] + summary[kLightSumSolid] == L.nvox);
+    CHECK(summary[kLightSumUsed] + summary[kLightSumUsed + 1] + summary[kLightSumUsed + 2] + summary[kLightSumUsed + 3] == A.n_emitters);
+
+    FILE* out = fopen(argv[2], "wb");
+    if (!out)
+        return 2;
+    fwrite(summary, 4, kLightSumWords, out);
+    fwrite(levels.data(), 1, L.nvox, out);
+    fclose(out);
+    printf("%u solid, %u exposed, %llu indices checked, failures %d\n%s\n", summary[kLightSumSolid], summary[kLightSumExposed],
+           (unsigned long long)checked, fails, fails ? "FAILED" : "ALL OK");
+    return fails ? 1 : 0;
+}

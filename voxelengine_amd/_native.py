@@ -31,6 +31,7 @@ EXPORTS = [
     "vxrt_voxelize_workspace_bytes", "vxrt_voxelize_mesh", "vxrt_voxelize_mesh_host",
     "vxrt_surface_workspace_bytes", "vxrt_extract_surface", "vxrt_extract_surface_host",
     "vxrt_lod_workspace_bytes", "vxrt_downsample_region", "vxrt_downsample_region_host",
+    "vxrt_light_workspace_bytes", "vxrt_light_field", "vxrt_light_field_host",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
@@ -45,6 +46,7 @@ DIST_TO_SOLID, DIST_TO_EMPTY, DIST_FAR, DIST_MAX_RADIUS = 0, 1, 0xFFFF, 255
 VOX_SURFACE, VOX_SOLID, VOX_FRAC_BITS, VOX_MAX_DIM, VOX_MAX_COORD, VOX_MAX_TRIANGLES = 1, 2, 8, 1024, 1 << 18, 1 << 24
 SURF_CAP, SURF_OPEN, SURF_MAX_DIM = 0, 1, 1024
 LOD_MAX_SHIFT = 5
+LIGHT_SKY, LIGHT_BLOCK, LIGHT_MAX, LIGHT_MAX_EMITTERS = 1, 2, 15, 65536
 
 
 class WorldDesc(C.Structure):
@@ -241,6 +243,12 @@ def load() -> C.CDLL:
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_downsample_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_light_workspace_bytes.restype = C.c_uint64
+    L.vxrt_light_workspace_bytes.argtypes = [C.POINTER(C.c_int32), C.c_uint32]
+    L.vxrt_light_field.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_light_field_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32,
+                                        C.c_uint32, C.c_void_p, C.c_void_p]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

@@ -309,6 +309,17 @@ int VoxelRaytracer3D::DistanceField(const int32_t origin[3], const int32_t dims[
     return vxrt_distance_field_host(ctx, origin, dims, radius, mode, dist2.data(), &summary);
 }
 
+int VoxelRaytracer3D::LightField(const int32_t origin[3], const int32_t dims[3], const std::vector<int32_t>& emitters,
+                                 uint32_t channels, std::vector<uint8_t>& levels, vxrt_light_summary& summary)
+{
+    Flush();
+    // the vector is sized only for a box within the limits; the call itself refuses anything else, in its own order
+    const bool sized = vxrt_light_workspace_bytes(dims, channels) != 0;
+    levels.assign(sized ? (size_t)dims[0] * dims[1] * dims[2] : 1u, 0u);
+    return vxrt_light_field_host(ctx, origin, dims, emitters.empty() ? nullptr : emitters.data(), (uint32_t)(emitters.size() / 4u),
+                                 channels, levels.data(), &summary);
+}
+
 int VoxelRaytracer3D::DownsampleRegion(const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
                                        std::vector<uint32_t>& bits, vxrt_lod_summary& summary, std::vector<uint16_t>* counts)
 {

@@ -3,6 +3,7 @@
 // process globals (hFrameInfo / g_env, VoxelRT/Renderer.cu:24-25,89) and the launches.
 #include "../../include/vxrt.h"
 #include "vxrt_dist.hpp"
+#include "vxrt_light.hpp"
 #include "vxrt_edit.hpp"
 #include "vxrt_kernels.hpp"
 #include "vxrt_islands.hpp"
@@ -63,6 +64,9 @@ hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[
                      uint32_t ngoals, uint32_t max_dist, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
                      vxrt_nav_summary* summary, hipStream_t stream);
 hipError_t nav_paths(const NavPathArgs& P, hipStream_t stream);
+// light fields (vxrt_light.hip)
+hipError_t light_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t channels, const int32_t* emitters,
+                       uint32_t n_emitters, void* work, uint8_t* levels, vxrt_light_summary* summary, hipStream_t stream);
 // distance fields (vxrt_dist.hip)
 hipError_t distance_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t radius, uint32_t mode, void* work,
                           uint16_t* dist2, vxrt_distance_summary* summary, hipStream_t stream);
@@ -2390,6 +2394,68 @@ int vxrt_downsample_region_host(vxrt_ctx* c, const int32_t origin[3], const int3
     VX_HIP(hipMemcpy(bits, T.at<uint32_t>(2), bb, hipMemcpyDeviceToHost));
     if (cb)
         VX_HIP(hipMemcpy(counts_or_null, T.at<uint16_t>(3), cb, hipMemcpyDeviceToHost));
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- light fields ----------------------------------------------------------------------------------------------------------
+uint64_t vxrt_light_workspace_bytes(const int32_t dims[3], uint32_t channels)
+{
+    vxrt::LightLayout L;
+    return dims && vxrt::light_layout(nullptr, dims, channels, L) ? L.total_bytes : 0;
+}
+
+// the checks both light calls make after their NULL checks, in the order of include/vxrt.h
+static int light_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const void* emitters, uint32_t n_emitters,
+                       uint32_t channels)
+{
+    vxrt::LightLayout L;
+    if (channels < 1u || channels > (VXRT_LIGHT_SKY | VXRT_LIGHT_BLOCK))
+        return fail(VXRT_ERR_INVALID, "light channels: VXRT_LIGHT_SKY, VXRT_LIGHT_BLOCK or both");
+    if (n_emitters > VXRT_LIGHT_MAX_EMITTERS)
+        return fail(VXRT_ERR_INVALID, "light: more than VXRT_LIGHT_MAX_EMITTERS emitters");
+    if (!emitters && n_emitters && (channels & VXRT_LIGHT_BLOCK))
+        return fail(VXRT_ERR_INVALID, "light: emitters NULL with n_emitters > 0 and the block channel");
+    if (!vxrt::light_layout(nullptr, dims, channels, L))
+        return fail(VXRT_ERR_INVALID, "light box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36");
+    if (!vxrt::light_layout(origin, dims, channels, L))
+        return fail(VXRT_ERR_INVALID, "light box: origin - 14 or origin + dims + 14 beyond int32");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_light_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const int32_t* d_emitters, uint32_t n_emitters,
+                     uint32_t channels, void* d_work, uint8_t* d_levels, vxrt_light_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !d_work || !d_levels || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = light_ready(c, origin, dims, d_emitters, n_emitters, channels))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::light_field(vxrt::query_world(c), origin, dims, channels, d_emitters, n_emitters, d_work, d_levels, d_summary,
+                             (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_light_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const int32_t* emitters, uint32_t n_emitters,
+                          uint32_t channels, uint8_t* levels, vxrt_light_summary* summary)
+{
+    if (!c || !origin || !dims || !levels || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = light_ready(c, origin, dims, emitters, n_emitters, channels))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::LightLayout L;
+    vxrt::light_layout(origin, dims, channels, L);
+    const size_t ob = L.nvox, eb = (channels & VXRT_LIGHT_BLOCK) ? (size_t)n_emitters * 16u : 0;
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({L.total_bytes, ob, sizeof(vxrt_light_summary), eb}))
+        return fail(VXRT_ERR_NOMEM, std::string("light_field_host: ") + hipGetErrorString(e));
+    if (eb)
+        VX_HIP(hipMemcpy(T.at<int32_t>(3), emitters, eb, hipMemcpyHostToDevice));
+    VX_HIP(vxrt::light_field(vxrt::query_world(c), origin, dims, channels, T.at<int32_t>(3), n_emitters, T.base, T.at<uint8_t>(1),
+                             T.at<vxrt_light_summary>(2), nullptr));
+    VX_HIP(hipMemcpy(summary, T.at<vxrt_light_summary>(2), sizeof(vxrt_light_summary), hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(levels, T.at<uint8_t>(1), ob, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }

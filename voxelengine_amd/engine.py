@@ -412,6 +412,64 @@ class Context:
         return DistanceField(origin=tuple(int(v) for v in origin), dims=dims, radius=int(radius), mode=int(mode),
                              dist2=out[:nvox].reshape(dims[::-1]).transpose(2, 1, 0), _summary=summary, _stream=None)
 
+    # ---- voxel light fields (extension, include/vxrt.h) ------------------------------------------------------------------
+    def light_workspace_bytes(self, dims, channels: int = N.LIGHT_SKY | N.LIGHT_BLOCK) -> int:
+        """vxrt_light_workspace_bytes: the workspace of one light_field call, 0 outside the contract"""
+        c = int(channels)
+        return int(self._L.vxrt_light_workspace_bytes(_i3(dims), c)) if 0 <= c < 1 << 32 else 0
+
+    def light_field(self, origin, dims, emitters=None, channels: int = N.LIGHT_SKY | N.LIGHT_BLOCK, out=None, work=None,
+                    stream: int | None = None) -> "LightField":
+        """The light levels of the box ``origin`` .. ``origin + dims - 1``: include/vxrt.h, vxrt_light_field.  ``emitters``:
+        rows of (x, y, z, level) as a numpy array, a list or a device int32 tensor (None: no emitters).  Asynchronous on
+        ``stream`` (default: torch's current stream).  ``out``: a device tensor of one-byte elements to write the levels to
+        (one per voxel; default: a new one); ``work``: a device tensor of at least light_workspace_bytes bytes to use as
+        the workspace (default: a new one).  Returns a LightField; reading its ``summary`` waits for the call."""
+        import torch
+        dims = tuple(int(v) for v in dims)
+        ws = self.light_workspace_bytes(dims, channels)
+        dev = "cuda:%d" % self.device
+        nvox = dims[0] * dims[1] * dims[2] if ws else 0
+        if work is None:
+            work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
+        elif work.element_size() * work.numel() < ws or not work.is_contiguous():
+            raise ValueError("work: a contiguous device tensor of at least light_workspace_bytes(dims, channels) bytes")
+        if out is None:
+            out = torch.empty(max(nvox, 1), dtype=torch.uint8, device=dev)
+        elif out.element_size() != 1 or out.numel() < nvox or not out.is_contiguous():
+            raise ValueError("out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] one-byte elements")
+        if emitters is None:
+            em, n = None, 0
+        elif isinstance(emitters, torch.Tensor):
+            em = emitters.to(device=dev, dtype=torch.int32).contiguous().view(-1, 4)
+            n = em.shape[0]
+        else:
+            rows = np.ascontiguousarray(np.asarray(emitters, np.int32).reshape(-1, 4))
+            n = rows.shape[0]
+            em = torch.from_numpy(rows).to(dev) if n else None
+        summary = torch.zeros(42, dtype=torch.int32, device=dev)
+        s = _stream(stream)
+        N.check(self._L.vxrt_light_field(self._h, _i3(origin), _i3(dims), _ptr(em) if n else None, n, _u32(channels), _ptr(work),
+                                         _ptr(out), _ptr(summary), s))
+        for t in (work, em):  # freed here, still in use on the call's stream
+            if t is not None:
+                t.record_stream(torch.cuda.ExternalStream(s, device=dev))
+        return LightField(origin=tuple(int(v) for v in origin), dims=dims, channels=int(channels), levels=out.view(-1)[:nvox],
+                          _summary=summary, _stream=s)
+
+    def light_field_host(self, origin, dims, emitters=None, channels: int = N.LIGHT_SKY | N.LIGHT_BLOCK) -> "LightField":
+        """light_field through the synchronous host call (vxrt_light_field_host): ``levels`` is a numpy uint8 [x, y, z]
+        grid."""
+        dims = tuple(int(v) for v in dims)
+        nvox = dims[0] * dims[1] * dims[2] if self.light_workspace_bytes(dims, channels) else 0
+        rows = np.zeros((0, 4), np.int32) if emitters is None else np.ascontiguousarray(np.asarray(emitters, np.int32).reshape(-1, 4))
+        out = np.zeros(max(nvox, 1), np.uint8)
+        summary = np.zeros(42, np.uint32)
+        N.check(self._L.vxrt_light_field_host(self._h, _i3(origin), _i3(dims), rows.ctypes.data if len(rows) else None, len(rows),
+                                              _u32(channels), out.ctypes.data, summary.ctypes.data))
+        return LightField(origin=tuple(int(v) for v in origin), dims=dims, channels=int(channels),
+                          levels=out[:nvox].reshape(dims[::-1]).transpose(2, 1, 0), _summary=summary, _stream=None)
+
     # ---- mesh voxelization (extension, include/vxrt.h) ----------------------------------------------------------------
     def voxelize_workspace_bytes(self, dims, n_triangles: int) -> int:
         """vxrt_voxelize_workspace_bytes: the workspace of one voxelize_mesh call, 0 outside the contract"""
@@ -1083,6 +1141,60 @@ class Downsampled:
         import torch
         torch.cuda.ExternalStream(self._stream, device=self.counts.device).synchronize()
         return self.counts.cpu().numpy().view(np.uint16).reshape(self.dims[::-1]).transpose(2, 1, 0)
+
+
+class LightSummary(NamedTuple):
+    """vxrt_light_summary: solid and exposed voxels of the box, its empty voxels by sky and by block level (16 entries
+    each), the sums of the two channels' levels, and the emitter entries by class"""
+    solid: int
+    exposed: int
+    hist_sky: tuple
+    hist_block: tuple
+    sum_sky: int
+    sum_block: int
+    emitters_used: int
+    emitters_solid: int
+    emitters_far: int
+    emitters_invalid: int
+
+
+@dataclass
+class LightField:
+    """The result of Context.light_field: ``levels`` one byte (sky << 4 | block) per voxel in region order on the device (a
+    numpy uint8 [x, y, z] grid from light_field_host), ``summary`` a LightSummary."""
+    origin: tuple
+    dims: tuple
+    channels: int
+    levels: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> LightSummary:
+        """the summary; for a device field this waits for the call's stream"""
+        w = self._summary
+        if not isinstance(w, np.ndarray):
+            import torch
+            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
+            w = self._summary = w.cpu().numpy().view(np.uint32)
+        v = [int(x) for x in w]
+        return LightSummary(v[0], v[1], tuple(v[2:18]), tuple(v[18:34]), v[34] | v[35] << 32, v[36] | v[37] << 32, *v[38:42])
+
+    def grid(self) -> np.ndarray:
+        """the packed levels as a numpy uint8 [x, y, z] grid (a device field is copied to the host)"""
+        if isinstance(self.levels, np.ndarray):
+            return self.levels
+        import torch
+        torch.cuda.ExternalStream(self._stream, device=self.levels.device).synchronize()
+        return self.levels.cpu().numpy().reshape(self.dims[::-1]).transpose(2, 1, 0)
+
+    def sky(self) -> np.ndarray:
+        """the sky levels, 0 .. 15, as a numpy uint8 [x, y, z] grid"""
+        return self.grid() >> 4
+
+    def block(self) -> np.ndarray:
+        """the block levels, 0 .. 15, as a numpy uint8 [x, y, z] grid"""
+        return self.grid() & 15
 
 
 class DistanceSummary(NamedTuple):
