@@ -849,6 +849,12 @@ int vxrt_render_views(vxrt_ctx *ctx, uint32_t width, uint32_t height, uint32_t n
 /* the kernel (7 or 1) a vxrt_render (nviews = 0) or vxrt_render_views launch of this shape would run under the
  * context's current variant; -1 on bad arguments.  For tools that label measurements by kernel (bench.py). */
 int vxrt_kernel_for_launch(const vxrt_ctx *ctx, uint32_t width, uint32_t height, const vxrt_render_flags *flags, uint32_t nviews);
+/* 1 when a vxrt_render (nviews = 0) or vxrt_render_views launch of this shape would run the persistent kernel's instantiation
+ * for plain shaded frames -- shaded mode, perspective camera, no checkerboard, no strips, no accumulation history, no
+ * hit-index AOV, on an ordinary grid with brick edge 32 -- in which those launch flags are compile-time constants; 0 when it runs the general instantiation (or kernel 1, or no world is resident); -1 on bad arguments.  Host
+ * only: nothing is launched.  For a multi-view launch a non-NULL flags->d_hit_aov stands for "some view has a hit-index
+ * AOV" (only here: vxrt_render_views itself reads the views' own pointers).  The frames are the same bit for bit either way. */
+int vxrt_render_specialisation(const vxrt_ctx *ctx, uint32_t width, uint32_t height, const vxrt_render_flags *flags, uint32_t nviews);
 /* number of frame rows owned by a shard, = rows of its compact buffer */
 uint32_t vxrt_compact_rows(uint32_t height, int32_t strip_rows, int32_t strip_count, int32_t strip_index);
 /* counters accumulated by the launches on this context since the previous read, whatever their streams; synchronises

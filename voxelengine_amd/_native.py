@@ -15,6 +15,7 @@ MODE_SHADED, MODE_DEBUG = 0, 1
 # every symbol include/vxrt.h declares
 EXPORTS = [
     "vxrt_abi_version", "vxrt_create", "vxrt_destroy", "vxrt_last_error", "vxrt_synchronize", "vxrt_set_kernel_variant", "vxrt_kernel_for_launch",
+    "vxrt_render_specialisation",
     "vxrt_has_experiments", "vxrt_set_persistent_waves_per_cu", "vxrt_debug_guard_pretend_no_slack",
     "vxrt_upload_world", "vxrt_build_world_procedural", "vxrt_world_info_get", "vxrt_download_world",
     "vxrt_save_world", "vxrt_load_world", "vxrt_world_file_info",
@@ -163,6 +164,8 @@ def load() -> C.CDLL:
     L.vxrt_set_persistent_waves_per_cu.argtypes = [C.c_void_p, C.c_int]
     L.vxrt_kernel_for_launch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
     L.vxrt_kernel_for_launch.restype = C.c_int
+    L.vxrt_render_specialisation.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.vxrt_render_specialisation.restype = C.c_int
     L.vxrt_upload_world.argtypes = [C.c_void_p, C.POINTER(WorldDesc)]
     L.vxrt_build_world_procedural.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.vxrt_world_info_get.argtypes = [C.c_void_p, C.POINTER(WorldInfo)]

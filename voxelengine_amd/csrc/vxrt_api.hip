@@ -31,6 +31,7 @@
 namespace vxrt {
 hipError_t launch_render(const RenderArgs& A, bool stats, int variant, hipStream_t stream);
 int resolve_render_variant(const RenderArgs& A, int variant);
+bool launch_is_common(const RenderArgs& A);
 hipError_t launch_trace_batch(const BatchArgs& B, bool stats, int variant, hipStream_t stream);
 void launch_deinterleave(const void* shards, unsigned long long shard_stride_bytes, void* fb, uint32_t width,
                          uint32_t height, uint32_t strip_rows, uint32_t strip_count, hipStream_t stream, uint32_t n_views = 1,
@@ -437,6 +438,30 @@ int vxrt_kernel_for_launch(const vxrt_ctx* c, uint32_t width, uint32_t height, c
     else
         A.launch_rows = height;
     return vxrt::resolve_render_variant(A, c->kernel_variant);
+}
+
+int vxrt_render_specialisation(const vxrt_ctx* c, uint32_t width, uint32_t height, const vxrt_render_flags* fl, uint32_t nviews)
+{
+    if (!c || !fl || fl->struct_size != sizeof(vxrt_render_flags))
+        return -1;
+    (void)width;
+    (void)height;
+    if (!c->has_world || c->kernel_variant == 1)
+        return 0;
+    // the arguments launch_is_common reads, as vxrt_render_views fills them in
+    vxrt::RenderArgs A;
+    memset(&A, 0, sizeof(A));
+    A.W = c->view;
+    A.mode = fl->mode;
+    A.checkerboard = fl->checkerboard ? 1 : 0;
+    A.ortho = fl->ortho ? 1 : 0;
+    A.strip_count = fl->strip_count > 1 ? fl->strip_count : 1;
+    A.compact = fl->compact ? 1 : 0;
+    A.accum = reinterpret_cast<float4*>(fl->d_accum);
+    A.nviews = nviews;
+    A.hit_aov = (long long*)fl->d_hit_aov;
+    A.want_hit_aov = fl->d_hit_aov != nullptr;
+    return vxrt::launch_is_common(A) ? 1 : 0;
 }
 
 int vxrt_set_persistent_waves_per_cu(vxrt_ctx* c, int waves_per_cu)

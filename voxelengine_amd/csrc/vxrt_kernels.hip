@@ -408,6 +408,23 @@ int resolve_render_variant(const RenderArgs& A, int variant)
     return variant == 1 ? 1 : 7;
 }
 
+// The launches that run the persistent kernel's COMMON instantiations (vxrt_persist2.hpp): the plain shaded frame -- shaded
+// mode, perspective camera, no checkerboard, no strips (hence no packed rows), no accumulation history, no hit-index AOV in
+// any view -- of an ordinary grid with brick edge 32.  Everything else runs the general instantiations.  (The flags
+// FrameTraits<true> replaces by constants are exactly the ones tested here.  The kernel does not depend on the brick edge;
+// the edge is part of the predicate because edge 32 is what the instantiations were verified and measured on.)
+bool launch_is_common(const RenderArgs& A)
+{
+#ifdef VXRT_NO_COMMON  // A/B builds (tools/build_variant.sh): every launch runs the general instantiation
+    (void)A;
+    return false;
+#else
+    const bool hit_aov = A.nviews ? A.want_hit_aov != 0 : A.hit_aov != nullptr;
+    return A.mode == 0 && !A.ortho && !A.checkerboard && A.strip_count <= 1 && !A.compact && A.accum == nullptr && !hit_aov &&
+           A.W.f == 32 && !A.W.c_wide;
+#endif
+}
+
 // The persistent grid of a launch.  A full grid is VXRT_PERSIST2_OCC waves per SIMD: what a large launch wants (latency hiding
 // in steady state).  A small launch ends in a tail in which every resident wave still carries a few pixel chains at low lane
 // utilisation, and that tail's work grows with the number of waves while its length shrinks with the waves per SIMD; so a
@@ -460,10 +477,15 @@ hipError_t launch_render(const RenderArgs& A, bool stats, int variant, hipStream
         return e;
     const bool second_bounce = A.bounce_depth >= 2 && A.bounce_samples > 0;
     const dim3 g(waves), b(64);
-    // (ordinary grids and wide ones -- beyond the tracer's packed step counters -- run their own instantiation of the kernel)
+    // (ordinary grids and wide ones -- beyond the tracer's packed step counters -- run their own instantiation of the kernel,
+    // and so does the plain shaded frame on brick edge 32: launch_is_common.  A probe-counting launch takes the same road,
+    // so that it stays the timed kernel's sibling.)
+    const bool common = launch_is_common(A);
 #define VXRT_LAUNCH_PERSIST(S, B2, M)                                                                    \
     do {                                                                                                 \
-        if (A.W.c_wide)                                                                                  \
+        if (common)                                                                                      \
+            hipLaunchKernelGGL((k_render_persist2<S, B2, M, false, true>), g, b, 0, stream, A);          \
+        else if (A.W.c_wide)                                                                             \
             hipLaunchKernelGGL((k_render_persist2<S, B2, M, true>), g, b, 0, stream, A);                 \
         else                                                                                             \
             hipLaunchKernelGGL((k_render_persist2<S, B2, M, false>), g, b, 0, stream, A);                \

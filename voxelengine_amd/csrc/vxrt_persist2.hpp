@@ -42,13 +42,15 @@ struct LaneView {
 };
 
 // getRayDirection / getRayDirectionOrtho (Renderer.cu:44-70)
+// (FT: the launch's frame flags as the kernel reads them, FrameTraits -- the camera kind is a constant in the COMMON instantiations)
+template <class FT>
 __device__ __forceinline__ void camera_ray(const RenderArgs& A, const LaneView& V, int x, int y, f3& origin, f3& ray)
 {
     // (x / W and y / H: small integers over small integers, by the host's reciprocals and one correction step -- exact for
     // every such pair, tests/tools/exact_div_check.c)
     const float u = div_rn((float)x, (float)(int)A.width, A.inv_width), v = div_rn((float)y, (float)(int)A.height, A.inv_height);
     origin = V.origin;
-    if (A.ortho) {
+    if (FT::ortho(A)) {
         ray = V.fwd;
         origin = origin + ((V.right * (u * 2 - 1)) * A.ortho_x) * A.ratio;
         origin = origin + (V.up * (v * 2 - 1)) * A.ortho_y;
@@ -67,10 +69,11 @@ __device__ __forceinline__ void camera_ray(const RenderArgs& A, const LaneView& 
 
 // the ray origin alone (perspective: the camera; ortho: per pixel) -- what shading and the debug view need of a
 // pixel's camera ray once the primary ray has been traced
+template <class FT>
 __device__ __forceinline__ f3 camera_origin(const RenderArgs& A, const LaneView& V, int x, int y)
 {
     f3 origin = V.origin;
-    if (A.ortho) {
+    if (FT::ortho(A)) {
         const float u = div_rn((float)x, (float)(int)A.width, A.inv_width), v = div_rn((float)y, (float)(int)A.height, A.inv_height);
         origin = origin + ((V.right * (u * 2 - 1)) * A.ortho_x) * A.ratio;
         origin = origin + (V.up * (v * 2 - 1)) * A.ortho_y;
@@ -163,13 +166,23 @@ __device__ __forceinline__ bool vote2(int parked, int others, int num, int k)
 #define PX_LD_COL() do { PX_LD_F(PF_COL_X, color.x); PX_LD_F(PF_COL_Y, color.y); PX_LD_F(PF_COL_Z, color.z); } while (0)
 #define PX_ST_COL() do { PX_ST_F(PF_COL_X, color.x); PX_ST_F(PF_COL_Y, color.y); PX_ST_F(PF_COL_Z, color.z); } while (0)
 
-template <bool STATS, bool BOUNCE2, bool MULTI, bool WIDE>
+// COMMON: the instantiations for the plain shaded frame on a world of brick edge 32 (launch_is_common, vxrt_kernels.hip:
+// by far the most common launch, and the bench's).  The kernel reads the launch-uniform frame flags through FrameTraits
+// (vxrt_pixel_map.hpp).  In a COMMON instantiation the flags are constants: the debug view, the orthographic camera, the
+// checkerboard, strips and packed rows, accumulation and the hit-index AOV are not compiled.  One source text; the results
+// are the general instantiation's bit for bit.  Ordinary grids only (never with WIDE).  The brick edge stays a run-time
+// value: as the literal 32 in the tracer it was measured slower and is not built (profiles/r17_common_frames.md).
+template <bool STATS, bool BOUNCE2, bool MULTI, bool WIDE, bool COMMON = false>
 __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(RenderArgs A_kern)
 {
+    static_assert(!(COMMON && WIDE), "COMMON launches run on ordinary grids");
+    using FT = FrameTraits<COMMON>;
+    using Tracer = WaveTracerT<WIDE>;
     constexpr bool LDS = true;  // (the PX_* macros and the tracer's LDS_COLD parameter)
     // shadow rays are launched from the end-of-walk phase (shadow_from_end below).  Not in the multi-view second-bounce
-    // instantiations: with the continuation they spill 8 vector registers, so they keep the ray-finished phase's path.
-    constexpr bool END_SHADOW = !(BOUNCE2 && MULTI);
+    // general instantiations: with the continuation they spill 8 vector registers, so they keep the ray-finished phase's path
+    // (their COMMON forms hold 0 spilled VGPRs with it and have it).
+    constexpr bool END_SHADOW = !(BOUNCE2 && MULTI) || COMMON;
     __shared__ uint32_t cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64 + WV_WORDS];  // + the wave's own words (WV_*)
     const WorldView& W = A_kern.W;
     const int lane = threadIdx.x & 63;
@@ -179,12 +192,12 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     auto lane_view = [&](const RenderArgs& A, uint32_t v) -> LaneView {
         if (MULTI) {
             const ViewArgs& S = A.views[v];
-            return LaneView{S.origin, S.fwd, S.up, S.right, S.frame_number, S.fb, S.color_aov, S.hit_aov};
+            return LaneView{S.origin, S.fwd, S.up, S.right, S.frame_number, S.fb, S.color_aov, FT::hit_aov(S.hit_aov)};
         }
-        return LaneView{A.origin, A.fwd, A.up, A.right, A.frame_number, A.fb, A.color_aov, A.hit_aov};
+        return LaneView{A.origin, A.fwd, A.up, A.right, A.frame_number, A.fb, A.color_aov, FT::hit_aov(A.hit_aov)};
     };
 
-    WaveTracerT<WIDE> T;
+    Tracer T;
     T.init(W, &cold_block[lane]);  // st = ST_DONE: every lane starts by asking for a pixel
     uint32_t stage = PX_NONE;
     uint32_t px_tx = 0, px_row = 0;
@@ -215,7 +228,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             liz = 1.0f / (ld.z == 0 ? kFltEps : ld.z);
         }
         const bool light_special = !(fabsf(ld.x) >= kMinFastDir && fabsf(ld.y) >= kMinFastDir && fabsf(ld.z) >= kMinFastDir);
-        const bool aov = MULTI ? A_kern.want_hit_aov != 0 : A_kern.hit_aov != nullptr;
+        const bool aov = FT::want_hit_aov(A_kern, MULTI);
         if (lane == 0) {
             WV[WV_LIGHT_DX] = __float_as_uint(ld.x);
             WV[WV_LIGHT_DY] = __float_as_uint(ld.y);
@@ -227,7 +240,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             WV[WV_LIGHT_STEP_X] = __float_as_uint(A_kern.light_step.x);
             WV[WV_LIGHT_STEP_Y] = __float_as_uint(A_kern.light_step.y);
             WV[WV_LIGHT_STEP_Z] = __float_as_uint(A_kern.light_step.z);
-            WV[WV_SHADOW_FROM_END] = (END_SHADOW && A_kern.mode == 0 && A_kern.shadow && !light_special && !aov) ? 1u : 0u;
+            WV[WV_SHADOW_FROM_END] = (END_SHADOW && FT::mode(A_kern) == 0 && A_kern.shadow && !light_special && !aov) ? 1u : 0u;
         }
     }
 
@@ -255,7 +268,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
         PixelSink sink{A, pc.out_row, V.fb, V.color_aov};
         const int Wd = (int)A.width, Hd = (int)A.height;
         if (hit) {
-            if (A.mode == 1) {  // DEBUG_VIEW quadrants, Renderer.cu:215-243
+            if (FT::mode(A) == 1) {  // DEBUG_VIEW quadrants, Renderer.cu:215-243
                 f3 dv = pos - origin;
                 float dist = sqrtf(dot3(dv, dv));
                 const float wrap = (float)(1.0 + 1e-6);
@@ -268,7 +281,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 } else
                     sink.put(pc.x, pc.y, mk3(dist * 0.01f, 0, 0));
             } else {
-                if (!MULTI && A.accum)  // temporal accumulation (extension, include/vxrt.h): the mean of the history is tonemapped
+                if (!MULTI && FT::accum(A))  // temporal accumulation (extension, include/vxrt.h): the mean of the history is tonemapped
                     shaded = accumulate_color(A, pc.out_row, pc.x, shaded);
                 // Tonemap c / (c + 1) (Renderer.cu:170-177): the short exact division for colours of ordinary size (or zero)
                 const float tx = shaded.x + 1.0f, ty = shaded.y + 1.0f, tz = shaded.z + 1.0f;
@@ -289,7 +302,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                        // the kernel's only scratch use)
             sink.put(pc.x, pc.y, mk3(ten, ten, ten));
         }
-        if (A.mode == 1 && pc.x < (Wd >> 1) && pc.y > (Hd >> 1))  // :270-275
+        if (FT::mode(A) == 1 && pc.x < (Wd >> 1) && pc.y > (Hd >> 1))  // :270-275
             sink.put(pc.x, pc.y, mk3((float)p_steps / 256.0f, 0, 0));
     };
 
@@ -299,7 +312,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     // invariants from the wave's words instead of begin_ray_deferred's normalisation and reciprocals, and without the world-entry
     // test: only a start inside the coarse grid takes this path, and only one without a -0.0 component (`special`).  Every other
     // lane stays ST_DONE with its fields untouched, for the ray-finished phase.
-    auto shadow_from_end = [&](WaveTracerT<WIDE>& Tr, const lanemask_t ended) -> lanemask_t {
+    auto shadow_from_end = [&](Tracer& Tr, const lanemask_t ended) -> lanemask_t {
         if (ended == 0ull)
             return 0ull;
         bool go = false;
@@ -428,8 +441,8 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             int l_max = kMaxSteps;
             if (T.st == ST_DONE && stage != PX_NONE) {
                 const LaneView V = lane_view(A, MULTI ? px_row >> 16 : 0u);
-                const PixelCoords pc = pixel_coords(A, V.frame_number, px_tx, MULTI ? px_row & 0xFFFFu : px_row);
-                const f3 origin = camera_origin(A, V, pc.x, pc.y);
+                const PixelCoords pc = pixel_coords<COMMON>(A, V.frame_number, px_tx, MULTI ? px_row & 0xFFFFu : px_row);
+                const f3 origin = camera_origin<FT>(A, V, pc.x, pc.y);
                 TraceResult r;
                 T.result(W, r);
                 bool finalize = false, do_shade = false, shadowed = false, bounce = false, bounce2 = false;
@@ -448,7 +461,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                         color = mk3(0, 0, 0);  // a miss keeps the ray direction stored at launch: it is the pixel's colour
                         PX_ST_COL();
                     }
-                    if (!(r.hit && A.mode == 0)) {
+                    if (!(r.hit && FT::mode(A) == 0)) {
                         stage = r.hit ? PX_PRIMARY : PX_NONE;  // remember hit/miss for the store below
                         finalize = true;
                     } else if (A.shadow) {
@@ -605,7 +618,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                     const uint32_t p = tile_used + rank;
                     new_tx = (tile % ntx) * 8u + (p & 7u);
                     new_row = (tile / ntx) * 8u + (p >> 3);
-                    got = pixel_coords(A, MULTI ? A.views[tile_view].frame_number : A.frame_number, new_tx, new_row).live;
+                    got = pixel_coords<COMMON>(A, MULTI ? A.views[tile_view].frame_number : A.frame_number, new_tx, new_row).live;
                     if (MULTI)
                         new_row |= tile_view << 16;
                 }
@@ -617,8 +630,8 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 PX_ST_U(PF_TX, new_tx);
                 PX_ST_U(PF_ROW, new_row);
                 const LaneView V = lane_view(A, MULTI ? new_row >> 16 : 0u);
-                const PixelCoords pc = pixel_coords(A, V.frame_number, new_tx, MULTI ? new_row & 0xFFFFu : new_row);
-                camera_ray(A, V, pc.x, pc.y, l_origin, l_dir);
+                const PixelCoords pc = pixel_coords<COMMON>(A, V.frame_number, new_tx, MULTI ? new_row & 0xFFFFu : new_row);
+                camera_ray<FT>(A, V, pc.x, pc.y, l_origin, l_dir);
                 color = l_dir;  // the pixel's colour if the primary ray misses (Renderer.cu:254-258)
                 PX_ST_COL();
                 l_max = kMaxSteps;

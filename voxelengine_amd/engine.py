@@ -901,6 +901,19 @@ class Context:
             raise N.VxrtError("vxrt_kernel_for_launch: bad arguments")
         return k
 
+    def render_specialisation(self, width: int, height: int, opts: "RenderOptions | None" = None, nviews: int = 0,
+                              hit_aov=None, accum=None) -> int:
+        """1 when a RenderScreen (nviews = 0) or RenderViews launch of this shape runs the persistent kernel's
+        instantiation for plain shaded frames on brick edge 32 (vxrt_render_specialisation), 0 when it runs the general
+        one.  ``hit_aov`` / ``accum``: what the launch would pass (for RenderViews: any view's hit-index AOV).  Host only."""
+        fl = self._flags(opts, None)
+        fl.d_hit_aov = _ptr(hit_aov)
+        fl.d_accum = _ptr(accum)
+        k = int(self._L.vxrt_render_specialisation(self._h, int(width), int(height), C.byref(fl), int(nviews)))
+        if k < 0:
+            raise N.VxrtError("vxrt_render_specialisation: bad arguments")
+        return k
+
     def synchronize(self) -> None:
         N.check(self._L.vxrt_synchronize(self._h))
 
