@@ -46,6 +46,10 @@
 // `value & 3` (1 = sky, 2 = block), with one emitter of level 15 in the cell that holds frame N's camera position when the
 // block channel is set, and prints one line "light frame N solid .. exposed .. sky_sum .. block_sum .. used ..", then one
 // line "light hash frame N levels .." with the 64-bit FNV-1a hash of the level bytes.
+// Kind 11 drops the floating islands of the box of origin a and dims b instead of deleting them (VoxelRaytracer3D::DropIslands,
+// anchored as kind 4: each island falls along -y until it lands, lowest first) and prints one line "drop before frame N: I
+// islands, V island voxels, M moved, max_fall F, sum_contact C", then one line "drop hash frame N rows .." with the 64-bit
+// FNV-1a hash of the rows' bytes (id, voxels, travel, contact: 16 bytes each, in dropping order).
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -324,6 +328,28 @@ int main(int argc, char** argv)
                 for (size_t i = 0; i < levels.size(); ++i)
                     h = (h ^ levels[i]) * 0x100000001b3ull;
                 std::printf("light hash frame %d levels %016llx\n", from, (unsigned long long)h);
+            } else if (e.op.kind == 11) {  // drop the islands
+                flush_ops();
+                std::vector<VoxelRaytracer3D::DroppedIsland> rows;
+                if (raytracer->DropIslands(e.op.a, e.op.b, VXRT_ISLAND_ANCHOR_FACES | VXRT_ISLAND_ANCHOR_FLOOR, rows) != VXRT_OK) {
+                    std::cerr << "drop before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                unsigned long long voxels = 0, contact = 0;
+                unsigned moved = 0;
+                int fall = 0;
+                for (const auto& r : rows) {
+                    voxels += r.voxels;
+                    contact += r.contact;
+                    moved += r.travel != 0;
+                    fall = -r.travel > fall ? -r.travel : fall;
+                }
+                std::printf("drop before frame %d: %zu islands, %llu island voxels, %u moved, max_fall %d, sum_contact %llu\n", from,
+                            rows.size(), voxels, moved, fall, contact);
+                uint64_t h = 0xcbf29ce484222325ull;
+                for (size_t i = 0; i < rows.size() * sizeof(rows[0]); ++i)
+                    h = (h ^ ((const unsigned char*)rows.data())[i]) * 0x100000001b3ull;
+                std::printf("drop hash frame %d rows %016llx\n", from, (unsigned long long)h);
             } else if (e.op.kind == 7) {  // stamp the built-in mesh
                 flush_ops();
                 const int32_t r = 256 * e.op.b[0], c = 128;  // mesh frame: the origin is the corner of voxel a

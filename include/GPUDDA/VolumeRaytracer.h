@@ -26,6 +26,9 @@ struct vxrt_edit_stats;
 struct vxrt_body;
 struct vxrt_island;
 struct vxrt_island_summary;
+struct vxrt_piece;
+struct vxrt_placement;
+struct vxrt_placed;
 struct vxrt_nav_agent;
 struct vxrt_nav_summary;
 struct vxrt_distance_summary;
@@ -164,6 +167,26 @@ public:
     int FindIslands(const int32_t origin[3], const int32_t dims[3], uint32_t anchors, std::vector<uint32_t>& floating,
                     vxrt_island_summary& summary, std::vector<vxrt_island>* islands = nullptr, uint32_t max_islands = 4096,
                     std::vector<uint32_t>* labels = nullptr);
+    // voxel piece queries (extension, include/vxrt.h, vxrt_place_pieces_host): n placements of up to VXRT_PLACE_MAX_PIECES
+    // rigid pieces against the resident world -- per placement the solid voxels overlapped at the origin, the travel along
+    // one axis before the first overlap, the contact voxels and the VXRT_PLACED_* flags.  The pieces' d_bits are HOST words
+    // here.  Pending uploads are flushed first.  Returns the vxrt_status.
+    int PlacePieces(const vxrt_piece* pieces, size_t n_pieces, const vxrt_placement* placements, size_t n, vxrt_placed* results);
+    // falling islands: the islands of the box origin .. origin + dims - 1 (FindIslands with labels) fall and land instead of
+    // vanishing.  If the island table was cut short (more than max_islands islands) or an island's box exceeds the piece
+    // limits, VXRT_ERR_INVALID before any change.  Otherwise one VXRT_STAMP_SUBTRACT stamp of the floating bits, then the
+    // islands in ascending (lo[1], id): the island's piece is the bits of labels == id over its box lo .. hi, placed at lo with
+    // axis 1 and dist = -min(lo[1], VXRT_PLACE_MAX_DIST), and written back with one VXRT_STAMP_UNION stamp at
+    // lo + (0, travel, 0).  Later islands land on earlier ones: a deterministic sequential rule, not a physics engine; an
+    // island that starts overlapping one that has already landed merges with it, and the cost is one synchronising edit per
+    // island.  `rows` gets one {id, voxels, travel, contact} per island in dropping order.  Returns the vxrt_status.
+    struct DroppedIsland {
+        uint32_t id, voxels;
+        int32_t travel;
+        uint32_t contact;
+    };
+    int DropIslands(const int32_t origin[3], const int32_t dims[3], uint32_t anchors, std::vector<DroppedIsland>& rows,
+                    uint32_t max_islands = 4096);
     // navigation fields (extension, include/vxrt.h, vxrt_nav_field_host): the walkable bits (region words), one next code
     // per cell and optionally the distances of the box origin .. origin + dims - 1 for `agent` toward the n_goals world
     // cells `goals` (3 int32 each), and the summary.  Pending uploads are flushed first.  Returns the vxrt_status.

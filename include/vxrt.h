@@ -371,6 +371,57 @@ int vxrt_find_islands_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t
                            uint32_t *floating, uint32_t *labels_or_null, vxrt_island *islands_or_null, uint32_t max_islands,
                            vxrt_island_summary *summary);
 
+/* ---- voxel piece queries -- an EXTENSION (with the stamps and islands above: a stamp tested before it is written, loose
+ * terrain that falls and lands).  A piece is a rigid dense bit volume in the region layout of vxrt_read_region; a call places
+ * up to VXRT_PLACE_MAX_PIECES pieces at n placements against the resident world and only reads it.  Integer arithmetic only.
+ *   Piece voxels.  P is the set of voxels p of the piece whose bit is set.  Padding bits at the end of a row are ignored, as a
+ *     stamp ignores them.  W(v) is the world's voxel; voxels outside the world are empty, as for every other query.
+ *   Overlap at an offset.  For a placement with origin o, axis a and signed distance d let s = sign(d), e the unit vector of
+ *     axis a and ov(j) = |{p in P : W(o + p + s * j * e)}|.
+ *   overlap = ov(0).
+ *   travel = s * k, k the largest integer in [0, |d|] with ov(j) = 0 for every 1 <= j <= k: every step is tested, nothing
+ *     tunnels, and ov(0) plays no part, so a piece that starts inside terrain can move out.  Equivalently k = min(|d|, the
+ *     least clearance of a piece voxel along the axis).
+ *   Blocked.  If k < |d|, flags = VXRT_PLACED_BLOCKED and contact = ov(k + 1), the voxels that stop the piece; otherwise
+ *     contact = 0.  d = 0 is a pure fit test.  A piece with no set bit travels the whole distance with overlap 0.
+ *   Validity (per placement, like the body validity rule).  A placement is valid when 0 <= piece < n_pieces, axis is 0, 1 or
+ *     2, |dist| <= VXRT_PLACE_MAX_DIST and |origin[k]| <= 2^30 on every axis.  An invalid placement returns
+ *     {0, 0, 0, VXRT_PLACED_INVALID}.
+ * Call rules, checked in this order: a NULL ctx gives VXRT_ERR_INVALID; so do n_pieces outside 1 .. 64, a NULL `pieces`, a
+ *   piece with NULL bits, nonzero `reserved`, a dim outside 1 .. VXRT_PLACE_MAX_DIM or more than VXRT_PLACE_MAX_VOXELS voxels;
+ *   n = 0 is then a no-op (VXRT_OK); NULL placements or results give VXRT_ERR_INVALID; no world VXRT_ERR_NO_WORLD; a streamed
+ *   world VXRT_ERR_INVALID.  `pieces` is a HOST array whose descriptors travel by value; the bits they name stay on the
+ *   device.  Asynchronous on `stream`.  The library allocates nothing per call and needs no workspace: d_results holds the
+ *   accumulators while the call runs.  The call never loads outside the tables, or outside vxrt_region_words(dims) words of
+ *   a piece.  Every result is its placement's own: it does not depend on the batch, the launch shape or the scheduling, and
+ *   is bit-identical from call to call.  (All placements of a call share one launch shape, sized by the piece with the most
+ *   rows: batch big pieces apart from small ones for speed, not for results.) */
+#define VXRT_PLACE_MAX_PIECES 64
+#define VXRT_PLACE_MAX_DIM 1024          /* per axis */
+#define VXRT_PLACE_MAX_VOXELS (1u << 24) /* dims[0] * dims[1] * dims[2] */
+#define VXRT_PLACE_MAX_DIST 4096
+#define VXRT_PLACED_BLOCKED 1u
+#define VXRT_PLACED_INVALID 2u
+typedef struct vxrt_piece {
+    const uint32_t *d_bits; /* device, region layout: vxrt_region_words(dims) words */
+    int32_t dims[3];
+    int32_t reserved;       /* 0 */
+} vxrt_piece;
+typedef struct vxrt_placement {
+    int32_t piece, origin[3], axis, dist; /* 24 bytes */
+} vxrt_placement;
+typedef struct vxrt_placed {
+    uint32_t overlap;
+    int32_t travel;
+    uint32_t contact, flags; /* 16 bytes */
+} vxrt_placed;
+int vxrt_place_pieces(vxrt_ctx *ctx, const vxrt_piece *pieces /* HOST array */, uint32_t n_pieces,
+                      const vxrt_placement *d_placements, uint64_t n, vxrt_placed *d_results, void *stream);
+/* the same with the pieces' bits (the pointers in `pieces`), the placements and the results in host memory: copied in and
+ * out, synchronous; allocates its own device buffers (like vxrt_read_region_host) */
+int vxrt_place_pieces_host(vxrt_ctx *ctx, const vxrt_piece *pieces, uint32_t n_pieces, const vxrt_placement *placements,
+                           uint64_t n, vxrt_placed *results);
+
 /* ---- navigation fields -- an EXTENSION (with the editing above: where a body can walk, and which way is the goal).  A call
  * looks at one box B = [origin, origin + dims) of world cells, with the limits of vxrt_find_islands: 1 <= dims[k],
  * dims[0] * dims[1] * dims[2] <= 2^28, origin[k] + dims[k] <= 2^31 - 1.  Voxels outside the world are empty.

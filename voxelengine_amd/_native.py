@@ -27,6 +27,7 @@ EXPORTS = [
     "vxrt_region_words", "vxrt_read_region", "vxrt_read_region_host", "vxrt_edit_stamps",
     "vxrt_move_boxes", "vxrt_overlap_boxes", "vxrt_move_boxes_host", "vxrt_overlap_boxes_host",
     "vxrt_islands_workspace_bytes", "vxrt_find_islands", "vxrt_find_islands_host",
+    "vxrt_place_pieces", "vxrt_place_pieces_host",
     "vxrt_nav_workspace_bytes", "vxrt_nav_field", "vxrt_nav_paths", "vxrt_nav_field_host",
     "vxrt_distance_workspace_bytes", "vxrt_distance_field", "vxrt_distance_field_host",
     "vxrt_voxelize_workspace_bytes", "vxrt_voxelize_mesh", "vxrt_voxelize_mesh_host",
@@ -41,6 +42,8 @@ BODY_MAX_EXTENT, BODY_MAX_DELTA = 64, 64
 BODY_BLOCKED_X, BODY_BLOCKED_Y, BODY_BLOCKED_Z, BODY_INVALID = 1, 2, 4, 8
 ISLAND_ANCHOR_X_LO, ISLAND_ANCHOR_X_HI, ISLAND_ANCHOR_Y_LO, ISLAND_ANCHOR_Y_HI = 0x01, 0x02, 0x04, 0x08
 ISLAND_ANCHOR_Z_LO, ISLAND_ANCHOR_Z_HI, ISLAND_ANCHOR_FACES, ISLAND_ANCHOR_FLOOR = 0x10, 0x20, 0x3F, 0x40
+PLACE_MAX_PIECES, PLACE_MAX_DIM, PLACE_MAX_VOXELS, PLACE_MAX_DIST = 64, 1024, 1 << 24, 4096
+PLACED_BLOCKED, PLACED_INVALID = 1, 2
 NAV_MAX_GOALS, NAV_NONE, NAV_MAX_STEPS = 4096, 0xFF, 65535
 NAV_AT_GOAL, NAV_NO_PATH, NAV_TRUNCATED, NAV_OUTSIDE = 0, 1, 2, 3
 DIST_TO_SOLID, DIST_TO_EMPTY, DIST_FAR, DIST_MAX_RADIUS = 0, 1, 0xFFFF, 255
@@ -103,6 +106,11 @@ class StampDesc(C.Structure):
     """vxrt_stamp: a dense bit volume (region layout, include/vxrt.h) written at `origin` in `mode`."""
     _fields_ = [("d_bits", C.c_void_p), ("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("mode", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class PieceDesc(C.Structure):
+    """vxrt_piece: a rigid dense bit volume (region layout, include/vxrt.h) for vxrt_place_pieces."""
+    _fields_ = [("d_bits", C.c_void_p), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
 
 
 class RenderFlags(C.Structure):
@@ -214,6 +222,8 @@ def load() -> C.CDLL:
                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.vxrt_find_islands_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.vxrt_place_pieces.argtypes = [C.c_void_p, C.POINTER(PieceDesc), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.vxrt_place_pieces_host.argtypes = [C.c_void_p, C.POINTER(PieceDesc), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     L.vxrt_nav_workspace_bytes.restype = C.c_uint64
     L.vxrt_nav_workspace_bytes.argtypes = [C.POINTER(C.c_int32), C.c_void_p]
     L.vxrt_nav_field.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint32,

@@ -282,6 +282,80 @@ int VoxelRaytracer3D::FindIslands(const int32_t origin[3], const int32_t dims[3]
     return rc;
 }
 
+int VoxelRaytracer3D::PlacePieces(const vxrt_piece* pieces, size_t n_pieces, const vxrt_placement* placements, size_t n,
+                                  vxrt_placed* results)
+{
+    Flush();
+    if (n_pieces > VXRT_PLACE_MAX_PIECES)
+        return VXRT_ERR_INVALID;
+    return vxrt_place_pieces_host(ctx, pieces, (uint32_t)n_pieces, placements, n, results);
+}
+
+int VoxelRaytracer3D::DropIslands(const int32_t origin[3], const int32_t dims[3], uint32_t anchors, std::vector<DroppedIsland>& rows,
+                                  uint32_t max_islands)
+{
+    rows.clear();
+    std::vector<uint32_t> floating, labels;
+    std::vector<vxrt_island> table;
+    vxrt_island_summary sum{};
+    int rc = FindIslands(origin, dims, anchors, floating, sum, &table, max_islands, &labels);
+    if (rc != VXRT_OK)
+        return rc;
+    if (sum.islands > table.size())
+        return VXRT_ERR_INVALID;  // the table was cut short
+    for (const vxrt_island& t : table) {
+        uint64_t vol = 1;
+        for (int k = 0; k < 3; ++k) {
+            if (t.hi[k] - t.lo[k] > VXRT_PLACE_MAX_DIM)
+                return VXRT_ERR_INVALID;
+            vol *= (uint64_t)(t.hi[k] - t.lo[k]);
+        }
+        if (vol > VXRT_PLACE_MAX_VOXELS)
+            return VXRT_ERR_INVALID;
+    }
+    if (table.empty())
+        return VXRT_OK;
+    rc = StampVoxels(origin, dims, floating.data(), VXRT_STAMP_SUBTRACT);
+    if (rc != VXRT_OK)
+        return rc;
+    std::sort(table.begin(), table.end(), [](const vxrt_island& a, const vxrt_island& b) {
+        return a.lo[1] != b.lo[1] ? a.lo[1] < b.lo[1] : a.id < b.id;
+    });
+    for (const vxrt_island& t : table) {
+        const int32_t e[3] = {t.hi[0] - t.lo[0], t.hi[1] - t.lo[1], t.hi[2] - t.lo[2]};
+        const size_t wpr = ((size_t)e[0] + 31) / 32;
+        std::vector<uint32_t> bits(wpr * e[1] * e[2], 0u);
+        for (int z = 0; z < e[2]; ++z)
+            for (int y = 0; y < e[1]; ++y)
+                for (int x = 0; x < e[0]; ++x) {
+                    const size_t i = (size_t)(t.lo[0] - origin[0] + x) +
+                                     (size_t)dims[0] * ((size_t)(t.lo[1] - origin[1] + y) + (size_t)dims[1] * (size_t)(t.lo[2] - origin[2] + z));
+                    if (labels[i] == t.id)
+                        bits[((size_t)y + (size_t)e[1] * z) * wpr + (x >> 5)] |= 1u << (x & 31);
+                }
+        vxrt_piece piece{};
+        piece.d_bits = bits.data();
+        vxrt_placement pl{};
+        pl.piece = 0;
+        for (int k = 0; k < 3; ++k) {
+            piece.dims[k] = e[k];
+            pl.origin[k] = t.lo[k];
+        }
+        pl.axis = 1;
+        pl.dist = -(t.lo[1] < VXRT_PLACE_MAX_DIST ? t.lo[1] : VXRT_PLACE_MAX_DIST);
+        vxrt_placed res{};
+        rc = PlacePieces(&piece, 1, &pl, 1, &res);
+        if (rc != VXRT_OK)
+            return rc;
+        const int32_t at[3] = {t.lo[0], t.lo[1] + res.travel, t.lo[2]};
+        rc = StampVoxels(at, e, bits.data(), VXRT_STAMP_UNION);
+        if (rc != VXRT_OK)
+            return rc;
+        rows.push_back(DroppedIsland{t.id, t.voxels, res.travel, res.contact});
+    }
+    return VXRT_OK;
+}
+
 int VoxelRaytracer3D::NavField(const int32_t origin[3], const int32_t dims[3], const vxrt_nav_agent& agent, const int32_t* goals,
                                uint32_t n_goals, uint32_t max_dist, std::vector<uint32_t>& walkable, std::vector<uint8_t>& next,
                                vxrt_nav_summary& summary, std::vector<uint32_t>* dist)

@@ -9,6 +9,7 @@
 #include "vxrt_islands.hpp"
 #include "vxrt_lod.hpp"
 #include "vxrt_nav.hpp"
+#include "vxrt_place.hpp"
 #include "vxrt_region.hpp"
 #include "vxrt_stream.hpp"
 #include "vxrt_surface.hpp"
@@ -60,6 +61,8 @@ hipError_t overlap_boxes(const CollideWorld& W, const float* bodies, uint64_t n,
 hipError_t find_islands(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t anchors, void* work,
                         uint32_t* floating, uint32_t* labels, vxrt_island* table, uint32_t max_islands,
                         vxrt_island_summary* summary, hipStream_t stream);
+// voxel piece queries (vxrt_place.hip)
+hipError_t place_pieces(const PlaceArgs& A, hipStream_t stream);
 // navigation fields (vxrt_nav.hip)
 hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], const vxrt_nav_agent& ag, const int32_t* goals,
                      uint32_t ngoals, uint32_t max_dist, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
@@ -2063,6 +2066,90 @@ int vxrt_find_islands_host(vxrt_ctx* c, const int32_t origin[3], const int32_t d
         if (rows)
             VX_HIP(hipMemcpy(islands_or_null, d_tab, rows * sizeof(vxrt_island), hipMemcpyDeviceToHost));
     }
+    VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- voxel piece queries ---------------------------------------------------------------------------------------------
+// the checks both piece calls make after the NULL ctx, in the order of include/vxrt.h; fills A's pieces and launch shape
+static int place_ready(const vxrt_piece* pieces, uint32_t n_pieces, vxrt::PlaceArgs& A)
+{
+    if (n_pieces < 1 || n_pieces > vxrt::kPlaceMaxPieces)
+        return fail(VXRT_ERR_INVALID, "n_pieces: 1 .. VXRT_PLACE_MAX_PIECES");
+    if (!pieces)
+        return fail(VXRT_ERR_INVALID, "pieces is NULL");
+    A.n_pieces = n_pieces;
+    for (uint32_t k = 0; k < n_pieces; ++k)
+        if (vxrt::piece_prepare(pieces[k].d_bits, pieces[k].dims, pieces[k].reserved, A.pieces[k]))
+            return fail(VXRT_ERR_INVALID, "piece " + std::to_string(k) +
+                                              ": bits NULL, nonzero reserved, a dim outside 1 .. 1024 or more than 2^24 voxels");
+    vxrt::place_shape(A);
+    return VXRT_OK;
+}
+
+int vxrt_place_pieces(vxrt_ctx* c, const vxrt_piece* pieces, uint32_t n_pieces, const vxrt_placement* d_placements, uint64_t n,
+                      vxrt_placed* d_results, void* stream)
+{
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    vxrt::PlaceArgs A{};
+    if (int rc = place_ready(pieces, n_pieces, A))
+        return rc;
+    if (n == 0)
+        return VXRT_OK;
+    if (!d_placements || !d_results)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = vxrt::world_ready(c, "queried"))
+        return rc;
+    A.W = vxrt::query_world(c);
+    A.placements = (const int32_t*)d_placements;
+    A.results = (uint32_t*)d_results;
+    A.n = n;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::place_pieces(A, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_place_pieces_host(vxrt_ctx* c, const vxrt_piece* pieces, uint32_t n_pieces, const vxrt_placement* placements, uint64_t n,
+                           vxrt_placed* results)
+{
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    vxrt::PlaceArgs A{};
+    if (int rc = place_ready(pieces, n_pieces, A))
+        return rc;
+    if (n == 0)
+        return VXRT_OK;
+    if (!placements || !results)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = vxrt::world_ready(c, "queried"))
+        return rc;
+    if (n > (1ull << 36))
+        return fail(VXRT_ERR_INVALID, "too many placements for one call");
+    VX_HIP(hipSetDevice(c->device));
+    // one allocation: the placements, the results, then every piece's words (each section on a 256-byte boundary)
+    const size_t pb = (size_t)n * sizeof(vxrt_placement), rb = (size_t)n * sizeof(vxrt_placed);
+    size_t off[vxrt::kPlaceMaxPieces], total = vxrt::section_up(pb) + vxrt::section_up(rb);
+    for (uint32_t k = 0; k < n_pieces; ++k) {
+        off[k] = total;
+        total += vxrt::section_up((size_t)vxrt::region_words(pieces[k].dims) * 4u);
+    }
+    vxrt::HostScratch T;
+    if (hipError_t e = T.alloc({total}))
+        return fail(VXRT_ERR_NOMEM, std::string("place_pieces_host: ") + hipGetErrorString(e));
+    vxrt_placement* d_pl = (vxrt_placement*)T.base;
+    vxrt_placed* d_res = (vxrt_placed*)(T.base + vxrt::section_up(pb));
+    VX_HIP(hipMemcpy(d_pl, placements, pb, hipMemcpyHostToDevice));
+    for (uint32_t k = 0; k < n_pieces; ++k) {
+        VX_HIP(hipMemcpy(T.base + off[k], pieces[k].d_bits, (size_t)vxrt::region_words(pieces[k].dims) * 4u, hipMemcpyHostToDevice));
+        A.pieces[k].bits = (const uint32_t*)(T.base + off[k]);
+    }
+    A.W = vxrt::query_world(c);
+    A.placements = (const int32_t*)d_pl;
+    A.results = (uint32_t*)d_res;
+    A.n = n;
+    VX_HIP(vxrt::place_pieces(A, nullptr));
+    VX_HIP(hipMemcpy(results, d_res, rb, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
     return VXRT_OK;
 }

@@ -318,6 +318,107 @@ class Context:
         st = self.edit_stamps([Stamp(isl.origin, isl.floating, N.STAMP_SUBTRACT, isl.dims)])
         return isl, st
 
+    # ---- voxel piece queries (extension, include/vxrt.h) -------------------------------------------------------------
+    def _piece_descs(self, pieces, host: bool):
+        """(keep-alive list, PieceDesc array) of Piece objects: device words for place_pieces, host words for the _host call"""
+        import torch
+        keep, descs = [], []
+        for p in pieces:
+            bits, dims = p.bits, p.dims
+            if isinstance(bits, np.ndarray) and bits.dtype == bool:
+                dims = tuple(int(v) for v in bits.shape) if dims is None else dims
+                bits = pack_region(bits)
+            elif dims is None:
+                raise ValueError("a piece of region words needs its dims")
+            d = N.PieceDesc()
+            if host:
+                if hasattr(bits, "cpu"):
+                    bits = bits.cpu().numpy()
+                bits = np.ascontiguousarray(bits).view(np.uint32)
+                d.d_bits = bits.ctypes.data
+            else:
+                if isinstance(bits, np.ndarray):
+                    bits = torch.from_numpy(np.ascontiguousarray(bits).view(np.int32)).to("cuda:%d" % self.device)
+                d.d_bits = _ptr(bits)
+            words = bits.size if isinstance(bits, np.ndarray) else bits.numel() * bits.element_size() // 4
+            if words < region_words(dims):
+                raise ValueError("a piece holds fewer than region_words(dims) words")
+            keep.append(bits)
+            d.dims = _i3(dims)
+            d.reserved = 0
+            descs.append(d)
+        return keep, (N.PieceDesc * max(len(descs), 1))(*descs)
+
+    def place_pieces(self, pieces, placements, stream: int | None = None):
+        """Place rigid pieces against the resident world (include/vxrt.h, vxrt_place_pieces): per placement the solid voxels
+        the piece overlaps at its origin, and how far it travels along one axis before it first overlaps.  ``pieces``: up to
+        PLACE_MAX_PIECES Piece objects; ``placements``: an (n, 6) int32 cuda tensor of rows piece, origin[3], axis, dist, or
+        a list of Placement / an (n, 6) numpy array (copied to the device here).  Asynchronous on ``stream`` (default: torch's
+        current stream).  Returns an (n, 4) int32 device tensor of rows overlap, travel, contact, flags (PLACED_BLOCKED,
+        PLACED_INVALID); the pieces' device words must stay alive until the call has run."""
+        import torch
+        if not hasattr(placements, "data_ptr"):
+            placements = torch.from_numpy(_placements_np(placements)).to("cuda:%d" % self.device)
+        if placements.dtype != torch.int32 or placements.dim() != 2 or placements.shape[1] != 6:
+            raise ValueError("placements must be an (n, 6) int32 tensor: piece, origin[3], axis, dist")
+        pl = placements.contiguous()
+        keep, arr = self._piece_descs(pieces, host=False)
+        out = torch.empty((pl.shape[0], 4), dtype=torch.int32, device=pl.device)
+        N.check(self._L.vxrt_place_pieces(self._h, arr if len(pieces) else None, len(pieces), _ptr(pl) if pl.shape[0] else None,
+                                          pl.shape[0], _ptr(out) if pl.shape[0] else None, _stream(stream)))
+        out._vxrt_keep = (keep, pl)  # the launch reads them after this call returns
+        return out
+
+    def place_pieces_host(self, pieces, placements) -> np.ndarray:
+        """place_pieces through the synchronous host call (vxrt_place_pieces_host): numpy in, a PLACED_DTYPE array out."""
+        pl = _placements_np(placements)
+        keep, arr = self._piece_descs(pieces, host=True)
+        out = np.zeros((len(pl), 4), np.int32)
+        N.check(self._L.vxrt_place_pieces_host(self._h, arr if len(pieces) else None, len(pieces), pl.ctypes.data if len(pl) else None,
+                                               len(pl), out.ctypes.data if len(pl) else None))
+        del keep
+        return out.view(PLACED_DTYPE).reshape(-1)
+
+    def drop_islands(self, origin, dims, anchors: int = N.ISLAND_ANCHOR_FACES | N.ISLAND_ANCHOR_FLOOR, max_islands: int = 4096):
+        """Let the islands of the box ``origin`` .. ``origin + dims - 1`` fall and land instead of deleting them:
+          1. find_islands with labels; 2. if the island table was cut short (more than ``max_islands`` islands) or an island's
+          box exceeds the piece limits (PLACE_MAX_DIM per axis, PLACE_MAX_VOXELS), raise ValueError before any change;
+          3. one STAMP_SUBTRACT stamp of the floating bits, exactly as collapse_islands; 4. the islands in ascending
+          (lo[1], id): the island's piece is the bits of labels == id over its box lo .. hi, placed at lo with axis 1 and
+          dist = -min(lo[1], PLACE_MAX_DIST), then written back with one STAMP_UNION stamp at lo + (0, travel, 0).
+        Later islands land on earlier ones: a deterministic sequential rule, not a physics engine.  An island that starts
+        overlapping one that has already landed merges with it (the sweep ignores the overlap at the start), and the cost
+        is one synchronising edit per island.  Returns a DROP_DTYPE array, one row (id, voxels, travel, contact) per island in
+        dropping order."""
+        import torch
+        isl = self.find_islands(origin, dims, anchors, labels=True, max_islands=max_islands)
+        if isl.summary.islands > len(isl.table):
+            raise ValueError("drop_islands: %d islands, table of %d" % (isl.summary.islands, len(isl.table)))
+        for r in isl.table:
+            ext = [int(h) - int(l) for l, h in zip(r["lo"], r["hi"])]
+            if max(ext) > N.PLACE_MAX_DIM or ext[0] * ext[1] * ext[2] > N.PLACE_MAX_VOXELS:
+                raise ValueError("drop_islands: island %d is beyond the piece limits" % int(r["id"]))
+        rows = np.zeros(len(isl.table), DROP_DTYPE)
+        if not len(isl.table):
+            return rows
+        self.edit_stamps([Stamp(isl.origin, isl.floating, N.STAMP_SUBTRACT, isl.dims)])
+        X, Y, Z = isl.dims
+        lab = isl.labels.view(Z, Y, X)
+        order = sorted(range(len(isl.table)), key=lambda k: (int(isl.table[k]["lo"][1]), int(isl.table[k]["id"])))
+        for n, k in enumerate(order):
+            r = isl.table[k]
+            lo, hi = [int(v) for v in r["lo"]], [int(v) for v in r["hi"]]
+            a = [lo[j] - isl.origin[j] for j in range(3)]
+            e = [hi[j] - lo[j] for j in range(3)]
+            ident = int(np.uint32(r["id"]).view(np.int32))
+            grid = (lab[a[2]: a[2] + e[2], a[1]: a[1] + e[1], a[0]: a[0] + e[0]] == ident).permute(2, 1, 0).cpu().numpy()
+            piece = Piece(torch.from_numpy(pack_region(grid).view(np.int32)).to(lab.device), tuple(e))
+            res = self.place_pieces([piece], [Placement(0, tuple(lo), 1, -min(lo[1], N.PLACE_MAX_DIST))]).cpu().numpy()[0]
+            travel = int(res[1])
+            self.edit_stamps([Stamp((lo[0], lo[1] + travel, lo[2]), piece.bits, N.STAMP_UNION, piece.dims)])
+            rows[n] = (int(r["id"]), int(r["voxels"]), travel, int(np.int32(res[2]).view(np.uint32)))
+        return rows
+
     # ---- navigation fields (extension, include/vxrt.h) ----------------------------------------------------------------
     def nav_field(self, origin, dims, goals, agent: "NavAgent | None" = None, max_dist: int = 1 << 24, dist: bool = True,
                   stream: int | None = None) -> "NavField":
@@ -960,6 +1061,33 @@ class Body:
     @staticmethod
     def pack(bodies) -> np.ndarray:
         return np.stack([b.row() for b in bodies]) if len(bodies) else np.zeros((0, 9), np.float32)
+
+
+@dataclass
+class Piece:
+    """A rigid voxel piece (include/vxrt.h, vxrt_piece): ``bits`` a bool [x, y, z] numpy grid (packed on the host as
+    edit_stamps packs a stamp), or region words (a device tensor, or a uint32 numpy array) with ``dims`` given."""
+    bits: object
+    dims: tuple | None = None
+
+
+class Placement(NamedTuple):
+    """vxrt_placement: piece index, the world voxel of the piece's voxel (0, 0, 0), the sweep's axis and signed distance"""
+    piece: int
+    origin: tuple
+    axis: int = 1
+    dist: int = 0
+
+
+PLACED_DTYPE = np.dtype([("overlap", "<u4"), ("travel", "<i4"), ("contact", "<u4"), ("flags", "<u4")])  # vxrt_placed
+DROP_DTYPE = np.dtype([("id", "<u4"), ("voxels", "<u4"), ("travel", "<i4"), ("contact", "<u4")])  # drop_islands rows
+
+
+def _placements_np(placements) -> np.ndarray:
+    if isinstance(placements, (list, tuple)):
+        placements = [[p.piece, *p.origin, p.axis, p.dist] if isinstance(p, Placement) else list(p) for p in placements]
+    pl = np.ascontiguousarray(np.asarray(placements, np.int64).reshape(-1, 6).astype(np.int32))
+    return pl
 
 
 ISLAND_DTYPE = np.dtype([("id", "<u4"), ("voxels", "<u4"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])  # vxrt_island
