@@ -886,8 +886,37 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  * frame number and flags.  `flags` applies to all views; its frame_number, d_color_aov, d_hit_aov and d_tile_order
  * are ignored (per-view members below).  1 <= n_views <= 16.  Launches issued on different streams may also be in
  * flight together: up to 64 launches (16 of them multi-view) per context share no state; the call that would exceed that
- * waits on the host for the oldest launch to finish before it reuses its queue head / view slot.  (Inside a stream capture
- * nothing can be waited for: the capturing caller keeps within those limits.)  Host calls on a context stay serialised. */
+ * waits on the host for the oldest launch to finish before it reuses its queue head / view slot.  Host calls on a context
+ * stay serialised.
+ *
+ * STREAM CAPTURE (hipStreamBeginCapture on `stream`; tests/test_gpu_capture.py captures in the strictest, global mode and
+ * holds the sentences below to the references of the eager paths).
+ *   May be captured: vxrt_render, vxrt_render_views and vxrt_trace_batch without stats; vxrt_deinterleave_strips and
+ *     vxrt_deinterleave_views; and the purely stream-ordered queries vxrt_read_region, vxrt_move_boxes, vxrt_overlap_boxes,
+ *     vxrt_distance_field, vxrt_light_field, vxrt_extract_surface, vxrt_downsample_region and vxrt_find_islands.  Under
+ *     capture they allocate nothing, wait for nothing and read no host memory after they return: a captured multi-view
+ *     launch stores its views from kernel arguments, which the graph owns.  Every replay gives what the eager call gives.
+ *   Refused under capture, with VXRT_ERR_INVALID and a message that names capture: a render launch with frame_number < 0, in
+ *     the flags of vxrt_render or in any view of vxrt_render_views (the graph would bake the context counter's value of the
+ *     moment: pass explicit frame numbers); vxrt_trace_batch with stats_or_null != NULL and vxrt_nav_field (both synchronise
+ *     with the host); and vxrt_render_views on a context that has never issued a multi-view launch -- the view slots are
+ *     allocated by the first one, so issue one multi-view launch before capturing (the warm-up rule).  A refusal comes before
+ *     anything is enqueued and moves neither the frame counter nor the rings: the capture stays valid and goes on.
+ *   collect_stats is allowed: the counters grow once per replay, and vxrt_frame_stats_get after the replays reads them.
+ *   What a replay sees.  A graph bakes the ADDRESSES of the world tables, not their contents.  vxrt_edit_voxels and
+ *     vxrt_edit_stamps that do not grow the pool change the tables in place (the cell table and the coarse bits never move;
+ *     only pool growth moves the pool), so later replays see the edited world: reserve with vxrt_edit_reserve before
+ *     capturing and check vxrt_edit_stats.pool_capacity.  After pool growth, vxrt_upload_world, vxrt_build_world_procedural,
+ *     vxrt_load_world or any vxrt_stream_* call the old tables are freed: every graph captured before must be captured again.
+ *     The environment, the FOV and the ortho window are baked as they were at capture; later vxrt_set_* calls reach only
+ *     later launches.
+ *   Keeping within the limits.  Inside a capture nothing can be waited for or recorded, so the in-flight limits above are
+ *     the caller's: a graph bakes the queue head (and, multi-view, the view slot) its launch took from the rings, resets and
+ *     fills them with nodes of its own at every replay, and holds them for the duration of the replay.  Its replays must be
+ *     ordered -- on the same stream, or by events -- with each other and with the context's other launches; then any number
+ *     of eager launches may come between capture and replay.
+ *   Outside the contract: every other call that takes a stream (vxrt_place_pieces, vxrt_voxelize_mesh, vxrt_nav_paths) and
+ *     every call that takes none. */
 typedef struct vxrt_view {
     void *d_fb;             /* W*H*4 bytes BGRA8 (or the compact size) */
     float origin[3], fwd[3], up[3], right[3];

@@ -284,15 +284,21 @@ int adopt_world(vxrt_ctx* c, int factor, const int cd[3], uint64_t nslots, uint3
 int set_error(int code, const char* msg) { return fail(code, msg); }
 void abandon_world(vxrt_ctx* c) { free_world(c); }
 
-// Take ring entry `i`: if the launch that used it last has not finished, wait for it (the documented in-flight limits are
-// enforced here instead of silently sharing a queue head).  Inside a stream capture nothing can be waited for or
-// recorded: the capturing caller keeps within the limits itself.
-static hipError_t ring_acquire(hipEvent_t& ev, hipStream_t stream, bool& capturing)
+// Whether `stream` is being captured into a graph (include/vxrt.h, "Stream capture"); asked once per call.  The NULL
+// stream is never asked: it cannot be captured, and asking while another stream captures is itself an error.
+static bool stream_capturing(hipStream_t stream)
 {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (stream && hipStreamIsCapturing(stream, &cs) != hipSuccess)
         (void)hipGetLastError();
-    capturing = cs != hipStreamCaptureStatusNone;
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// Take ring entry `i`: if the launch that used it last has not finished, wait for it (the documented in-flight limits are
+// enforced here instead of silently sharing a queue head).  Inside a stream capture nothing can be waited for or
+// recorded: the capturing caller keeps within the limits itself.
+static hipError_t ring_acquire(hipEvent_t& ev, bool capturing)
+{
     if (capturing || !ev)
         return hipSuccess;
     hipError_t e = hipEventQuery(ev);
@@ -311,6 +317,15 @@ static hipError_t ring_release(hipEvent_t& ev, hipStream_t stream, bool capturin
             return e;
     }
     return hipEventRecord(ev, stream);
+}
+
+// One view's arguments stored to its place in a device view slot: what a CAPTURED multi-view launch issues instead of the
+// copy from host memory.  Kernel arguments are copied into the graph's node, so every replay writes what the capture
+// saw and reads no host memory (a captured hipMemcpyAsync keeps the host pointer).  One lane, about 1.1 KB.
+__global__ void k_store_view(ViewArgs v, ViewArgs* dst)
+{
+    if (threadIdx.x == 0)
+        *dst = v;
 }
 
 // Default hand-out order of the persistent kernel's tile queue: expected-longest ray chains first, so that what is
@@ -776,6 +791,14 @@ static int render_launch(vxrt_ctx* c, uint32_t width, uint32_t height, unsigned 
         return fail(VXRT_ERR_INVALID, "d_accum must be 16-byte aligned");
     VX_HIP(hipSetDevice(c->device));
     hipStream_t stream = (hipStream_t)fl->stream;
+    const bool capturing = vxrt::stream_capturing(stream);
+    if (capturing) {  // (include/vxrt.h, "Stream capture": refused before anything is enqueued or counted)
+        for (unsigned v = 0; v < n; ++v)
+            if (views[v].frame_number < 0)
+                return fail(VXRT_ERR_INVALID, "stream capture: frame_number < 0 would bake the context's frame counter into the graph; pass an explicit frame_number");
+        if (nviews != 0 && c->kernel_variant != 1 && !c->d_views)
+            return fail(VXRT_ERR_INVALID, "stream capture: the context's view slots are allocated by its first multi-view launch; issue one vxrt_render_views launch before capturing");
+    }
 
     vxrt::RenderArgs A;
     memset(&A, 0, sizeof(A));
@@ -858,8 +881,7 @@ static int render_launch(vxrt_ctx* c, uint32_t width, uint32_t height, unsigned 
             if (schedule && !A.tile_order)
                 vxrt::schedule_tile_rows(A, A.fwd, A.up, A.row_order, A.row_order_n);
             const unsigned slot = c->launch_seq.fetch_add(1u) % kTileCounterRing;
-            bool capturing = false;
-            VX_HIP(vxrt::ring_acquire(c->counter_busy[slot], stream, capturing));
+            VX_HIP(vxrt::ring_acquire(c->counter_busy[slot], capturing));
             A.tile_counter = c->d_queues + (size_t)slot * vxrt::kQueueWords;
             VX_HIP(vxrt::launch_render(A, fl->collect_stats != 0, c->kernel_variant, stream));
             VX_HIP(hipGetLastError());
@@ -888,11 +910,16 @@ static int render_launch(vxrt_ctx* c, uint32_t width, uint32_t height, unsigned 
             vxrt::schedule_tile_rows(A, S.fwd, S.up, S.row_order, S.row_order_n);
     }
     const unsigned vslot = c->view_seq.fetch_add(1u) % kViewSlots, cslot = c->launch_seq.fetch_add(1u) % kTileCounterRing;
-    bool capturing = false, capturing2 = false;
-    VX_HIP(vxrt::ring_acquire(c->views_busy[vslot], stream, capturing));
-    VX_HIP(vxrt::ring_acquire(c->counter_busy[cslot], stream, capturing2));
+    VX_HIP(vxrt::ring_acquire(c->views_busy[vslot], capturing));
+    VX_HIP(vxrt::ring_acquire(c->counter_busy[cslot], capturing));
     vxrt::ViewArgs* slot = c->d_views + (size_t)vslot * vxrt::kMaxViews;
-    VX_HIP(hipMemcpyAsync(slot, host.data(), sizeof(vxrt::ViewArgs) * n, hipMemcpyHostToDevice, stream));
+    if (!capturing) {
+        VX_HIP(hipMemcpyAsync(slot, host.data(), sizeof(vxrt::ViewArgs) * n, hipMemcpyHostToDevice, stream));
+    } else {  // a graph owns what its replays read: the views travel as kernel arguments, not through `host`
+        for (unsigned v = 0; v < n; ++v)
+            hipLaunchKernelGGL(vxrt::k_store_view, dim3(1), dim3(64), 0, stream, host[v], slot + v);
+        VX_HIP(hipGetLastError());
+    }
     A.views = slot;
     A.nviews = n;
     A.tile_counter = c->d_queues + (size_t)cslot * vxrt::kQueueWords;
@@ -1021,6 +1048,9 @@ int vxrt_trace_batch(vxrt_ctx* c, const float* d_origins, const float* d_dirs, u
         return fail(VXRT_ERR_NO_WORLD, "no world resident");
     VX_HIP(hipSetDevice(c->device));
     hipStream_t stream = (hipStream_t)stream_;
+    const bool capturing = vxrt::stream_capturing(stream);
+    if (capturing && stats)  // (include/vxrt.h, "Stream capture": refused before anything is enqueued or counted)
+        return fail(VXRT_ERR_INVALID, "stream capture: a batch with stats synchronises with the host; pass stats_or_null = NULL and read vxrt_frame_stats_get after the replays");
     vxrt::BatchArgs B;
     memset(&B, 0, sizeof(B));
     B.W = c->view;
@@ -1034,8 +1064,7 @@ int vxrt_trace_batch(vxrt_ctx* c, const float* d_origins, const float* d_dirs, u
     B.voxel = (long long*)d_voxel;
     B.stats = c->d_stats;
     const unsigned tslot = c->launch_seq.fetch_add(1u) % kTileCounterRing;
-    bool capturing = false;
-    VX_HIP(vxrt::ring_acquire(c->counter_busy[tslot], stream, capturing));
+    VX_HIP(vxrt::ring_acquire(c->counter_busy[tslot], capturing));
     B.ticket = c->d_queues + (size_t)tslot * vxrt::kQueueWords;
     B.persistent_waves = c->persistent_waves;
     B.max_steps = c->batch_max_steps;
@@ -2188,6 +2217,8 @@ int vxrt_nav_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], 
     if (int rc = nav_ready(c, origin, dims, agent, n_goals, max_dist))
         return rc;
     VX_HIP(hipSetDevice(c->device));
+    if (vxrt::stream_capturing((hipStream_t)stream))  // (include/vxrt.h, "Stream capture": refused before anything is enqueued)
+        return fail(VXRT_ERR_INVALID, "stream capture: vxrt_nav_field reads a termination flag on the host every few levels and cannot be captured");
     VX_HIP(vxrt::nav_field(vxrt::query_world(c), origin, dims, *agent, d_goals, n_goals, max_dist, d_work, d_walkable, d_next,
                            d_dist_or_null, d_summary, (hipStream_t)stream));
     return VXRT_OK;
