@@ -50,6 +50,12 @@
 // anchored as kind 4: each island falls along -y until it lands, lowest first) and prints one line "drop before frame N: I
 // islands, V island voxels, M moved, max_fall F, sum_contact C", then one line "drop hash frame N rows .." with the 64-bit
 // FNV-1a hash of the rows' bytes (id, voxels, travel, contact: 16 bytes each, in dropping order).
+// A line "frame denoise iterations color_scale" switches the frame denoiser on from that frame (vxrt_frame_guides +
+// vxrt_denoise_frame; "frame denoise 0" switches it off again): such a frame is rendered through vxrt_render with the colour
+// and hit-index AOVs, its guide keys are computed and the filtered colour replaces the frame -- the dumped PPMs are the
+// denoised frames -- with one line "denoise frame N iterations .. color_scale .. hit .. faces .. hash .." (hit pixels, distinct
+// keys, the 64-bit FNV-1a hash of the BGRA frame).  Whole frames only: shaded=0 or 2, views_per_launch=1, frames_in_flight=1.
+// The AOVs, the keys and the workspace are allocated once.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -97,6 +103,11 @@ int main(int argc, char** argv)
         vxrt_edit_op op;
     };
     std::vector<EditLine> edits;
+    struct DenoiseLine {
+        int frame, iterations;
+        float color_scale;
+    };
+    std::vector<DenoiseLine> denoise_lines;
     if (argc > 12 && std::string(argv[12]) != "-") {
         std::ifstream in(argv[12]);
         if (!in) {
@@ -109,6 +120,11 @@ int main(int argc, char** argv)
             if (hash != std::string::npos)
                 line.resize(hash);
             EditLine e{};
+            DenoiseLine dl{0, 0, 0.0f};
+            if (std::sscanf(line.c_str(), "%d denoise %d %f", &dl.frame, &dl.iterations, &dl.color_scale) >= 2) {
+                denoise_lines.push_back(dl);
+                continue;
+            }
             if (std::sscanf(line.c_str(), "%d %d %d %d %d %d %d %d %d", &e.frame, &e.op.kind, &e.op.value, &e.op.a[0], &e.op.a[1],
                             &e.op.a[2], &e.op.b[0], &e.op.b[1], &e.op.b[2]) == 9)
                 edits.push_back(e);
@@ -529,13 +545,74 @@ int main(int argc, char** argv)
         for (auto p : d_views)
             (void)hipFree(p);
     }
+    // the frame denoiser's buffers: colour AOV, hit-index AOV, keys, workspace -- allocated once, when the script asks for it
+    float* d_color = nullptr;
+    int64_t* d_hit = nullptr;
+    uint32_t* d_keys = nullptr;
+    void* d_dn_work = nullptr;
+    if (!denoise_lines.empty()) {
+        const size_t n = (size_t)width * height;
+        if (batch > 1 || in_flight >= 2 || shade_mode == 1 || vxrt_denoise_workspace_bytes(width, height) == 0) {
+            std::cerr << "denoise: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
+            return 2;
+        }
+        if (hipMalloc((void**)&d_color, n * 12) != hipSuccess || hipMalloc((void**)&d_hit, n * 8) != hipSuccess ||
+            hipMalloc((void**)&d_keys, n * 4) != hipSuccess ||
+            hipMalloc(&d_dn_work, vxrt_denoise_workspace_bytes(width, height)) != hipSuccess)
+            return 1;
+    }
+    vxrt_denoise_params dn{sizeof(vxrt_denoise_params), 0, 0.0f, 0};
     for (int i = 0; batch <= 1 && in_flight < 2 && i < nframes; ++i) {
         apply_edits(i, i + 1);
+        for (const DenoiseLine& l : denoise_lines)
+            if (l.frame == i) {
+                dn.iterations = l.iterations;
+                dn.color_scale = l.color_scale;
+            }
         pose_for(i);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
-        RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);
+        if (dn.iterations > 0) {
+            // the frame with its AOVs through the C ABI (the facade's RenderScreen has no AOV arguments), then keys and filter
+            vxrt_ctx* c = raytracer->Context();
+            const float o[3] = {cam_pos.x, cam_pos.y, cam_pos.z}, f[3] = {cam_forward.x, cam_forward.y, cam_forward.z},
+                        u[3] = {cam_up.x, cam_up.y, cam_up.z}, r[3] = {cam_right.x, cam_right.y, cam_right.z};
+            const float L[3] = {env.LightDirection.x, env.LightDirection.y, env.LightDirection.z}, C[3] = {2, 2, 2}, A[3] = {0.5f, 0.5f, 0.5f};
+            vxrt_render_flags fl;
+            vxrt_render_flags_default(&fl);
+            fl.mode = shaded ? VXRT_MODE_SHADED : VXRT_MODE_DEBUG;
+            fl.shadow = shaded;
+            fl.bounce_samples = shaded ? 1 : 0;
+            fl.d_color_aov = d_color;
+            fl.d_hit_aov = d_hit;
+            if (vxrt_set_environment(c, L, C, A) != VXRT_OK || vxrt_set_fov(c, 90) != VXRT_OK || vxrt_set_ortho_window_size(c, 10, 10) != VXRT_OK ||
+                vxrt_render(c, width, height, d_pixels, o, f, u, r, &fl) != VXRT_OK ||
+                vxrt_frame_guides(c, width, height, o, f, u, r, 0, d_hit, d_keys, nullptr) != VXRT_OK ||
+                vxrt_denoise_frame(c, width, height, d_color, d_keys, &dn, d_dn_work, d_color, d_pixels, nullptr) != VXRT_OK ||
+                vxrt_synchronize(c) != VXRT_OK) {
+                std::cerr << "denoise, frame " << i << ": " << vxrt_last_error() << std::endl;
+                return 3;
+            }
+        } else {
+            RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);
+        }
         (void)hipMemcpy(pixels.data(), d_pixels, pixels.size() * sizeof(BGRA8888), hipMemcpyDeviceToHost);
+        if (dn.iterations > 0) {
+            std::vector<uint32_t> keys((size_t)width * height);
+            (void)hipMemcpy(keys.data(), d_keys, keys.size() * 4, hipMemcpyDeviceToHost);
+            size_t hit = 0;
+            std::map<uint32_t, int> faces;
+            for (uint32_t k : keys)
+                if (k) {
+                    ++hit;
+                    faces[k] = 1;
+                }
+            uint64_t h = 0xcbf29ce484222325ull;
+            for (size_t b = 0; b < pixels.size() * sizeof(BGRA8888); ++b)
+                h = (h ^ ((const unsigned char*)pixels.data())[b]) * 0x100000001b3ull;
+            std::printf("denoise frame %d iterations %d color_scale %g hit %zu faces %zu hash %016llx\n", i, dn.iterations,
+                        (double)dn.color_scale, hit, faces.size(), (unsigned long long)h);
+        }
         auto f1 = std::chrono::high_resolution_clock::now();
         double td = std::chrono::duration_cast<std::chrono::microseconds>(f1 - f0).count() / 1000.0;
         avgFrameTime = i == 0 ? td : avgFrameTime * 0.9 + td * 0.1;
@@ -567,6 +644,10 @@ int main(int argc, char** argv)
         (void)hipEventDestroy(copied[k]);
     }
     (void)hipStreamDestroy(copy_stream);
+    (void)hipFree(d_color);
+    (void)hipFree(d_hit);
+    (void)hipFree(d_keys);
+    (void)hipFree(d_dn_work);
     (void)hipFree(d_pixels);
     delete raytracer;
     return 0;

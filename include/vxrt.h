@@ -893,7 +893,8 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  * holds the sentences below to the references of the eager paths).
  *   May be captured: vxrt_render, vxrt_render_views and vxrt_trace_batch without stats; vxrt_deinterleave_strips and
  *     vxrt_deinterleave_views; and the purely stream-ordered queries vxrt_read_region, vxrt_move_boxes, vxrt_overlap_boxes,
- *     vxrt_distance_field, vxrt_light_field, vxrt_extract_surface, vxrt_downsample_region and vxrt_find_islands.  Under
+ *     vxrt_distance_field, vxrt_light_field, vxrt_extract_surface, vxrt_downsample_region and vxrt_find_islands; and the
+ *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame.  Under
  *     capture they allocate nothing, wait for nothing and read no host memory after they return: a captured multi-view
  *     launch stores its views from kernel arguments, which the graph owns.  Every replay gives what the eager call gives.
  *   Refused under capture, with VXRT_ERR_INVALID and a message that names capture: a render launch with frame_number < 0, in
@@ -951,6 +952,58 @@ int vxrt_deinterleave_strips(vxrt_ctx *ctx, uint32_t width, uint32_t height, int
 int vxrt_deinterleave_views(vxrt_ctx *ctx, uint32_t width, uint32_t height, int32_t strip_rows, int32_t strip_count,
                             const void *d_shards, uint64_t shard_stride_bytes, uint64_t view_stride_bytes,
                             uint32_t n_views, void *d_fb, uint64_t fb_stride_bytes, void *stream);
+
+/* ---- frame denoiser -- an EXTENSION (the reference's to-do item "Proper indirect lighting (denoise, temporal accumulation,
+ * ...)", README.md:19; its screenshots are captioned "no denoise"): an edge-avoiding a-trous filter over the colour AOV of a
+ * frame, guided by the voxel face every pixel shows.  Every surface of this renderer is an axis-aligned voxel face, so "the
+ * same surface" is an exact integer predicate and the filter is specified bit for bit.  A post-process of two calls over
+ * buffers the renderer already writes (vxrt_render_flags.d_color_aov and d_hit_aov); the render launches know nothing of it.
+ *   Frames.  Whole frames only: 1 <= W, H <= 65535 and W * H <= 2^26, pixel (x, y) at index x + W * y.  Strips, compact
+ *     shards and checkerboard frames are outside the contract (their AOVs hold some of the frame's pixels only).
+ *   Guide keys (vxrt_frame_guides).  d_keys[i] is 0 for a miss, else 1<<31 | axis<<26 | toward<<25 | plane with axis 0 .. 2 and
+ *     plane < 2^25.  The world sits at the origin with unit voxels; X, Y, Z are its voxel extents (at most 2^24 each).  A hit
+ *     index h = x + X * (y + Y * z) in 0 .. X*Y*Z - 1 names the voxel v; -1 and every index outside that range give key 0.
+ *     (o, d) is the pixel's primary ray exactly as vxrt_render forms it for the same W, H, camera vectors and `ortho` flag,
+ *     under the context's FOV and ortho window at the time of the call.  For each axis k with d[k] != 0: p[k] = d[k] > 0 ?
+ *     v[k] : v[k] + 1 and t[k] = (p[k] - o[k]) / d[k], one binary32 subtraction and one IEEE division; an axis with d[k] == 0
+ *     has t[k] = -inf (and p[k] = v[k] + 1).  axis = the first k with the largest t[k], toward = d[axis] > 0, plane = p[axis].
+ *     This is the face of the voxel's box that the ray enters, defined by this rule alone and not by the tracer's normal.
+ *     The call reads the hit AOV and the world's extents, no world table.
+ *   Filter (vxrt_denoise_frame).  h = (3/8, 1/4, 1/16) for |offset| = 0, 1, 2.  Iteration i = 0 .. iterations - 1 has step
+ *     s = 2^i and maps colour c_i to c_{i+1}, c_0 = d_color_in.  A pixel p with key 0 is copied.  Otherwise, with sw = 0 and
+ *     sc = (0, 0, 0), for dy = -2 .. 2 (outer loop) and dx = -2 .. 2 (inner loop) let q = p + s * (dx, dy); q is skipped when
+ *     it lies outside the frame or key(q) != key(p); else
+ *         w = h[|dx|] * h[|dy|]
+ *         if color_scale > 0:  e = c_i(q) - c_i(p) per channel;  d2 = (e.r*e.r + e.g*e.g) + e.b*e.b;
+ *                              t = 1 - d2 * color_scale;  w = w * (t > 0 ? t : 0)
+ *         sw += w;  sc.ch += w * c_i(q).ch for each channel
+ *     and c_{i+1}(p) = sc / sw, three IEEE divisions (the centre tap keeps sw > 0 for finite colours and color_scale).  All
+ *     operations are binary32, in this order, without contraction.  The last iteration is stored to d_color_out and, when
+ *     d_fb_or_null is given, as a BGRA8 pixel by the rule of the render launches (clamp to 0 .. 1, * 255, truncate; bytes
+ *     b, g, r, 255).  d_color_in may be the colour AOV of an accumulated frame (d_accum): the filter then works on the mean.
+ *     d_color_out may be d_color_in.  d_work, d_keys and the outputs must not overlap otherwise.
+ *   Workspace.  d_work holds vxrt_denoise_workspace_bytes(W, H) = 2 * W * H * 16 bytes (two buffers of one 16-byte record
+ *     {r, g, b, key} per pixel; 0 outside the limits on W and H), 16-byte aligned.  The caller owns it.
+ *   Call rules.  Both calls are asynchronous on `stream`, allocate nothing, wait for nothing and read no host memory after
+ *     they return; both may be captured (STREAM CAPTURE above).  Refusals, each VXRT_ERR_INVALID before anything is enqueued
+ *     or written, checked in this order: a NULL ctx; no world resident (vxrt_frame_guides only); W or H outside the limits;
+ *     params NULL or its struct_size; iterations outside 1 .. 6; a color_scale that is negative or NaN; a NULL origin, fwd,
+ *     up, right, d_hit_aov or d_keys (guides), a NULL d_color_in, d_keys, d_work or d_color_out (filter); a world axis longer
+ *     than 2^24 voxels (guides).
+ *   The cost is one launch for the keys and one per iteration: an iteration reads 25 records per filtered pixel, lanes
+ *     along x, and writes one; the first reads the float3 colours and the keys instead, the last writes float3 and BGRA8. */
+typedef struct vxrt_denoise_params {
+    uint32_t struct_size;
+    int32_t iterations;   /* 1 .. 6 */
+    float color_scale;    /* k >= 0; 0 = no colour stop */
+    int32_t reserved_;
+} vxrt_denoise_params;
+int vxrt_frame_guides(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float origin[3], const float fwd[3], const float up[3],
+                      const float right[3], int32_t ortho, const int64_t *d_hit_aov, uint32_t *d_keys, void *stream);
+uint64_t vxrt_denoise_workspace_bytes(uint32_t W, uint32_t H); /* 2 * W * H * 16; 0 outside the contract */
+int vxrt_denoise_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color_in /* W*H*3 */, const uint32_t *d_keys,
+                       const vxrt_denoise_params *params, void *d_work, float *d_color_out /* W*H*3, may alias d_color_in */,
+                       void *d_fb_or_null /* BGRA8 */, void *stream);
 
 /* ---- batch query.  Replaces VoxelRaytracer3D::Raytrace + kernel dispatch
  * (VoxelRT/VolumeRaytracer.cu:95-117,574-618).  Results follow the reference

@@ -34,6 +34,7 @@ EXPORTS = [
     "vxrt_surface_workspace_bytes", "vxrt_extract_surface", "vxrt_extract_surface_host",
     "vxrt_lod_workspace_bytes", "vxrt_downsample_region", "vxrt_downsample_region_host",
     "vxrt_light_workspace_bytes", "vxrt_light_field", "vxrt_light_field_host",
+    "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
@@ -123,6 +124,10 @@ class RenderFlags(C.Structure):
         ("d_color_aov", C.c_void_p), ("d_hit_aov", C.c_void_p), ("d_tile_order", C.c_void_p), ("stream", C.c_void_p),
         ("d_accum", C.c_void_p), ("accum_reset", C.c_int32), ("reserved_", C.c_int32),
     ]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("color_scale", C.c_float), ("reserved_", C.c_int32)]
 
 
 class View(C.Structure):
@@ -262,6 +267,11 @@ def load() -> C.CDLL:
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_light_field_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_void_p]
+    L.vxrt_frame_guides.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, f3, f3, f3, f3, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_denoise_workspace_bytes.restype = C.c_uint64
+    L.vxrt_denoise_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    L.vxrt_denoise_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

@@ -2,6 +2,7 @@
 // Owns the HBM-resident world tables, the camera/lighting state the reference keeps in
 // process globals (hFrameInfo / g_env, VoxelRT/Renderer.cu:24-25,89) and the launches.
 #include "../../include/vxrt.h"
+#include "vxrt_denoise.hpp"
 #include "vxrt_dist.hpp"
 #include "vxrt_light.hpp"
 #include "vxrt_edit.hpp"
@@ -81,6 +82,9 @@ hipError_t voxelize_mesh(const int32_t* verts, uint32_t nv, const uint32_t* tris
 hipError_t extract_surface(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t mode, void* work, vxrt_quad* quads,
                            uint32_t capacity, int32_t* verts, uint32_t* tris, vxrt_surface_summary* summary, hipStream_t stream);
 // occupancy LOD (vxrt_lod.hip)
+hipError_t frame_guides(const RenderArgs& R, uint32_t Z, uint32_t* keys, hipStream_t stream);
+hipError_t denoise_frame(uint32_t W, uint32_t H, const float* color_in, const uint32_t* keys, int32_t iterations, float k,
+                         void* work, float* color_out, void* fb, hipStream_t stream);
 hipError_t downsample_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t shift, uint32_t threshold,
                              void* work, uint32_t* bits, uint16_t* counts, vxrt_lod_summary* summary, hipStream_t stream);
 }  // namespace vxrt
@@ -758,6 +762,24 @@ uint32_t vxrt_compact_rows(uint32_t height, int32_t strip_rows, int32_t strip_co
     return rows;
 }
 
+// What camera_ray (vxrt_camera.hpp) reads of a launch besides the view: the frame size and getRayDirection's per-pixel
+// constants (Renderer.cu:46,50-52), hoisted to the host.  One place for the render launches and vxrt_frame_guides, whose keys
+// are defined by the renderer's own primary rays.
+static void camera_args(const vxrt_ctx* c, uint32_t width, uint32_t height, vxrt::RenderArgs& A)
+{
+    A.width = width;
+    A.height = height;
+    float aspect = (float)width / (float)height;
+    float fov = (float)((double)c->fov * 3.1415 / 180.0);
+    A.kx = tanf(fov / 2.0f) * aspect;
+    A.ky = tanf(fov / 2.0f);
+    A.ratio = (float)width / (float)height;
+    A.ortho_x = c->ortho[0];
+    A.ortho_y = c->ortho[1];
+    A.inv_width = 1.0f / (float)(int)width;
+    A.inv_height = 1.0f / (float)(int)height;
+}
+
 // one launch for `nviews` views; nviews == 0: the single view `views[0]` through the single-view kernel arguments
 static int render_launch(vxrt_ctx* c, uint32_t width, uint32_t height, unsigned nviews, const vxrt_view* views,
                          const vxrt_render_flags* fl)
@@ -803,17 +825,7 @@ static int render_launch(vxrt_ctx* c, uint32_t width, uint32_t height, unsigned 
     vxrt::RenderArgs A;
     memset(&A, 0, sizeof(A));
     A.W = c->view;
-    A.width = width;
-    A.height = height;
-    {   // getRayDirection's per-pixel constants (Renderer.cu:46,50-52), hoisted to the host
-        float aspect = (float)width / (float)height;
-        float fov = (float)((double)c->fov * 3.1415 / 180.0);
-        A.kx = tanf(fov / 2.0f) * aspect;
-        A.ky = tanf(fov / 2.0f);
-        A.ratio = (float)width / (float)height;
-        A.ortho_x = c->ortho[0];
-        A.ortho_y = c->ortho[1];
-    }
+    camera_args(c, width, height, A);
     A.light_dir = vxrt::f3{c->light_dir[0], c->light_dir[1], c->light_dir[2]};
     {   // unit3() of vxrt_device.hpp on the host: v * (1 / sqrt(dot(v, v))), binary32 throughout, no contraction
         const float lx = c->light_dir[0], ly = c->light_dir[1], lz = c->light_dir[2];
@@ -829,8 +841,6 @@ static int render_launch(vxrt_ctx* c, uint32_t width, uint32_t height, unsigned 
     A.shadow = fl->shadow ? 1 : 0;
     A.bounce_samples = fl->bounce_samples < 0 ? 0 : fl->bounce_samples;
     A.bounce_samples_f = (float)A.bounce_samples;
-    A.inv_width = 1.0f / (float)(int)width;
-    A.inv_height = 1.0f / (float)(int)height;
     A.inv_bounce_samples = A.bounce_samples > 0 ? 1.0f / A.bounce_samples_f : 0.0f;
     A.bounce_all_hits = fl->bounce_all_hits ? 1 : 0;
     A.bounce_depth = fl->bounce_depth >= 2 ? 2 : 1;
@@ -2600,6 +2610,62 @@ int vxrt_light_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t di
     VX_HIP(hipMemcpy(summary, T.at<vxrt_light_summary>(2), sizeof(vxrt_light_summary), hipMemcpyDeviceToHost));
     VX_HIP(hipMemcpy(levels, T.at<uint8_t>(1), ob, hipMemcpyDeviceToHost));
     VX_HIP(hipDeviceSynchronize());
+    return VXRT_OK;
+}
+
+// ---- frame denoiser ----------------------------------------------------------------------------------------------------
+uint64_t vxrt_denoise_workspace_bytes(uint32_t W, uint32_t H) { return vxrt::denoise_workspace_bytes(W, H); }
+
+int vxrt_frame_guides(vxrt_ctx* c, uint32_t W, uint32_t H, const float origin[3], const float fwd[3], const float up[3],
+                      const float right[3], int32_t ortho, const int64_t* d_hit_aov, uint32_t* d_keys, void* stream)
+{
+    // the order of include/vxrt.h
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (!c->has_world)
+        return fail(VXRT_ERR_INVALID, "frame guides: no world resident (its extents decode the hit index)");
+    if (!vxrt::denoise_frame_ok(W, H))
+        return fail(VXRT_ERR_INVALID, "frame guides: 1 <= W, H <= 65535 and W * H <= 2^26");
+    if (!origin || !fwd || !up || !right || !d_hit_aov || !d_keys)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    const int64_t X = c->view.X, Y = c->view.Y, Z = (int64_t)c->view.cz * c->view.f;
+    if (X > (int64_t)vxrt::kDnMaxAxis || Y > (int64_t)vxrt::kDnMaxAxis || Z > (int64_t)vxrt::kDnMaxAxis)
+        return fail(VXRT_ERR_INVALID, "frame guides: a world axis longer than 2^24 voxels");
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::RenderArgs A;
+    memset(&A, 0, sizeof(A));
+    A.W.X = (int)X;
+    A.W.Y = (int)Y;
+    camera_args(c, W, H, A);
+    A.ortho = ortho ? 1 : 0;
+    A.origin = vxrt::f3{origin[0], origin[1], origin[2]};
+    A.fwd = vxrt::f3{fwd[0], fwd[1], fwd[2]};
+    A.up = vxrt::f3{up[0], up[1], up[2]};
+    A.right = vxrt::f3{right[0], right[1], right[2]};
+    A.hit_aov = (long long*)d_hit_aov;
+    VX_HIP(vxrt::frame_guides(A, (uint32_t)Z, d_keys, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_denoise_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_in, const uint32_t* d_keys,
+                       const vxrt_denoise_params* params, void* d_work, float* d_color_out, void* d_fb_or_null, void* stream)
+{
+    // the order of include/vxrt.h
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (!vxrt::denoise_frame_ok(W, H))
+        return fail(VXRT_ERR_INVALID, "denoise: 1 <= W, H <= 65535 and W * H <= 2^26");
+    if (!params || params->struct_size != sizeof(vxrt_denoise_params))
+        return fail(VXRT_ERR_INVALID, "vxrt_denoise_params missing or size mismatch");
+    if (params->iterations < 1 || params->iterations > vxrt::kDnMaxIterations)
+        return fail(VXRT_ERR_INVALID, "denoise iterations: 1 .. 6");
+    if (!(params->color_scale >= 0.0f))
+        return fail(VXRT_ERR_INVALID, "denoise color_scale: negative or NaN");
+    if (!d_color_in || !d_keys || !d_work || !d_color_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::denoise_frame(W, H, d_color_in, d_keys, params->iterations, params->color_scale, d_work, d_color_out,
+                               d_fb_or_null, (hipStream_t)stream));
     return VXRT_OK;
 }
 

@@ -718,6 +718,70 @@ class Context:
                                 vertices=verts[:4 * n] if triangles else None, triangles=tris[:2 * n] if triangles else None,
                                 _summary=summary, _stream=None)
 
+    # ---- frame denoiser (extension, include/vxrt.h) ---------------------------------------------------------------------
+    def frame_guides(self, width: int, height: int, origin, fwd, up, right, hit_aov, ortho: bool = False, out=None,
+                     stream: int | None = None):
+        """The guide keys of a whole frame (include/vxrt.h, vxrt_frame_guides): per pixel 0 for a miss, else the voxel face the
+        pixel's primary ray enters, from ``hit_aov`` (the int64 hit-index AOV of a render of the same size, camera and
+        ``ortho`` flag) and the context's FOV / ortho window.  Asynchronous on ``stream`` (default: torch's current stream).
+        ``out``: a contiguous device tensor of width * height four-byte elements (default: a new int32 one).  Returns it,
+        shaped (height, width)."""
+        import torch
+        width, height = int(width), int(height)
+        n = width * height if self.denoise_workspace_bytes(width, height) else 0
+        if hit_aov.element_size() != 8 or hit_aov.numel() < n or not hit_aov.is_contiguous():
+            raise ValueError("hit_aov: a contiguous device tensor of width * height int64 elements")
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int32, device="cuda:%d" % self.device)
+        elif out.element_size() != 4 or out.numel() < n or not out.is_contiguous():
+            raise ValueError("out: a contiguous device tensor of width * height four-byte elements")
+        N.check(self._L.vxrt_frame_guides(self._h, _u32(width), _u32(height), _f3(origin), _f3(fwd), _f3(up), _f3(right),
+                                          1 if ortho else 0, _ptr(hit_aov), _ptr(out), _stream(stream)))
+        return out.view(-1)[:n].view(height, width) if n else out
+
+    def denoise_workspace_bytes(self, width: int, height: int) -> int:
+        """vxrt_denoise_workspace_bytes: the workspace of one denoise call (2 * W * H * 16), 0 outside the contract"""
+        width, height = int(width), int(height)
+        return int(self._L.vxrt_denoise_workspace_bytes(width, height)) if 0 <= width < 1 << 32 and 0 <= height < 1 << 32 else 0
+
+    def denoise_frame(self, color, keys, iterations: int = 4, color_scale: float = 0.0, out=None, fb=None, work=None,
+                      stream: int | None = None):
+        """The edge-avoiding a-trous filter of include/vxrt.h (vxrt_denoise_frame) over ``color``, a float32 device tensor
+        (height, width, 3) such as the colour AOV of a render, guided by ``keys`` (frame_guides): ``iterations`` passes of
+        step 1, 2, 4, ..., pixels of one voxel face averaged with B3-spline weights, with ``color_scale`` > 0 also stopped
+        by colour distance.  Asynchronous on ``stream`` (default: torch's current stream); the tensors this method allocates
+        are torch's, made on torch's current stream, so a ``stream`` other than that one must already be ordered after it.
+        ``out``: float32 (height, width, 3), may be ``color`` itself (default: a new tensor); ``fb``: optional uint8
+        (height, width, 4) BGRA8 frame written as well; ``work``: a device tensor of at least
+        denoise_workspace_bytes(width, height) bytes (default: a new one).  Returns ``out``."""
+        import torch
+        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
+            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
+        height, width = int(color.shape[0]), int(color.shape[1])
+        dev = "cuda:%d" % self.device
+        ws = self.denoise_workspace_bytes(width, height)
+        n = width * height
+        if keys.element_size() != 4 or keys.numel() < n or not keys.is_contiguous():
+            raise ValueError("keys: a contiguous device tensor of width * height four-byte elements")
+        if out is None:
+            out = torch.empty_like(color)
+        elif out.dtype != torch.float32 or out.numel() < 3 * n or not out.is_contiguous():
+            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
+        if fb is not None and (fb.numel() * fb.element_size() < 4 * n or not fb.is_contiguous()):
+            raise ValueError("fb: a contiguous device tensor of width * height * 4 bytes")
+        own_work = work is None
+        if own_work:
+            work = torch.empty(max(ws, 16), dtype=torch.uint8, device=dev)
+        elif work.numel() * work.element_size() < ws or not work.is_contiguous():
+            raise ValueError("work: a contiguous device tensor of at least denoise_workspace_bytes(width, height) bytes")
+        p = N.DenoiseParams(struct_size=C.sizeof(N.DenoiseParams), iterations=int(iterations), color_scale=float(color_scale))
+        s = _stream(stream)
+        N.check(self._L.vxrt_denoise_frame(self._h, _u32(width), _u32(height), _ptr(color), _ptr(keys), C.byref(p), _ptr(work),
+                                           _ptr(out), _ptr(fb), s))
+        if own_work:
+            work.record_stream(torch.cuda.ExternalStream(s, device=dev))  # freed here, still in use on the call's stream
+        return out
+
     # ---- occupancy LOD (extension, include/vxrt.h) ----------------------------------------------------------------------
     def lod_workspace_bytes(self, dims, shift: int) -> int:
         """vxrt_lod_workspace_bytes: the workspace of one downsample call, 0 outside the contract"""
