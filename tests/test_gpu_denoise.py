@@ -313,6 +313,35 @@ def test_refusals_in_the_documented_order_with_nothing_written(eng, vxo, scenes)
         empty.close()
 
 
+def test_strided_tensors_are_refused_and_left_unchanged(eng, scenes):
+    """frame_guides and denoise_frame hand the library the tensors' addresses as dense buffers: a tensor with a stride is
+    refused before the library is called, and the dense part of the same memory is accepted"""
+    vx, torch = eng
+    ctx, _ = scenes[min(WORLDS)]
+    Wf, Hf = 16, 8
+    n = Wf * Hf
+    cam = ((1.0, 2.0, 3.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    hit = torch.full((2 * n,), -1, dtype=torch.int64, device="cuda")  # every pixel a miss
+    keys = torch.full((2 * n,), 0x1234, dtype=torch.int32, device="cuda")
+    col = torch.full((Hf, Wf, 3), 0.5, dtype=torch.float32, device="cuda")
+    out = torch.full((Hf, Wf, 6), 9.0, dtype=torch.float32, device="cuda")
+    fb = torch.full((2 * n,), 0x1234, dtype=torch.int32, device="cuda")
+    work = torch.full((2 * ctx.denoise_workspace_bytes(Wf, Hf),), 0xA5, dtype=torch.uint8, device="cuda")
+    for h, k in ((hit[:n], keys[::2]), (hit[::2], keys[:n])):
+        with pytest.raises(ValueError):
+            ctx.frame_guides(Wf, Hf, *cam, h, out=k)
+    for kw in (dict(out=out[:, :, ::2]), dict(fb=fb[::2]), dict(work=work[::2])):
+        with pytest.raises(ValueError):
+            ctx.denoise_frame(col, keys[:n], 2, 0.0, **kw)
+    with pytest.raises(ValueError):
+        ctx.denoise_frame(col, keys[::2], 2, 0.0)
+    torch.cuda.synchronize()
+    assert bool((keys == 0x1234).all()) and bool((out == 9.0).all()) and bool((fb == 0x1234).all()) and bool((work == 0xA5).all())
+    got = ctx.frame_guides(Wf, Hf, *cam, hit[:n], out=keys[:n])
+    torch.cuda.synchronize()
+    assert got.shape == (Hf, Wf) and not bool(got.any()) and bool((keys[n:] == 0x1234).all())
+
+
 def test_no_world_reaches_the_refusal_of_an_axis_longer_than_2_24_voxels(eng):
     """the last refusal of vxrt_frame_guides guards the binary32 form of a face plane; the world paths admit at most 65535
     coarse cells of at most 32 voxels per axis (below 2^21), so no resident world can reach it: a longer world is refused

@@ -290,6 +290,33 @@ def test_determinism_batches_and_streams(eng, vxo):
         ctx.close()
 
 
+def test_host_placements_on_a_side_stream_and_pieces_dropped_after_the_call(eng, vxo):
+    """place_pieces with a list of Placement copies it on torch's current stream and launches on ``stream``; every reference
+    to the pieces' device words is dropped as soon as it returns, and memory of their sizes is handed out and overwritten on
+    torch's current stream while the side stream may still run.  The results equal the default stream's: nothing but the
+    call itself keeps the launch's inputs alive (64^3 is the smallest world of factor 8: 8 coarse cells per axis)"""
+    vx, torch = eng
+    rng = np.random.default_rng(23)
+    vox = random_world(rng, (64, 64, 64))
+    grids = random_pieces(rng)
+    ctx = _ctx(vx, vxo, vox, 8)
+    try:
+        pl = random_placements(rng, (64, 64, 64), 500, len(grids))
+        first = _place(vx, torch, ctx, grids, pl)
+        rows = [vx.Placement(int(r[0]), (int(r[1]), int(r[2]), int(r[3])), int(r[4]), int(r[5])) for r in pl]
+        pieces = [vx.Piece(_dev(torch, vx.pack_region(g).view(np.int32)), g.shape) for g in grids]
+        sizes = [p.bits.numel() for p in pieces] + [pl.size]
+        side = torch.cuda.Stream()
+        got = ctx.place_pieces(pieces, rows, stream=side.cuda_stream)
+        del pieces
+        junk = [torch.full((k,), -1, dtype=torch.int32, device="cuda") for k in sizes]
+        side.synchronize()
+        assert torch.equal(got, first)
+        del junk
+    finally:
+        ctx.close()
+
+
 def test_memory_and_refusals(eng, vxo, tmp_path):
     vx, torch = eng
     ctx = vx.Context(0)

@@ -336,6 +336,27 @@ def test_refusals(eng, vxo, tmp_path):
         ctx.close()
 
 
+def test_a_strided_out_is_refused_and_left_unchanged(eng, vxo):
+    """read_region writes dense words through ``out``'s address: an ``out`` with a stride is refused before the library is
+    called, and its dense half is accepted (64^3 is the smallest world of factor 8: 8 coarse cells per axis)"""
+    vx, torch = eng
+    ctx = new_ctx(vx)
+    try:
+        vox = np.random.default_rng(21).random((64, 64, 64)) < 0.4
+        upload(ctx, vxo.World.from_voxels(vox, 8))
+        o, d = (28, 27, 26), (8, 8, 8)
+        n = vx.region_words(d)
+        buf = torch.full((2 * n,), 0x1234, dtype=torch.int32, device="cuda")
+        with pytest.raises(ValueError):
+            ctx.read_region(o, d, out=buf[::2])
+        torch.cuda.synchronize()
+        assert bool((buf == 0x1234).all())
+        got = ctx.read_region(o, d, out=buf[:n])
+        assert np.array_equal(vx.unpack_region(got, d), vox[28:36, 27:35, 26:34]) and bool((buf[n:] == 0x1234).all())
+    finally:
+        ctx.close()
+
+
 def test_read_after_render_on_a_stream_sees_the_renders_world(eng, vxo):
     vx, torch = eng
     X = Y = Z = 128

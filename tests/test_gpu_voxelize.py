@@ -227,6 +227,30 @@ def test_refusals_leave_the_output_untouched_and_no_triangle_is_valid(eng, vxo, 
         ctx.close()
 
 
+def test_strided_out_and_work_are_refused_and_left_unchanged(eng):
+    """voxelize_mesh hands the library the tensors' addresses as dense buffers: a tensor with a stride is refused before
+    the library is called, and the dense part of the same memory is accepted"""
+    vx, torch = eng
+    ctx = vx.Context(0)
+    try:
+        mesh, dims = R.octahedron((1000, 1000, 1000), 700), (8, 8, 8)
+        n = vx.region_words(dims)
+        ws = ctx.voxelize_workspace_bytes(dims, len(mesh[1]))
+        out = torch.full((2 * n,), 0x1234, dtype=torch.int32, device="cuda")
+        work = torch.full((2 * ws,), 0xA5, dtype=torch.uint8, device="cuda")
+        for kw in (dict(out=out[::2]), dict(work=work[::2]), dict(out=out[::2], work=work[::2])):
+            with pytest.raises(ValueError):
+                ctx.voxelize_mesh(mesh[0], mesh[1], dims, 3, **kw)
+        torch.cuda.synchronize()
+        assert bool((out == 0x1234).all()) and bool((work == 0xA5).all())
+        got = ctx.voxelize_mesh(mesh[0], mesh[1], dims, 3, out=out[:n], work=work[:ws])
+        want = R.voxelize(*mesh, dims, 3)
+        assert np.array_equal(got.grid(), want["grid"]) and tuple(got.summary) == want["summary"]
+        assert bool((out[n:] == 0x1234).all()) and bool((work[ws:] == 0xA5).all())
+    finally:
+        ctx.close()
+
+
 # ---- composition with the resident world --------------------------------------------------------------------------------------
 def _bbox(mesh):
     v = mesh[0].astype(np.int64)

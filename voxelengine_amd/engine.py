@@ -183,13 +183,11 @@ class Context:
         """The voxels of the box ``origin`` .. ``origin + dims - 1`` as region words (include/vxrt.h: x in 32-bit words,
         rows y fastest, then z; voxels outside the world read 0) in a device tensor of ``region_words(dims)`` int32 (the
         bits of uint32 words), or into ``out``.  Asynchronous on ``stream`` (default: torch's current stream)."""
-        import torch
+        call = _Call(self, stream)
         n = region_words(dims)
-        if out is None:
-            out = torch.empty(max(n, 1), dtype=torch.int32, device="cuda:%d" % self.device)
-        elif out.numel() * out.element_size() < 4 * n:
-            raise ValueError("out holds fewer than region_words(dims) words")
-        N.check(self._L.vxrt_read_region(self._h, _i3(origin), _i3(dims), _ptr(out), _stream(stream)))
+        out = call.out(n, 4, call.torch.int32, out, "out: a contiguous device tensor of at least region_words(dims) words",
+                       any_size=True)
+        call.launch(self._L.vxrt_read_region, _i3(origin), _i3(dims), _ptr(out))
         return out[:n] if out.dim() == 1 and out.element_size() == 4 else out
 
     def read_region_host(self, origin, dims) -> np.ndarray:
@@ -239,11 +237,11 @@ class Context:
             flags = np.empty(len(b), np.uint32)
             N.check(self._L.vxrt_move_boxes_host(self._h, b.ctypes.data, len(b), order, lohi.ctypes.data, flags.ctypes.data))
             return lohi, flags
-        import torch
-        b = _bodies_dev(bodies)
-        lohi = torch.empty((b.shape[0], 6), dtype=torch.float32, device=b.device)
-        flags = torch.empty(b.shape[0], dtype=torch.int32, device=b.device)
-        N.check(self._L.vxrt_move_boxes(self._h, _ptr(b), b.shape[0], order, _ptr(lohi), _ptr(flags), _stream(stream)))
+        call = _Call(self, stream)
+        b = call.reads(_bodies_dev(bodies))
+        lohi = call.torch.empty((b.shape[0], 6), dtype=call.torch.float32, device=b.device)
+        flags = call.torch.empty(b.shape[0], dtype=call.torch.int32, device=b.device)
+        call.launch(self._L.vxrt_move_boxes, _ptr(b), b.shape[0], order, _ptr(lohi), _ptr(flags))
         return lohi, flags
 
     def overlap_boxes(self, bodies, stream: int | None = None):
@@ -255,11 +253,11 @@ class Context:
             flags = np.empty(len(b), np.uint32)
             N.check(self._L.vxrt_overlap_boxes_host(self._h, b.ctypes.data, len(b), counts.ctypes.data, flags.ctypes.data))
             return counts, flags
-        import torch
-        b = _bodies_dev(bodies)
-        counts = torch.empty(b.shape[0], dtype=torch.int32, device=b.device)
-        flags = torch.empty(b.shape[0], dtype=torch.int32, device=b.device)
-        N.check(self._L.vxrt_overlap_boxes(self._h, _ptr(b), b.shape[0], _ptr(counts), _ptr(flags), _stream(stream)))
+        call = _Call(self, stream)
+        b = call.reads(_bodies_dev(bodies))
+        counts = call.torch.empty(b.shape[0], dtype=call.torch.int32, device=b.device)
+        flags = call.torch.empty(b.shape[0], dtype=call.torch.int32, device=b.device)
+        call.launch(self._L.vxrt_overlap_boxes, _ptr(b), b.shape[0], _ptr(counts), _ptr(flags))
         return counts, flags
 
     # ---- floating islands (extension, include/vxrt.h) ----------------------------------------------------------------
@@ -270,34 +268,31 @@ class Context:
         torch's current stream) and waits for it to return the table and the summary.  Returns an Islands: the island
         voxels as device region words (a subtract stamp at ``origin``), the per-voxel component ids when ``labels``, and
         up to ``max_islands`` table rows in ascending id."""
-        import torch
-        dims = tuple(int(v) for v in dims)
+        call = _Call(self, stream)
+        i32 = call.torch.int32
+        origin, dims = _box(origin, dims)
         ws = int(self._L.vxrt_islands_workspace_bytes(_i3(dims)))
-        dev = "cuda:%d" % self.device
-        work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
-        floating = torch.empty(max(region_words(dims), 1), dtype=torch.int32, device=dev)
-        nvox = dims[0] * dims[1] * dims[2] if ws else 0
-        lab = torch.empty(max(nvox, 1), dtype=torch.int32, device=dev) if labels else None
-        table = torch.empty((max(int(max_islands), 1), 8), dtype=torch.int32, device=dev)
-        summary = torch.zeros(3, dtype=torch.int32, device=dev)
-        s = _stream(stream)
-        N.check(self._L.vxrt_find_islands(self._h, _i3(origin), _i3(dims), int(anchors), _ptr(work), _ptr(floating), _ptr(lab),
-                                          _ptr(table), int(max_islands), _ptr(summary), s))
-        torch.cuda.ExternalStream(s, device=dev).synchronize()
+        nvox, nw = _counts(dims, ws)
+        work = call.work(ws)
+        floating = call.out(nw, 4, i32)
+        lab = call.out(nvox, 4, i32) if labels else None
+        table = call.out(8 * max(int(max_islands), 1), 4, i32).view(-1, 8)
+        summary = call.summary(3)
+        call.launch(self._L.vxrt_find_islands, _i3(origin), _i3(dims), int(anchors), _ptr(work), _ptr(floating), _ptr(lab),
+                    _ptr(table), int(max_islands), _ptr(summary))
+        call.stream.synchronize()
         comps, islands, voxels = (int(v) for v in summary.cpu().numpy().view(np.uint32))
         rows = table[: min(islands, int(max_islands))].cpu().numpy()
-        return Islands(origin=tuple(int(v) for v in origin), dims=dims, floating=floating[: region_words(dims)],
-                       labels=lab[:nvox] if labels else None, table=_island_table(rows),
-                       summary=IslandSummary(comps, islands, voxels))
+        return Islands(origin=origin, dims=dims, floating=floating[:nw], labels=lab[:nvox] if labels else None,
+                       table=_island_table(rows), summary=IslandSummary(comps, islands, voxels))
 
     def find_islands_host(self, origin, dims, anchors: int = N.ISLAND_ANCHOR_FACES | N.ISLAND_ANCHOR_FLOOR,
                           labels: bool = False, max_islands: int = 4096) -> "Islands":
         """find_islands through the synchronous host call (vxrt_find_islands_host): numpy outputs, floating as a bool
         [x, y, z] grid and labels as uint32 [x, y, z]."""
-        dims = tuple(int(v) for v in dims)
-        n = region_words(dims)
+        origin, dims = _box(origin, dims)
+        nvox, n = _counts(dims, region_words(dims))
         floating = np.zeros(max(n, 1), np.uint32)
-        nvox = dims[0] * dims[1] * dims[2] if n else 0
         lab = np.zeros(max(nvox, 1), np.uint32) if labels else None
         table = np.zeros((max(int(max_islands), 1), 8), np.int32)
         summary = np.zeros(3, np.uint32)
@@ -305,8 +300,7 @@ class Context:
                                                lab.ctypes.data if labels else None, table.ctypes.data, int(max_islands),
                                                summary.ctypes.data))
         comps, islands, voxels = (int(v) for v in summary)
-        return Islands(origin=tuple(int(v) for v in origin), dims=dims, floating=unpack_region(floating, dims),
-                       labels=lab[:nvox].reshape(dims[::-1]).transpose(2, 1, 0) if labels else None,
+        return Islands(origin=origin, dims=dims, floating=unpack_region(floating, dims), labels=_grid(lab, dims) if labels else None,
                        table=_island_table(table[: min(islands, int(max_islands))]),
                        summary=IslandSummary(comps, islands, voxels))
 
@@ -319,30 +313,29 @@ class Context:
         return isl, st
 
     # ---- voxel piece queries (extension, include/vxrt.h) -------------------------------------------------------------
-    def _piece_descs(self, pieces, host: bool):
-        """(keep-alive list, PieceDesc array) of Piece objects: device words for place_pieces, host words for the _host call"""
-        import torch
+    def _piece_descs(self, pieces, call: "_Call | None"):
+        """(keep-alive list, PieceDesc array) of Piece objects: device words, kept alive by ``call``, for place_pieces; host
+        words (``call`` None) for the _host call"""
         keep, descs = [], []
         for p in pieces:
             bits, dims = p.bits, p.dims
             if isinstance(bits, np.ndarray) and bits.dtype == bool:
-                dims = tuple(int(v) for v in bits.shape) if dims is None else dims
+                dims = _ints(bits.shape) if dims is None else dims
                 bits = pack_region(bits)
             elif dims is None:
                 raise ValueError("a piece of region words needs its dims")
-            d = N.PieceDesc()
-            if host:
-                if hasattr(bits, "cpu"):
-                    bits = bits.cpu().numpy()
+            if call is None and hasattr(bits, "cpu"):
+                bits = bits.cpu().numpy()
+            if isinstance(bits, np.ndarray):
                 bits = np.ascontiguousarray(bits).view(np.uint32)
-                d.d_bits = bits.ctypes.data
-            else:
-                if isinstance(bits, np.ndarray):
-                    bits = torch.from_numpy(np.ascontiguousarray(bits).view(np.int32)).to("cuda:%d" % self.device)
-                d.d_bits = _ptr(bits)
             words = bits.size if isinstance(bits, np.ndarray) else bits.numel() * bits.element_size() // 4
             if words < region_words(dims):
                 raise ValueError("a piece holds fewer than region_words(dims) words")
+            d = N.PieceDesc()
+            if call is None:
+                d.d_bits = bits.ctypes.data
+            else:
+                d.d_bits = _ptr(call.upload(bits) if isinstance(bits, np.ndarray) else call.reads(bits))
             keep.append(bits)
             d.dims = _i3(dims)
             d.reserved = 0
@@ -355,24 +348,25 @@ class Context:
         PLACE_MAX_PIECES Piece objects; ``placements``: an (n, 6) int32 cuda tensor of rows piece, origin[3], axis, dist, or
         a list of Placement / an (n, 6) numpy array (copied to the device here).  Asynchronous on ``stream`` (default: torch's
         current stream).  Returns an (n, 4) int32 device tensor of rows overlap, travel, contact, flags (PLACED_BLOCKED,
-        PLACED_INVALID); the pieces' device words must stay alive until the call has run."""
-        import torch
+        PLACED_INVALID).  Torch's allocator keeps the pieces' and placements' device memory from reuse until ``stream`` has
+        passed the call, so torch tensors may be dropped as soon as it returns."""
+        call = _Call(self, stream)
+        torch = call.torch
         if not hasattr(placements, "data_ptr"):
-            placements = torch.from_numpy(_placements_np(placements)).to("cuda:%d" % self.device)
+            placements = call.upload(_placements_np(placements))
         if placements.dtype != torch.int32 or placements.dim() != 2 or placements.shape[1] != 6:
             raise ValueError("placements must be an (n, 6) int32 tensor: piece, origin[3], axis, dist")
-        pl = placements.contiguous()
-        keep, arr = self._piece_descs(pieces, host=False)
+        pl = call.reads(placements.contiguous())
+        _, arr = self._piece_descs(pieces, call)
         out = torch.empty((pl.shape[0], 4), dtype=torch.int32, device=pl.device)
-        N.check(self._L.vxrt_place_pieces(self._h, arr if len(pieces) else None, len(pieces), _ptr(pl) if pl.shape[0] else None,
-                                          pl.shape[0], _ptr(out) if pl.shape[0] else None, _stream(stream)))
-        out._vxrt_keep = (keep, pl)  # the launch reads them after this call returns
+        call.launch(self._L.vxrt_place_pieces, arr if len(pieces) else None, len(pieces), _ptr(pl) if pl.shape[0] else None,
+                    pl.shape[0], _ptr(out) if pl.shape[0] else None)
         return out
 
     def place_pieces_host(self, pieces, placements) -> np.ndarray:
         """place_pieces through the synchronous host call (vxrt_place_pieces_host): numpy in, a PLACED_DTYPE array out."""
         pl = _placements_np(placements)
-        keep, arr = self._piece_descs(pieces, host=True)
+        keep, arr = self._piece_descs(pieces, None)
         out = np.zeros((len(pl), 4), np.int32)
         N.check(self._L.vxrt_place_pieces_host(self._h, arr if len(pieces) else None, len(pieces), pl.ctypes.data if len(pl) else None,
                                                len(pl), out.ctypes.data if len(pl) else None))
@@ -428,38 +422,33 @@ class Context:
         NavField of device tensors (walkable region words, one next code per cell, dist when ``dist``) and the summary.
 
         A body steered with move_boxes can follow ``NavField.paths``: each move is one cell, ``nav_move(code, agent)``."""
-        import torch
+        call = _Call(self, stream)
+        torch = call.torch
         agent = agent or NavAgent()
-        dims = tuple(int(v) for v in dims)
+        origin, dims = _box(origin, dims)
         g = np.ascontiguousarray(np.asarray(goals, np.int32).reshape(-1, 3))
         ag = agent._c()
         ws = int(self._L.vxrt_nav_workspace_bytes(_i3(dims), C.byref(ag)))
-        dev = "cuda:%d" % self.device
-        nvox = dims[0] * dims[1] * dims[2] if ws else 0
-        work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
-        walk = torch.empty(max(region_words(dims) if ws else 0, 1), dtype=torch.int32, device=dev)
-        nxt = torch.empty(max(nvox, 1), dtype=torch.uint8, device=dev)
-        dst = torch.empty(max(nvox, 1), dtype=torch.int32, device=dev) if dist else None
-        summary = torch.zeros(8, dtype=torch.int32, device=dev)
-        dg = torch.from_numpy(g).to(dev) if len(g) else None
-        s = _stream(stream)
-        if dg is not None:  # the goals' copy is on torch's current stream: order it before the call's stream
-            torch.cuda.current_stream(dev).synchronize()
-        N.check(self._L.vxrt_nav_field(self._h, _i3(origin), _i3(dims), C.byref(ag), _ptr(dg), len(g), int(max_dist),
-                                       _ptr(work), _ptr(walk), _ptr(nxt), _ptr(dst), _ptr(summary), s))
-        return NavField(origin=tuple(int(v) for v in origin), dims=dims, agent=agent, walkable=walk[: region_words(dims)],
-                        next=nxt[:nvox], dist=dst[:nvox] if dist else None,
+        nvox, nw = _counts(dims, ws)
+        work = call.work(ws)
+        walk = call.out(nw, 4, torch.int32)
+        nxt = call.out(nvox, 1, torch.uint8)
+        dst = call.out(nvox, 4, torch.int32) if dist else None
+        summary = call.summary(8)
+        dg = call.upload(g)
+        call.launch(self._L.vxrt_nav_field, _i3(origin), _i3(dims), C.byref(ag), _ptr(dg) if len(g) else None, len(g), int(max_dist),
+                    _ptr(work), _ptr(walk), _ptr(nxt), _ptr(dst), _ptr(summary))
+        return NavField(origin=origin, dims=dims, agent=agent, walkable=walk[:nw], next=nxt[:nvox], dist=dst[:nvox] if dist else None,
                         summary=NavSummary(*(int(v) for v in summary.cpu().numpy().view(np.uint32))), ctx=self)
 
     def nav_field_host(self, origin, dims, goals, agent: "NavAgent | None" = None, max_dist: int = 1 << 24) -> "NavField":
         """nav_field through the synchronous host call (vxrt_nav_field_host): numpy outputs -- walkable as a bool [x, y, z]
         grid, next as uint8 [x, y, z], dist as uint32 [x, y, z]."""
         agent = agent or NavAgent()
-        dims = tuple(int(v) for v in dims)
+        origin, dims = _box(origin, dims)
         g = np.ascontiguousarray(np.asarray(goals, np.int32).reshape(-1, 3))
         ag = agent._c()
-        n = region_words(dims)
-        nvox = dims[0] * dims[1] * dims[2] if n else 0
+        nvox, n = _counts(dims, region_words(dims))
         walk = np.zeros(max(n, 1), np.uint32)
         nxt = np.zeros(max(nvox, 1), np.uint8)
         dst = np.zeros(max(nvox, 1), np.uint32)
@@ -467,9 +456,8 @@ class Context:
         N.check(self._L.vxrt_nav_field_host(self._h, _i3(origin), _i3(dims), C.byref(ag), g.ctypes.data if len(g) else None,
                                             len(g), int(max_dist), walk.ctypes.data, nxt.ctypes.data, dst.ctypes.data,
                                             summary.ctypes.data))
-        grid = lambda a: a[:nvox].reshape(dims[::-1]).transpose(2, 1, 0)
-        return NavField(origin=tuple(int(v) for v in origin), dims=dims, agent=agent, walkable=unpack_region(walk, dims),
-                        next=grid(nxt), dist=grid(dst), summary=NavSummary(*(int(v) for v in summary)), ctx=self)
+        return NavField(origin=origin, dims=dims, agent=agent, walkable=unpack_region(walk, dims), next=_grid(nxt, dims),
+                        dist=_grid(dst, dims), summary=NavSummary(*(int(v) for v in summary)), ctx=self)
 
     # ---- exact distance fields (extension, include/vxrt.h) -----------------------------------------------------------
     def distance_workspace_bytes(self, dims, radius: int) -> int:
@@ -483,35 +471,29 @@ class Context:
         include/vxrt.h, vxrt_distance_field.  Asynchronous on ``stream`` (default: torch's current stream).  ``out``: a
         device tensor of two-byte elements to write the field to (one per voxel; default: a new one).  Returns a
         DistanceField; reading its ``summary`` waits for the call."""
-        import torch
-        dims = tuple(int(v) for v in dims)
+        call = _Call(self, stream)
+        origin, dims = _box(origin, dims)
         ws = self.distance_workspace_bytes(dims, radius)
-        dev = "cuda:%d" % self.device
-        nvox = dims[0] * dims[1] * dims[2] if ws else 0
-        work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
-        if out is None:
-            out = torch.empty(max(nvox, 1), dtype=torch.int16, device=dev)
-        elif out.element_size() != 2 or out.numel() < nvox or not out.is_contiguous():
-            raise ValueError("out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] two-byte elements")
-        summary = torch.zeros(6, dtype=torch.int32, device=dev)
-        s = _stream(stream)
-        N.check(self._L.vxrt_distance_field(self._h, _i3(origin), _i3(dims), int(radius), int(mode), _ptr(work), _ptr(out),
-                                            _ptr(summary), s))
-        work.record_stream(torch.cuda.ExternalStream(s, device=dev))  # freed here, still in use on the call's stream
-        return DistanceField(origin=tuple(int(v) for v in origin), dims=dims, radius=int(radius), mode=int(mode),
-                             dist2=out.view(-1)[:nvox], _summary=summary, _stream=s)
+        nvox, _ = _counts(dims, ws)
+        work = call.work(ws)
+        out = call.out(nvox, 2, call.torch.int16, out,
+                       "out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] two-byte elements")
+        summary = call.summary(6)
+        call.launch(self._L.vxrt_distance_field, _i3(origin), _i3(dims), int(radius), int(mode), _ptr(work), _ptr(out), _ptr(summary))
+        return DistanceField(origin=origin, dims=dims, radius=int(radius), mode=int(mode), dist2=out.view(-1)[:nvox],
+                             _summary=summary, _stream=call.s)
 
     def distance_field_host(self, origin, dims, radius: int, mode: int = N.DIST_TO_SOLID) -> "DistanceField":
         """distance_field through the synchronous host call (vxrt_distance_field_host): ``dist2`` is a numpy uint16
         [x, y, z] grid."""
-        dims = tuple(int(v) for v in dims)
-        nvox = dims[0] * dims[1] * dims[2] if self.distance_workspace_bytes(dims, radius) else 0
+        origin, dims = _box(origin, dims)
+        nvox, _ = _counts(dims, self.distance_workspace_bytes(dims, radius))
         out = np.zeros(max(nvox, 1), np.uint16)
         summary = np.zeros(6, np.uint32)
         N.check(self._L.vxrt_distance_field_host(self._h, _i3(origin), _i3(dims), int(radius), int(mode), out.ctypes.data,
                                                  summary.ctypes.data))
-        return DistanceField(origin=tuple(int(v) for v in origin), dims=dims, radius=int(radius), mode=int(mode),
-                             dist2=out[:nvox].reshape(dims[::-1]).transpose(2, 1, 0), _summary=summary, _stream=None)
+        return DistanceField(origin=origin, dims=dims, radius=int(radius), mode=int(mode), dist2=_grid(out, dims),
+                             _summary=summary, _stream=None)
 
     # ---- voxel light fields (extension, include/vxrt.h) ------------------------------------------------------------------
     def light_workspace_bytes(self, dims, channels: int = N.LIGHT_SKY | N.LIGHT_BLOCK) -> int:
@@ -526,50 +508,36 @@ class Context:
         ``stream`` (default: torch's current stream).  ``out``: a device tensor of one-byte elements to write the levels to
         (one per voxel; default: a new one); ``work``: a device tensor of at least light_workspace_bytes bytes to use as
         the workspace (default: a new one).  Returns a LightField; reading its ``summary`` waits for the call."""
-        import torch
-        dims = tuple(int(v) for v in dims)
+        call = _Call(self, stream)
+        torch = call.torch
+        origin, dims = _box(origin, dims)
         ws = self.light_workspace_bytes(dims, channels)
-        dev = "cuda:%d" % self.device
-        nvox = dims[0] * dims[1] * dims[2] if ws else 0
-        if work is None:
-            work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
-        elif work.element_size() * work.numel() < ws or not work.is_contiguous():
-            raise ValueError("work: a contiguous device tensor of at least light_workspace_bytes(dims, channels) bytes")
-        if out is None:
-            out = torch.empty(max(nvox, 1), dtype=torch.uint8, device=dev)
-        elif out.element_size() != 1 or out.numel() < nvox or not out.is_contiguous():
-            raise ValueError("out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] one-byte elements")
-        if emitters is None:
-            em, n = None, 0
-        elif isinstance(emitters, torch.Tensor):
-            em = emitters.to(device=dev, dtype=torch.int32).contiguous().view(-1, 4)
-            n = em.shape[0]
+        nvox, _ = _counts(dims, ws)
+        work = call.work(ws, work, "work: a contiguous device tensor of at least light_workspace_bytes(dims, channels) bytes")
+        out = call.out(nvox, 1, torch.uint8, out,
+                       "out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] one-byte elements")
+        if isinstance(emitters, torch.Tensor):
+            em = call.reads(emitters.to(device=call.dev, dtype=torch.int32).contiguous().view(-1, 4))
         else:
-            rows = np.ascontiguousarray(np.asarray(emitters, np.int32).reshape(-1, 4))
-            n = rows.shape[0]
-            em = torch.from_numpy(rows).to(dev) if n else None
-        summary = torch.zeros(42, dtype=torch.int32, device=dev)
-        s = _stream(stream)
-        N.check(self._L.vxrt_light_field(self._h, _i3(origin), _i3(dims), _ptr(em) if n else None, n, _u32(channels), _ptr(work),
-                                         _ptr(out), _ptr(summary), s))
-        for t in (work, em):  # freed here, still in use on the call's stream
-            if t is not None:
-                t.record_stream(torch.cuda.ExternalStream(s, device=dev))
-        return LightField(origin=tuple(int(v) for v in origin), dims=dims, channels=int(channels), levels=out.view(-1)[:nvox],
-                          _summary=summary, _stream=s)
+            em = call.upload(_emitter_rows(emitters))
+        n = em.shape[0]
+        summary = call.summary(42)
+        call.launch(self._L.vxrt_light_field, _i3(origin), _i3(dims), _ptr(em) if n else None, n, _u32(channels), _ptr(work),
+                    _ptr(out), _ptr(summary))
+        return LightField(origin=origin, dims=dims, channels=int(channels), levels=out.view(-1)[:nvox], _summary=summary,
+                          _stream=call.s)
 
     def light_field_host(self, origin, dims, emitters=None, channels: int = N.LIGHT_SKY | N.LIGHT_BLOCK) -> "LightField":
         """light_field through the synchronous host call (vxrt_light_field_host): ``levels`` is a numpy uint8 [x, y, z]
         grid."""
-        dims = tuple(int(v) for v in dims)
-        nvox = dims[0] * dims[1] * dims[2] if self.light_workspace_bytes(dims, channels) else 0
-        rows = np.zeros((0, 4), np.int32) if emitters is None else np.ascontiguousarray(np.asarray(emitters, np.int32).reshape(-1, 4))
+        origin, dims = _box(origin, dims)
+        nvox, _ = _counts(dims, self.light_workspace_bytes(dims, channels))
+        rows = _emitter_rows(emitters)
         out = np.zeros(max(nvox, 1), np.uint8)
         summary = np.zeros(42, np.uint32)
         N.check(self._L.vxrt_light_field_host(self._h, _i3(origin), _i3(dims), rows.ctypes.data if len(rows) else None, len(rows),
                                               _u32(channels), out.ctypes.data, summary.ctypes.data))
-        return LightField(origin=tuple(int(v) for v in origin), dims=dims, channels=int(channels),
-                          levels=out[:nvox].reshape(dims[::-1]).transpose(2, 1, 0), _summary=summary, _stream=None)
+        return LightField(origin=origin, dims=dims, channels=int(channels), levels=_grid(out, dims), _summary=summary, _stream=None)
 
     # ---- mesh voxelization (extension, include/vxrt.h) ----------------------------------------------------------------
     def voxelize_workspace_bytes(self, dims, n_triangles: int) -> int:
@@ -584,50 +552,34 @@ class Context:
         (m, 3) vertex indices; numpy arrays or device tensors.  ``modes``: VOX_SURFACE, VOX_SOLID or both.  Asynchronous on
         ``stream`` (default: torch's current stream).  ``work`` / ``out``: device tensors to reuse as the workspace and the
         output words.  Returns a VoxelizedMesh; ``.bits`` is a stamp's device words as it is."""
-        import torch
-        dev = "cuda:%d" % self.device
-        dims = tuple(int(v) for v in dims)
-        copied = False
+        call = _Call(self, stream)
+        torch = call.torch
+        dims = _ints(dims)
 
         def on_device(a, np_dtype):
-            nonlocal copied
             if isinstance(a, torch.Tensor):
                 if a.dtype not in (torch.int32, torch.uint32) or not a.is_contiguous() or a.numel() % 3 or not a.is_cuda:
                     raise ValueError("mesh tensors: contiguous device tensors of int32, 3 per row")
-                return a
-            a = _mesh_array(a, np_dtype)
-            copied = copied or a.size > 0
-            return torch.from_numpy(a.view(np.int32)).to(dev) if a.size else torch.empty((0, 3), dtype=torch.int32, device=dev)
+                return call.reads(a)
+            return call.upload(_mesh_array(a, np_dtype))
 
         v, t = on_device(vertices, np.int32), on_device(triangles, np.uint32)
         nv, nt = v.numel() // 3, t.numel() // 3
         ws = self.voxelize_workspace_bytes(dims, nt)
-        nw = region_words(dims) if ws else 0
-        if work is None:
-            work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
-        elif work.numel() * work.element_size() < ws:
-            raise ValueError("work holds fewer than voxelize_workspace_bytes(dims, n_triangles) bytes")
-        if out is None:
-            out = torch.empty(max(nw, 1), dtype=torch.int32, device=dev)
-        elif out.numel() * out.element_size() < 4 * nw:
-            raise ValueError("out holds fewer than region_words(dims) words")
-        summary = torch.zeros(8, dtype=torch.int32, device=dev)
-        s = _stream(stream)
-        if copied:  # the mesh's copy is on torch's current stream: order it before the call's stream
-            torch.cuda.current_stream(dev).synchronize()
-        N.check(self._L.vxrt_voxelize_mesh(self._h, _ptr(v) if nt else None, nv, _ptr(t) if nt else None, nt, _i3(dims), int(modes),
-                                           _ptr(work), _ptr(out), _ptr(summary), s))
-        es = torch.cuda.ExternalStream(s, device=dev)
-        for a in (work, v, t):
-            a.record_stream(es)
+        _, nw = _counts(dims, ws)
+        work = call.work(ws, work, "work: a contiguous device tensor of at least voxelize_workspace_bytes(dims, n_triangles) bytes")
+        out = call.out(nw, 4, torch.int32, out, "out: a contiguous device tensor of at least region_words(dims) words", any_size=True)
+        summary = call.summary(8)
+        call.launch(self._L.vxrt_voxelize_mesh, _ptr(v) if nt else None, nv, _ptr(t) if nt else None, nt, _i3(dims), int(modes),
+                    _ptr(work), _ptr(out), _ptr(summary))
         return VoxelizedMesh(dims=dims, modes=int(modes), bits=out.view(-1)[:nw] if out.element_size() == 4 else out,
-                             _summary=summary, _stream=s)
+                             _summary=summary, _stream=call.s)
 
     def voxelize_mesh_host(self, vertices, triangles, dims, modes: int = N.VOX_SURFACE | N.VOX_SOLID) -> "VoxelizedMesh":
         """voxelize_mesh through the synchronous host call (vxrt_voxelize_mesh_host): ``bits`` is a bool [x, y, z] grid."""
-        dims = tuple(int(v) for v in dims)
+        dims = _ints(dims)
         v, t = _mesh_array(vertices, np.int32), _mesh_array(triangles, np.uint32)
-        nw = region_words(dims) if self.voxelize_workspace_bytes(dims, len(t)) else 0
+        _, nw = _counts(dims, self.voxelize_workspace_bytes(dims, len(t)))
         words = np.zeros(max(nw, 1), np.uint32)
         summary = np.zeros(8, np.uint32)
         N.check(self._L.vxrt_voxelize_mesh_host(self._h, v.ctypes.data if len(t) else None, len(v), t.ctypes.data if len(t) else None,
@@ -664,39 +616,36 @@ class Context:
         world's voxels).  ``capacity``: quads to make room for; None counts first (one more call, and a wait for it) and
         makes room for all.  Asynchronous on ``stream`` (default: torch's current stream).  Returns an ExtractedSurface of
         device tensors sized to the capacity; its ``summary`` tells how many records were written."""
-        import torch
-        dev = "cuda:%d" % self.device
-        dims = tuple(int(v) for v in dims)
-        work = torch.empty(max(self.surface_workspace_bytes(dims), 4), dtype=torch.uint8, device=dev)
-        s = _stream(stream)
-        es = torch.cuda.ExternalStream(s, device=dev)
+        call = _Call(self, stream)
+        torch = call.torch
+        origin, dims = _box(origin, dims)
+        work = call.work(self.surface_workspace_bytes(dims))
 
-        def call(cap, quads, verts, tris):
-            summary = torch.zeros(16, dtype=torch.int32, device=dev)
-            N.check(self._L.vxrt_extract_surface(self._h, _i3(origin), _i3(dims), int(mode), _ptr(work), _ptr(quads), cap,
-                                                 _ptr(verts), _ptr(tris), _ptr(summary), s))
+        def extract(cap, quads, verts, tris):
+            summary = call.summary(16)
+            call.launch(self._L.vxrt_extract_surface, _i3(origin), _i3(dims), int(mode), _ptr(work), _ptr(quads), cap, _ptr(verts),
+                        _ptr(tris), _ptr(summary))
             return summary
 
         if capacity is None:
-            counted = call(0, None, None, None)
-            es.synchronize()
+            counted = extract(0, None, None, None)
+            call.stream.synchronize()
             capacity = int(counted.cpu().numpy().view(np.uint32)[2])
         capacity = int(capacity)
         if not 0 <= capacity < 1 << 32:
             raise ValueError("capacity: 0 .. 2^32 - 1 quads")
-        quads = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
-        verts = torch.empty((4 * capacity, 3), dtype=torch.int32, device=dev) if triangles else None
-        tris = torch.empty((2 * capacity, 3), dtype=torch.int32, device=dev) if triangles else None
-        summary = call(capacity, quads if capacity else None, verts, tris)
-        work.record_stream(es)  # freed here, still in use on the call's stream
-        return ExtractedSurface(origin=tuple(int(v) for v in origin), dims=dims, mode=int(mode), quads=quads, vertices=verts,
-                                triangles=tris, _summary=summary, _stream=s)
+        quads = torch.empty((capacity, 2), dtype=torch.int32, device=call.dev)
+        verts = torch.empty((4 * capacity, 3), dtype=torch.int32, device=call.dev) if triangles else None
+        tris = torch.empty((2 * capacity, 3), dtype=torch.int32, device=call.dev) if triangles else None
+        summary = extract(capacity, quads if capacity else None, verts, tris)
+        return ExtractedSurface(origin=origin, dims=dims, mode=int(mode), quads=quads, vertices=verts, triangles=tris,
+                                _summary=summary, _stream=call.s)
 
     def extract_surface_host(self, origin, dims, mode: int = N.SURF_CAP, triangles: bool = False,
                              capacity: int | None = None) -> "ExtractedSurface":
         """extract_surface through the synchronous host call (vxrt_extract_surface_host): numpy arrays, cut to the records
         written."""
-        dims = tuple(int(v) for v in dims)
+        origin, dims = _box(origin, dims)
 
         def call(cap, quads, verts, tris):
             summary = np.zeros(16, np.uint32)
@@ -714,7 +663,7 @@ class Context:
         tris = np.zeros((2 * capacity, 3), np.uint32)
         summary = call(capacity, quads, verts, tris)
         n = int(summary[3])
-        return ExtractedSurface(origin=tuple(int(v) for v in origin), dims=dims, mode=int(mode), quads=quads[:n],
+        return ExtractedSurface(origin=origin, dims=dims, mode=int(mode), quads=quads[:n],
                                 vertices=verts[:4 * n] if triangles else None, triangles=tris[:2 * n] if triangles else None,
                                 _summary=summary, _stream=None)
 
@@ -726,17 +675,13 @@ class Context:
         ``ortho`` flag) and the context's FOV / ortho window.  Asynchronous on ``stream`` (default: torch's current stream).
         ``out``: a contiguous device tensor of width * height four-byte elements (default: a new int32 one).  Returns it,
         shaped (height, width)."""
-        import torch
+        call = _Call(self, stream)
         width, height = int(width), int(height)
         n = width * height if self.denoise_workspace_bytes(width, height) else 0
-        if hit_aov.element_size() != 8 or hit_aov.numel() < n or not hit_aov.is_contiguous():
-            raise ValueError("hit_aov: a contiguous device tensor of width * height int64 elements")
-        if out is None:
-            out = torch.empty(max(n, 1), dtype=torch.int32, device="cuda:%d" % self.device)
-        elif out.element_size() != 4 or out.numel() < n or not out.is_contiguous():
-            raise ValueError("out: a contiguous device tensor of width * height four-byte elements")
-        N.check(self._L.vxrt_frame_guides(self._h, _u32(width), _u32(height), _f3(origin), _f3(fwd), _f3(up), _f3(right),
-                                          1 if ortho else 0, _ptr(hit_aov), _ptr(out), _stream(stream)))
+        call.reads(call.fits(hit_aov, n, 8, "hit_aov: a contiguous device tensor of width * height int64 elements"))
+        out = call.out(n, 4, call.torch.int32, out, "out: a contiguous device tensor of width * height four-byte elements")
+        call.launch(self._L.vxrt_frame_guides, _u32(width), _u32(height), _f3(origin), _f3(fwd), _f3(up), _f3(right),
+                    1 if ortho else 0, _ptr(hit_aov), _ptr(out))
         return out.view(-1)[:n].view(height, width) if n else out
 
     def denoise_workspace_bytes(self, width: int, height: int) -> int:
@@ -754,32 +699,25 @@ class Context:
         ``out``: float32 (height, width, 3), may be ``color`` itself (default: a new tensor); ``fb``: optional uint8
         (height, width, 4) BGRA8 frame written as well; ``work``: a device tensor of at least
         denoise_workspace_bytes(width, height) bytes (default: a new one).  Returns ``out``."""
-        import torch
+        call = _Call(self, stream)
+        torch = call.torch
         if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
             raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
         height, width = int(color.shape[0]), int(color.shape[1])
-        dev = "cuda:%d" % self.device
-        ws = self.denoise_workspace_bytes(width, height)
         n = width * height
-        if keys.element_size() != 4 or keys.numel() < n or not keys.is_contiguous():
-            raise ValueError("keys: a contiguous device tensor of width * height four-byte elements")
+        call.reads(color)
+        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
         if out is None:
             out = torch.empty_like(color)
-        elif out.dtype != torch.float32 or out.numel() < 3 * n or not out.is_contiguous():
+        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
             raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
-        if fb is not None and (fb.numel() * fb.element_size() < 4 * n or not fb.is_contiguous()):
-            raise ValueError("fb: a contiguous device tensor of width * height * 4 bytes")
-        own_work = work is None
-        if own_work:
-            work = torch.empty(max(ws, 16), dtype=torch.uint8, device=dev)
-        elif work.numel() * work.element_size() < ws or not work.is_contiguous():
-            raise ValueError("work: a contiguous device tensor of at least denoise_workspace_bytes(width, height) bytes")
+        if fb is not None:
+            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        work = call.work(self.denoise_workspace_bytes(width, height), work,
+                         "work: a contiguous device tensor of at least denoise_workspace_bytes(width, height) bytes", least=16)
         p = N.DenoiseParams(struct_size=C.sizeof(N.DenoiseParams), iterations=int(iterations), color_scale=float(color_scale))
-        s = _stream(stream)
-        N.check(self._L.vxrt_denoise_frame(self._h, _u32(width), _u32(height), _ptr(color), _ptr(keys), C.byref(p), _ptr(work),
-                                           _ptr(out), _ptr(fb), s))
-        if own_work:
-            work.record_stream(torch.cuda.ExternalStream(s, device=dev))  # freed here, still in use on the call's stream
+        call.launch(self._L.vxrt_denoise_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), C.byref(p), _ptr(work), _ptr(out),
+                    _ptr(fb))
         return out
 
     # ---- occupancy LOD (extension, include/vxrt.h) ----------------------------------------------------------------------
@@ -799,45 +737,32 @@ class Context:
         device tensor of region_words(dims) four-byte elements for the bits; ``work``: a device tensor of at least
         lod_workspace_bytes(dims, shift) bytes (default: new ones).  Returns a Downsampled; reading its ``summary`` waits for
         the call."""
-        import torch
-        dims = tuple(int(v) for v in dims)
-        dev = "cuda:%d" % self.device
+        call = _Call(self, stream)
+        torch = call.torch
+        origin, dims = _box(origin, dims)
         ws = self.lod_workspace_bytes(dims, shift)
-        n = region_words(dims) if ws else 0
-        ncell = dims[0] * dims[1] * dims[2] if ws else 0
-        own_work = work is None
-        if own_work:
-            work = torch.empty(max(ws, 4), dtype=torch.uint8, device=dev)
-        elif work.numel() * work.element_size() < ws or not work.is_contiguous():
-            raise ValueError("work: a contiguous device tensor of at least lod_workspace_bytes(dims, shift) bytes")
-        if out is None:
-            out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        elif out.element_size() != 4 or out.numel() < n or not out.is_contiguous():
-            raise ValueError("out: a contiguous device tensor of at least region_words(dims) four-byte elements")
-        cnt = torch.empty(max(ncell, 1), dtype=torch.int16, device=dev) if counts else None
-        summary = torch.zeros(8, dtype=torch.int32, device=dev)
-        s = _stream(stream)
-        N.check(self._L.vxrt_downsample_region(self._h, _i3(origin), _i3(dims), _u32(shift), _u32(threshold), _ptr(work), _ptr(out),
-                                               _ptr(cnt), _ptr(summary), s))
-        if own_work:
-            work.record_stream(torch.cuda.ExternalStream(s, device=dev))  # freed here, still in use on the call's stream
-        return Downsampled(origin=tuple(int(v) for v in origin), dims=dims, shift=int(shift), threshold=int(threshold),
-                           bits=out.view(-1)[:n], counts=cnt[:ncell] if counts else None, _summary=summary, _stream=s)
+        ncell, n = _counts(dims, ws)
+        work = call.work(ws, work, "work: a contiguous device tensor of at least lod_workspace_bytes(dims, shift) bytes")
+        out = call.out(n, 4, torch.int32, out, "out: a contiguous device tensor of at least region_words(dims) four-byte elements")
+        cnt = call.out(ncell, 2, torch.int16) if counts else None
+        summary = call.summary(8)
+        call.launch(self._L.vxrt_downsample_region, _i3(origin), _i3(dims), _u32(shift), _u32(threshold), _ptr(work), _ptr(out),
+                    _ptr(cnt), _ptr(summary))
+        return Downsampled(origin=origin, dims=dims, shift=int(shift), threshold=int(threshold), bits=out.view(-1)[:n],
+                           counts=cnt[:ncell] if counts else None, _summary=summary, _stream=call.s)
 
     def downsample_host(self, origin, dims, shift: int, threshold: int = 1, counts: bool = True) -> "Downsampled":
         """downsample through the synchronous host call (vxrt_downsample_region_host): ``bits`` is a numpy bool [x, y, z] grid
         and ``counts`` a numpy uint16 [x, y, z] grid (None without ``counts``)."""
-        dims = tuple(int(v) for v in dims)
-        ok = self.lod_workspace_bytes(dims, shift) != 0
-        words = np.zeros(max(region_words(dims) if ok else 0, 1), np.uint32)
-        ncell = dims[0] * dims[1] * dims[2] if ok else 0
+        origin, dims = _box(origin, dims)
+        ncell, n = _counts(dims, self.lod_workspace_bytes(dims, shift))
+        words = np.zeros(max(n, 1), np.uint32)
         cnt = np.zeros(max(ncell, 1), np.uint16)
         summary = np.zeros(8, np.uint32)
         N.check(self._L.vxrt_downsample_region_host(self._h, _i3(origin), _i3(dims), _u32(shift), _u32(threshold), words.ctypes.data,
                                                     cnt.ctypes.data if counts else None, summary.ctypes.data))
-        return Downsampled(origin=tuple(int(v) for v in origin), dims=dims, shift=int(shift), threshold=int(threshold),
-                           bits=unpack_region(words, dims), counts=cnt[:ncell].reshape(dims[::-1]).transpose(2, 1, 0) if counts else None,
-                           _summary=summary, _stream=None)
+        return Downsampled(origin=origin, dims=dims, shift=int(shift), threshold=int(threshold), bits=unpack_region(words, dims),
+                           counts=_grid(cnt, dims) if counts else None, _summary=summary, _stream=None)
 
     def lod_world(self, shift: int, threshold: int = 1, into: "Context | None" = None, box=None,
                   slab_cells: int | None = None) -> "Context":
@@ -1201,6 +1126,11 @@ def _mesh_array(a, np_dtype) -> np.ndarray:
     return np.ascontiguousarray(a.reshape(-1, 3).astype(np_dtype))
 
 
+def _emitter_rows(emitters) -> np.ndarray:
+    """host emitters (None, a list or a numpy array) as contiguous (n, 4) int32 rows x, y, z, level"""
+    return np.ascontiguousarray(np.asarray([] if emitters is None else emitters, np.int32).reshape(-1, 4))
+
+
 def quantize_vertices(xyz) -> np.ndarray:
     """float voxel coordinates -> the int32 fixed point of voxelize_mesh: x * 256 rounded half to even"""
     return np.rint(np.asarray(xyz, np.float64) * 256.0).astype(np.int32).reshape(-1, 3)
@@ -1218,8 +1148,35 @@ class VoxelizeSummary(NamedTuple):
     outside: int
 
 
+class _LazyResult:
+    """What the results of the asynchronous queries share.  Each is a dataclass that ends in ``_summary`` (the summary words:
+    a device tensor until first read, then a numpy uint32 array; a numpy array from the start in a host result) and
+    ``_stream`` (the raw handle of the call's stream; None in a host result), and has ``dims``."""
+
+    def _host(self, t, np_dtype) -> np.ndarray:
+        """a numpy array as it is; a device tensor copied to the host once the call's stream has passed the call"""
+        if isinstance(t, np.ndarray):
+            return t
+        import torch
+        torch.cuda.ExternalStream(self._stream, device=t.device).synchronize()
+        return t.cpu().numpy().view(np_dtype)
+
+    def _words(self) -> list:
+        """the summary words as ints; for a device result the first read waits for the call's stream"""
+        self._summary = self._host(self._summary, np.uint32)
+        return [int(x) for x in self._summary]
+
+    def _xyz(self, t, np_dtype) -> np.ndarray:
+        """one value per voxel as a numpy [x, y, z] grid: a host result holds one already, a device result region order"""
+        return t if isinstance(t, np.ndarray) else _grid(self._host(t, np_dtype), self.dims)
+
+    def _bits(self, t) -> np.ndarray:
+        """bits as a numpy bool [x, y, z] grid: a host result holds one already, a device result region words"""
+        return t if isinstance(t, np.ndarray) else unpack_region(self._host(t, np.uint32), self.dims)
+
+
 @dataclass
-class VoxelizedMesh:
+class VoxelizedMesh(_LazyResult):
     """The result of Context.voxelize_mesh: ``bits`` the region words on the device (a bool [x, y, z] grid from
     voxelize_mesh_host), ``summary`` a VoxelizeSummary."""
     dims: tuple
@@ -1231,20 +1188,11 @@ class VoxelizedMesh:
     @property
     def summary(self) -> VoxelizeSummary:
         """the summary; for a device result this waits for the call's stream"""
-        w = self._summary
-        if not isinstance(w, np.ndarray):
-            import torch
-            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
-            w = self._summary = w.cpu().numpy().view(np.uint32)
-        return VoxelizeSummary(*(int(x) for x in w[:7]))
+        return VoxelizeSummary(*self._words()[:7])
 
     def grid(self) -> np.ndarray:
         """the voxels as a bool [x, y, z] numpy grid (device words are copied to the host)"""
-        if isinstance(self.bits, np.ndarray):
-            return self.bits
-        import torch
-        torch.cuda.ExternalStream(self._stream, device=self.bits.device).synchronize()
-        return unpack_region(self.bits.cpu().numpy().view(np.uint32), self.dims)
+        return self._bits(self.bits)
 
 
 class SurfaceSummary(NamedTuple):
@@ -1259,7 +1207,7 @@ class SurfaceSummary(NamedTuple):
 
 
 @dataclass
-class ExtractedSurface:
+class ExtractedSurface(_LazyResult):
     """The result of Context.extract_surface: ``quads`` (capacity, 2) words pos, ext; ``vertices`` (4 * capacity, 3) int32 at
     256 units per voxel in the box's frame and ``triangles`` (2 * capacity, 3) indices, or None; device tensors (numpy arrays
     cut to the records written from extract_surface_host).  Only the first ``summary.written`` quads hold records."""
@@ -1275,21 +1223,12 @@ class ExtractedSurface:
     @property
     def summary(self) -> SurfaceSummary:
         """the summary; for a device result this waits for the call's stream"""
-        w = self._summary
-        if not isinstance(w, np.ndarray):
-            import torch
-            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
-            w = self._summary = w.cpu().numpy().view(np.uint32)
-        return SurfaceSummary(int(w[0]), int(w[1]), int(w[2]), int(w[3]), tuple(int(x) for x in w[4:10]),
-                              tuple(int(x) for x in w[10:16]))
+        w = self._words()
+        return SurfaceSummary(*w[:4], tuple(w[4:10]), tuple(w[10:16]))
 
     def decode(self):
         """the written quads as numpy arrays (d, x, y, z, w, h): direction, lowest box-relative voxel, extent along u and v"""
-        n = self.summary.written
-        q = self.quads
-        if not isinstance(q, np.ndarray):
-            q = q[:n].cpu().numpy()
-        q = np.ascontiguousarray(q[:n]).view(np.uint32).reshape(-1, 2)
+        q = np.ascontiguousarray(self._host(self.quads[: self.summary.written], np.uint32)).view(np.uint32).reshape(-1, 2)
         pos, ext = q[:, 0], q[:, 1]
         return (ext >> 20, pos & 1023, pos >> 10 & 1023, pos >> 20 & 1023, (ext & 1023) + 1, (ext >> 10 & 1023) + 1)
 
@@ -1306,7 +1245,7 @@ class LodSummary(NamedTuple):
 
 
 @dataclass
-class Downsampled:
+class Downsampled(_LazyResult):
     """The result of Context.downsample: ``bits`` the cell bits as region words of ``dims`` on the device (a Stamp's bits),
     ``counts`` one two-byte count per cell in region order or None; from downsample_host a numpy bool [x, y, z] grid and a
     numpy uint16 [x, y, z] grid.  ``summary`` is a LodSummary."""
@@ -1322,30 +1261,18 @@ class Downsampled:
     @property
     def summary(self) -> LodSummary:
         """the summary; for a device result this waits for the call's stream"""
-        w = self._summary
-        if not isinstance(w, np.ndarray):
-            import torch
-            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
-            w = self._summary = w.cpu().numpy().view(np.uint32)
-        return LodSummary(int(w[0]) | int(w[1]) << 32, int(w[2]), int(w[3]), int(w[4]), int(w[5]), int(w[6]))
+        w = self._words()
+        return LodSummary(w[0] | w[1] << 32, *w[2:7])
 
     def grid(self) -> np.ndarray:
         """the cell bits as a numpy bool [x, y, z] grid (a device result is copied to the host)"""
-        if isinstance(self.bits, np.ndarray):
-            return self.bits
-        import torch
-        torch.cuda.ExternalStream(self._stream, device=self.bits.device).synchronize()
-        return unpack_region(self.bits, self.dims)
+        return self._bits(self.bits)
 
     def count_grid(self) -> np.ndarray:
         """the counts as a numpy uint16 [x, y, z] grid (a device result is copied to the host)"""
         if self.counts is None:
             raise ValueError("the call asked for no counts")
-        if isinstance(self.counts, np.ndarray):
-            return self.counts
-        import torch
-        torch.cuda.ExternalStream(self._stream, device=self.counts.device).synchronize()
-        return self.counts.cpu().numpy().view(np.uint16).reshape(self.dims[::-1]).transpose(2, 1, 0)
+        return self._xyz(self.counts, np.uint16)
 
 
 class LightSummary(NamedTuple):
@@ -1364,7 +1291,7 @@ class LightSummary(NamedTuple):
 
 
 @dataclass
-class LightField:
+class LightField(_LazyResult):
     """The result of Context.light_field: ``levels`` one byte (sky << 4 | block) per voxel in region order on the device (a
     numpy uint8 [x, y, z] grid from light_field_host), ``summary`` a LightSummary."""
     origin: tuple
@@ -1377,21 +1304,12 @@ class LightField:
     @property
     def summary(self) -> LightSummary:
         """the summary; for a device field this waits for the call's stream"""
-        w = self._summary
-        if not isinstance(w, np.ndarray):
-            import torch
-            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
-            w = self._summary = w.cpu().numpy().view(np.uint32)
-        v = [int(x) for x in w]
+        v = self._words()
         return LightSummary(v[0], v[1], tuple(v[2:18]), tuple(v[18:34]), v[34] | v[35] << 32, v[36] | v[37] << 32, *v[38:42])
 
     def grid(self) -> np.ndarray:
         """the packed levels as a numpy uint8 [x, y, z] grid (a device field is copied to the host)"""
-        if isinstance(self.levels, np.ndarray):
-            return self.levels
-        import torch
-        torch.cuda.ExternalStream(self._stream, device=self.levels.device).synchronize()
-        return self.levels.cpu().numpy().reshape(self.dims[::-1]).transpose(2, 1, 0)
+        return self._xyz(self.levels, np.uint8)
 
     def sky(self) -> np.ndarray:
         """the sky levels, 0 .. 15, as a numpy uint8 [x, y, z] grid"""
@@ -1413,7 +1331,7 @@ class DistanceSummary(NamedTuple):
 
 
 @dataclass
-class DistanceField:
+class DistanceField(_LazyResult):
     """The result of Context.distance_field: ``dist2`` one two-byte value per voxel in region order on the device (a numpy
     uint16 [x, y, z] grid from distance_field_host), ``summary`` a DistanceSummary."""
     origin: tuple
@@ -1427,20 +1345,12 @@ class DistanceField:
     @property
     def summary(self) -> DistanceSummary:
         """the summary; for a device field this waits for the call's stream"""
-        w = self._summary
-        if not isinstance(w, np.ndarray):
-            import torch
-            torch.cuda.ExternalStream(self._stream, device=w.device).synchronize()
-            w = self._summary = w.cpu().numpy().view(np.uint32)
-        return DistanceSummary(int(w[0]), int(w[1]), int(w[2]), int(w[3]), int(w[4]) | int(w[5]) << 32)
+        w = self._words()
+        return DistanceSummary(*w[:4], w[4] | w[5] << 32)
 
     def grid(self) -> np.ndarray:
         """the field as a numpy uint16 [x, y, z] grid (a device field is copied to the host)"""
-        if isinstance(self.dist2, np.ndarray):
-            return self.dist2
-        import torch
-        torch.cuda.ExternalStream(self._stream, device=self.dist2.device).synchronize()
-        return self.dist2.cpu().numpy().view(np.uint16).reshape(self.dims[::-1]).transpose(2, 1, 0)
+        return self._xyz(self.dist2, np.uint16)
 
 
 class NavAgent(NamedTuple):
@@ -1504,26 +1414,20 @@ class NavField:
         """Follow the next codes from each world cell of ``starts`` ((n, 3)) for at most ``max_steps`` moves
         (vxrt_nav_paths; asynchronous on ``stream``, default torch's current stream).  Needs the device field of
         Context.nav_field."""
-        import torch
         if not hasattr(self.next, "data_ptr"):
             raise ValueError("paths needs the device field of Context.nav_field")
-        dev = self.next.device
+        call = _Call(self.ctx, stream)
+        i32 = call.torch.int32
         st = np.ascontiguousarray(np.asarray(starts, np.int32).reshape(-1, 3))
         n = st.shape[0]
-        st = torch.as_tensor(st if n else np.zeros((1, 3), np.int32)).to(dev)  # never NULL: n == 0 is the call's no-op
-        out = torch.empty((max(n, 1), int(max_steps) + 1, 3), dtype=torch.int32, device=dev) if cells else None
-        lengths = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        a = self.agent
+        st = call.upload(st) if n else call.out(3, 4, i32)  # never NULL: n == 0 is the call's no-op
+        out = call.torch.empty((max(n, 1), int(max_steps) + 1, 3), dtype=i32, device=call.dev) if cells else None
+        lengths, status = call.out(n, 4, i32), call.out(n, 4, i32)
 
         class _Desc(C.Structure):
             _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("agent", C.c_int32 * 4), ("d_next", C.c_void_p)]
-        desc = _Desc(_i3(self.origin), _i3(self.dims), a._c(), self.next.data_ptr())
-        s = _stream(stream)
-        if n:
-            torch.cuda.current_stream(dev).synchronize()  # the starts' copy, ordered before the call's stream
-        N.check(self.ctx._L.vxrt_nav_paths(self.ctx._h, C.byref(desc), _ptr(st), n, int(max_steps),
-                                           _ptr(out), _ptr(lengths), _ptr(status), s))
+        desc = _Desc(_i3(self.origin), _i3(self.dims), self.agent._c(), call.reads(self.next).data_ptr())
+        call.launch(self.ctx._L.vxrt_nav_paths, C.byref(desc), _ptr(st), n, int(max_steps), _ptr(out), _ptr(lengths), _ptr(status))
         return NavPaths(out[:n] if cells else None, lengths[:n], status[:n])
 
 
@@ -1541,6 +1445,96 @@ def _bodies_dev(bodies):
     if bodies.dtype != torch.float32 or bodies.dim() != 2 or bodies.shape[1] != 9:
         raise ValueError("bodies must be an (n, 9) float32 tensor: lo[3], hi[3], delta[3]")
     return bodies.contiguous()
+
+
+class _Call:
+    """One device query: its stream, its buffers and its one exit.  The four things every query decides the same way:
+    which tensors must outlive the Python call (``work``, ``upload``, ``reads`` note them and ``launch`` records them on the
+    call's stream, so that torch's allocator does not hand their memory out again before the stream has passed the call),
+    how a host array reaches the device ordered before that stream (``upload`` and ``launch``), which tensors of the
+    caller's are accepted (``fits``), and what a placeholder for a refused or empty call looks like (``out``, ``work``)."""
+
+    def __init__(self, ctx: "Context", stream):
+        import torch
+        self.torch, self.ctx = torch, ctx
+        self.dev = "cuda:%d" % ctx.device
+        self.s = _stream(stream)  # the raw handle the library takes
+        self._stream = None
+        self._held = []
+        self._uploaded = False
+
+    @property
+    def stream(self):
+        """the call's stream as torch's"""
+        if self._stream is None:
+            self._stream = self.torch.cuda.ExternalStream(self.s, device=self.dev)
+        return self._stream
+
+    def fits(self, t, count: int, elem_size: int, what: str, any_size: bool = False):
+        """``t``, the caller's: a contiguous device tensor of at least ``count`` elements of ``elem_size`` bytes, or with
+        ``any_size`` of as many bytes in elements of any size; ValueError(``what``) otherwise"""
+        if any_size:
+            enough = t.numel() * t.element_size() >= count * elem_size
+        else:
+            enough = t.element_size() == elem_size and t.numel() >= count
+        if not (enough and t.is_cuda and t.is_contiguous()):  # data_ptr() of a strided tensor is not a dense buffer
+            raise ValueError(what)
+        return t
+
+    def out(self, count: int, elem_size: int, dtype, given=None, what: str = "", any_size: bool = False):
+        """an output of ``count`` elements: a new tensor (one element for a count of 0, never NULL), or ``given`` if it fits"""
+        if given is None:
+            return self.torch.empty(max(count, 1), dtype=dtype, device=self.dev)
+        return self.fits(given, count, elem_size, what, any_size)
+
+    def work(self, nbytes: int, given=None, what: str = "", least: int = 4):
+        """the workspace: new bytes (``least`` for a size of 0, never NULL), or ``given`` if it holds ``nbytes``"""
+        if given is None:
+            return self.reads(self.torch.empty(max(nbytes, least), dtype=self.torch.uint8, device=self.dev))
+        return self.reads(self.fits(given, nbytes, 1, what, any_size=True))
+
+    def summary(self, nwords: int):
+        return self.torch.zeros(nwords, dtype=self.torch.int32, device=self.dev)
+
+    def reads(self, t):
+        """``t``, a device tensor the launch reads or scratches: the caller's, or a temporary dropped when the method returns"""
+        self._held.append(t)
+        return t
+
+    def upload(self, a: np.ndarray):
+        """a host array of four-byte values as an int32 device tensor of its shape, copied on torch's current stream"""
+        self._uploaded = self._uploaded or a.size > 0
+        return self.reads(self.torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(self.dev))
+
+    def launch(self, fn, *args) -> None:
+        """``fn(ctx, *args, stream)`` checked.  An upload was queued on torch's current stream, which need not be the call's:
+        the host waits for it first.  Afterwards every tensor noted is recorded on the call's stream."""
+        if self._uploaded:
+            self.torch.cuda.current_stream(self.dev).synchronize()
+            self._uploaded = False
+        N.check(fn(self.ctx._h, *args, self.s))
+        for t in self._held:
+            t.record_stream(self.stream)
+
+
+def _ints(v) -> tuple:
+    return tuple(int(x) for x in v)
+
+
+def _box(origin, dims):
+    """a box as the results carry it: (origin, dims) as tuples of ints"""
+    return _ints(origin), _ints(dims)
+
+
+def _counts(dims, accepted) -> tuple:
+    """(voxels, region words) of a box the call's contract accepts -- ``accepted``: its workspace size or word count, 0 for
+    a box it refuses -- else (0, 0): the buffers are then one-element placeholders and the library does the refusing"""
+    return (dims[0] * dims[1] * dims[2], region_words(dims)) if accepted else (0, 0)
+
+
+def _grid(a: np.ndarray, dims) -> np.ndarray:
+    """one value per voxel in region order (x fastest, then y, then z) -> [x, y, z]"""
+    return a[: dims[0] * dims[1] * dims[2]].reshape(dims[::-1]).transpose(2, 1, 0)
 
 
 def _i3(v):
