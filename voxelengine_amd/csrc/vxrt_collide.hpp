@@ -226,4 +226,11 @@ __host__ __device__ inline uint32_t collide_overlap_one(const CollideWorld& W, c
     return overlap_count(W, b, b + 3);
 }
 
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_collide.hip on n bodies
+hipError_t move_boxes(const CollideWorld& W, const float* bodies, uint64_t n, const int order[3], float* lohi, uint32_t* flags,
+                      hipStream_t stream);
+hipError_t overlap_boxes(const CollideWorld& W, const float* bodies, uint64_t n, uint32_t* counts, uint32_t* flags,
+                         hipStream_t stream);
+#endif
+
 }  // namespace vxrt

@@ -1,5 +1,5 @@
 // vxrt_denoise.hpp -- the edge-avoiding frame denoiser (include/vxrt.h, vxrt_frame_guides / vxrt_denoise_frame): the pieces
-// shared by the kernels of vxrt_denoise.hip, the host side in vxrt_api.hip and the host harness of the tests
+// shared by the kernels of vxrt_denoise.hip, the host side in vxrt_api_query.hip and the host harness of the tests
 // (tests/tools/denoise_check.cpp, through tests/tools/hoststub): the limits and the workspace formula, the guide key of a
 // pixel from its hit index and primary ray, the record of the ping-pong workspace, the tile a workgroup owns, the staging
 // of a tile with its halo, the 25 taps of a pixel in the order the contract fixes, and the stores.
@@ -227,5 +227,12 @@ inline void dn_grid(uint32_t W, uint32_t H, bool staged, uint32_t& gx, uint32_t&
     gx = (W + kDnTileW - 1u) / kDnTileW;
     gy = (H + th - 1u) / th;
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_denoise.hip
+struct RenderArgs;  // (vxrt_kernels.hpp)
+hipError_t frame_guides(const RenderArgs& R, uint32_t Z, uint32_t* keys, hipStream_t stream);
+hipError_t denoise_frame(uint32_t W, uint32_t H, const float* color_in, const uint32_t* keys, int32_t iterations, float k,
+                         void* work, float* color_out, void* fb, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

@@ -1,5 +1,5 @@
 // vxrt_dist.hpp -- exact distance fields (include/vxrt.h, vxrt_distance_field): the pieces shared by the kernels of
-// vxrt_dist.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/dist_check.cpp, through
+// vxrt_dist.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/dist_check.cpp, through
 // tests/tools/hoststub): the workspace layout, the x distance of one voxel from the halo's bits, the min-plus scan of one
 // column of a slab, the loads and stores of the two sweeps, the occupancy cells and live tiles of the empty-space skip
 // and the summary tally.
@@ -313,5 +313,10 @@ __host__ __device__ inline void dist_z_store(const DistArgs& A, const uint16_t* 
     A.out[i] = (uint16_t)v;
     dist_tally(t, v);
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_dist.hip on the box o, d
+hipError_t distance_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t radius, uint32_t mode, void* work,
+                          uint16_t* dist2, vxrt_distance_summary* summary, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

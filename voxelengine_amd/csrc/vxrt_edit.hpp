@@ -1,5 +1,5 @@
 // vxrt_edit.hpp -- voxel editing (include/vxrt.h, vxrt_edit_voxels): the pieces shared by the kernels of vxrt_edit.hip,
-// the host side in vxrt_api.hip and the host harness of the tests (tests/tools/edit_check.cpp, through
+// the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/edit_check.cpp, through
 // tests/tools/hoststub): op membership, the per-brick op filter, extent packing, and the slot plan.
 #pragma once
 
@@ -172,5 +172,13 @@ inline uint64_t edit_grown_capacity(uint64_t capacity, uint64_t needed)
     const uint64_t g = capacity + (capacity + 1) / 2;
     return needed > g ? needed : g;
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_edit.hip
+hipError_t edit_bricks(const uint32_t* cells, uint32_t n, const EditOpDev* ops, uint32_t nops, const uint2* meta,
+                       const uint32_t* pool, uint32_t* scratch, uint32_t* ext, uint2* info, int f, int cx, int cz);
+hipError_t edit_commit(const uint32_t* cells, const uint32_t* new_slot, uint32_t n, const uint32_t* zero, uint32_t nzero,
+                       const uint32_t* scratch, const uint32_t* ext, uint32_t* pool, uint2* meta, uint32_t* coarse, int f);
+hipError_t gather_bricks(const uint32_t* pool, const uint32_t* idx, uint32_t n, uint32_t* dst, int f);
+#endif
 
 }  // namespace vxrt

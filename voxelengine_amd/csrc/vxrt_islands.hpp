@@ -1,5 +1,5 @@
 // vxrt_islands.hpp -- floating-island detection (include/vxrt.h, vxrt_find_islands): the pieces shared by the kernels of
-// vxrt_islands.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/islands_check.cpp, through
+// vxrt_islands.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/islands_check.cpp, through
 // tests/tools/hoststub): the workspace layout, run starts, the union-find over uint32 parents, the tile-local union, the
 // border merge, the flatten step with its anchor test, the island rank and the table row.
 //
@@ -347,5 +347,11 @@ __host__ __device__ inline void isl_add_to_row(const IslandsArgs& A, uint32_t ra
         atom_max(row + 5 + k, hi[k] + 1);
     }
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_islands.hip on the box o, d
+hipError_t find_islands(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t anchors, void* work,
+                        uint32_t* floating, uint32_t* labels, vxrt_island* table, uint32_t max_islands,
+                        vxrt_island_summary* summary, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

@@ -114,4 +114,20 @@ struct BatchArgs {
     int max_steps;            // Raytrace's maxSteps (VolumeRaytracer.cu:354,386); kMaxSteps unless the caller lowered it
 };
 
+#ifndef VXRT_HOST_CHECK
+// the render, batch and deinterleave launches (vxrt_kernels.hip)
+hipError_t launch_render(const RenderArgs& A, bool stats, int variant, hipStream_t stream);
+int resolve_render_variant(const RenderArgs& A, int variant);
+bool launch_is_common(const RenderArgs& A);
+hipError_t launch_trace_batch(const BatchArgs& B, bool stats, int variant, hipStream_t stream);
+void launch_deinterleave(const void* shards, unsigned long long shard_stride_bytes, void* fb, uint32_t width,
+                         uint32_t height, uint32_t strip_rows, uint32_t strip_count, hipStream_t stream, uint32_t n_views = 1,
+                         unsigned long long view_stride_bytes = 0, unsigned long long fb_stride_bytes = 0);
+// re-ordering between the reference's tiled bit order (the C ABI's and the file's) and the HBM order (vxrt_worldgen.hip)
+hipError_t layout_bits(const uint32_t* src, uint32_t* dst, const int cd[3], bool to_hbm);
+hipError_t layout_meta(const uint2* src, uint2* dst, const int cd[3], bool to_hbm);
+hipError_t layout_bricks(const uint32_t* src, uint32_t* dst, uint64_t nbricks, int f, bool to_hbm);  // src == dst: in place
+hipError_t chunk_tables(uint2* meta, uint32_t* coarse, const uint2* d_chunk_meta, int tx, int ty, int tz, int cx, int cz);
+#endif
+
 }  // namespace vxrt

@@ -1,5 +1,5 @@
 // vxrt_light.hpp -- voxel light fields (include/vxrt.h, vxrt_light_field): the pieces shared by the kernels of
-// vxrt_light.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/light_check.cpp, through
+// vxrt_light.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/light_check.cpp, through
 // tests/tools/hoststub): the workspace layout and, one lane at a time, the work of every launch.
 //
 // Halo.  H = 14.  Halo voxel (hx, hy, hz) is world voxel origin - H + (hx, hy, hz), so voxel (x, y, z) of B is halo voxel
@@ -422,5 +422,10 @@ __host__ __device__ inline void light_tally_lane(const LightArgs& A, uint32_t ch
         t.hist[l] += (uint32_t)__builtin_popcount(m);
     }
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_light.hip on the box o, d
+hipError_t light_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t channels, const int32_t* emitters,
+                       uint32_t n_emitters, void* work, uint8_t* levels, vxrt_light_summary* summary, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

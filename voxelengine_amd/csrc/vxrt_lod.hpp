@@ -1,5 +1,5 @@
 // vxrt_lod.hpp -- occupancy LOD (include/vxrt.h, vxrt_downsample_region): the pieces shared by the kernels of
-// vxrt_lod.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/lod_check.cpp, through
+// vxrt_lod.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/lod_check.cpp, through
 // tests/tools/hoststub): the limits and the workspace layout, the lane mapping, the bit-parallel count of a source word,
 // the walk of one lane over the source rows of its cells and the counts, bits and tallies a lane ends with.
 //
@@ -231,5 +231,10 @@ __host__ __device__ inline void lod_store(const LodArgs& A, uint32_t k, uint32_t
     VXRT_LOD_CHECK(kLodBits, i);
     A.bits[i] = word;
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_lod.hip on the box o, d
+hipError_t downsample_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t shift, uint32_t threshold,
+                             void* work, uint32_t* bits, uint16_t* counts, vxrt_lod_summary* summary, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

@@ -1,5 +1,5 @@
 // vxrt_nav.hpp -- navigation fields (include/vxrt.h, vxrt_nav_field / vxrt_nav_paths): the pieces shared by the kernels of
-// vxrt_nav.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/nav_check.cpp, through
+// vxrt_nav.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/nav_check.cpp, through
 // tests/tools/hoststub): the workspace layout, the three erosion passes that make the free and walkable bits, the goal
 // step, the tile marking, one BFS level of one region word, the next code of one cell and the walk of one path.
 //
@@ -493,5 +493,12 @@ __host__ __device__ inline void nav_path(const NavPathArgs& P, uint64_t i)
     P.lengths[i] = steps;
     P.status[i] = st;
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_nav.hip
+hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[3], const vxrt_nav_agent& ag, const int32_t* goals,
+                     uint32_t ngoals, uint32_t max_dist, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
+                     vxrt_nav_summary* summary, hipStream_t stream);
+hipError_t nav_paths(const NavPathArgs& P, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

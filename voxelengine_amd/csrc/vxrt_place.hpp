@@ -1,5 +1,5 @@
 // vxrt_place.hpp -- voxel piece queries (include/vxrt.h, vxrt_place_pieces): the pieces shared by the kernels of
-// vxrt_place.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/place_check.cpp, through
+// vxrt_place.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/place_check.cpp, through
 // tests/tools/hoststub): placement validation, the launch shape, the overlap count of one piece row at one offset, the
 // 32-step x window of one piece row, and the three per-lane passes (init, sweep, contact) and the finish.
 //
@@ -350,5 +350,9 @@ __host__ __device__ inline void place_finish(const PlaceArgs& A, uint64_t i)
     A.results[i * 4 + 1] = (uint32_t)(p[5] < 0 ? -k : k);
     A.results[i * 4 + 3] = first <= ad ? kPlacedBlocked : 0u;
 }
+
+#ifndef VXRT_HOST_CHECK
+hipError_t place_pieces(const PlaceArgs& A, hipStream_t stream);  // the kernels of vxrt_place.hip
+#endif
 
 }  // namespace vxrt

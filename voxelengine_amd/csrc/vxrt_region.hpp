@@ -1,5 +1,5 @@
 // vxrt_region.hpp -- region readback and voxel stamps (include/vxrt.h, vxrt_read_region / vxrt_edit_stamps): the pieces
-// shared by the kernels of vxrt_region.hip, the host side in vxrt_api.hip and the host harnesses of the tests
+// shared by the kernels of vxrt_region.hip, the host side in vxrt_api_query.hip and the host harnesses of the tests
 // (tests/tools/*_check.cpp, through tests/tools/hoststub): the brick row, the 32-voxel row gather of a read, the
 // funnel-shifted gather of a stamp's bits, the per-row stamp step, the per-brick stamp filter and stamp validation.
 // Every world query (edits, reads, collision, islands, navigation) reads the world through this layer, so it also holds
@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "vxrt_device.hpp"
+#include "../../include/vxrt.h"  // the table and summary types in the signatures of the query families' launchers
 
 namespace vxrt {
 
@@ -57,6 +58,9 @@ inline dim3 grid_2d(uint64_t blocks)
 
 // k_read_region of the box o, d into `out` (region layout); vxrt_region.hip
 hipError_t read_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t* out, hipStream_t stream);
+// k_stamp_bricks: the stamps (StampDev, below) applied to the touched cells, in k_edit_bricks' output format (vxrt_edit.hpp)
+hipError_t stamp_bricks(const uint32_t* cells, uint32_t n, const struct StampDev* stamps, uint32_t nst, const uint2* meta,
+                        const uint32_t* pool, uint32_t* scratch, uint32_t* ext, uint2* info, int f, int cx, int cz);
 
 __device__ inline uint32_t wave_sum(uint32_t v)
 {

@@ -1,7 +1,7 @@
 // vxrt_stream.hpp -- the bookkeeping of chunk streaming (include/vxrt.h, vxrt_stream_*), host C++ only: the chunk table
 // built from a brickmap file's coarse bits and cell records, the distance order, the radius test, the eviction scan and
 // the first-fit pool allocator.  What a load or an eviction does to the file and the device goes through StreamIO:
-// vxrt_api.hip implements it with the file reads, copies and re-ordering launches, tests/tools/stream_check.cpp with
+// vxrt_api_file.hip implements it with the file reads, copies and re-ordering launches, tests/tools/stream_check.cpp with
 // no-ops (and chunks whose read fails), so the policy that runs in the library is the one the host tests check against
 // tests/ref_stream.py.
 #pragma once

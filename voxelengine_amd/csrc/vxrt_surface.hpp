@@ -1,5 +1,5 @@
 // vxrt_surface.hpp -- surface extraction (include/vxrt.h, vxrt_extract_surface): the pieces shared by the kernels of
-// vxrt_surface.hip, the host side in vxrt_api.hip and the host harness of the tests (tests/tools/surface_check.cpp, through
+// vxrt_surface.hip, the host side in vxrt_api_query.hip and the host harness of the tests (tests/tools/surface_check.cpp, through
 // tests/tools/hoststub): the workspace layout, the face words and face bits of the halo, the walk over one row of a mask
 // (counting its quads, or writing them), the test for an identical run in another row and the records a quad writes.
 //
@@ -326,5 +326,10 @@ __host__ __device__ inline uint32_t surf_row_start(const SurfArgs& A, uint32_t i
     VXRT_SURF_CHECK(kSurfGroups, i / kSurfGroup);
     return A.counts[i] + A.groups[i / kSurfGroup];
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_surface.hip on the box o, d
+hipError_t extract_surface(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t mode, void* work, vxrt_quad* quads,
+                           uint32_t capacity, int32_t* verts, uint32_t* tris, vxrt_surface_summary* summary, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

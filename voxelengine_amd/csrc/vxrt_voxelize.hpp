@@ -1,5 +1,5 @@
 // vxrt_voxelize.hpp -- triangle meshes into region-layout bits (include/vxrt.h, vxrt_voxelize_mesh): the pieces shared by
-// the kernels of vxrt_voxelize.hip, the host side in vxrt_api.hip and the host harness of the tests
+// the kernels of vxrt_voxelize.hip, the host side in vxrt_api_query.hip and the host harness of the tests
 // (tests/tools/voxelize_check.cpp, through tests/tools/hoststub): the workspace layout, a triangle's validity, clipped
 // voxel boxes and work items, the integer separating-axis test, the three levels of the surface cull, the solid toggle of
 // one column, the item lookup and the last pass (suffix XOR along a row, the OR of the fields, the popcounts).
@@ -522,5 +522,10 @@ __host__ __device__ inline void vox_final_word(const VoxArgs& A, uint64_t g, boo
     t.surface += (uint32_t)__builtin_popcount(surface);
     t.solid += (uint32_t)__builtin_popcount(solid);
 }
+
+#ifndef VXRT_HOST_CHECK  // the kernels of vxrt_voxelize.hip on a box of d voxels
+hipError_t voxelize_mesh(const int32_t* verts, uint32_t nv, const uint32_t* tris, uint32_t nt, const int32_t d[3], uint32_t modes,
+                         void* work, uint32_t* bits, vxrt_voxelize_summary* summary, uint32_t work_waves, hipStream_t stream);
+#endif
 
 }  // namespace vxrt

@@ -6,19 +6,9 @@
 // workgroup owns one brick: every lane evaluates whole 32-bit words of the brick's tiled-linear bit
 // image (no atomics on bits, no dense intermediate, 64-bit addressing), extents are reduced through LDS,
 // and a second pass packs the non-empty bricks into the pool in coarse tiled-index order.
-#include "../../include/vxrt.h"
-#include "vxrt_kernels.hpp"
-
-#include <string>
-#include <vector>
-
-struct vxrt_ctx;
+#include "vxrt_host.hpp"
 
 namespace vxrt {
-
-int check_shape(int factor, const int cd[3]);
-int alloc_world(vxrt_ctx* c, int factor, const int cd[3], uint64_t pool_slots);
-void fill_view(vxrt_ctx* c, int factor, const int cd[3]);
 
 // ---- generators (must match oracle/vxo_world.c bit for bit; all float ops are exactly specified) ----
 
@@ -346,7 +336,7 @@ __global__ __launch_bounds__(512) void k_chunk_tables(uint2* __restrict__ meta, 
         atomicAnd(&coarse[at >> 5], ~(1u << (at & 31u)));
 }
 
-// host entry points of the above (vxrt_api.hip)
+// host entry points of the above (declared in vxrt_kernels.hpp)
 hipError_t layout_bits(const uint32_t* src, uint32_t* dst, const int cd[3], bool to_hbm)
 {
     const uint64_t nwords = ((uint64_t)cd[0] * cd[1] * cd[2] + 31) / 32;
@@ -386,90 +376,71 @@ hipError_t chunk_tables(uint2* meta, uint32_t* coarse, const uint2* d_chunk_meta
     return hipGetLastError();
 }
 
-}  // namespace vxrt
-
-namespace vxrt {
-
-// accessors into the opaque context (defined in vxrt_api.hip)
-int adopt_world(vxrt_ctx* c, int factor, const int cd[3], uint64_t nslots, uint32_t** d_coarse, uint2** d_meta,
-                uint32_t** d_pool);
-int set_error(int code, const char* msg);
-void abandon_world(vxrt_ctx* c);  // frees the tables of a world whose build failed half way
-
-#define WG_HIP(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            cleanup();                                                                             \
-            return set_error(VXRT_ERR_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-        }                                                                                          \
-    } while (0)
-
 int build_world_on_device(vxrt_ctx* c, int generator, int X, int Y, int Z, int factor)
 {
     if (generator < 0 || generator > 2)
-        return set_error(VXRT_ERR_INVALID, "unknown generator");
+        return fail(VXRT_ERR_INVALID, "unknown generator");
     if (factor <= 0 || X <= 0 || Y <= 0 || Z <= 0 || X % factor || Y % factor || Z % factor)
-        return set_error(VXRT_ERR_INVALID, "world size must be a multiple of the brick edge");
+        return fail(VXRT_ERR_INVALID, "world size must be a multiple of the brick edge");
     int cd[3] = {X / factor, Y / factor, Z / factor};
     int rc = check_shape(factor, cd);
     if (rc)
         return rc;
     const uint64_t ncells = (uint64_t)cd[0] * cd[1] * cd[2];
     const uint64_t bw = (uint64_t)factor * factor * factor / 32;
-    uint32_t *d_scratch = nullptr, *d_ext = nullptr, *d_slot = nullptr;
-    uint8_t* d_any = nullptr;
-    bool adopted = false, done = false;
-    auto cleanup = [&]() {
-        (void)hipFree(d_scratch); (void)hipFree(d_ext); (void)hipFree(d_slot); (void)hipFree(d_any);
-        if (adopted && !done)
-            abandon_world(c);  // a failed pack / coarse-bit pass must not leave a half-built world flagged resident
-    };
-    WG_HIP(hipMalloc((void**)&d_scratch, ncells * bw * sizeof(uint32_t)));
-    WG_HIP(hipMalloc((void**)&d_ext, ncells * sizeof(uint32_t)));
-    WG_HIP(hipMalloc((void**)&d_any, ncells));
+    struct Temps {  // freed on every path
+        uint32_t *scratch = nullptr, *ext = nullptr, *slot = nullptr;
+        uint8_t* any = nullptr;
+        vxrt_ctx* half_built = nullptr;  // a failed pack / coarse-bit pass must not leave a half-built world flagged resident
+        ~Temps()
+        {
+            (void)hipFree(scratch); (void)hipFree(ext); (void)hipFree(slot); (void)hipFree(any);
+            if (half_built)
+                abandon_world(half_built);
+        }
+    } T;
+    VX_HIP(hipMalloc((void**)&T.scratch, ncells * bw * sizeof(uint32_t)));
+    VX_HIP(hipMalloc((void**)&T.ext, ncells * sizeof(uint32_t)));
+    VX_HIP(hipMalloc((void**)&T.any, ncells));
     const unsigned gx = ncells > (1u << 20) ? (1u << 20) : (unsigned)ncells;
     dim3 grid(gx, (unsigned)((ncells + gx - 1) / gx)), block(256);
     if (generator == VXRT_GEN_HASH_HEIGHTFIELD)
-        hipLaunchKernelGGL(k_fill_bricks<VXRT_GEN_HASH_HEIGHTFIELD>, grid, block, 0, 0, d_scratch, d_ext, d_any, cd[0] / 8,
+        hipLaunchKernelGGL(k_fill_bricks<VXRT_GEN_HASH_HEIGHTFIELD>, grid, block, 0, 0, T.scratch, T.ext, T.any, cd[0] / 8,
                            cd[1] / 8, factor, Y, (uint32_t)ncells);
     else if (generator == VXRT_GEN_PERLIN_REF)
-        hipLaunchKernelGGL(k_fill_bricks<VXRT_GEN_PERLIN_REF>, grid, block, 0, 0, d_scratch, d_ext, d_any, cd[0] / 8,
+        hipLaunchKernelGGL(k_fill_bricks<VXRT_GEN_PERLIN_REF>, grid, block, 0, 0, T.scratch, T.ext, T.any, cd[0] / 8,
                            cd[1] / 8, factor, Y, (uint32_t)ncells);
     else
-        hipLaunchKernelGGL(k_fill_bricks<VXRT_GEN_INT_TERRAIN>, grid, block, 0, 0, d_scratch, d_ext, d_any, cd[0] / 8,
+        hipLaunchKernelGGL(k_fill_bricks<VXRT_GEN_INT_TERRAIN>, grid, block, 0, 0, T.scratch, T.ext, T.any, cd[0] / 8,
                            cd[1] / 8, factor, Y, (uint32_t)ncells);
-    WG_HIP(hipGetLastError());
-    WG_HIP(hipDeviceSynchronize());
+    VX_HIP(hipGetLastError());
+    VX_HIP(hipDeviceSynchronize());
 
     // slot numbers in the reference's tiled cell order (host scan of one byte per cell)
     std::vector<uint8_t> any(ncells);
-    WG_HIP(hipMemcpy(any.data(), d_any, ncells, hipMemcpyDeviceToHost));
+    VX_HIP(hipMemcpy(any.data(), T.any, ncells, hipMemcpyDeviceToHost));
     std::vector<uint32_t> slot(ncells);
     uint64_t nslots = 0;
     for (uint64_t i = 0; i < ncells; ++i)
         slot[i] = any[i] ? (uint32_t)nslots++ : kEmptySlot;
-    WG_HIP(hipMalloc((void**)&d_slot, ncells * sizeof(uint32_t)));
-    WG_HIP(hipMemcpy(d_slot, slot.data(), ncells * sizeof(uint32_t), hipMemcpyHostToDevice));
+    VX_HIP(hipMalloc((void**)&T.slot, ncells * sizeof(uint32_t)));
+    VX_HIP(hipMemcpy(T.slot, slot.data(), ncells * sizeof(uint32_t), hipMemcpyHostToDevice));
 
     uint32_t* d_coarse = nullptr;
     uint2* d_meta = nullptr;
     uint32_t* d_pool = nullptr;
     rc = adopt_world(c, factor, cd, nslots, &d_coarse, &d_meta, &d_pool);
-    if (rc) {
-        cleanup();
+    if (rc)
         return rc;
-    }
-    adopted = true;
-    hipLaunchKernelGGL(k_pack_bricks, grid, block, 0, 0, (const uint4*)d_scratch, d_slot, d_ext, (uint4*)d_pool, d_meta,
+    T.half_built = c;
+    hipLaunchKernelGGL(k_pack_bricks, grid, block, 0, 0, (const uint4*)T.scratch, T.slot, T.ext, (uint4*)d_pool, d_meta,
                        (uint32_t)(bw / 4), (uint32_t)ncells, cd[0], cd[1], cd[2]);
-    WG_HIP(hipGetLastError());
+    VX_HIP(hipGetLastError());
     uint64_t nwords = (ncells + 31) / 32;
-    hipLaunchKernelGGL(k_coarse_bits, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, 0, d_any, d_coarse, cd[0], cd[1], cd[2]);
-    WG_HIP(hipGetLastError());
-    WG_HIP(hipDeviceSynchronize());
-    done = true;
-    cleanup();
+    hipLaunchKernelGGL(k_coarse_bits, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, 0, T.any, d_coarse, cd[0], cd[1], cd[2]);
+    VX_HIP(hipGetLastError());
+    VX_HIP(hipDeviceSynchronize());
+    T.half_built = nullptr;
     return VXRT_OK;
 }
 
