@@ -981,7 +981,7 @@ int vxrt_deinterleave_views(vxrt_ctx *ctx, uint32_t width, uint32_t height, int3
  *     operations are binary32, in this order, without contraction.  The last iteration is stored to d_color_out and, when
  *     d_fb_or_null is given, as a BGRA8 pixel by the rule of the render launches (clamp to 0 .. 1, * 255, truncate; bytes
  *     b, g, r, 255).  d_color_in may be the colour AOV of an accumulated frame (d_accum): the filter then works on the mean.
- *     d_color_out may be d_color_in.  d_work, d_keys and the outputs must not overlap otherwise.
+ *     d_color_out may be d_color_in or overlap it in part.  d_work, d_keys and the outputs must not overlap otherwise.
  *   Workspace.  d_work holds vxrt_denoise_workspace_bytes(W, H) = 2 * W * H * 16 bytes (two buffers of one 16-byte record
  *     {r, g, b, key} per pixel; 0 outside the limits on W and H), 16-byte aligned.  The caller owns it.
  *   Call rules.  Both calls are asynchronous on `stream`, allocate nothing, wait for nothing and read no host memory after

@@ -334,27 +334,69 @@ def test_lod_world_built_refreshed_and_downsampled_again(eng, vxo):
         ctx.close()
 
 
-@pytest.mark.parametrize("shift,dims", [(5, (64, 64, 32)), (4, (128, 64, 128)), (3, (256, 128, 256))])
+def _reduce_waves(dims, shift):
+    """the waves of the plain reduce kernel (vxrt_lod.hpp, lod_layout): a cell row takes L lanes, the source row's words
+    rounded up to a power of two up to 64; a wave task is 64 lanes; a wave takes 16, 4 or 1 tasks in turn by shift"""
+    wps = -(-(dims[0] << shift) // 32)
+    L = 1
+    while L < wps and L < 64:
+        L *= 2
+    tasks = -(-wps // 64) * -(-dims[1] * dims[2] // (64 // L))
+    return -(-tasks // {1: 16, 2: 4}.get(shift, 1))
+
+
+def _assert_lod_of_the_part_inside(torch, ctx, vox, o, dims, shift, threshold, inside):
+    """_assert_lod with counts NULL for a box of 2^26 cells and more, which the reference cannot hold: the reference over the
+    cells `inside` that meet the world, the bits compared on the device with every word beyond them 0, and the summary the
+    reference's with the cells beyond the world counted empty"""
+    want = _want(vox, o, inside, shift, threshold)
+    got = ctx.downsample(o, dims, shift, threshold, counts=False)
+    s = list(_summary(want.summary))
+    s[2] += dims[0] * dims[1] * dims[2] - inside[0] * inside[1] * inside[2]
+    print("lod", (o, dims, shift, threshold), tuple(got.summary), tuple(s))
+    assert tuple(got.summary) == tuple(s) and got.counts is None
+    wpo, wpi = -(-dims[0] // 32), -(-inside[0] // 32)
+    expect = torch.zeros((dims[2], dims[1], wpo), dtype=torch.int32, device="cuda")
+    expect[:inside[2], :inside[1], :wpi] = torch.from_numpy(want.words.view(np.int32).reshape(inside[2], inside[1], wpi)).cuda()
+    assert torch.equal(got.bits.view(dims[2], dims[1], wpo), expect)
+    return got, want
+
+
+SOURCE_LIMIT = [(5, (64, 64, 32)), (4, (128, 64, 128)), (3, (256, 128, 256)), (2, (256, 256, 1024)), (1, (512, 1024, 1024))]
+# beside the limit: S = 2^32 makes every side a power of two and the waves a multiple of four
+IDLE_WAVES = [(2, (256, 255, 1023)), (1, (512, 1023, 1023))]
+
+
+@pytest.mark.parametrize("shift,dims", SOURCE_LIMIT + IDLE_WAVES)
 def test_one_call_at_the_source_limit(eng, vxo, shift, dims):
     """S = 2^32 voxels (a 512 MiB workspace), mostly outside the world, counts NULL: the summary equals the reference's over
     the part inside the world and the bits beyond the world are 0.  With 2048 wave tasks and more, these are also the calls
     that take the plain kernel at shifts 4 and 5, where every smaller box of this file takes the one that splits a cell
-    over a workgroup's waves"""
+    over a workgroup's waves.  At shifts 1 and 2 a wave takes 16 and 4 tasks in turn; the boxes of IDLE_WAVES, a cell row
+    and a slice short of the limit, have a wave count that is no multiple of 4, so that the last workgroup has idle waves.
+    Their boxes hold 2^26 cells and more: the reference covers the cells that meet the world, and the rest is compared
+    with 0 on the device"""
     vx, torch = eng
     f = 1 << shift
-    assert f ** 3 * dims[0] * dims[1] * dims[2] == 1 << 32
+    idle = (shift, dims) in IDLE_WAVES
+    S = f ** 3 * dims[0] * dims[1] * dims[2]
+    assert (1 << 32) - (1 << 25) < S < 1 << 32 and _reduce_waves(dims, shift) % 4 != 0 if idle else S == 1 << 32
     rng = np.random.default_rng(shift)
     vox = rng.random((256, 256, 256)) < 0.3
     ctx = vx.Context(0)
     try:
         upload(ctx, vxo.World.from_voxels(vox, 32))
-        assert ctx.lod_workspace_bytes(dims, shift) == 1 << 29
+        assert ctx.lod_workspace_bytes(dims, shift) == (R.workspace_bytes(dims, shift) if idle else 1 << 29)
         o = (-3 * f - 1, -2 * f - 5, -f - 2)
-        got, want = _assert_lod(ctx, vox, o, dims, shift, f ** 3 // 4, counts=False)
-        assert got.summary.solid == int(vox.sum()) and got.summary.set > 0
         inside = tuple(-(-(256 - a) // f) for a in o)  # cells that meet the world
-        grid = got.grid()
-        assert not grid[inside[0]:].any() and not grid[:, inside[1]:].any() and not grid[:, :, inside[2]:].any()
+        if shift <= 2:
+            got, want = _assert_lod_of_the_part_inside(torch, ctx, vox, o, dims, shift, f ** 3 // 4, inside)
+            assert all(a < b for a, b in zip(inside, dims))
+        else:
+            got, want = _assert_lod(ctx, vox, o, dims, shift, f ** 3 // 4, counts=False)
+            grid = got.grid()
+            assert not grid[inside[0]:].any() and not grid[:, inside[1]:].any() and not grid[:, :, inside[2]:].any()
+        assert got.summary.solid == int(vox.sum()) and got.summary.set > 0
     finally:
         ctx.close()
 

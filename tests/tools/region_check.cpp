@@ -2,7 +2,7 @@
 // k_read_region, the stamp filter, the funnel-shifted gather of a stamp's bits and the per-row stamp step of
 // k_stamp_bricks, stamp validation), compiled for the CPU through tests/tools/hoststub and compared with the oracle
 // (oracle/vxo_region.c: vxo_read_region, vxo_apply_stamps; oracle/vxo_world.c: the brickmap builder).  Run by
-// tests/test_region_host.py.
+// tests/test_region_host.py and, box by box, by tests/test_read_limits_host.py.
 // build: g++ -O1 -std=c++17 -Itests/tools/hoststub -Ioracle tests/tools/region_check.cpp -x c oracle/vxo_*.c -lm -lpthread
 #include "../../voxelengine_amd/csrc/vxrt_device.hpp"
 #include "../../voxelengine_amd/csrc/vxrt_edit.hpp"
@@ -107,6 +107,25 @@ static void check_read(int f, int X, int Y, int Z, int rounds, unsigned seed)
     printf("read f=%d %dx%dx%d: %zu words checked, %zu voxels set, failures %d\n", f, X, Y, Z, words, set, fails);
 }
 
+// one given box on a random world (tests/test_read_limits_host.py: the boxes of tests/read_limit_cases.py)
+static void check_box(int f, int X, int Y, int Z, const int32_t o[3], const int32_t d[3], unsigned seed)
+{
+    std::mt19937 rng(seed);
+    std::vector<uint32_t> dense = random_dense(rng, X, Y, Z, 0.4);
+    vxo_world* w = vxo_build_brickmap(dense.data(), X, Y, Z, f);
+    const HbmWorld h = to_hbm(w);
+    const std::vector<uint32_t> got = read_host(h.world(), o, d);
+    std::vector<uint32_t> want(got.size(), 0u);
+    CHECK(got.size() == region_words(d));
+    CHECK(vxo_read_region(dense.data(), X, Y, Z, o, d, want.data()) == 0);
+    CHECK(got == want);
+    size_t set = 0;
+    for (uint32_t v : got) set += __builtin_popcount(v);
+    vxo_world_free(w);
+    printf("box f=%d %dx%dx%d at %d %d %d of %d %d %d: %zu words checked, %zu voxels set, failures %d\n", f, X, Y, Z, o[0], o[1], o[2],
+           d[0], d[1], d[2], got.size(), set, fails);
+}
+
 // stamps: the per-brick logic against the oracle's rebuilt brickmap of the stamped dense grid, every brick of the world
 static void check_stamps(int f, int X, int Y, int Z, int rounds, unsigned seed)
 {
@@ -209,7 +228,10 @@ int main(int argc, char** argv)
     } else {
         const int f = argc > 2 ? atoi(argv[2]) : 8, X = argc > 3 ? atoi(argv[3]) : 64, Y = argc > 4 ? atoi(argv[4]) : X,
                   Z = argc > 5 ? atoi(argv[5]) : X, rounds = argc > 6 ? atoi(argv[6]) : 4;
-        if (mode[0] == 'r')
+        if (mode[0] == 'b' && argc > 11) {  // box f X Y Z ox oy oz dx dy dz
+            const int32_t o[3] = {atoi(argv[6]), atoi(argv[7]), atoi(argv[8])}, d[3] = {atoi(argv[9]), atoi(argv[10]), atoi(argv[11])};
+            check_box(f, X, Y, Z, o, d, 2468u + (unsigned)f);
+        } else if (mode[0] == 'r')
             check_read(f, X, Y, Z, rounds, 4321u + (unsigned)f);
         else
             check_stamps(f, X, Y, Z, rounds, 8765u + (unsigned)f);
