@@ -134,6 +134,9 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     // general instantiations: with the continuation they spill 8 vector registers, so they keep the ray-finished phase's path
     // (their COMMON forms hold 0 spilled VGPRs with it and have it).
     constexpr bool END_SHADOW = !(BOUNCE2 && MULTI) || COMMON;
+    // the round runs the tight-box phase LAST, behind a coarse set-up that probes (below).  Not in the multi-view second-bounce
+    // general instantiation of ordinary grids: in that order it spills 8 vector registers, so it keeps box -> end -> next.
+    constexpr bool BOX_LAST = !(BOUNCE2 && MULTI && !WIDE && !COMMON);
     __shared__ uint32_t cold_block[(CF_TRACER_FIELDS + PF_PIXEL_FIELDS) * 64 + WV_WORDS];  // + the wave's own words (WV_*)
     const WorldView& W = A_kern.W;
     const int lane = threadIdx.x & 63;
@@ -329,12 +332,17 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             dg_drain += drained ? 1ull : 0ull;
         }
 
-        // The parked phases run box -> end -> next inside one round, each vote on fresh counts: a lane whose box test
-        // hits can enter its brick, and a lane whose ray ends can start its next ray, in the same round instead of
-        // waiting for the next round's vote (+4 % with several probes per round; with one probe per round it was +-0)
+        // The parked phases run end -> next -> (coarse set-up with its first probe) -> box inside one round, each vote on fresh
+        // counts: a lane whose ray ends can start its next ray, and a lane whose box test hits can enter its brick, in the same
+        // round instead of waiting for the next round's vote (+4 % with several probes per round; with one probe per round it
+        // was +-0).  The tight-box phase comes LAST (BOX_LAST) because most coarse walks start in an occupied cell: the set-up's
+        // probe parks those lanes and this round's box vote already sees them (profiles/r18_start_probe.md: -10 % rounds per
+        // wave, -2.8 % executed vector instructions, +1.4 %).  What the order gives up, both rare: a box miss that left the world
+        // waits a round for the end-of-walk phase, and a box hit on previous_cell a round for the ray-finished phase.
+        // (!BOX_LAST: box -> end -> next -> plain set-up, the order until then.)
         int c_walk = n_walk, c_box = n_box, c_end = n_end, c_next = n_next;
         bool dg_end_ran = false, dg_end_restarted = false;  // STATS only: this round's end-of-walk phase ran / restarted a lane
-        if (vote2(c_box, c_walk, VXRT_VOTE2_BOX, VXRT_VOTE2_ABS_BOX)) {
+        if (!BOX_LAST && vote2(c_box, c_walk, VXRT_VOTE2_BOX, VXRT_VOTE2_ABS_BOX)) {
             if (STATS) {
                 dg_runs[2] += 1u;
                 dg_lanes[2] += (unsigned)c_box;
@@ -627,8 +635,29 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
         // Before the probes, the coarse walks this round's phases recorded -- restarts after a brick miss (end-of-walk phase) and
         // new rays (ray-finished phase) -- are set up in ONE execution of start_walk<false> over the union of their lanes: the
         // two phases usually run in the same round (finished lanes come from the end-of-walk phase), and the kernel holds one
-        // inlined copy of the set-up instead of two (profiles/r10_coarse_start.md).
-        T.start_pending(W);
+        // inlined copy of the set-up instead of two (profiles/r10_coarse_start.md).  BOX_LAST: the set-up also runs the walks'
+        // first probe, and the tight-box vote follows on fresh ballots -- last burst's box lanes plus the lanes the set-up's probe
+        // has just parked; a brick entry made here has its `fix` consumed by the burst's first probe as before.
+        if constexpr (!BOX_LAST) {
+            T.start_pending(W);
+        } else {
+            const bool set_up = T.pend_m != 0ull;
+            T.template start_pending_probed<STATS>(W);
+            if (set_up) {
+                c_walk = __popcll(__ballot(T.st == ST_WALK));
+                c_box = __popcll(__ballot(T.st == ST_BOX));
+            }
+            if (vote2(c_box, c_walk, VXRT_VOTE2_BOX, VXRT_VOTE2_ABS_BOX)) {
+                if (STATS) {
+                    dg_runs[2] += 1u;
+                    dg_lanes[2] += (unsigned)c_box;
+                    dg_park_ticks -= wall_clock64();
+                }
+                T.template phase_box<STATS>(W);
+                if (STATS)
+                    dg_park_ticks += wall_clock64();
+            }
+        }
         T.template probe_pairs<VXRT_SUBROUNDS2, STATS>(W);
     }
 

@@ -412,6 +412,55 @@ struct WaveTracerT {
         pend_m = 0ull;
     }
 
+    // ... and the FIRST PROBE of the walks it set up, right behind the set-up: the lanes of pend_m that came out ST_WALK load
+    // the word of their start cell, advance once (the same `advance` as the probes', under their mask), consume `fix`, and
+    // are parked ST_BOX (start cell occupied) or ST_END (beyond t_hi / left the grid; every lane in single-step mode), or walk
+    // on.  Most coarse walks start in an occupied cell (profiles/r18_start_probe.md): a caller that runs its tight-box vote
+    // AFTER this sees those lanes in the same round instead of one burst later.  Invariant: the lane's state afterwards is bit
+    // for bit what the first probe of probe_pairs leaves -- tn / idx / rem advanced, rp / rpp / tl / tp the history, fix == 0
+    // -- so the burst that follows is probe 2 onwards for it, and its `idx -= fix` at k == 0 is a no-op for these lanes while
+    // it still serves the brick entries a tight-box phase made in between.  Lanes whose start lies outside the grid (ST_END
+    // from the set-up) probe nothing; no other lane's state is touched (every lane loads, as in the probes).  GUARD: as
+    // probe_pairs'.
+    template <bool GUARD = false>
+    __device__ __forceinline__ void start_pending_probed(const WorldView& W)
+    {
+        if (pend_m == 0ull)
+            return;
+        if (lane_pending())
+            start_walk<false>(W, mk3(__uint_as_float(cold[CF_START_X * 64]), __uint_as_float(cold[CF_START_Y * 64]),
+                                     __uint_as_float(cold[CF_START_Z * 64])));
+#ifdef VXRT_HOST_CHECK
+        if (lane_pending())
+            probe_one<GUARD>(W, true);
+        pend_m = 0ull;
+#else
+        const lanemask_t w = pend_m & lane_mask(st == ST_WALK);
+        pend_m = 0ull;
+        const uint32_t i1 = idx;
+        const uint32_t* a1 = bits + (i1 >> 5);
+        const uint32_t word1 = *a1;
+        if (GUARD)
+            guard_load(W, a1);
+        lanemask_t sus, gd;
+        advance<WIDE || VXRT_PROBE_GD>(w, sus, gd);
+        const lanemask_t park = lane_mask(bit_of(word1, i1) != 0u) & w;
+        const lanemask_t other = w & ~park & (sus | gd);
+        // (exec is all ones here, as in probe_pairs)
+        asm volatile("s_mov_b64 exec, %[w]\n\t"
+                     "v_sub_u32 %[idx], %[idx], %[fix]\n\t"
+                     "v_mov_b32 %[fix], 0\n\t"
+                     "s_mov_b64 exec, %[park]\n\t"
+                     "v_mov_b32 %[st], 1\n\t"
+                     "s_mov_b64 exec, %[other]\n\t"
+                     "v_mov_b32 %[st], 2\n\t"
+                     "s_mov_b64 exec, -1"
+                     : [st] "+v"(st), [idx] "+v"(idx), [fix] "+v"(fix)
+                     : [w] "s"(w), [park] "s"(park), [other] "s"(other));
+        static_assert(ST_BOX == 1u && ST_END == 2u, "state codes of the asm above");
+#endif
+    }
+
     // Raytrace's prologue (:359-384): per-ray constants, world entry, first coarse walk.  Per lane; the caller clears the
     // lanes' bits in fine_m afterwards (after_begin_ray), where the wave is converged again.
     __device__ __forceinline__ void begin_ray(const WorldView& W, f3 origin, f3 ray, int max_steps_)
@@ -776,41 +825,7 @@ struct WaveTracerT {
         for (int p = 0; p < 2 * PAIRS; ++p) {
             if (st != ST_WALK)
                 return;
-            const uint32_t i1 = idx;
-            const uint32_t word = bits[i1 >> 5];
-            if (GUARD)
-                guard_load(W, bits + (i1 >> 5));
-            const bool a0 = tn_x < tn_y && tn_x < tn_z;
-            const bool a1 = !(tn_x < tn_y) && tn_y < tn_z;
-            tp = tl;
-            rpp = rp;
-            rp = rem;
-            tl = lo(lo(tn_x, tn_y), tn_z);
-            if (a0) {
-                tn_x += fabsf(ivx);
-                idx += di_x;
-                rem -= kRemDecX;
-            } else if (a1) {
-                tn_y += fabsf(ivy);
-                idx += di_y;
-                rem -= kRemDecY;
-            } else {
-                tn_z += fabsf(ivz);
-                idx += di_z;
-                rem -= kRemDecZ;
-            }
-            if (p == 0) {
-                idx -= fix;
-                fix = 0u;
-            }
-            const bool sus = !(tl < t_hi), gd = WIDE && (rem & kRemGuards) != 0u;  // (ordinary grids: t_hi stops a lane that leaves)
-            if (!WIDE && (rem & kRemGuards) != 0u && !sus)  // the invariant the GPU probe relies on, counted by the host harness
-                host_unsuspected_exits() += 1;
-            const bool solid = ((word >> (i1 & 31u)) & 1u) != 0u;
-            if (solid)
-                st = lane_fine() ? (uint32_t)ST_ENDHIT : (uint32_t)ST_BOX;
-            else if (sus || gd)
-                st = ST_END;
+            probe_one<GUARD>(W, p == 0);
         }
 #else
         const lanemask_t w0 = lane_mask(st == ST_WALK);
@@ -867,6 +882,51 @@ struct WaveTracerT {
         static_assert(ST_BOX == 1u && ST_ENDHIT == 3u && ST_END == 2u, "state codes of the asm above");
 #endif
     }
+
+#ifdef VXRT_HOST_CHECK
+    // (host build) one probe of a walking lane, as one lane of the GPU's probe executes it; `first`: the probe that consumes fix
+    template <bool GUARD>
+    __device__ __forceinline__ void probe_one(const WorldView& W, const bool first)
+    {
+        if (st != ST_WALK)
+            return;
+        const uint32_t i1 = idx;
+        const uint32_t word = bits[i1 >> 5];
+        if (GUARD)
+            guard_load(W, bits + (i1 >> 5));
+        const bool a0 = tn_x < tn_y && tn_x < tn_z;
+        const bool a1 = !(tn_x < tn_y) && tn_y < tn_z;
+        tp = tl;
+        rpp = rp;
+        rp = rem;
+        tl = lo(lo(tn_x, tn_y), tn_z);
+        if (a0) {
+            tn_x += fabsf(ivx);
+            idx += di_x;
+            rem -= kRemDecX;
+        } else if (a1) {
+            tn_y += fabsf(ivy);
+            idx += di_y;
+            rem -= kRemDecY;
+        } else {
+            tn_z += fabsf(ivz);
+            idx += di_z;
+            rem -= kRemDecZ;
+        }
+        if (first) {
+            idx -= fix;
+            fix = 0u;
+        }
+        const bool sus = !(tl < t_hi), gd = WIDE && (rem & kRemGuards) != 0u;  // (ordinary grids: t_hi stops a lane that leaves)
+        if (!WIDE && (rem & kRemGuards) != 0u && !sus)  // the invariant the GPU probe relies on, counted by the host harness
+            host_unsuspected_exits() += 1;
+        const bool solid = ((word >> (i1 & 31u)) & 1u) != 0u;
+        if (solid)
+            st = lane_fine() ? (uint32_t)ST_ENDHIT : (uint32_t)ST_BOX;
+        else if (sus || gd)
+            st = ST_END;
+    }
+#endif
 
     __device__ __forceinline__ void guard_load(const WorldView& W, const uint32_t* a)
     {
