@@ -56,6 +56,12 @@
 // denoised frames -- with one line "denoise frame N iterations .. color_scale .. hit .. faces .. hash .." (hit pixels, distinct
 // keys, the 64-bit FNV-1a hash of the BGRA frame).  Whole frames only: shaded=0 or 2, views_per_launch=1, frames_in_flight=1.
 // The AOVs, the keys and the workspace are allocated once.
+// A line "frame temporal on|off [max_history]" switches the temporal filter on or off from that frame (vxrt_reproject_frame;
+// max_history defaults to 32): such a frame is rendered with the AOVs, its guide keys are computed and the frame history of
+// the previous frame is reprojected from that frame's pose into this one's -- before the denoiser when both are on, which
+// then filters the accumulated mean -- with one line "temporal frame N max_history .. hit .. reused .. offscreen ..
+// rejected ..".  The history starts anew at the first such frame and after every frame with an edit line.  The same
+// restrictions as for the denoiser; two history and two key buffers are allocated once.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -108,6 +114,11 @@ int main(int argc, char** argv)
         float color_scale;
     };
     std::vector<DenoiseLine> denoise_lines;
+    struct TemporalLine {
+        int frame, max_history;
+        bool on;
+    };
+    std::vector<TemporalLine> temporal_lines;
     if (argc > 12 && std::string(argv[12]) != "-") {
         std::ifstream in(argv[12]);
         if (!in) {
@@ -123,6 +134,14 @@ int main(int argc, char** argv)
             DenoiseLine dl{0, 0, 0.0f};
             if (std::sscanf(line.c_str(), "%d denoise %d %f", &dl.frame, &dl.iterations, &dl.color_scale) >= 2) {
                 denoise_lines.push_back(dl);
+                continue;
+            }
+            TemporalLine tl{0, 32, false};
+            char word[8] = "";
+            if (std::sscanf(line.c_str(), "%d temporal %7s %d", &tl.frame, word, &tl.max_history) >= 2 &&
+                (std::string(word) == "on" || std::string(word) == "off")) {
+                tl.on = std::string(word) == "on";
+                temporal_lines.push_back(tl);
                 continue;
             }
             if (std::sscanf(line.c_str(), "%d %d %d %d %d %d %d %d %d", &e.frame, &e.op.kind, &e.op.value, &e.op.a[0], &e.op.a[1],
@@ -548,20 +567,30 @@ int main(int argc, char** argv)
     // the frame denoiser's buffers: colour AOV, hit-index AOV, keys, workspace -- allocated once, when the script asks for it
     float* d_color = nullptr;
     int64_t* d_hit = nullptr;
-    uint32_t* d_keys = nullptr;
+    uint32_t* d_keys_pair[2] = {nullptr, nullptr};  // this frame's keys and the previous frame's, swapped per frame
     void* d_dn_work = nullptr;
-    if (!denoise_lines.empty()) {
+    vxrt_history* d_hist[2] = {nullptr, nullptr};
+    vxrt_reproject_summary* d_rp_sum = nullptr;
+    if (!denoise_lines.empty() || !temporal_lines.empty()) {
         const size_t n = (size_t)width * height;
         if (batch > 1 || in_flight >= 2 || shade_mode == 1 || vxrt_denoise_workspace_bytes(width, height) == 0) {
-            std::cerr << "denoise: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
+            std::cerr << "denoise, temporal: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
             return 2;
         }
         if (hipMalloc((void**)&d_color, n * 12) != hipSuccess || hipMalloc((void**)&d_hit, n * 8) != hipSuccess ||
-            hipMalloc((void**)&d_keys, n * 4) != hipSuccess ||
+            hipMalloc((void**)&d_keys_pair[0], n * 4) != hipSuccess || hipMalloc((void**)&d_keys_pair[1], n * 4) != hipSuccess ||
             hipMalloc(&d_dn_work, vxrt_denoise_workspace_bytes(width, height)) != hipSuccess)
+            return 1;
+        if (!temporal_lines.empty() &&
+            (hipMalloc((void**)&d_hist[0], n * 16) != hipSuccess || hipMalloc((void**)&d_hist[1], n * 16) != hipSuccess ||
+             hipMalloc((void**)&d_rp_sum, sizeof(vxrt_reproject_summary)) != hipSuccess))
             return 1;
     }
     vxrt_denoise_params dn{sizeof(vxrt_denoise_params), 0, 0.0f, 0};
+    vxrt_reproject_params rp{};
+    rp.struct_size = sizeof(vxrt_reproject_params);
+    bool temporal = false, have_history = false;
+    vxrt_reproject_summary rp_sum{};
     for (int i = 0; batch <= 1 && in_flight < 2 && i < nframes; ++i) {
         apply_edits(i, i + 1);
         for (const DenoiseLine& l : denoise_lines)
@@ -569,10 +598,19 @@ int main(int argc, char** argv)
                 dn.iterations = l.iterations;
                 dn.color_scale = l.color_scale;
             }
+        for (const TemporalLine& l : temporal_lines)
+            if (l.frame == i) {
+                temporal = l.on;
+                rp.max_history = l.max_history;
+            }
+        for (const EditLine& e : edits)
+            if (e.frame == i)
+                have_history = false;  // shadows and bounces change far from an edit's box: the history starts anew
+        uint32_t* const d_keys = d_keys_pair[i & 1];
         pose_for(i);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
-        if (dn.iterations > 0) {
+        if (dn.iterations > 0 || temporal) {
             // the frame with its AOVs through the C ABI (the facade's RenderScreen has no AOV arguments), then keys and filter
             vxrt_ctx* c = raytracer->Context();
             const float o[3] = {cam_pos.x, cam_pos.y, cam_pos.z}, f[3] = {cam_forward.x, cam_forward.y, cam_forward.z},
@@ -587,15 +625,43 @@ int main(int argc, char** argv)
             fl.d_hit_aov = d_hit;
             if (vxrt_set_environment(c, L, C, A) != VXRT_OK || vxrt_set_fov(c, 90) != VXRT_OK || vxrt_set_ortho_window_size(c, 10, 10) != VXRT_OK ||
                 vxrt_render(c, width, height, d_pixels, o, f, u, r, &fl) != VXRT_OK ||
-                vxrt_frame_guides(c, width, height, o, f, u, r, 0, d_hit, d_keys, nullptr) != VXRT_OK ||
-                vxrt_denoise_frame(c, width, height, d_color, d_keys, &dn, d_dn_work, d_color, d_pixels, nullptr) != VXRT_OK ||
+                vxrt_frame_guides(c, width, height, o, f, u, r, 0, d_hit, d_keys, nullptr) != VXRT_OK) {
+                std::cerr << "render and guides, frame " << i << ": " << vxrt_last_error() << std::endl;
+                return 3;
+            }
+            if (temporal) {
+                // the previous frame's history and keys (none at the first such frame and after an edit), its pose in rp.cur
+                rp.prev = rp.cur;
+                for (int k = 0; k < 3; ++k) {
+                    rp.cur.origin[k] = o[k];
+                    rp.cur.fwd[k] = f[k];
+                    rp.cur.up[k] = u[k];
+                    rp.cur.right[k] = r[k];
+                }
+                if (!have_history)
+                    rp.prev = rp.cur;
+                if (vxrt_reproject_frame(c, width, height, d_color, d_keys, have_history ? d_hist[(i + 1) & 1] : nullptr,
+                                         have_history ? d_keys_pair[(i + 1) & 1] : nullptr, &rp, d_hist[i & 1], d_color, d_pixels, d_rp_sum,
+                                         nullptr) != VXRT_OK) {
+                    std::cerr << "temporal, frame " << i << ": " << vxrt_last_error() << std::endl;
+                    return 3;
+                }
+            }
+            if ((dn.iterations > 0 &&
+                 vxrt_denoise_frame(c, width, height, d_color, d_keys, &dn, d_dn_work, d_color, d_pixels, nullptr) != VXRT_OK) ||
                 vxrt_synchronize(c) != VXRT_OK) {
                 std::cerr << "denoise, frame " << i << ": " << vxrt_last_error() << std::endl;
                 return 3;
             }
+            if (temporal)
+                (void)hipMemcpy(&rp_sum, d_rp_sum, sizeof(rp_sum), hipMemcpyDeviceToHost);
         } else {
             RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);
         }
+        have_history = temporal;
+        if (temporal)
+            std::printf("temporal frame %d max_history %d hit %u reused %u offscreen %u rejected %u\n", i, rp.max_history, rp_sum.hit,
+                        rp_sum.reused, rp_sum.offscreen, rp_sum.rejected);
         (void)hipMemcpy(pixels.data(), d_pixels, pixels.size() * sizeof(BGRA8888), hipMemcpyDeviceToHost);
         if (dn.iterations > 0) {
             std::vector<uint32_t> keys((size_t)width * height);
@@ -646,7 +712,11 @@ int main(int argc, char** argv)
     (void)hipStreamDestroy(copy_stream);
     (void)hipFree(d_color);
     (void)hipFree(d_hit);
-    (void)hipFree(d_keys);
+    (void)hipFree(d_keys_pair[0]);
+    (void)hipFree(d_keys_pair[1]);
+    (void)hipFree(d_hist[0]);
+    (void)hipFree(d_hist[1]);
+    (void)hipFree(d_rp_sum);
     (void)hipFree(d_dn_work);
     (void)hipFree(d_pixels);
     delete raytracer;

@@ -894,7 +894,7 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  *   May be captured: vxrt_render, vxrt_render_views and vxrt_trace_batch without stats; vxrt_deinterleave_strips and
  *     vxrt_deinterleave_views; and the purely stream-ordered queries vxrt_read_region, vxrt_move_boxes, vxrt_overlap_boxes,
  *     vxrt_distance_field, vxrt_light_field, vxrt_extract_surface, vxrt_downsample_region and vxrt_find_islands; and the
- *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame.  Under
+ *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame and the temporal filter's vxrt_reproject_frame.  Under
  *     capture they allocate nothing, wait for nothing and read no host memory after they return: a captured multi-view
  *     launch stores its views from kernel arguments, which the graph owns.  Every replay gives what the eager call gives.
  *   Refused under capture, with VXRT_ERR_INVALID and a message that names capture: a render launch with frame_number < 0, in
@@ -1004,6 +1004,74 @@ uint64_t vxrt_denoise_workspace_bytes(uint32_t W, uint32_t H); /* 2 * W * H * 16
 int vxrt_denoise_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color_in /* W*H*3 */, const uint32_t *d_keys,
                        const vxrt_denoise_params *params, void *d_work, float *d_color_out /* W*H*3, may alias d_color_in */,
                        void *d_fb_or_null /* BGRA8 */, void *stream);
+
+/* ---- temporal filter -- an EXTENSION (the same to-do item of the reference, "... temporal accumulation"): the frame history
+ * reprojected across camera moves.  vxrt_render_flags.d_accum averages the stochastic bounce term over frames but needs a
+ * static camera; this call carries a running mean per pixel from the previous frame to the current one through the surface
+ * point every pixel shows.  Every surface is an axis-aligned voxel face and vxrt_frame_guides names it per pixel, so the
+ * hit point is "primary ray meets plane", "the previous frame showed the same surface there" is key equality, and the filter
+ * is specified bit for bit: no depth or normal heuristics, no tolerances.  A post-process over buffers the renderer and
+ * vxrt_frame_guides already write; the render launches know nothing of it and d_accum stays as it is.  A frame pipeline
+ * reads: render with AOVs, guide keys, reproject, a-trous over the accumulated mean (d_color_out is a d_color_in of
+ * vxrt_denoise_frame).
+ *   Frames.  Whole frames with the denoiser's limits: 1 <= W, H <= 65535 and W * H <= 2^26, pixel (x, y) at index x + W * y.
+ *     Strips, compact shards and checkerboard frames are outside the contract.
+ *   Inputs.  d_color_in (W*H*3) and d_keys (W*H) are the colour AOV and the guide keys of the current frame; d_keys_prev and
+ *     d_hist_in are the keys and the d_hist_out of the previous call.  If either of the two is NULL there is no history (the
+ *     first frame, or the caller's reset): no tap is accepted.  The caller ping-pongs two history and two key buffers, and
+ *     resets after vxrt_edit_voxels / vxrt_edit_stamps (shadows and bounces change far from an edit's box) and after a change
+ *     of the FOV or the ortho window.  A record is {r, g, b, n}: the mean and the number of frames in it, 0 on a miss pixel.
+ *   Camera constants.  Both cameras use the context's FOV and ortho window at the time of the call and params->ortho: kx, ky,
+ *     ortho_x, ortho_y and ratio below are the per-launch constants of the render launches (kx = tan(fov / 2) * (W / H),
+ *     ky = tan(fov / 2), ratio = W / H, ortho_x and ortho_y the ortho window).
+ *   All arithmetic is binary32, in the order written, without contraction.  For pixel p = (x, y) with colour c and key k:
+ *     1. Miss.  k == 0: the record is {c, 0}; the pixel counts nowhere.
+ *     2. Hit point.  `hit` is counted.  a = the key's axis, pl = (float)plane.  (o, d) is the pixel's primary ray under `cur`
+ *        exactly as vxrt_render forms it (the ray of vxrt_frame_guides).  t = (pl - o[a]) / d[a]; if d[a] == 0 or t is not
+ *        finite the pixel is offscreen.  P[j] = o[j] + t * d[j] for j != a (one multiply, one add), P[a] = pl.
+ *     3. Into the previous camera.  r = P - prev.origin; dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z.
+ *        Perspective: z = dot(r, prev.fwd); the pixel is offscreen unless z > 0; su = dot(r, prev.right) / (z * kx),
+ *        sv = dot(r, prev.up) / (z * ky).  Ortho: su = dot(r, prev.right) / (ortho_x * ratio), sv = dot(r, prev.up) / ortho_y.
+ *        fx = ((su + 1) * 0.5f) * (float)W and fy likewise with H (pixel x looks through u = x / W, so an integer fx is a
+ *        pixel exactly).  The pixel is offscreen unless fx >= -1 && fx <= W && fy >= -1 && fy <= H (a NaN fails).
+ *     4. Taps.  x0 = floor(fx), wx = fx - x0; y0 and wy likewise.  The four taps, in this order: (x0, y0), (x0+1, y0),
+ *        (x0, y0+1), (x0+1, y0+1), with weights (1-wx)*(1-wy), wx*(1-wy), (1-wx)*wy, wx*wy.  A tap q is accepted when it lies
+ *        in the frame, its weight is > 0, keys_prev(q) == k and hist_in(q).n >= 1.  With sw = 0, sc = (0, 0, 0) and
+ *        nmin = +inf, an accepted tap does sw += w, sc.ch += w * hist_in(q).ch per channel and nmin = min(nmin, hist_in(q).n).
+ *        A tap that is not accepted leaves the sums untouched -- a select, not an addition of zero: a NaN behind a foreign
+ *        key stays out, as in the denoiser.
+ *     5. Blend.  If no tap lies in the frame the pixel is offscreen; else, if none is accepted, it is rejected (a
+ *        disocclusion).  Both give the record {c, 1}.  Otherwise the pixel is reused: m = sc / sw per channel,
+ *        n' = min(nmin + 1, (float)max_history), out = m + (c - m) / n' (one subtract, one divide, one add); record {out, n'}.
+ *     6. Outputs.  d_hist_out takes the record, d_color_out (if given) its rgb, d_fb (if given) the BGRA8 pixel by the rule
+ *        of the render launches (clamp to 0 .. 1, * 255, truncate; bytes b, g, r, 255).  d_summary (if given) is zeroed on
+ *        the stream by the call and then takes the four counts: hit = reused + offscreen + rejected.
+ *   Why key equality is enough.  P lies on plane k by construction.  If the previous pixel q showed plane k from the same
+ *     side, then q's ray met that plane within about a pixel's footprint of P -- the same surface point, up to the footprint
+ *     every bilinear tap has.  Two faces of one plane and side that are apart in the world are apart in the frame as well.
+ *   Aliasing.  d_color_out may be d_color_in.  d_hist_out must not overlap d_hist_in.  Nothing else may overlap.
+ *   Call rules.  Asynchronous on `stream`; allocates nothing, waits for nothing and reads no host memory after it returns;
+ *     may be captured (STREAM CAPTURE above).  No world is needed: the keys carry the geometry.  Refusals, each
+ *     VXRT_ERR_INVALID before anything is enqueued or written, checked in this order: a NULL ctx; W or H outside the limits;
+ *     params NULL or its struct_size; max_history outside 1 .. 65535 or a nonzero reserved_; a non-finite component in either
+ *     pose; a NULL d_color_in, d_keys or d_hist_out.
+ *   The cost is one launch (and one 16-byte memset with a summary): per pixel 16 bytes read of its own, four 16-byte records
+ *     and four keys of the previous frame, which neighbouring lanes largely share, and 32 bytes written. */
+typedef struct vxrt_history { float r, g, b, n; } vxrt_history; /* 16 bytes, 16-byte aligned; n = frames in the mean */
+typedef struct vxrt_camera_pose { float origin[3], fwd[3], up[3], right[3]; } vxrt_camera_pose;
+typedef struct vxrt_reproject_params {
+    uint32_t struct_size;
+    int32_t ortho;
+    int32_t max_history;  /* 1 .. 65535 */
+    int32_t reserved_;    /* 0 */
+    vxrt_camera_pose cur, prev;
+} vxrt_reproject_params;
+typedef struct vxrt_reproject_summary { uint32_t hit, reused, offscreen, rejected; } vxrt_reproject_summary;
+int vxrt_reproject_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color_in, const uint32_t *d_keys,
+                         const vxrt_history *d_hist_in_or_null, const uint32_t *d_keys_prev_or_null,
+                         const vxrt_reproject_params *params, vxrt_history *d_hist_out,
+                         float *d_color_out_or_null, void *d_fb_or_null,
+                         vxrt_reproject_summary *d_summary_or_null, void *stream);
 
 /* ---- batch query.  Replaces VoxelRaytracer3D::Raytrace + kernel dispatch
  * (VoxelRT/VolumeRaytracer.cu:95-117,574-618).  Results follow the reference

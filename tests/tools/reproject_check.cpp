@@ -1,0 +1,212 @@
+// Host harness of the temporal filter (voxelengine_amd/csrc/vxrt_reproject.hpp: the limits, the hit point of a pixel, its
+// position in the previous frame, the four taps, the blend and the stores), compiled for the CPU through tests/tools/hoststub
+// and run workgroup by workgroup and lane by lane.  The harness restates what vxrt_reproject.hip adds around that code,
+// which the GPU suite covers:
+//   the launch      rp_launch_shape's workgroups, every lane on the pixels rp_wave_pixel gives its wave (every pixel of the
+//                   frame exactly once), lanes outside the frame idle;
+//   the camera      one lane per pixel, its primary ray handed in (the camera is the renderer's, covered on the GPU);
+//   the summary     zeroed, then the lanes' results counted.
+// Every index the code forms into an input or an output is checked against that array's size (an array the call was not
+// given has size 0); every array carries a guard behind it.  Self-contained (no oracle code), so that a stand-alone
+// sanitizer build is one compiler line.  Run by tests/test_reproject_host.py, which compares with tests/ref_reproject.py.
+//
+//   reproject_check in.bin out.bin
+//   in:  i32 op, W, H, flags, max_history, compute units, 0, 0
+//   op 0 (filter): flags: 1 ortho, 2 history given, 4 fb, 8 colour output, 16 the colour output is the colour input, 32 summary;
+//        then 5 f32 kx, ky, ortho_x, ortho_y, ratio; 12 f32 the previous camera's origin, fwd, up, right; W * H * 3 f32 colours;
+//        W * H u32 keys; W * H * 3 f32 ray origins; W * H * 3 f32 ray directions; (history) W * H * 4 f32 records, W * H u32 keys
+//        out: W * H * 4 f32 records; (colour output) W * H * 3 f32; (fb) W * H u32 BGRA8; (summary) 4 u32
+//   op 2 (limits; nothing is read beyond the header): out: u32 frame accepted, u32 max_history accepted
+//   stdout: indices checked, "ALL OK" or "FAILED"
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+static int fails = 0;
+static uint64_t checked = 0;
+static uint64_t g_size[16];
+#define CHECK(c)                                                    \
+    do {                                                            \
+        if (!(c)) {                                                 \
+            if (fails < 20)                                         \
+                printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); \
+            ++fails;                                                \
+        }                                                           \
+    } while (0)
+static bool check_index(int array, uint64_t index)
+{
+    ++checked;
+    if (index < g_size[array])
+        return true;
+    if (fails < 20)
+        printf("FAIL: index %llu of array %d (size %llu)\n", (unsigned long long)index, array, (unsigned long long)g_size[array]);
+    ++fails;
+    return false;
+}
+// an index outside its array ends the run before the access
+#define VXRT_RP_CHECK(array, index)                   \
+    do {                                              \
+        if (!check_index(array, (uint64_t)(index))) { \
+            printf("FAILED\n");                       \
+            exit(1);                                  \
+        }                                             \
+    } while (0)
+
+#include "../../voxelengine_amd/csrc/vxrt_reproject.hpp"
+using namespace vxrt;
+
+static int run_filter(const int32_t* hd, FILE* in, const char* out_path)
+{
+    const uint32_t W = (uint32_t)hd[1], H = (uint32_t)hd[2], flags = (uint32_t)hd[3];
+    const bool ortho = flags & 1u, history = flags & 2u, fb = flags & 4u, cout_given = flags & 8u, alias = flags & 16u, summary = flags & 32u;
+    if (!denoise_frame_ok(W, H) || !reproject_history_ok(hd[4]) || (alias && !cout_given)) {
+        printf("outside the contract\n");
+        return 2;
+    }
+    const uint64_t n = (uint64_t)W * H;
+    const uint32_t guard = 0x5A5A5A5Au;
+    float guardf;
+    memcpy(&guardf, &guard, 4);
+    float consts[5], pose[12];
+    std::vector<float> cin(3u * n + 1u), cout_(3u * n + 1u, guardf), o(3u * n), d(3u * n);
+    std::vector<uint32_t> keys(n + 1u), kprev(n + 1u), fbv(n + 1u, guard), sum(5u, guard);
+    std::vector<RpRec> hin(n + 1u), hout(n + 1u, RpRec{guardf, guardf, guardf, guardf});
+    if (fread(consts, 4, 5, in) != 5 || fread(pose, 4, 12, in) != 12 || fread(cin.data(), 4, 3u * n, in) != 3u * n ||
+        fread(keys.data(), 4, n, in) != n || fread(o.data(), 4, 3u * n, in) != 3u * n || fread(d.data(), 4, 3u * n, in) != 3u * n)
+        return 2;
+    if (history && (fread(hin.data(), 16, n, in) != n || fread(kprev.data(), 4, n, in) != n))
+        return 2;
+    cin[3u * n] = guardf;
+    keys[n] = kprev[n] = guard;
+    hin[n] = RpRec{guardf, guardf, guardf, guardf};
+    const std::vector<float> cin0 = cin;
+    const std::vector<uint32_t> keys0 = keys, kprev0 = kprev;
+    const std::vector<RpRec> hin0 = hin;
+
+    ReprojectArgs A{};
+    A.color_in = cin.data();
+    A.keys = keys.data();
+    A.hist_in = history ? hin.data() : nullptr;
+    A.keys_prev = history ? kprev.data() : nullptr;
+    A.hist_out = hout.data();
+    A.color_out = !cout_given ? nullptr : alias ? cin.data() : cout_.data();
+    A.fb = fb ? fbv.data() : nullptr;
+    A.summary = summary ? sum.data() : nullptr;
+    A.W = W;
+    A.H = H;
+    A.ortho = ortho ? 1 : 0;
+    A.max_history = (float)hd[4];
+    A.kx = consts[0];
+    A.ky = consts[1];
+    A.ortho_x = consts[2];
+    A.ortho_y = consts[3];
+    A.ratio = consts[4];
+    for (int k = 0; k < 3; ++k) {
+        A.po[k] = pose[k];
+        A.pf[k] = pose[3 + k];
+        A.pu[k] = pose[6 + k];
+        A.pr[k] = pose[9 + k];
+    }
+    g_size[kRpColorIn] = 3u * n;
+    g_size[kRpKeys] = n;
+    g_size[kRpHistIn] = history ? n : 0u;
+    g_size[kRpKeysPrev] = history ? n : 0u;
+    g_size[kRpHistOut] = n;
+    g_size[kRpColorOut] = cout_given ? 3u * n : 0u;
+    g_size[kRpFb] = fb ? n : 0u;
+
+    // the launch of vxrt_reproject.hip, restated: every lane of every workgroup walks its wave's tiles
+    uint32_t block = 0u, grid = 0u;
+    rp_launch_shape(W, H, summary, (uint32_t)hd[5], block, grid);
+    CHECK(grid >= 1u && (block == kRpPlain || block == kRpCounted) && (summary || grid == rp_tiles(W, H)));
+    CHECK(!summary || grid <= (uint32_t)hd[5] * kRpCountedPerCu);
+    const uint32_t per = block >> 6, waves = grid * per;
+    uint32_t count[4] = {0u, 0u, 0u, 0u};
+    uint64_t pixels = 0;
+    std::vector<uint8_t> seen(n, 0);
+    for (uint32_t b = 0; b < grid; ++b)
+        for (uint32_t tid = 0; tid < block; ++tid) {
+            uint32_t x, y;
+            for (uint32_t i = 0; rp_wave_pixel(W, H, b * per + (tid >> 6), waves, i, tid & 63u, x, y); ++i) {
+                if (x >= W || y >= H)
+                    continue;
+                const uint64_t at = (uint64_t)y * W + x;
+                CHECK(!seen[at]);
+                seen[at] = 1;
+                const uint32_t what = rp_pixel(A, x, y, &o[3u * at], &d[3u * at]);
+                CHECK(what <= (uint32_t)kRpRejected);
+                CHECK((what == (uint32_t)kRpMiss) == (keys0[at] == 0u));
+                ++count[what];
+                ++pixels;
+            }
+        }
+    CHECK(pixels == n);
+    if (summary) {
+        sum[0] = count[kRpReused] + count[kRpOffscreen] + count[kRpRejected];
+        sum[1] = count[kRpReused];
+        sum[2] = count[kRpOffscreen];
+        sum[3] = count[kRpRejected];
+    }
+
+    // guards, and the inputs unchanged (the colours: unless they are the output)
+    uint32_t g[2];
+    memcpy(&g[0], &cin[3u * n], 4);
+    memcpy(&g[1], &cout_[3u * n], 4);
+    CHECK(g[0] == guard && g[1] == guard && keys[n] == guard && kprev[n] == guard && fbv[n] == guard && sum[4] == guard);
+    CHECK(memcmp(&hin[n], &hin0[n], 16) == 0 && memcmp(&hout[n].n, &guard, 4) == 0);
+    CHECK(keys == keys0 && kprev == kprev0 && memcmp(hin.data(), hin0.data(), 16u * n) == 0);
+    if (!alias)
+        CHECK(memcmp(cin.data(), cin0.data(), 12u * n) == 0);
+    if (!cout_given || alias)
+        for (uint64_t i = 0; i < 3u * n; ++i)
+            CHECK(memcmp(&cout_[i], &guard, 4) == 0);
+    if (!fb)
+        for (uint64_t i = 0; i < n; ++i)
+            CHECK(fbv[i] == guard);
+    if (!summary)
+        for (int i = 0; i < 4; ++i)
+            CHECK(sum[i] == guard);
+
+    FILE* out = fopen(out_path, "wb");
+    if (!out)
+        return 2;
+    fwrite(hout.data(), 16, n, out);
+    if (cout_given)
+        fwrite(alias ? cin.data() : cout_.data(), 4, 3u * n, out);
+    if (fb)
+        fwrite(fbv.data(), 4, n, out);
+    if (summary)
+        fwrite(sum.data(), 4, 4, out);
+    fclose(out);
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) {
+        printf("usage: reproject_check in.bin out.bin\n");
+        return 2;
+    }
+    FILE* in = fopen(argv[1], "rb");
+    int32_t hd[8];
+    if (!in || fread(hd, 4, 8, in) != 8)
+        return 2;
+    int rc = 0;
+    if (hd[0] == 0) {
+        rc = run_filter(hd, in, argv[2]);
+    } else {
+        const uint32_t ok[2] = {denoise_frame_ok((uint32_t)hd[1], (uint32_t)hd[2]) ? 1u : 0u, reproject_history_ok(hd[4]) ? 1u : 0u};
+        FILE* out = fopen(argv[2], "wb");
+        if (!out)
+            return 2;
+        fwrite(ok, 4, 2, out);
+        fclose(out);
+    }
+    fclose(in);
+    if (rc)
+        return rc;
+    printf("%llu indices checked, failures %d\n%s\n", (unsigned long long)checked, fails, fails ? "FAILED" : "ALL OK");
+    return fails ? 1 : 0;
+}

@@ -8,7 +8,7 @@ from ._native import (PLACE_MAX_DIM, PLACE_MAX_DIST, PLACE_MAX_PIECES, PLACE_MAX
                       ISLAND_ANCHOR_Y_LO, ISLAND_ANCHOR_Z_HI, ISLAND_ANCHOR_Z_LO, BODY_BLOCKED_X, BODY_BLOCKED_Y, BODY_BLOCKED_Z, BODY_INVALID, BODY_MAX_DELTA, BODY_MAX_EXTENT, EDIT_BOX, EDIT_MAX_OPS, EDIT_SPHERE, EMPTY_SLOT, GEN_HASH_HEIGHTFIELD, GEN_INT_TERRAIN, GEN_PERLIN_REF,
                       MAX_STEPS, MODE_DEBUG, MODE_SHADED, STAMP_REPLACE, STAMP_SUBTRACT, STAMP_UNION, EXPORTS, EditOp,
                       EditStats, FrameStats, StampDesc, VxrtError, lib_path, load)
-from .engine import (Piece, Placement, PLACED_DTYPE, DROP_DTYPE, LightField, LightSummary, Downsampled, LodSummary, ExtractedSurface, SurfaceSummary, VoxelizedMesh, VoxelizeSummary, quantize_vertices, DistanceField, DistanceSummary, NavAgent, NavField, NavPaths, NavSummary, nav_move, ISLAND_DTYPE, Body, Context, Islands, IslandSummary, EditBox, EditSphere, GetDirections, RenderOptions, Stamp, compact_rows, grid_is_wide,
+from .engine import (Reprojected, ReprojectSummary, Piece, Placement, PLACED_DTYPE, DROP_DTYPE, LightField, LightSummary, Downsampled, LodSummary, ExtractedSurface, SurfaceSummary, VoxelizedMesh, VoxelizeSummary, quantize_vertices, DistanceField, DistanceSummary, NavAgent, NavField, NavPaths, NavSummary, nav_move, ISLAND_DTYPE, Body, Context, Islands, IslandSummary, EditBox, EditSphere, GetDirections, RenderOptions, Stamp, compact_rows, grid_is_wide,
                      pack_region, region_words, tile_schedule, unpack_region, world_file_info)
 
 __all__ = ["Context", "RenderOptions", "GetDirections", "compact_rows", "grid_is_wide", "tile_schedule", "world_file_info", "FrameStats",
@@ -25,6 +25,7 @@ __all__ = ["Context", "RenderOptions", "GetDirections", "compact_rows", "grid_is
            "DistanceField", "DistanceSummary", "DIST_TO_SOLID", "DIST_TO_EMPTY", "DIST_FAR", "DIST_MAX_RADIUS",
            "VoxelizedMesh", "VoxelizeSummary", "quantize_vertices", "VOX_SURFACE", "VOX_SOLID", "VOX_FRAC_BITS", "VOX_MAX_DIM",
            "VOX_MAX_COORD", "VOX_MAX_TRIANGLES", "ExtractedSurface", "SurfaceSummary", "SURF_CAP", "SURF_OPEN", "SURF_MAX_DIM", "Downsampled", "LodSummary", "LOD_MAX_SHIFT",
+           "Reprojected", "ReprojectSummary",
            "LightField", "LightSummary", "LIGHT_SKY", "LIGHT_BLOCK", "LIGHT_MAX", "LIGHT_MAX_EMITTERS",
            "Piece", "Placement", "PieceDesc", "PLACED_DTYPE", "DROP_DTYPE", "PLACE_MAX_PIECES", "PLACE_MAX_DIM", "PLACE_MAX_VOXELS",
            "PLACE_MAX_DIST", "PLACED_BLOCKED", "PLACED_INVALID"]

@@ -34,7 +34,7 @@ EXPORTS = [
     "vxrt_surface_workspace_bytes", "vxrt_extract_surface", "vxrt_extract_surface_host",
     "vxrt_lod_workspace_bytes", "vxrt_downsample_region", "vxrt_downsample_region_host",
     "vxrt_light_workspace_bytes", "vxrt_light_field", "vxrt_light_field_host",
-    "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame",
+    "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
@@ -128,6 +128,15 @@ class RenderFlags(C.Structure):
 
 class DenoiseParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("color_scale", C.c_float), ("reserved_", C.c_int32)]
+
+
+class CameraPose(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("fwd", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3)]
+
+
+class ReprojectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("max_history", C.c_int32), ("reserved_", C.c_int32),
+                ("cur", CameraPose), ("prev", CameraPose)]
 
 
 class View(C.Structure):
@@ -272,6 +281,8 @@ def load() -> C.CDLL:
     L.vxrt_denoise_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
     L.vxrt_denoise_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams),
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_reproject_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(ReprojectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

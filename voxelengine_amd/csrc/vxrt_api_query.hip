@@ -1,5 +1,5 @@
 // vxrt_api_query.hip -- the part of the C ABI (include/vxrt.h) that works on the resident world: the edit path (vxrt_edit_*),
-// every query family with its _host twin, and the frame denoiser's entry points.  No kernel is defined here: each family's
+// every query family with its _host twin, and the entry points of the frame denoiser and the temporal filter.  No kernel is defined here: each family's
 // launcher is declared in its header and defined in its own .hip.
 #include "vxrt_collide.hpp"
 #include "vxrt_denoise.hpp"
@@ -11,10 +11,12 @@
 #include "vxrt_lod.hpp"
 #include "vxrt_nav.hpp"
 #include "vxrt_place.hpp"
+#include "vxrt_reproject.hpp"
 #include "vxrt_surface.hpp"
 #include "vxrt_voxelize.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 // ---- voxel editing (include/vxrt.h): host side of the two kernels of vxrt_edit.hip -----------------------------------------
@@ -934,6 +936,66 @@ int vxrt_denoise_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color
     VX_HIP(hipSetDevice(c->device));
     VX_HIP(vxrt::denoise_frame(W, H, d_color_in, d_keys, params->iterations, params->color_scale, d_work, d_color_out,
                                d_fb_or_null, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+// ---- temporal filter ---------------------------------------------------------------------------------------------------
+int vxrt_reproject_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_in, const uint32_t* d_keys,
+                         const vxrt_history* d_hist_in_or_null, const uint32_t* d_keys_prev_or_null,
+                         const vxrt_reproject_params* params, vxrt_history* d_hist_out, float* d_color_out_or_null, void* d_fb_or_null,
+                         vxrt_reproject_summary* d_summary_or_null, void* stream)
+{
+    // the order of include/vxrt.h
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (!vxrt::denoise_frame_ok(W, H))
+        return fail(VXRT_ERR_INVALID, "reproject: 1 <= W, H <= 65535 and W * H <= 2^26");
+    if (!params || params->struct_size != sizeof(vxrt_reproject_params))
+        return fail(VXRT_ERR_INVALID, "vxrt_reproject_params missing or size mismatch");
+    if (!vxrt::reproject_history_ok(params->max_history) || params->reserved_ != 0)
+        return fail(VXRT_ERR_INVALID, "reproject max_history: 1 .. 65535 (and reserved_ 0)");
+    const vxrt_camera_pose* const poses[2] = {&params->cur, &params->prev};
+    for (const vxrt_camera_pose* p : poses)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->origin[k]) || !std::isfinite(p->fwd[k]) || !std::isfinite(p->up[k]) || !std::isfinite(p->right[k]))
+                return fail(VXRT_ERR_INVALID, "reproject: a camera pose with a non-finite component");
+    if (!d_color_in || !d_keys || !d_hist_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::RenderArgs R;
+    memset(&R, 0, sizeof(R));
+    vxrt::camera_args(c, W, H, R);
+    R.ortho = params->ortho ? 1 : 0;
+    R.origin = vxrt::f3{params->cur.origin[0], params->cur.origin[1], params->cur.origin[2]};
+    R.fwd = vxrt::f3{params->cur.fwd[0], params->cur.fwd[1], params->cur.fwd[2]};
+    R.up = vxrt::f3{params->cur.up[0], params->cur.up[1], params->cur.up[2]};
+    R.right = vxrt::f3{params->cur.right[0], params->cur.right[1], params->cur.right[2]};
+    vxrt::ReprojectArgs A{};
+    const bool history = d_hist_in_or_null && d_keys_prev_or_null;
+    A.color_in = d_color_in;
+    A.keys = d_keys;
+    A.hist_in = history ? (const vxrt::RpRec*)d_hist_in_or_null : nullptr;
+    A.keys_prev = history ? d_keys_prev_or_null : nullptr;
+    A.hist_out = (vxrt::RpRec*)d_hist_out;
+    A.color_out = d_color_out_or_null;
+    A.fb = (uint32_t*)d_fb_or_null;
+    A.summary = (uint32_t*)d_summary_or_null;
+    A.W = W;
+    A.H = H;
+    A.ortho = R.ortho;
+    A.max_history = (float)params->max_history;
+    A.kx = R.kx;
+    A.ky = R.ky;
+    A.ortho_x = R.ortho_x;
+    A.ortho_y = R.ortho_y;
+    A.ratio = R.ratio;
+    for (int k = 0; k < 3; ++k) {
+        A.po[k] = params->prev.origin[k];
+        A.pf[k] = params->prev.fwd[k];
+        A.pu[k] = params->prev.up[k];
+        A.pr[k] = params->prev.right[k];
+    }
+    VX_HIP(vxrt::reproject_frame(R, A, c->cus, (hipStream_t)stream));
     return VXRT_OK;
 }
 

@@ -720,6 +720,52 @@ class Context:
                     _ptr(fb))
         return out
 
+    # ---- temporal filter (extension, include/vxrt.h) --------------------------------------------------------------------
+    def reproject_frame(self, color, keys, cur, prev, history=None, prev_keys=None, max_history: int = 32, ortho: bool = False,
+                        out_history=None, out=None, fb=None, summary: bool = True, stream: int | None = None):
+        """The frame history reprojected across a camera move (include/vxrt.h, vxrt_reproject_frame): ``color`` a float32
+        device tensor (height, width, 3) such as the colour AOV of a render, ``keys`` its guide keys (frame_guides), ``cur``
+        and ``prev`` the cameras of this frame and the previous one as (origin, fwd, up, right), ``history`` and
+        ``prev_keys`` the ``history`` and the keys of the previous call's result (either None: no history, every hit pixel
+        starts a new mean).  Every hit pixel takes the running mean of the surface point it shows from the previous frame,
+        where that frame showed the same voxel face, and blends its colour in: out = m + (c - m) / n, n at most
+        ``max_history``.  Asynchronous on ``stream`` (default: torch's current stream), as denoise_frame.
+        ``out_history``: float32 (height, width, 4), must not be ``history`` (default: a new tensor); ``out``: float32
+        (height, width, 3), may be ``color`` itself (default: a new tensor); ``fb``: optional uint8 (height, width, 4) BGRA8
+        frame written as well.  Returns a Reprojected: ``history``, ``color`` and, with ``summary``, a lazily read
+        ReprojectSummary."""
+        call = _Call(self, stream)
+        torch = call.torch
+        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
+            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
+        height, width = int(color.shape[0]), int(color.shape[1])
+        n = width * height
+        call.reads(color)
+        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
+        if history is not None:
+            if call.fits(history, 4 * n, 4, "history: a contiguous float32 device tensor (height, width, 4)").dtype != torch.float32:
+                raise ValueError("history: a contiguous float32 device tensor (height, width, 4)")
+            call.reads(history)
+        if prev_keys is not None:
+            call.reads(call.fits(prev_keys, n, 4, "prev_keys: a contiguous device tensor of width * height four-byte elements"))
+        if out_history is None:
+            out_history = torch.empty((height, width, 4), dtype=torch.float32, device=call.dev)
+        elif call.fits(out_history, 4 * n, 4, "out_history: a contiguous float32 device tensor (height, width, 4)").dtype != torch.float32:
+            raise ValueError("out_history: a contiguous float32 device tensor (height, width, 4)")
+        if out is None:
+            out = torch.empty_like(color)
+        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
+            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
+        if fb is not None:
+            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        words = call.summary(4) if summary else None
+        p = N.ReprojectParams(struct_size=C.sizeof(N.ReprojectParams), ortho=1 if ortho else 0, max_history=int(max_history))
+        for pose, cam in ((p.cur, cur), (p.prev, prev)):
+            pose.origin, pose.fwd, pose.up, pose.right = (_f3(v) for v in cam)
+        call.launch(self._L.vxrt_reproject_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), _ptr(history), _ptr(prev_keys),
+                    C.byref(p), _ptr(out_history), _ptr(out), _ptr(fb), _ptr(words))
+        return Reprojected(dims=(width, height), history=out_history, color=out, _summary=words, _stream=call.s)
+
     # ---- occupancy LOD (extension, include/vxrt.h) ----------------------------------------------------------------------
     def lod_workspace_bytes(self, dims, shift: int) -> int:
         """vxrt_lod_workspace_bytes: the workspace of one downsample call, 0 outside the contract"""
@@ -1351,6 +1397,32 @@ class DistanceField(_LazyResult):
     def grid(self) -> np.ndarray:
         """the field as a numpy uint16 [x, y, z] grid (a device field is copied to the host)"""
         return self._xyz(self.dist2, np.uint16)
+
+
+class ReprojectSummary(NamedTuple):
+    """vxrt_reproject_summary: hit pixels, and of them those that took over a history, those whose surface point lay outside
+    the previous frame, and those the previous frame showed another face at (disocclusions); hit is the sum of the three"""
+    hit: int
+    reused: int
+    offscreen: int
+    rejected: int
+
+
+@dataclass
+class Reprojected(_LazyResult):
+    """The result of Context.reproject_frame: ``history`` float32 (height, width, 4) records {r, g, b, frames in the mean} --
+    the ``history`` argument of the next frame's call --, ``color`` float32 (height, width, 3) its rgb, device tensors;
+    ``dims`` is (width, height).  ``summary`` is a ReprojectSummary, or None when the call was made without one."""
+    dims: tuple
+    history: object
+    color: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> ReprojectSummary | None:
+        """the summary; the first read waits for the call's stream"""
+        return None if self._summary is None else ReprojectSummary(*self._words()[:4])
 
 
 class NavAgent(NamedTuple):
