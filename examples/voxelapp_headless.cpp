@@ -62,6 +62,12 @@
 // then filters the accumulated mean -- with one line "temporal frame N max_history .. hit .. reused .. offscreen ..
 // rejected ..".  The history starts anew at the first such frame and after every frame with an edit line.  The same
 // restrictions as for the denoiser; two history and two key buffers are allocated once.
+// A line "frame rule x0 y0 z0 x1 y1 z1 n6|n18|n26 born_hex survive_hex iterations box|world" applies a neighbour-count rule
+// (VoxelRaytracer3D::ApplyRule) to the box of the inclusive corners (x0, y0, z0) .. (x1, y1, z1) -- born_hex / survive_hex: bit
+// c set = an empty voxel is born / a solid voxel survives with c solid neighbours -- stamps the result (replace) and prints one
+// line "rule before frame N: before .. after .. born .. died .. changed_last .. box <lo x3> <hi x3>, ... bricks touched".
+// "frame smooth x0 y0 z0 x1 y1 z1 iterations" is the shorthand for the majority rule on the box alone
+// (VoxelRaytracer3D::SmoothVoxels), with the same line.  Both are applied in file order with the edit lines.
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -106,7 +112,8 @@ int main(int argc, char** argv)
 
     struct EditLine {
         int frame;
-        vxrt_edit_op op;
+        vxrt_edit_op op;  // kind 12: a rule line (a = the box's origin, b = its dims; value 1: the smooth shorthand)
+        vxrt_rule rule;
     };
     std::vector<EditLine> edits;
     struct DenoiseLine {
@@ -143,6 +150,36 @@ int main(int argc, char** argv)
                 tl.on = std::string(word) == "on";
                 temporal_lines.push_back(tl);
                 continue;
+            }
+            {
+                int c[6], iterations = 1;
+                char nb[8] = "", scope[8] = "";
+                unsigned born = 0, survive = 0;
+                const bool rule = std::sscanf(line.c_str(), "%d rule %d %d %d %d %d %d %7s %x %x %d %7s", &e.frame, &c[0], &c[1], &c[2], &c[3],
+                                              &c[4], &c[5], nb, &born, &survive, &iterations, scope) == 12;
+                const bool smooth = !rule && std::sscanf(line.c_str(), "%d smooth %d %d %d %d %d %d %d", &e.frame, &c[0], &c[1], &c[2], &c[3],
+                                                         &c[4], &c[5], &iterations) == 8;
+                if (rule || smooth) {
+                    const std::string n(nb), sc(scope);
+                    if (rule && ((n != "n6" && n != "n18" && n != "n26") || (sc != "box" && sc != "world"))) {
+                        std::cerr << "edit script: cannot read \"" << line << "\"" << std::endl;
+                        return 2;
+                    }
+                    e.op.kind = 12;
+                    e.op.value = smooth ? 1 : 0;
+                    for (int k = 0; k < 3; ++k) {
+                        e.op.a[k] = c[k];
+                        e.op.b[k] = c[3 + k] - c[k] + 1;
+                    }
+                    e.rule.struct_size = sizeof(vxrt_rule);
+                    e.rule.neighbours = n == "n6" ? VXRT_RULE_N6 : n == "n18" ? VXRT_RULE_N18 : VXRT_RULE_N26;
+                    e.rule.born = born;
+                    e.rule.survive = survive;
+                    e.rule.iterations = iterations;
+                    e.rule.scope = sc == "world" ? VXRT_RULE_WORLD : VXRT_RULE_BOX;
+                    edits.push_back(e);
+                    continue;
+                }
             }
             if (std::sscanf(line.c_str(), "%d %d %d %d %d %d %d %d %d", &e.frame, &e.op.kind, &e.op.value, &e.op.a[0], &e.op.a[1],
                             &e.op.a[2], &e.op.b[0], &e.op.b[1], &e.op.b[2]) == 9)
@@ -363,6 +400,27 @@ int main(int argc, char** argv)
                 for (size_t i = 0; i < levels.size(); ++i)
                     h = (h ^ levels[i]) * 0x100000001b3ull;
                 std::printf("light hash frame %d levels %016llx\n", from, (unsigned long long)h);
+            } else if (e.op.kind == 12) {  // a neighbour-count rule, or the smooth shorthand, stamped
+                flush_ops();
+                vxrt_rule_summary sum{};
+                vxrt_edit_stats st{};
+                int rc;
+                if (e.op.value) {
+                    rc = raytracer->SmoothVoxels(e.op.a, e.op.b, e.rule.iterations, &st, &sum);
+                } else {
+                    std::vector<uint32_t> bits;
+                    rc = raytracer->ApplyRule(e.op.a, e.op.b, e.rule, bits, sum);
+                    if (rc == VXRT_OK)
+                        rc = raytracer->StampVoxels(e.op.a, e.op.b, bits.data(), VXRT_STAMP_REPLACE, &st);
+                }
+                if (rc != VXRT_OK) {
+                    std::cerr << "rule before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("rule before frame %d: before %u after %u born %u died %u changed_last %u box %d %d %d %d %d %d, %llu bricks "
+                            "touched\n", from, sum.solid_before, sum.solid_after, sum.born, sum.died, sum.changed_last, sum.changed_min[0],
+                            sum.changed_min[1], sum.changed_min[2], sum.changed_max[0], sum.changed_max[1], sum.changed_max[2],
+                            (unsigned long long)st.bricks_touched);
             } else if (e.op.kind == 11) {  // drop the islands
                 flush_ops();
                 std::vector<VoxelRaytracer3D::DroppedIsland> rows;

@@ -37,6 +37,8 @@ struct vxrt_quad;
 struct vxrt_surface_summary;
 struct vxrt_lod_summary;
 struct vxrt_light_summary;
+struct vxrt_rule;
+struct vxrt_rule_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -235,6 +237,17 @@ public:
     // queued edits first.  Returns the vxrt_status.
     int LightField(const int32_t origin[3], const int32_t dims[3], const std::vector<int32_t>& emitters, uint32_t channels,
                    std::vector<uint8_t>& levels, vxrt_light_summary& summary);
+
+    // voxel rules (extension, include/vxrt.h, vxrt_apply_rule_host): the box origin .. origin + dims - 1 after the rule's
+    // iterations as region words (a StampVoxels argument as it is) and the summary; the world is not changed.  `mask`:
+    // region words of `dims` (VXRT_RULE_BOX only: the voxels a step may change) or NULL.  Flushes queued edits first.
+    // Returns the vxrt_status.
+    int ApplyRule(const int32_t origin[3], const int32_t dims[3], const vxrt_rule& rule, std::vector<uint32_t>& bits,
+                  vxrt_rule_summary& summary, const uint32_t* mask = nullptr);
+    // ApplyRule with the majority rule (N26, born with 14 or more solid neighbours, kept with 13 or more) on the box alone,
+    // then one StampVoxels of the result in VXRT_STAMP_REPLACE: the box is smoothed in place.  Returns the vxrt_status.
+    int SmoothVoxels(const int32_t origin[3], const int32_t dims[3], int32_t iterations = 1, vxrt_edit_stats* stats = nullptr,
+                     vxrt_rule_summary* summary = nullptr);
 
 private:
     void Flush();

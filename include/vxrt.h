@@ -795,6 +795,77 @@ int vxrt_light_field(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[
 int vxrt_light_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const int32_t *emitters,
                           uint32_t n_emitters, uint32_t channels, uint8_t *levels, vxrt_light_summary *summary);
 
+/* ---- voxel rules -- an EXTENSION (the reference's to-do item "Better landscape generation" in its classic cheap form, a
+ * 3-D cellular automaton, and with the editing above the smooth / grow / erode brush): every voxel of a box replaced by a
+ * function of itself and of how many of its neighbours are solid, a few times over, without leaving the bit-packed form.  A
+ * call looks at one box B = [origin, origin + dims) of world voxels and changes nothing: its result is a stamp.
+ *   Neighbourhoods.  For an offset d != 0 with d in {-1, 0, 1}^3: VXRT_RULE_N6 holds the offsets with |d|_1 = 1, VXRT_RULE_N18
+ *     those with |d|_1 <= 2, VXRT_RULE_N26 all 26.  N = 6, 18, 26 is their number.
+ *   Step.  For a world state W (one bit per voxel), S(W)(v) = bit c of `survive` if W(v) = 1, else bit c of `born`, where
+ *     c = the sum over the neighbourhood's offsets d of W(v + d).  A voxel outside the world has the constant value
+ *     `outside` (0: empty, as for vxrt_read_region; 1: solid) in every W_i and is never changed.
+ *   Free voxels.  F is the set a step may change.
+ *     VXRT_RULE_BOX: F = B intersected with the world and, with a mask, only the voxels whose mask bit is 1.  The mask is in
+ *       B's region layout, vxrt_region_words(dims) words; its padding bits are ignored.  Everything else is frozen at W_0:
+ *       the rule runs on the box alone, and n iterations give exactly what n calls of one iteration would give, each
+ *       followed by a VXRT_STAMP_REPLACE stamp of its result.  The halo is h = 1.
+ *     VXRT_RULE_WORLD: F = the world.  B is a window into the result of running the rule n times on the whole world, so
+ *       tiles computed from the same W_0 meet without seams.  A value in B after n steps depends on W_0 within Chebyshev
+ *       distance n, so the halo is h = iterations.  A mask is refused.
+ *   Iteration.  W_0 = the resident world; W_i+1(v) = S(W_i)(v) for v in F, and W_i(v) otherwise, for i = 0 .. n - 1 with
+ *     n = `iterations`.  The result is a function of the world, the arguments and the mask alone: it does not depend on the
+ *     scheduling, and two calls are bit-identical.
+ *   Limits.  1 <= dims[k]; dims[0] * dims[1] * dims[2] <= 2^28; the halo box (dims[k] + 2 h per axis) within
+ *     vxrt_read_region's 2^36 voxels; origin[k] - h >= -2^31 and origin[k] + dims[k] + h <= 2^31 - 1;
+ *     1 <= iterations <= VXRT_RULE_MAX_ITERATIONS = 16.
+ * Outputs:
+ *   d_bits: W_n over B in region layout (vxrt_region_words(dims) words), padding bits 0.  Voxels of B outside the world are 0
+ *     whatever `outside` says.  It is directly usable as a VXRT_STAMP_REPLACE stamp at `origin`.
+ *   d_summary: over the world voxels of B only.  solid_before = the voxels with W_0 = 1, solid_after those with W_n = 1;
+ *     born = the voxels that are 0 in W_0 and 1 in W_n, died those that are 1 in W_0 and 0 in W_n, so
+ *     solid_after = solid_before + born - died; changed_last = the voxels with W_n != W_n-1 (0: a fixed point was reached);
+ *     changed_min / changed_max = the inclusive bounding box, in world coordinates, of the voxels with W_n != W_0, and
+ *     INT32_MAX / INT32_MIN on every axis when there is none: the box to stamp, to relight (grown by 14) and after which to
+ *     reset a frame history.  reserved_ is 0.  Integer sums and integer min / max only.
+ * Workspace.  d_work holds vxrt_rule_workspace_bytes(dims, rule) bytes, 0 outside the limits on dims and the rule's fields.
+ *   It depends on dims and the rule only, never on the world.  With r(n) = n rounded up to a multiple of 256, h the halo,
+ *   hd[k] = dims[k] + 2 h, wh = ceil(hd[0] / 32) and P = 4 * wh * hd[1] * hd[2] (one bit plane of the halo box):
+ *     bytes = 4 * r(P)
+ *   (W_0, F and the two planes the rounds write in turn).  The caller owns it; the library allocates nothing per call.
+ * Call rules (as vxrt_light_field): asynchronous on `stream`; the launches follow from the arguments alone (`iterations`
+ *   rounds whatever the world holds), the call never synchronises with the host and can be captured.  Checked in this order:
+ *   a NULL ctx, origin, dims, rule, d_work, d_bits or d_summary; the rule's struct_size; neighbours; bits of born or survive
+ *   above N; iterations; scope; outside; a nonzero reserved_; a mask given with VXRT_RULE_WORLD; the dims and the halo box;
+ *   the origin -- each VXRT_ERR_INVALID; then no world: VXRT_ERR_NO_WORLD; then a streamed world: VXRT_ERR_INVALID (a cache is
+ *   not queried).  A refused call enqueues and writes nothing.  The call never loads outside the tables.
+ * vxrt_apply_rule_host takes host buffers (the mask in; bits and summary out, the same sizes), allocates its own workspace
+ *   and is synchronous.
+ * The cost is one region read of the halo box and `iterations` rounds of word operations over its bit planes: per output
+ *   word 27 plane words read and about 200 word operations, no voxel visited on its own.  A world-sized pass is made of
+ *   VXRT_RULE_WORLD calls on tiles, all made before the first of their stamps is written. */
+#define VXRT_RULE_MAX_ITERATIONS 16
+typedef enum vxrt_rule_neighbours { VXRT_RULE_N6 = 0, VXRT_RULE_N18 = 1, VXRT_RULE_N26 = 2 } vxrt_rule_neighbours;
+typedef enum vxrt_rule_scope { VXRT_RULE_BOX = 0, VXRT_RULE_WORLD = 1 } vxrt_rule_scope;
+typedef struct vxrt_rule {
+    uint32_t struct_size;
+    int32_t neighbours;  /* vxrt_rule_neighbours; N = 6, 18, 26 */
+    uint32_t born;       /* bit c: an empty voxel with c solid neighbours becomes solid; bits above N must be 0 */
+    uint32_t survive;    /* bit c: a solid voxel with c solid neighbours stays solid; bits above N must be 0 */
+    int32_t iterations;  /* 1 .. VXRT_RULE_MAX_ITERATIONS */
+    int32_t scope;       /* vxrt_rule_scope */
+    int32_t outside;     /* 0: voxels outside the world count as empty (as vxrt_read_region); 1: as solid */
+    int32_t reserved_;   /* 0 */
+} vxrt_rule;
+typedef struct vxrt_rule_summary {
+    uint32_t solid_before, solid_after, born, died, changed_last, reserved_;
+    int32_t changed_min[3], changed_max[3];
+} vxrt_rule_summary;
+uint64_t vxrt_rule_workspace_bytes(const int32_t dims[3], const vxrt_rule *rule); /* 0 outside the contract */
+int vxrt_apply_rule(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_rule *rule,
+                    const uint32_t *d_mask_or_null, void *d_work, uint32_t *d_bits, vxrt_rule_summary *d_summary, void *stream);
+int vxrt_apply_rule_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_rule *rule,
+                         const uint32_t *mask_or_null, uint32_t *bits, vxrt_rule_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],
@@ -893,7 +964,8 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  * holds the sentences below to the references of the eager paths).
  *   May be captured: vxrt_render, vxrt_render_views and vxrt_trace_batch without stats; vxrt_deinterleave_strips and
  *     vxrt_deinterleave_views; and the purely stream-ordered queries vxrt_read_region, vxrt_move_boxes, vxrt_overlap_boxes,
- *     vxrt_distance_field, vxrt_light_field, vxrt_extract_surface, vxrt_downsample_region and vxrt_find_islands; and the
+ *     vxrt_distance_field, vxrt_light_field, vxrt_apply_rule (tests/test_gpu_rule.py), vxrt_extract_surface,
+ *     vxrt_downsample_region and vxrt_find_islands; and the
  *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame and the temporal filter's vxrt_reproject_frame.  Under
  *     capture they allocate nothing, wait for nothing and read no host memory after they return: a captured multi-view
  *     launch stores its views from kernel arguments, which the graph owns.  Every replay gives what the eager call gives.

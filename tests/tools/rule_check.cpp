@@ -1,0 +1,183 @@
+// Host harness of the neighbour-count voxel rules (voxelengine_amd/csrc/vxrt_rule.hpp: the set-up of the W_0 and F planes, the
+// rounds with their bit-sliced count and mux trees, the funnel-shifted output and its tally, of the kernels of
+// vxrt_rule.hip), compiled for the CPU through tests/tools/hoststub and run one lane at a time, launch by launch, in the
+// order vxrt_rule.hip launches them.  The world is the oracle's brickmap (oracle/vxo_world.c) of a dense grid, laid out as
+// the library holds it in HBM; the halo's bits come from region_row_word, clipped as k_read_region clips.  Every index the
+// code forms into a plane, the mask or the output is checked against that array's size, and after every launch the padding
+// bits of the plane it wrote.  Run by tests/test_rule_host.py, which compares the outputs with tests/ref_rule.py.
+//
+//   rule_check in.bin out.bin
+//   in:  i32 op, f, X, Y, Z, origin[3], dims[3], neighbours, born, survive, iterations, scope, outside, has_mask;
+//        X * Y * Z / 32 u32 dense words (vxo_sample_index64); with has_mask region_words(dims) u32 mask words
+//   op 0 (apply): out: 12 u32 (vxrt_rule_summary), region_words(dims) u32 bits
+//   op 1 (layout only; no world is built): out: u32 rule_check's code, u32 accepted by rule_layout with the origin, u32
+//        accepted without it, u64 total_bytes
+//   stdout: indices checked, "ALL OK" or "FAILED"
+#include <cstdint>
+#include <cstdio>
+
+static void check_index(int array, uint64_t index);
+#define VXRT_RULE_CHECK(array, index) check_index(array, (uint64_t)(index))
+
+#include "../../voxelengine_amd/csrc/vxrt_rule.hpp"
+#include "hbm_world.h"
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+using namespace vxrt;
+
+// the padding bits of every row of a plane are 0
+static void check_padding(const RuleArgs& A, const uint32_t* plane)
+{
+    const uint32_t rem = ((uint32_t)A.d[0] + 2u * A.h) & 31u;
+    if (!rem)
+        return;
+    for (uint64_t row = 0; row < (uint64_t)A.hy * A.hz; ++row)
+        CHECK((plane[row * A.wh + A.wh - 1u] >> rem) == 0u);
+}
+
+template <int NB>
+static void round_all(const RuleArgs& A, int32_t i)
+{
+    const uint32_t* src = rule_src(A, i);
+    uint32_t* dst = rule_dst(A, i);
+    CHECK(src != dst && dst != A.w0 && dst != A.free);
+    for (uint64_t w = 0; w < A.np; ++w)
+        rule_round_lane<NB>(A, src, dst, w);
+    check_padding(A, dst);
+}
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) {
+        printf("usage: rule_check in.bin out.bin\n");
+        return 2;
+    }
+    FILE* in = fopen(argv[1], "rb");
+    int32_t hd[18];
+    if (!in || fread(hd, 4, 18, in) != 18)
+        return 2;
+    const int op = hd[0], f = hd[1], X = hd[2], Y = hd[3], Z = hd[4];
+    const int32_t o[3] = {hd[5], hd[6], hd[7]}, d[3] = {hd[8], hd[9], hd[10]};
+    vxrt_rule rule{};
+    rule.struct_size = sizeof(vxrt_rule);
+    rule.neighbours = hd[11];
+    rule.born = (uint32_t)hd[12];
+    rule.survive = (uint32_t)hd[13];
+    rule.iterations = hd[14];
+    rule.scope = hd[15];
+    rule.outside = hd[16];
+    const bool has_mask = hd[17] != 0;
+    RuleLayout L{};
+    if (op == 1) {
+        fclose(in);
+        const uint32_t code = (uint32_t)rule_check(rule);
+        const int32_t h = code ? 1 : rule_halo(rule);
+        const uint32_t with = !code && rule_layout(o, d, h, L) ? 1u : 0u, without = !code && rule_layout(nullptr, d, h, L) ? 1u : 0u;
+        const uint64_t bytes = without ? L.total_bytes : 0u;
+        FILE* out = fopen(argv[2], "wb");
+        if (!out)
+            return 2;
+        fwrite(&code, 4, 1, out);
+        fwrite(&with, 4, 1, out);
+        fwrite(&without, 4, 1, out);
+        fwrite(&bytes, 8, 1, out);
+        fclose(out);
+        printf("layout %u %u %u\nALL OK\n", code, with, without);
+        return 0;
+    }
+    if (rule_check(rule) != 0 || !rule_layout(o, d, rule_halo(rule), L)) {
+        printf("outside the contract\n");
+        return 2;
+    }
+    std::vector<uint32_t> dense((size_t)X * Y * Z / 32);
+    std::vector<uint32_t> mask(has_mask ? L.nb : 0u);
+    if (fread(dense.data(), 4, dense.size(), in) != dense.size() || fread(mask.data(), 4, mask.size(), in) != mask.size())
+        return 2;
+    fclose(in);
+
+    // the oracle's brickmap in HBM order
+    vxo_world* w = vxo_build_brickmap(dense.data(), X, Y, Z, f);
+    const HbmWorld hw = to_hbm(w);
+    vxo_world_free(w);
+    const CollideWorld W = hw.world();
+
+    const size_t guard = 64;
+    std::vector<uint8_t> work(L.total_bytes + guard, 0xA5);
+    std::vector<uint32_t> bits(L.nb + guard, 0x5A5A5A5Au);
+    uint32_t summary[kRuleSumWords + 1];
+    memset(summary, 0x77, sizeof(summary));
+    summary[kRuleSumWords] = 0xC0FFEEu;
+    g_size[kRulePlane] = L.np;
+    g_size[kRuleMask] = has_mask ? L.nb : 0u;
+    g_size[kRuleOut] = L.nb;
+    // four sections in order, each on a 256-byte boundary and as large as a plane
+    const uint64_t pb = 4u * L.np;
+    CHECK(L.w0 == 0 && L.free - L.w0 >= pb && L.turn[0] - L.free >= pb && L.turn[1] - L.turn[0] >= pb && L.total_bytes - L.turn[1] >= pb);
+    CHECK(L.free % 256u == 0 && L.turn[0] % 256u == 0 && L.turn[1] % 256u == 0 && L.total_bytes % 256u == 0);
+    CHECK(L.h == (uint32_t)(rule.scope == kRuleWorld ? rule.iterations : 1));
+    RuleArgs A{};
+    rule_args(A, L, W, o, d, rule, has_mask ? mask.data() : nullptr, work.data(), bits.data(), summary);
+
+    // k_read_region of the halo: clipped to the world before any load
+    const int32_t H = (int32_t)L.h;
+    const int32_t ho[3] = {o[0] - H, o[1] - H, o[2] - H}, hdim[3] = {d[0] + 2 * H, d[1] + 2 * H, d[2] + 2 * H};
+    const std::vector<uint32_t> halo = read_host(W, ho, hdim);
+    CHECK(halo.size() == L.np);
+    for (uint64_t i = 0; i < halo.size(); ++i)
+        A.w0[i] = halo[i];
+
+    // k_rule_setup
+    for (uint64_t i = 0; i < (L.np > kRuleSumWords ? L.np : (uint64_t)kRuleSumWords); ++i) {
+        if (i < kRuleSumWords)
+            summary[i] = rule_summary_init((uint32_t)i);
+        if (i < L.np)
+            rule_setup_lane(A, i);
+    }
+    check_padding(A, A.w0);
+    check_padding(A, A.free);
+
+    // `iterations` x k_rule_round
+    for (int32_t i = 0; i < rule.iterations; ++i) {
+        if (rule.neighbours == kRuleN6)
+            round_all<kRuleN6>(A, i);
+        else if (rule.neighbours == kRuleN18)
+            round_all<kRuleN18>(A, i);
+        else
+            round_all<kRuleN26>(A, i);
+    }
+
+    // k_rule_output and its reduction
+    RuleTally t;
+    rule_tally_clear(t);
+    for (uint64_t i = 0; i < L.nb; ++i)
+        rule_output_lane(A, rule_src(A, rule.iterations), rule_src(A, rule.iterations - 1), i, t);
+    int32_t* box = (int32_t*)summary;
+    for (int k = 0; k < 5; ++k)
+        atom_add(summary + k, t.n[k]);
+    for (int k = 0; k < 3; ++k) {
+        atom_min(box + kRuleSumMin + k, t.lo[k]);
+        atom_max(box + kRuleSumMax + k, t.hi[k]);
+    }
+
+    // nothing written behind the output, the workspace or the summary; the output's padding bits are 0
+    for (size_t i = 0; i < guard; ++i) {
+        CHECK(bits[L.nb + i] == 0x5A5A5A5Au);
+        CHECK(work[L.total_bytes + i] == 0xA5);
+    }
+    CHECK(summary[kRuleSumWords] == 0xC0FFEEu && summary[5] == 0u);
+    if (d[0] & 31)
+        for (uint64_t row = 0; row < (uint64_t)d[1] * d[2]; ++row)
+            CHECK((bits[row * L.mw + L.mw - 1u] >> (d[0] & 31)) == 0u);
+    CHECK(summary[kRuleSumAfter] == summary[kRuleSumBefore] + summary[kRuleSumBorn] - summary[kRuleSumDied]);
+
+    FILE* out = fopen(argv[2], "wb");
+    if (!out)
+        return 2;
+    fwrite(summary, 4, kRuleSumWords, out);
+    fwrite(bits.data(), 4, L.nb, out);
+    fclose(out);
+    printf("%u solid before, %u after, %llu indices checked, failures %d\n%s\n", summary[kRuleSumBefore], summary[kRuleSumAfter],
+           (unsigned long long)checked, fails, fails ? "FAILED" : "ALL OK");
+    return fails ? 1 : 0;
+}

@@ -34,6 +34,7 @@ EXPORTS = [
     "vxrt_surface_workspace_bytes", "vxrt_extract_surface", "vxrt_extract_surface_host",
     "vxrt_lod_workspace_bytes", "vxrt_downsample_region", "vxrt_downsample_region_host",
     "vxrt_light_workspace_bytes", "vxrt_light_field", "vxrt_light_field_host",
+    "vxrt_rule_workspace_bytes", "vxrt_apply_rule", "vxrt_apply_rule_host",
     "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
@@ -52,6 +53,7 @@ VOX_SURFACE, VOX_SOLID, VOX_FRAC_BITS, VOX_MAX_DIM, VOX_MAX_COORD, VOX_MAX_TRIAN
 SURF_CAP, SURF_OPEN, SURF_MAX_DIM = 0, 1, 1024
 LOD_MAX_SHIFT = 5
 LIGHT_SKY, LIGHT_BLOCK, LIGHT_MAX, LIGHT_MAX_EMITTERS = 1, 2, 15, 65536
+RULE_N6, RULE_N18, RULE_N26, RULE_BOX, RULE_WORLD, RULE_MAX_ITERATIONS = 0, 1, 2, 0, 1, 16
 
 
 class WorldDesc(C.Structure):
@@ -128,6 +130,12 @@ class RenderFlags(C.Structure):
 
 class DenoiseParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("color_scale", C.c_float), ("reserved_", C.c_int32)]
+
+
+class RuleDesc(C.Structure):
+    """vxrt_rule: a neighbour-count rule (include/vxrt.h, vxrt_apply_rule)."""
+    _fields_ = [("struct_size", C.c_uint32), ("neighbours", C.c_int32), ("born", C.c_uint32), ("survive", C.c_uint32),
+                ("iterations", C.c_int32), ("scope", C.c_int32), ("outside", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class CameraPose(C.Structure):
@@ -276,6 +284,12 @@ def load() -> C.CDLL:
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_light_field_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_void_p]
+    L.vxrt_rule_workspace_bytes.restype = C.c_uint64
+    L.vxrt_rule_workspace_bytes.argtypes = [C.POINTER(C.c_int32), C.c_void_p]
+    L.vxrt_apply_rule.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_apply_rule_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
     L.vxrt_frame_guides.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, f3, f3, f3, f3, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_denoise_workspace_bytes.restype = C.c_uint64
     L.vxrt_denoise_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]

@@ -394,6 +394,36 @@ int VoxelRaytracer3D::LightField(const int32_t origin[3], const int32_t dims[3],
                                  channels, levels.data(), &summary);
 }
 
+int VoxelRaytracer3D::ApplyRule(const int32_t origin[3], const int32_t dims[3], const vxrt_rule& rule, std::vector<uint32_t>& bits,
+                                vxrt_rule_summary& summary, const uint32_t* mask)
+{
+    Flush();
+    // the vector is sized only for a box within the limits; the call itself refuses anything else, in its own order
+    const bool sized = vxrt_rule_workspace_bytes(dims, &rule) != 0;
+    bits.assign(sized ? (size_t)vxrt_region_words(dims) : 1u, 0u);
+    return vxrt_apply_rule_host(ctx, origin, dims, &rule, mask, bits.data(), &summary);
+}
+
+int VoxelRaytracer3D::SmoothVoxels(const int32_t origin[3], const int32_t dims[3], int32_t iterations, vxrt_edit_stats* stats,
+                                   vxrt_rule_summary* summary)
+{
+    vxrt_rule rule{};
+    rule.struct_size = sizeof(rule);
+    rule.neighbours = VXRT_RULE_N26;
+    rule.born = 0x7FFFFFFu & ~0x3FFFu;     // counts 14 .. 26
+    rule.survive = 0x7FFFFFFu & ~0x1FFFu;  // counts 13 .. 26
+    rule.iterations = iterations;
+    rule.scope = VXRT_RULE_BOX;
+    std::vector<uint32_t> bits;
+    vxrt_rule_summary sum{};
+    const int rc = ApplyRule(origin, dims, rule, bits, sum);
+    if (rc != VXRT_OK)
+        return rc;
+    if (summary)
+        *summary = sum;
+    return StampVoxels(origin, dims, bits.data(), VXRT_STAMP_REPLACE, stats);
+}
+
 int VoxelRaytracer3D::DownsampleRegion(const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
                                        std::vector<uint32_t>& bits, vxrt_lod_summary& summary, std::vector<uint16_t>* counts)
 {

@@ -12,6 +12,7 @@
 #include "vxrt_nav.hpp"
 #include "vxrt_place.hpp"
 #include "vxrt_reproject.hpp"
+#include "vxrt_rule.hpp"
 #include "vxrt_surface.hpp"
 #include "vxrt_voxelize.hpp"
 
@@ -880,6 +881,67 @@ int vxrt_light_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t di
     if (int rc = T.alloc(VXRT_ERR_NOMEM, "light_field_host"))
         return rc;
     VX_HIP(vxrt::light_field(vxrt::query_world(c), origin, dims, channels, d_emitters, n_emitters, d_work, d_levels, d_sum, nullptr));
+    return T.finish();
+}
+
+// ---- voxel rules -----------------------------------------------------------------------------------------------------------
+uint64_t vxrt_rule_workspace_bytes(const int32_t dims[3], const vxrt_rule* rule)
+{
+    vxrt::RuleLayout L;
+    if (!dims || !rule || vxrt::rule_check(*rule) != 0)
+        return 0;
+    return vxrt::rule_layout(nullptr, dims, vxrt::rule_halo(*rule), L) ? L.total_bytes : 0;
+}
+
+// the checks both rule calls make after their NULL checks, in the order of include/vxrt.h
+static int rule_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_rule* rule, const void* mask)
+{
+    static const char* const what[] = {
+        "", "vxrt_rule size mismatch", "rule neighbours: VXRT_RULE_N6, VXRT_RULE_N18 or VXRT_RULE_N26",
+        "rule born / survive: a bit above the number of neighbours", "rule iterations: 1 .. VXRT_RULE_MAX_ITERATIONS",
+        "rule scope: VXRT_RULE_BOX or VXRT_RULE_WORLD", "rule outside: 0 or 1", "rule reserved_: 0"};
+    if (const int bad = vxrt::rule_check(*rule))
+        return fail(VXRT_ERR_INVALID, what[bad]);
+    if (mask && rule->scope == VXRT_RULE_WORLD)
+        return fail(VXRT_ERR_INVALID, "rule: a mask with VXRT_RULE_WORLD");
+    vxrt::RuleLayout L;
+    if (!vxrt::rule_layout(nullptr, dims, vxrt::rule_halo(*rule), L))
+        return fail(VXRT_ERR_INVALID, "rule box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36");
+    if (!vxrt::rule_layout(origin, dims, vxrt::rule_halo(*rule), L))
+        return fail(VXRT_ERR_INVALID, "rule box: origin - halo or origin + dims + halo beyond int32");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_apply_rule(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_rule* rule, const uint32_t* d_mask_or_null,
+                    void* d_work, uint32_t* d_bits, vxrt_rule_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !rule || !d_work || !d_bits || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = rule_ready(c, origin, dims, rule, d_mask_or_null))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::apply_rule(vxrt::query_world(c), origin, dims, *rule, d_mask_or_null, d_work, d_bits, d_summary, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_apply_rule_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_rule* rule,
+                         const uint32_t* mask_or_null, uint32_t* bits, vxrt_rule_summary* summary)
+{
+    if (!c || !origin || !dims || !rule || !bits || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = rule_ready(c, origin, dims, rule, mask_or_null))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::RuleLayout L;
+    vxrt::rule_layout(origin, dims, vxrt::rule_halo(*rule), L);
+    vxrt::HostScratch T;
+    const auto d_work = T.work(L.total_bytes);
+    const auto d_sum = T.out(sizeof(vxrt_rule_summary), summary);
+    const auto d_bits = T.out(4u * (size_t)L.nb, bits);
+    const auto d_mask = T.in(mask_or_null ? 4u * (size_t)L.nb : 0, mask_or_null);
+    if (int rc = T.alloc(VXRT_ERR_NOMEM, "apply_rule_host"))
+        return rc;
+    VX_HIP(vxrt::apply_rule(vxrt::query_world(c), origin, dims, *rule, d_mask, d_work, d_bits, d_sum, nullptr));
     return T.finish();
 }
 

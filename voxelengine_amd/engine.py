@@ -539,6 +539,57 @@ class Context:
                                               _u32(channels), out.ctypes.data, summary.ctypes.data))
         return LightField(origin=origin, dims=dims, channels=int(channels), levels=_grid(out, dims), _summary=summary, _stream=None)
 
+    # ---- voxel rules (extension, include/vxrt.h) ---------------------------------------------------------------------------
+    def rule_workspace_bytes(self, dims, rule: "Rule") -> int:
+        """vxrt_rule_workspace_bytes: the workspace of one apply_rule call, 0 outside the contract"""
+        r = rule._c()
+        return int(self._L.vxrt_rule_workspace_bytes(_i3(dims), C.byref(r)))
+
+    def apply_rule(self, origin, dims, rule: "Rule", mask=None, stream: int | None = None, *, out=None, work=None) -> "RuleResult":
+        """The voxels of the box ``origin`` .. ``origin + dims - 1`` after ``rule.iterations`` steps of the neighbour-count
+        rule: include/vxrt.h, vxrt_apply_rule.  The world is not changed: the result's ``stamp()`` writes it.  ``mask``
+        (RULE_BOX only): the voxels a step may change, a bool [x, y, z] numpy grid of ``dims`` or a device tensor of region
+        words.  Asynchronous on ``stream`` (default: torch's current stream).  ``out``: a device tensor of at least
+        region_words(dims) words for the bits; ``work``: one of at least rule_workspace_bytes bytes (defaults: new ones).
+        Returns a RuleResult; reading its ``summary`` waits for the call."""
+        call = _Call(self, stream)
+        origin, dims = _box(origin, dims)
+        r = rule._c()
+        ws = self.rule_workspace_bytes(dims, rule)
+        _, nw = _counts(dims, ws)
+        work = call.work(ws, work, "work: a contiguous device tensor of at least rule_workspace_bytes(dims, rule) bytes")
+        bits = call.out(nw, 4, call.torch.int32, out, "out: a contiguous device tensor of at least region_words(dims) words",
+                        any_size=True)
+        if isinstance(mask, np.ndarray):
+            mask = call.upload(_mask_words(mask, dims))
+        elif mask is not None:
+            mask = call.reads(call.fits(mask, nw, 4, "mask: a contiguous device tensor of at least region_words(dims) words",
+                                        any_size=True))
+        summary = call.summary(12)
+        call.launch(self._L.vxrt_apply_rule, _i3(origin), _i3(dims), C.byref(r), _ptr(mask), _ptr(work), _ptr(bits), _ptr(summary))
+        return RuleResult(bits=bits.view(-1)[:nw] if bits.element_size() == 4 else bits, origin=origin, dims=dims, _summary=summary,
+                          _stream=call.s)
+
+    def apply_rule_host(self, origin, dims, rule: "Rule", mask=None) -> "RuleResult":
+        """apply_rule through the synchronous host call (vxrt_apply_rule_host): ``bits`` is a numpy bool [x, y, z] grid;
+        ``mask`` a bool [x, y, z] numpy grid or None."""
+        origin, dims = _box(origin, dims)
+        r = rule._c()
+        _, nw = _counts(dims, self.rule_workspace_bytes(dims, rule))
+        words = np.zeros(max(nw, 1), np.uint32)
+        summary = np.zeros(12, np.uint32)
+        m = None if mask is None else _mask_words(mask, dims)
+        N.check(self._L.vxrt_apply_rule_host(self._h, _i3(origin), _i3(dims), C.byref(r), None if m is None else m.ctypes.data,
+                                             words.ctypes.data, summary.ctypes.data))
+        return RuleResult(bits=unpack_region(words, dims), origin=origin, dims=dims, _summary=summary, _stream=None)
+
+    def smooth_voxels(self, origin, dims, iterations: int = 1, mask=None):
+        """apply_rule with Rule.smooth(iterations) on the box alone (RULE_BOX), then one STAMP_REPLACE edit_stamps of its
+        result at ``origin``: the box is smoothed in the resident world.  Returns (EditStats, RuleSummary)."""
+        res = self.apply_rule(origin, dims, Rule.smooth(iterations), mask)
+        st = self.edit_stamps([res.stamp()])
+        return st, res.summary
+
     # ---- mesh voxelization (extension, include/vxrt.h) ----------------------------------------------------------------
     def voxelize_workspace_bytes(self, dims, n_triangles: int) -> int:
         """vxrt_voxelize_workspace_bytes: the workspace of one voxelize_mesh call, 0 outside the contract"""
@@ -1364,6 +1415,115 @@ class LightField(_LazyResult):
     def block(self) -> np.ndarray:
         """the block levels, 0 .. 15, as a numpy uint8 [x, y, z] grid"""
         return self.grid() & 15
+
+
+def _count_mask(counts) -> int:
+    """the ``born`` / ``survive`` table of a Rule: an int as it is, an iterable of neighbour counts as their bits"""
+    if isinstance(counts, (int, np.integer)):
+        return int(counts)
+    m = 0
+    for c in counts:
+        if not 0 <= int(c) < 32:
+            raise ValueError("a neighbour count is 0 .. 26")
+        m |= 1 << int(c)
+    return m
+
+
+def _mask_words(mask: np.ndarray, dims) -> np.ndarray:
+    """a rule's mask, a bool [x, y, z] grid of ``dims``, as region words"""
+    mask = np.asarray(mask, bool)
+    if tuple(mask.shape) != tuple(dims):
+        raise ValueError("mask: a bool [x, y, z] grid of the box's dims")
+    return pack_region(mask)
+
+
+@dataclass
+class Rule:
+    """A neighbour-count rule (include/vxrt.h, vxrt_rule): an empty voxel with c solid voxels among its ``neighbours``
+    (RULE_N6, RULE_N18, RULE_N26) becomes solid when c is in ``born``, a solid one stays solid when c is in ``survive``;
+    ``iterations`` steps.  ``born`` / ``survive``: an iterable of counts, or an int with bit c set.  ``scope``: RULE_BOX
+    (the box alone changes, everything else is frozen) or RULE_WORLD (the box is a window into the rule run on the whole
+    world).  ``outside``: what voxels outside the world count as, 0 or 1."""
+    neighbours: int = N.RULE_N26
+    born: object = 0
+    survive: object = 0
+    iterations: int = 1
+    scope: int = N.RULE_BOX
+    outside: int = 0
+
+    def __post_init__(self):
+        self.born, self.survive = _count_mask(self.born), _count_mask(self.survive)
+
+    def _c(self) -> "N.RuleDesc":
+        i32 = lambda v: max(-1 << 31, min(int(v), (1 << 31) - 1))  # a value outside int32 is the library's to refuse
+        return N.RuleDesc(C.sizeof(N.RuleDesc), i32(self.neighbours), _u32(self.born), _u32(self.survive), i32(self.iterations),
+                          i32(self.scope), i32(self.outside), 0)
+
+    @staticmethod
+    def count(neighbours: int) -> int:
+        """the neighbours of a voxel: 6, 18 or 26"""
+        return {N.RULE_N6: 6, N.RULE_N18: 18, N.RULE_N26: 26}[int(neighbours)]
+
+    @classmethod
+    def smooth(cls, iterations: int = 1, **kw) -> "Rule":
+        """the majority of the 27 voxels around and including each: born with 14 or more solid neighbours of 26, kept with 13"""
+        return cls(N.RULE_N26, range(14, 27), range(13, 27), iterations, **kw)
+
+    @classmethod
+    def grow(cls, neighbours: int = N.RULE_N26, iterations: int = 1, **kw) -> "Rule":
+        """thicken by one voxel: born with any solid neighbour, every solid voxel kept"""
+        n = cls.count(neighbours)
+        return cls(neighbours, range(1, n + 1), range(0, n + 1), iterations, **kw)
+
+    @classmethod
+    def erode(cls, neighbours: int = N.RULE_N26, iterations: int = 1, **kw) -> "Rule":
+        """shrink by one voxel: nothing born, a solid voxel kept only when all its neighbours are solid"""
+        n = cls.count(neighbours)
+        return cls(neighbours, 0, (n,), iterations, **kw)
+
+    @classmethod
+    def caves(cls, born_min: int, survive_min: int, iterations: int = 4, **kw) -> "Rule":
+        """the cave automaton over noise: born with at least ``born_min`` solid neighbours of 26, kept with ``survive_min``"""
+        return cls(N.RULE_N26, range(int(born_min), 27), range(int(survive_min), 27), iterations, **kw)
+
+
+class RuleSummary(NamedTuple):
+    """vxrt_rule_summary over the world voxels of the box: solid before and after, voxels born and died between W_0 and W_n,
+    voxels the last step changed (0: a fixed point), and the inclusive world box of the voxels that differ from W_0
+    (INT32_MAX / INT32_MIN per axis when none does)"""
+    solid_before: int
+    solid_after: int
+    born: int
+    died: int
+    changed_last: int
+    changed_min: tuple
+    changed_max: tuple
+
+
+@dataclass
+class RuleResult(_LazyResult):
+    """The result of Context.apply_rule: ``bits`` the box after the rule's steps as region words on the device (a numpy
+    bool [x, y, z] grid from apply_rule_host), ``summary`` a RuleSummary."""
+    bits: object
+    origin: tuple
+    dims: tuple
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> RuleSummary:
+        """the summary; for a device result this waits for the call's stream"""
+        self._summary = self._host(self._summary, np.uint32)
+        box = [int(v) for v in np.asarray(self._summary[6:12]).view(np.int32)]
+        return RuleSummary(*(int(v) for v in self._summary[:5]), tuple(box[:3]), tuple(box[3:]))
+
+    def grid(self) -> np.ndarray:
+        """the voxels as a bool [x, y, z] numpy grid (device words are copied to the host)"""
+        return self._bits(self.bits)
+
+    def stamp(self) -> "Stamp":
+        """the result as a STAMP_REPLACE stamp at the box's origin, for edit_stamps"""
+        return Stamp(self.origin, self.bits, N.STAMP_REPLACE, self.dims)
 
 
 class DistanceSummary(NamedTuple):
