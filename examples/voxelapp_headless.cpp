@@ -68,6 +68,11 @@
 // line "rule before frame N: before .. after .. born .. died .. changed_last .. box <lo x3> <hi x3>, ... bricks touched".
 // "frame smooth x0 y0 z0 x1 y1 z1 iterations" is the shorthand for the majority rule on the box alone
 // (VoxelRaytracer3D::SmoothVoxels), with the same line.  Both are applied in file order with the edit lines.
+// "frame turn axis quarter_turns [slot=0]" and "frame mirror axis [slot=0]" re-orient the clipboard slot a copy line filled
+// (vxrt_orientation_rotation / a flip of one axis, then vxrt_transform_stamp): the slot's bits are kept on the device from the
+// first such line on, each line transforms them into a second device buffer and swaps the two, and a following paste pastes
+// the turned stamp, its voxel (0,0,0) at the paste's a.  One line "turn before frame N: slot S, dims X Y Z, V voxels, box
+// <lo x3> <hi x3>, hash H" (the 64-bit FNV-1a hash of the turned words; "mirror before frame ..." for a mirror line).
 // walk=1 (box collision, VoxelRaytracer3D::MoveBoxes): the camera is a body of half-extents (2, 6, 2) voxels that starts at
 // the first frame's pose; every frame, after that frame's edits, it moves toward the frame's pose -- delta = pose - centre,
 // each axis clamped to VXRT_BODY_MAX_DELTA, in the order y, x, z -- instead of jumping there, and the frame renders from the
@@ -113,6 +118,7 @@ int main(int argc, char** argv)
     struct EditLine {
         int frame;
         vxrt_edit_op op;  // kind 12: a rule line (a = the box's origin, b = its dims; value 1: the smooth shorthand)
+                          // kind 13 / 14: a turn / mirror line (value = the slot, a[0] = the axis, a[1] = the quarter turns)
         vxrt_rule rule;
     };
     std::vector<EditLine> edits;
@@ -150,6 +156,19 @@ int main(int argc, char** argv)
                 tl.on = std::string(word) == "on";
                 temporal_lines.push_back(tl);
                 continue;
+            }
+            {
+                int axis = 0, turns = 0, slot = 0;
+                const bool turn = std::sscanf(line.c_str(), "%d turn %d %d %d", &e.frame, &axis, &turns, &slot) >= 3;
+                const bool mirror = !turn && std::sscanf(line.c_str(), "%d mirror %d %d", &e.frame, &axis, &slot) >= 2;
+                if (turn || mirror) {
+                    e.op.kind = turn ? 13 : 14;
+                    e.op.value = slot;
+                    e.op.a[0] = axis;
+                    e.op.a[1] = turns;
+                    edits.push_back(e);
+                    continue;
+                }
             }
             {
                 int c[6], iterations = 1;
@@ -271,6 +290,7 @@ int main(int argc, char** argv)
     struct Clip {
         int32_t dims[3];
         std::vector<uint32_t> bits;
+        uint32_t* d_bits = nullptr;  // the same bits on the device once a turn or mirror line has used the slot
     };
     std::map<int, Clip> clipboard;
     auto apply_edits = [&](int from, int to) {
@@ -294,6 +314,8 @@ int main(int argc, char** argv)
             if (e.op.kind == 2) {  // copy
                 flush_ops();
                 Clip& c = clipboard[e.op.value];
+                (void)hipFree(c.d_bits);
+                c.d_bits = nullptr;
                 for (int k = 0; k < 3; ++k)
                     c.dims[k] = e.op.b[k];
                 if (raytracer->ReadRegion(e.op.a, c.dims, c.bits) != VXRT_OK) {
@@ -457,6 +479,54 @@ int main(int argc, char** argv)
                 }
                 std::printf("mesh before frame %d: %u triangles, %u set voxels, %llu bricks touched, %llu created\n", from, sum.triangles,
                             sum.set, (unsigned long long)st.bricks_touched, (unsigned long long)st.bricks_created);
+            } else if (e.op.kind == 13 || e.op.kind == 14) {  // turn or mirror the clipboard slot on the device
+                flush_ops();
+                const char* what = e.op.kind == 13 ? "turn" : "mirror";
+                const auto it = clipboard.find(e.op.value);
+                vxrt_orientation o{{0, 1, 2}, 0u};
+                int32_t dd[3] = {0, 0, 0};
+                bool ok = it != clipboard.end();
+                if (ok && e.op.kind == 13)
+                    ok = vxrt_orientation_rotation(e.op.a[0], e.op.a[1], &o) == VXRT_OK;
+                else if (ok && (ok = e.op.a[0] >= 0 && e.op.a[0] <= 2))
+                    o.flip = 1u << e.op.a[0];
+                vxrt_transform_summary sum{};
+                if (ok) {
+                    Clip& c = it->second;
+                    (void)vxrt_orientation_dims(&o, c.dims, dd);
+                    const size_t nsrc = c.bits.size(), ndst = (size_t)vxrt_region_words(dd);
+                    uint32_t* d_turned = nullptr;
+                    vxrt_transform_summary* d_sum = nullptr;
+                    std::vector<uint32_t> turned(ndst);
+                    ok = (c.d_bits || (hipMalloc((void**)&c.d_bits, nsrc * 4) == hipSuccess &&
+                                       hipMemcpy(c.d_bits, c.bits.data(), nsrc * 4, hipMemcpyHostToDevice) == hipSuccess)) &&
+                         hipMalloc((void**)&d_turned, ndst * 4) == hipSuccess && hipMalloc((void**)&d_sum, sizeof sum) == hipSuccess &&
+                         vxrt_transform_stamp(raytracer->Context(), c.d_bits, c.dims, &o, d_turned, d_sum, nullptr) == VXRT_OK &&
+                         hipMemcpy(turned.data(), d_turned, ndst * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                         hipMemcpy(&sum, d_sum, sizeof sum, hipMemcpyDeviceToHost) == hipSuccess;
+                    (void)hipFree(d_sum);
+                    if (ok) {  // the swap: the turned buffer is the slot from here on
+                        (void)hipFree(c.d_bits);
+                        c.d_bits = d_turned;
+                        c.bits.swap(turned);
+                        for (int k = 0; k < 3; ++k)
+                            c.dims[k] = dd[k];
+                    } else {
+                        (void)hipFree(d_turned);
+                    }
+                }
+                if (!ok) {
+                    std::cerr << what << " before frame " << from << ": "
+                              << (it == clipboard.end() ? "empty clipboard slot" : vxrt_last_error()) << std::endl;
+                    std::exit(3);
+                }
+                uint64_t h = 0xcbf29ce484222325ull;
+                const std::vector<uint32_t>& bits = it->second.bits;
+                for (size_t i = 0; i < bits.size() * 4; ++i)
+                    h = (h ^ ((const unsigned char*)bits.data())[i]) * 0x100000001b3ull;
+                std::printf("%s before frame %d: slot %d, dims %d %d %d, %llu voxels, box %d %d %d %d %d %d, hash %016llx\n", what, from,
+                            e.op.value, dd[0], dd[1], dd[2], (unsigned long long)sum.voxels, sum.set_min[0], sum.set_min[1], sum.set_min[2],
+                            sum.set_max[0], sum.set_max[1], sum.set_max[2], (unsigned long long)h);
             } else if (e.op.kind == 3) {  // paste
                 flush_ops();
                 const auto it = clipboard.find(e.op.value);

@@ -422,6 +422,66 @@ int vxrt_place_pieces(vxrt_ctx *ctx, const vxrt_piece *pieces /* HOST array */, 
 int vxrt_place_pieces_host(vxrt_ctx *ctx, const vxrt_piece *pieces, uint32_t n_pieces, const vxrt_placement *placements,
                            uint64_t n, vxrt_placed *results);
 
+/* ---- stamp orientations -- an EXTENSION (with the stamps and pieces above: a clipboard that turns).  Everything in the
+ * region layout of vxrt_read_region -- a region read, a stamp, a piece, a voxelized mesh, the island bits, the result of a
+ * rule or of a downsampling -- can be rotated and mirrored on the device into one of its 48 orientations.
+ *   Orientation.  A signed axis permutation: destination axis k runs along source axis axis[k], and against it when bit k
+ *     of `flip` is set.  For source dims sd the destination dims are dd[k] = sd[axis[k]], and source voxel p lands at q with
+ *     q[k] = flip bit k ? sd[axis[k]] - 1 - p[axis[k]] : p[axis[k]]; equivalently dst(q) = src(p) for the p this inverts to.
+ *     axis must be a permutation of {0, 1, 2} and the bits of flip above 2 must be 0: all 48 such orientations are valid.
+ *     The 24 with sign(axis) * (-1)^popcount(flip) = +1 are rotations, the others mirror.
+ *   Helpers.  Host only, integer only, no context and no device (like vxrt_get_directions); each returns VXRT_ERR_INVALID for
+ *     a NULL argument or an invalid orientation, else VXRT_OK.  `out` may be an input.
+ *     vxrt_orientation_rotation: `quarter_turns` right-handed quarter turns about `axis` (0, 1, 2; anything else is invalid):
+ *       one turn takes axis a + 1 onto axis a + 2 (mod 3), so one turn about z is axis = {1, 0, 2}, flip = 1:
+ *       q = (sd[1] - 1 - p[1], p[0], p[2]).  Any turn count is taken mod 4, negative ones included.
+ *     vxrt_orientation_compose: a first, then b: out.axis[k] = a.axis[b.axis[k]],
+ *       out.flip bit k = b.flip bit k XOR a.flip bit b.axis[k].
+ *     vxrt_orientation_inverse: compose(o, inverse(o)) is the identity {0, 1, 2}, 0.
+ *     vxrt_orientation_dims and vxrt_orientation_voxel: dd and q of the rule above (a pivot, or where to paste); the dims and
+ *       the voxel are not checked.
+ *     vxrt_orientation_is_rotation: 1 or 0, VXRT_ERR_INVALID (negative) for an invalid orientation or NULL.
+ *   vxrt_transform_stamp.  d_src holds vxrt_region_words(src_dims) words; padding bits at the end of a source row are
+ *     ignored, as a stamp ignores them.  Every one of the vxrt_region_words(dd) words of d_dst is written exactly once, its
+ *     padding bits 0, and nothing behind them is touched: the result is directly a stamp, a piece or a mask.
+ *     d_summary_or_null: voxels = the set voxels of the source (padding ignored) = those of the destination; set_min /
+ *     set_max = their inclusive bounds in DESTINATION coordinates, INT32_MAX / INT32_MIN on every axis when there is none (as
+ *     vxrt_rule_summary).  The summary is accumulated in d_summary itself with integer atomics after an initialisation on
+ *     the stream; with NULL the bits are the same.
+ *   Limits.  src_dims within vxrt_region_words' contract; vxrt_region_words(src_dims) and vxrt_region_words(dd) both at
+ *     most VXRT_TRANSFORM_MAX_WORDS = 2^31 (a row of one voxel still takes a word, so dd can need 32 times the source's
+ *     words).  Word indices then fit 32 bits; byte offsets do not, and the library forms addresses in 64 bits.
+ *     d_src and d_dst must not overlap: overlapping ranges are refused.
+ *   Call rules.  The call needs a context but no world: it never returns VXRT_ERR_NO_WORLD and works with a streamed world
+ *     resident, because it reads no table.  Asynchronous on `stream`; no host synchronisation, no allocation per call and no
+ *     workspace, so it can be captured.  The result is a function of the arguments alone and bit-identical from call to
+ *     call.  Checked in this order, each VXRT_ERR_INVALID: a NULL ctx; a NULL d_src, src_dims, o or d_dst; an invalid
+ *     orientation; bad dims; the word caps; overlap.  A refused call enqueues and writes nothing.
+ *   vxrt_transform_stamp_host takes host buffers (src in; dst and the summary out), allocates its own device buffers and is
+ *     synchronous; its ranges may not overlap either.
+ * The cost is one pass: every source word is read once and every destination word written once.  Orientations that keep x
+ *   (axis[0] == 0, 16 of them) move whole rows; the 32 that move x transpose 32 x 32 bit tiles through LDS. */
+#define VXRT_TRANSFORM_MAX_WORDS (1ull << 31)
+typedef struct vxrt_orientation {
+    int32_t axis[3]; /* a permutation of {0,1,2}: destination axis k runs along source axis axis[k] */
+    uint32_t flip;   /* bit k: destination axis k runs against the source axis; bits above 2 must be 0 */
+} vxrt_orientation;
+typedef struct vxrt_transform_summary {
+    uint64_t voxels;                /* set voxels of the source (padding ignored) = set voxels of the destination */
+    int32_t set_min[3], set_max[3]; /* inclusive bounds of the set voxels in DESTINATION coordinates;
+                                       INT32_MAX / INT32_MIN on every axis when there is none (as vxrt_rule_summary) */
+} vxrt_transform_summary;           /* 32 bytes */
+int vxrt_orientation_rotation(int axis, int quarter_turns, vxrt_orientation *out);
+int vxrt_orientation_compose(const vxrt_orientation *a, const vxrt_orientation *b, vxrt_orientation *out);
+int vxrt_orientation_inverse(const vxrt_orientation *o, vxrt_orientation *out);
+int vxrt_orientation_dims(const vxrt_orientation *o, const int32_t src_dims[3], int32_t dst_dims[3]);
+int vxrt_orientation_voxel(const vxrt_orientation *o, const int32_t src_dims[3], const int32_t p[3], int32_t q[3]);
+int vxrt_orientation_is_rotation(const vxrt_orientation *o);
+int vxrt_transform_stamp(vxrt_ctx *ctx, const uint32_t *d_src, const int32_t src_dims[3], const vxrt_orientation *o,
+                         uint32_t *d_dst, vxrt_transform_summary *d_summary_or_null, void *stream);
+int vxrt_transform_stamp_host(vxrt_ctx *ctx, const uint32_t *src, const int32_t src_dims[3], const vxrt_orientation *o,
+                              uint32_t *dst, vxrt_transform_summary *summary_or_null);
+
 /* ---- navigation fields -- an EXTENSION (with the editing above: where a body can walk, and which way is the goal).  A call
  * looks at one box B = [origin, origin + dims) of world cells, with the limits of vxrt_find_islands: 1 <= dims[k],
  * dims[0] * dims[1] * dims[2] <= 2^28, origin[k] + dims[k] <= 2^31 - 1.  Voxels outside the world are empty.

@@ -28,6 +28,8 @@ EXPORTS = [
     "vxrt_move_boxes", "vxrt_overlap_boxes", "vxrt_move_boxes_host", "vxrt_overlap_boxes_host",
     "vxrt_islands_workspace_bytes", "vxrt_find_islands", "vxrt_find_islands_host",
     "vxrt_place_pieces", "vxrt_place_pieces_host",
+    "vxrt_orientation_rotation", "vxrt_orientation_compose", "vxrt_orientation_inverse", "vxrt_orientation_dims",
+    "vxrt_orientation_voxel", "vxrt_orientation_is_rotation", "vxrt_transform_stamp", "vxrt_transform_stamp_host",
     "vxrt_nav_workspace_bytes", "vxrt_nav_field", "vxrt_nav_paths", "vxrt_nav_field_host",
     "vxrt_distance_workspace_bytes", "vxrt_distance_field", "vxrt_distance_field_host",
     "vxrt_voxelize_workspace_bytes", "vxrt_voxelize_mesh", "vxrt_voxelize_mesh_host",
@@ -54,6 +56,7 @@ SURF_CAP, SURF_OPEN, SURF_MAX_DIM = 0, 1, 1024
 LOD_MAX_SHIFT = 5
 LIGHT_SKY, LIGHT_BLOCK, LIGHT_MAX, LIGHT_MAX_EMITTERS = 1, 2, 15, 65536
 RULE_N6, RULE_N18, RULE_N26, RULE_BOX, RULE_WORLD, RULE_MAX_ITERATIONS = 0, 1, 2, 0, 1, 16
+TRANSFORM_MAX_WORDS = 1 << 31
 
 
 class WorldDesc(C.Structure):
@@ -114,6 +117,16 @@ class StampDesc(C.Structure):
 class PieceDesc(C.Structure):
     """vxrt_piece: a rigid dense bit volume (region layout, include/vxrt.h) for vxrt_place_pieces."""
     _fields_ = [("d_bits", C.c_void_p), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+class OrientationDesc(C.Structure):
+    """vxrt_orientation: destination axis k runs along source axis axis[k], against it when bit k of flip is set."""
+    _fields_ = [("axis", C.c_int32 * 3), ("flip", C.c_uint32)]
+
+
+class TransformSummaryDesc(C.Structure):
+    """vxrt_transform_summary"""
+    _fields_ = [("voxels", C.c_uint64), ("set_min", C.c_int32 * 3), ("set_max", C.c_int32 * 3)]
 
 
 class RenderFlags(C.Structure):
@@ -246,6 +259,15 @@ def load() -> C.CDLL:
                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.vxrt_place_pieces.argtypes = [C.c_void_p, C.POINTER(PieceDesc), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.vxrt_place_pieces_host.argtypes = [C.c_void_p, C.POINTER(PieceDesc), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    po, i3 = C.POINTER(OrientationDesc), C.POINTER(C.c_int32)
+    L.vxrt_orientation_rotation.argtypes = [C.c_int, C.c_int, po]
+    L.vxrt_orientation_compose.argtypes = [po, po, po]
+    L.vxrt_orientation_inverse.argtypes = [po, po]
+    L.vxrt_orientation_dims.argtypes = [po, i3, i3]
+    L.vxrt_orientation_voxel.argtypes = [po, i3, i3, i3]
+    L.vxrt_orientation_is_rotation.argtypes = [po]
+    L.vxrt_transform_stamp.argtypes = [C.c_void_p, C.c_void_p, i3, po, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_transform_stamp_host.argtypes = [C.c_void_p, C.c_void_p, i3, po, C.c_void_p, C.c_void_p]
     L.vxrt_nav_workspace_bytes.restype = C.c_uint64
     L.vxrt_nav_workspace_bytes.argtypes = [C.POINTER(C.c_int32), C.c_void_p]
     L.vxrt_nav_field.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_uint32,

@@ -14,6 +14,7 @@
 #include "vxrt_reproject.hpp"
 #include "vxrt_rule.hpp"
 #include "vxrt_surface.hpp"
+#include "vxrt_transform.hpp"
 #include "vxrt_voxelize.hpp"
 
 #include <algorithm>
@@ -487,6 +488,124 @@ int vxrt_place_pieces_host(vxrt_ctx* c, const vxrt_piece* pieces, uint32_t n_pie
     A.results = d_res;
     A.n = n;
     VX_HIP(vxrt::place_pieces(A, nullptr));
+    return T.finish();
+}
+
+// ---- stamp orientations ----------------------------------------------------------------------------------------------
+// the orientation of the C ABI as the algebra of vxrt_transform.hpp holds it (the same layout); false for NULL or an invalid one
+static bool orient_of(const vxrt_orientation* o, vxrt::Orient& out)
+{
+    if (!o)
+        return false;
+    out = vxrt::Orient{{o->axis[0], o->axis[1], o->axis[2]}, o->flip};
+    return vxrt::orient_valid(out);
+}
+
+static int orient_out(const vxrt::Orient& r, vxrt_orientation* out)
+{
+    for (int k = 0; k < 3; ++k)
+        out->axis[k] = r.axis[k];
+    out->flip = r.flip;
+    return VXRT_OK;
+}
+
+int vxrt_orientation_rotation(int axis, int quarter_turns, vxrt_orientation* out)
+{
+    vxrt::Orient r;
+    if (!out || !vxrt::orient_rotation(axis, quarter_turns, r))
+        return VXRT_ERR_INVALID;
+    return orient_out(r, out);
+}
+
+int vxrt_orientation_compose(const vxrt_orientation* a, const vxrt_orientation* b, vxrt_orientation* out)
+{
+    vxrt::Orient x, y;
+    if (!out || !orient_of(a, x) || !orient_of(b, y))
+        return VXRT_ERR_INVALID;
+    return orient_out(vxrt::orient_compose(x, y), out);
+}
+
+int vxrt_orientation_inverse(const vxrt_orientation* o, vxrt_orientation* out)
+{
+    vxrt::Orient x;
+    if (!out || !orient_of(o, x))
+        return VXRT_ERR_INVALID;
+    return orient_out(vxrt::orient_inverse(x), out);
+}
+
+int vxrt_orientation_dims(const vxrt_orientation* o, const int32_t src_dims[3], int32_t dst_dims[3])
+{
+    vxrt::Orient x;
+    if (!src_dims || !dst_dims || !orient_of(o, x))
+        return VXRT_ERR_INVALID;
+    vxrt::orient_dims(x, src_dims, dst_dims);
+    return VXRT_OK;
+}
+
+int vxrt_orientation_voxel(const vxrt_orientation* o, const int32_t src_dims[3], const int32_t p[3], int32_t q[3])
+{
+    vxrt::Orient x;
+    if (!src_dims || !p || !q || !orient_of(o, x))
+        return VXRT_ERR_INVALID;
+    vxrt::orient_voxel(x, src_dims, p, q);
+    return VXRT_OK;
+}
+
+int vxrt_orientation_is_rotation(const vxrt_orientation* o)
+{
+    vxrt::Orient x;
+    if (!orient_of(o, x))
+        return VXRT_ERR_INVALID;
+    return vxrt::orient_is_rotation(x) ? 1 : 0;
+}
+
+// the checks both transform calls make, in the order of include/vxrt.h; fills A but for the summary
+static int transform_ready(vxrt_ctx* c, const uint32_t* src, const int32_t src_dims[3], const vxrt_orientation* o, uint32_t* dst,
+                           vxrt::TransformArgs& A)
+{
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    static const char* const what[] = {"", "NULL argument", "orientation: axis a permutation of {0, 1, 2}, flip below 8",
+                                       "src_dims: each at least 1, at most 2^36 voxels",
+                                       "more than VXRT_TRANSFORM_MAX_WORDS words in the source or the destination",
+                                       "the source and the destination overlap"};
+    vxrt::Orient x{};
+    if (o)
+        x = vxrt::Orient{{o->axis[0], o->axis[1], o->axis[2]}, o->flip};
+    if (const int bad = vxrt::transform_check(src, src_dims, o ? &x : nullptr, dst, A))
+        return fail(VXRT_ERR_INVALID, what[bad]);
+    return VXRT_OK;
+}
+
+int vxrt_transform_stamp(vxrt_ctx* c, const uint32_t* d_src, const int32_t src_dims[3], const vxrt_orientation* o, uint32_t* d_dst,
+                         vxrt_transform_summary* d_summary_or_null, void* stream)
+{
+    vxrt::TransformArgs A;
+    if (int rc = transform_ready(c, d_src, src_dims, o, d_dst, A))
+        return rc;
+    A.summary = (uint32_t*)d_summary_or_null;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::transform_stamp(A, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_transform_stamp_host(vxrt_ctx* c, const uint32_t* src, const int32_t src_dims[3], const vxrt_orientation* o, uint32_t* dst,
+                              vxrt_transform_summary* summary_or_null)
+{
+    vxrt::TransformArgs A;
+    if (int rc = transform_ready(c, src, src_dims, o, dst, A))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::HostScratch T;
+    const auto d_src = T.in(4u * (size_t)A.nsrc, src);
+    const auto d_dst = T.out(4u * (size_t)A.ndst, dst);
+    const auto d_sum = T.out(summary_or_null ? sizeof(vxrt_transform_summary) : 0, summary_or_null);
+    if (int rc = T.alloc(VXRT_ERR_NOMEM, "transform_stamp_host"))
+        return rc;
+    A.src = d_src;
+    A.dst = d_dst;
+    A.summary = (uint32_t*)(vxrt_transform_summary*)d_sum;
+    VX_HIP(vxrt::transform_stamp(A, nullptr));
     return T.finish();
 }
 

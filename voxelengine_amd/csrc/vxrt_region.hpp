@@ -81,6 +81,7 @@ template <class T>
 __device__ inline T atom_max(T* p, T v) { return atomicMax(p, v); }
 __device__ inline uint32_t atom_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
 __device__ inline uint32_t atom_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+__device__ inline uint64_t atom_add64(uint64_t* p, uint64_t v) { return atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 #else
 inline uint32_t atom_load(const uint32_t* p) { return *p; }
 template <class T>
@@ -108,6 +109,12 @@ inline uint32_t atom_or(uint32_t* p, uint32_t v)
 inline uint32_t atom_add(uint32_t* p, uint32_t v)
 {
     const uint32_t o = *p;
+    *p = o + v;
+    return o;
+}
+inline uint64_t atom_add64(uint64_t* p, uint64_t v)
+{
+    const uint64_t o = *p;
     *p = o + v;
     return o;
 }

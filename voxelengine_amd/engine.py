@@ -413,6 +413,44 @@ class Context:
             rows[n] = (int(r["id"]), int(r["voxels"]), travel, int(np.int32(res[2]).view(np.uint32)))
         return rows
 
+    # ---- stamp orientations (extension, include/vxrt.h) ---------------------------------------------------------------------
+    def transform_stamp(self, bits, dims, orientation: "Orientation", out=None, summary: bool = True, stream: int | None = None):
+        """Region words turned or mirrored on the device (include/vxrt.h, vxrt_transform_stamp).  ``bits``: a contiguous device
+        tensor of at least region_words(dims) words (a region read, a stamp, a piece, a voxelized mesh, ...); ``orientation``:
+        an Orientation.  ``out``: a device tensor of at least region_words(orientation.dims(dims)) words that does not
+        overlap ``bits`` (default: a new one).  Asynchronous on ``stream`` (default: torch's current stream); needs no world.
+        Returns a TransformedStamp: ``bits`` the destination words on the device, ``dims`` the destination dims and
+        ``summary`` a TransformSummary (None with ``summary=False``); reading the summary waits for the call."""
+        call = _Call(self, stream)
+        dims = _ints(dims)
+        o = orientation._c()
+        nsrc = region_words(dims)
+        ddims = _ints(dims[a] for a in orientation.axis)
+        ndst = region_words(ddims) if nsrc else 0
+        if nsrc > N.TRANSFORM_MAX_WORDS or ndst > N.TRANSFORM_MAX_WORDS:
+            nsrc = ndst = 0  # (one-word placeholders: the library does the refusing)
+        src = call.reads(call.fits(bits, nsrc, 4, "bits: a contiguous device tensor of at least region_words(dims) words", any_size=True))
+        dst = call.out(ndst, 4, call.torch.int32, out, "out: a contiguous device tensor of at least region_words of the turned dims",
+                       any_size=True)
+        words = call.summary(8) if summary else None
+        call.launch(self._L.vxrt_transform_stamp, _ptr(src), _i3(dims), C.byref(o), _ptr(dst), _ptr(words))
+        return TransformedStamp(bits=dst.view(-1)[:ndst] if dst.element_size() == 4 else dst, dims=ddims, orientation=orientation,
+                                _summary=words, _stream=call.s)
+
+    def transform_stamp_host(self, grid, orientation: "Orientation", summary: bool = True) -> "TransformedStamp":
+        """transform_stamp through the synchronous host call (vxrt_transform_stamp_host): ``grid`` a bool [x, y, z] numpy
+        grid, packed and unpacked here; the result's ``bits`` is the turned bool grid."""
+        g = np.asarray(grid, bool)
+        dims = _ints(g.shape)
+        ddims = _ints(dims[a] for a in orientation.axis)
+        o = orientation._c()
+        src = pack_region(g) if g.size else np.zeros(1, np.uint32)
+        dst = np.zeros(max(region_words(ddims), 1), np.uint32)
+        words = np.zeros(8, np.uint32) if summary else None
+        N.check(self._L.vxrt_transform_stamp_host(self._h, src.ctypes.data, _i3(dims), C.byref(o), dst.ctypes.data,
+                                                  words.ctypes.data if summary else None))
+        return TransformedStamp(bits=unpack_region(dst, ddims), dims=ddims, orientation=orientation, _summary=words, _stream=None)
+
     # ---- navigation fields (extension, include/vxrt.h) ----------------------------------------------------------------
     def nav_field(self, origin, dims, goals, agent: "NavAgent | None" = None, max_dist: int = 1 << 24, dist: bool = True,
                   stream: int | None = None) -> "NavField":
@@ -1524,6 +1562,128 @@ class RuleResult(_LazyResult):
     def stamp(self) -> "Stamp":
         """the result as a STAMP_REPLACE stamp at the box's origin, for edit_stamps"""
         return Stamp(self.origin, self.bits, N.STAMP_REPLACE, self.dims)
+
+
+@dataclass(frozen=True)
+class Orientation:
+    """One of the 48 orientations of a stamp (include/vxrt.h, vxrt_orientation): destination axis k runs along source axis
+    ``axis[k]``, against it when bit k of ``flip`` is set.  Every method goes through the library's C helpers."""
+    axis: tuple = (0, 1, 2)
+    flip: int = 0
+
+    def _c(self) -> "N.OrientationDesc":
+        d = N.OrientationDesc()
+        d.axis = (C.c_int32 * 3)(*[max(-(1 << 31), min(int(a), (1 << 31) - 1)) for a in self.axis])
+        d.flip = _u32(self.flip)
+        return d
+
+    @staticmethod
+    def _of(d: "N.OrientationDesc") -> "Orientation":
+        return Orientation(tuple(int(a) for a in d.axis), int(d.flip))
+
+    @staticmethod
+    def rotation(axis: int, turns: int = 1) -> "Orientation":
+        """``turns`` right-handed quarter turns about ``axis`` (vxrt_orientation_rotation); any integer, taken mod 4"""
+        out, t = N.OrientationDesc(), int(turns)
+        t = t if -(1 << 31) <= t < 1 << 31 else t % 4  # (the library reduces every int it can be given)
+        _helper_ok(N.load().vxrt_orientation_rotation(int(axis), t, C.byref(out)), "rotation axis")
+        return Orientation._of(out)
+
+    @staticmethod
+    def mirror(axis: int) -> "Orientation":
+        """the mirror image along ``axis``"""
+        if axis not in (0, 1, 2):
+            raise ValueError("mirror axis: 0, 1 or 2")
+        return Orientation((0, 1, 2), 1 << axis)
+
+    def then(self, other: "Orientation") -> "Orientation":
+        """this orientation first, then ``other`` (vxrt_orientation_compose)"""
+        a, b, out = self._c(), other._c(), N.OrientationDesc()
+        _helper_ok(N.load().vxrt_orientation_compose(C.byref(a), C.byref(b), C.byref(out)), "orientation")
+        return Orientation._of(out)
+
+    def inverse(self) -> "Orientation":
+        a, out = self._c(), N.OrientationDesc()
+        _helper_ok(N.load().vxrt_orientation_inverse(C.byref(a), C.byref(out)), "orientation")
+        return Orientation._of(out)
+
+    def dims(self, src_dims) -> tuple:
+        """the destination dims of a stamp of ``src_dims`` (vxrt_orientation_dims)"""
+        a, out = self._c(), (C.c_int32 * 3)()
+        _helper_ok(N.load().vxrt_orientation_dims(C.byref(a), _i3(src_dims), out), "orientation")
+        return tuple(int(v) for v in out)
+
+    def voxel(self, p, src_dims) -> tuple:
+        """where source voxel ``p`` of a stamp of ``src_dims`` lands (vxrt_orientation_voxel)"""
+        a, out = self._c(), (C.c_int32 * 3)()
+        _helper_ok(N.load().vxrt_orientation_voxel(C.byref(a), _i3(src_dims), _i3(p), out), "orientation")
+        return tuple(int(v) for v in out)
+
+    @property
+    def is_rotation(self) -> bool:
+        a = self._c()
+        rc = N.load().vxrt_orientation_is_rotation(C.byref(a))
+        _helper_ok(min(rc, 0), "orientation")
+        return rc == 1
+
+    @staticmethod
+    def all():
+        """the 48 orientations"""
+        import itertools
+        for axis in itertools.permutations((0, 1, 2)):
+            for flip in range(8):
+                yield Orientation(axis, flip)
+
+    @staticmethod
+    def rotations():
+        """the 24 rotations among them"""
+        return (o for o in Orientation.all() if o.is_rotation)
+
+
+def _helper_ok(rc: int, what: str) -> None:
+    """a host-only helper of the library refused its arguments"""
+    if rc != 0:
+        raise ValueError("invalid " + what)
+
+
+class TransformSummary(NamedTuple):
+    """vxrt_transform_summary: the set voxels, and their inclusive bounds in destination coordinates (INT32_MAX / INT32_MIN
+    per axis when there is none)"""
+    voxels: int
+    set_min: tuple
+    set_max: tuple
+
+
+@dataclass
+class TransformedStamp(_LazyResult):
+    """The result of Context.transform_stamp: ``bits`` the turned region words on the device (a numpy bool [x, y, z] grid
+    from transform_stamp_host), ``dims`` the destination dims, ``summary`` a TransformSummary or None."""
+    bits: object
+    dims: tuple
+    orientation: Orientation
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> "TransformSummary | None":
+        """the summary; for a device result this waits for the call's stream"""
+        if self._summary is None:
+            return None
+        self._summary = self._host(self._summary, np.uint32)
+        box = [int(v) for v in np.asarray(self._summary[2:8]).view(np.int32)]
+        return TransformSummary(int(self._summary[0]) | int(self._summary[1]) << 32, tuple(box[:3]), tuple(box[3:]))
+
+    def grid(self) -> np.ndarray:
+        """the voxels as a bool [x, y, z] numpy grid (device words are copied to the host)"""
+        return self._bits(self.bits)
+
+    def stamp(self, origin, mode: int = N.STAMP_REPLACE) -> "Stamp":
+        """the result as a stamp at ``origin``, for edit_stamps"""
+        return Stamp(_ints(origin), self.bits, mode, self.dims)
+
+    def piece(self) -> "Piece":
+        """the result as a piece, for place_pieces"""
+        return Piece(self.bits, self.dims)
 
 
 class DistanceSummary(NamedTuple):
