@@ -62,6 +62,13 @@
 // then filters the accumulated mean -- with one line "temporal frame N max_history .. hit .. reused .. offscreen ..
 // rejected ..".  The history starts anew at the first such frame and after every frame with an edit line.  The same
 // restrictions as for the denoiser; two history and two key buffers are allocated once.
+// A line "frame lit ox oy oz dx dy dz sky_floor [ex ey ez level]..." switches the light on frames on from that frame
+// (vxrt_light_frame; "frame lit off" switches it off again): at that frame the light field of the box of origin (ox, oy, oz)
+// and dims (dx, dy, dz) is computed once, in both channels and with the given emitters (vxrt_light_field_host), and from then
+// on every frame is rendered with the AOVs, its guide keys are computed and, as the last stage after the temporal filter and
+// the denoiser, every hit pixel is relit with both flags, outside_level 0xF0, the block colour (1, 0.8, 0.5) and the occlusion
+// curve (0.4, 0.6, 0.8, 1) -- the dumped PPMs are the lit frames -- with one line "lit frame N hit .. in_box .. occluded ..
+// dark ..".  The same restrictions as for the denoiser.
 // A line "frame rule x0 y0 z0 x1 y1 z1 n6|n18|n26 born_hex survive_hex iterations box|world" applies a neighbour-count rule
 // (VoxelRaytracer3D::ApplyRule) to the box of the inclusive corners (x0, y0, z0) .. (x1, y1, z1) -- born_hex / survive_hex: bit
 // c set = an empty voxel is born / a solid voxel survives with c solid neighbours -- stamps the result (replace) and prints one
@@ -91,6 +98,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -132,6 +140,14 @@ int main(int argc, char** argv)
         bool on;
     };
     std::vector<TemporalLine> temporal_lines;
+    struct LitLine {
+        int frame;
+        bool on;
+        int32_t origin[3], dims[3];
+        float sky_floor;
+        std::vector<int32_t> emitters;  // x, y, z, level each
+    };
+    std::vector<LitLine> lit_lines;
     if (argc > 12 && std::string(argv[12]) != "-") {
         std::ifstream in(argv[12]);
         if (!in) {
@@ -156,6 +172,30 @@ int main(int argc, char** argv)
                 tl.on = std::string(word) == "on";
                 temporal_lines.push_back(tl);
                 continue;
+            }
+            {
+                std::istringstream words(line);
+                LitLine ll{};
+                std::string word2, first;
+                if (words >> ll.frame >> word2 && word2 == "lit") {
+                    std::streampos at = words.tellg();
+                    if (words >> first && first == "off") {
+                        lit_lines.push_back(ll);
+                        continue;
+                    }
+                    words.clear();
+                    words.seekg(at);
+                    if (words >> ll.origin[0] >> ll.origin[1] >> ll.origin[2] >> ll.dims[0] >> ll.dims[1] >> ll.dims[2] >> ll.sky_floor) {
+                        int32_t e[4];
+                        while (words >> e[0] >> e[1] >> e[2] >> e[3])
+                            ll.emitters.insert(ll.emitters.end(), e, e + 4);
+                        ll.on = true;
+                        lit_lines.push_back(ll);
+                        continue;
+                    }
+                    std::cerr << "bad lit line: " << line << std::endl;
+                    return 2;
+                }
             }
             {
                 int axis = 0, turns = 0, slot = 0;
@@ -699,10 +739,13 @@ int main(int argc, char** argv)
     void* d_dn_work = nullptr;
     vxrt_history* d_hist[2] = {nullptr, nullptr};
     vxrt_reproject_summary* d_rp_sum = nullptr;
-    if (!denoise_lines.empty() || !temporal_lines.empty()) {
+    uint8_t* d_levels = nullptr;
+    float* d_lit = nullptr;  // the lit colours: the frame's own colours stay what the next frame's history expects
+    vxrt_light_frame_summary* d_lf_sum = nullptr;
+    if (!denoise_lines.empty() || !temporal_lines.empty() || !lit_lines.empty()) {
         const size_t n = (size_t)width * height;
         if (batch > 1 || in_flight >= 2 || shade_mode == 1 || vxrt_denoise_workspace_bytes(width, height) == 0) {
-            std::cerr << "denoise, temporal: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
+            std::cerr << "denoise, temporal, lit: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
             return 2;
         }
         if (hipMalloc((void**)&d_color, n * 12) != hipSuccess || hipMalloc((void**)&d_hit, n * 8) != hipSuccess ||
@@ -713,12 +756,24 @@ int main(int argc, char** argv)
             (hipMalloc((void**)&d_hist[0], n * 16) != hipSuccess || hipMalloc((void**)&d_hist[1], n * 16) != hipSuccess ||
              hipMalloc((void**)&d_rp_sum, sizeof(vxrt_reproject_summary)) != hipSuccess))
             return 1;
+        if (!lit_lines.empty() &&
+            (hipMalloc((void**)&d_lit, n * 12) != hipSuccess || hipMalloc((void**)&d_lf_sum, sizeof(vxrt_light_frame_summary)) != hipSuccess))
+            return 1;
     }
     vxrt_denoise_params dn{sizeof(vxrt_denoise_params), 0, 0.0f, 0};
     vxrt_reproject_params rp{};
     rp.struct_size = sizeof(vxrt_reproject_params);
     bool temporal = false, have_history = false;
     vxrt_reproject_summary rp_sum{};
+    vxrt_light_frame_params lf{};
+    lf.struct_size = sizeof(vxrt_light_frame_params);
+    lf.flags = VXRT_LF_SMOOTH | VXRT_LF_OCCLUSION;
+    lf.outside_level = 0xF0u;
+    const float lf_block[3] = {1.0f, 0.8f, 0.5f}, lf_curve[4] = {0.4f, 0.6f, 0.8f, 1.0f};
+    std::memcpy(lf.block_color, lf_block, sizeof lf_block);
+    std::memcpy(lf.ao_curve, lf_curve, sizeof lf_curve);
+    bool lit = false;
+    vxrt_light_frame_summary lf_sum{};
     for (int i = 0; batch <= 1 && in_flight < 2 && i < nframes; ++i) {
         apply_edits(i, i + 1);
         for (const DenoiseLine& l : denoise_lines)
@@ -731,6 +786,31 @@ int main(int argc, char** argv)
                 temporal = l.on;
                 rp.max_history = l.max_history;
             }
+        for (const LitLine& l : lit_lines)
+            if (l.frame == i) {
+                lit = l.on;
+                if (!lit)
+                    continue;
+                // the box's light field, once: both channels, the line's emitters; the levels stay on the device
+                const uint64_t nvox = (uint64_t)(l.dims[0] > 0 ? l.dims[0] : 0) * (uint64_t)(l.dims[1] > 0 ? l.dims[1] : 0) *
+                                      (uint64_t)(l.dims[2] > 0 ? l.dims[2] : 0);
+                std::vector<uint8_t> levels(nvox > 0 && nvox <= (1ull << 28) ? (size_t)nvox : 1u);
+                vxrt_light_summary ls{};
+                (void)hipFree(d_levels);
+                d_levels = nullptr;
+                if (vxrt_light_field_host(raytracer->Context(), l.origin, l.dims, l.emitters.empty() ? nullptr : l.emitters.data(),
+                                          (uint32_t)(l.emitters.size() / 4), VXRT_LIGHT_SKY | VXRT_LIGHT_BLOCK, levels.data(), &ls) != VXRT_OK ||
+                    hipMalloc((void**)&d_levels, levels.size()) != hipSuccess ||
+                    hipMemcpy(d_levels, levels.data(), levels.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                    std::cerr << "lit, frame " << i << ": " << vxrt_last_error() << std::endl;
+                    return 3;
+                }
+                for (int k = 0; k < 3; ++k) {
+                    lf.box_origin[k] = l.origin[k];
+                    lf.box_dims[k] = l.dims[k];
+                }
+                lf.sky_floor = l.sky_floor;
+            }
         for (const EditLine& e : edits)
             if (e.frame == i)
                 have_history = false;  // shadows and bounces change far from an edit's box: the history starts anew
@@ -738,7 +818,7 @@ int main(int argc, char** argv)
         pose_for(i);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
-        if (dn.iterations > 0 || temporal) {
+        if (dn.iterations > 0 || temporal || lit) {
             // the frame with its AOVs through the C ABI (the facade's RenderScreen has no AOV arguments), then keys and filter
             vxrt_ctx* c = raytracer->Context();
             const float o[3] = {cam_pos.x, cam_pos.y, cam_pos.z}, f[3] = {cam_forward.x, cam_forward.y, cam_forward.z},
@@ -783,6 +863,21 @@ int main(int argc, char** argv)
             }
             if (temporal)
                 (void)hipMemcpy(&rp_sum, d_rp_sum, sizeof(rp_sum), hipMemcpyDeviceToHost);
+            if (lit) {
+                for (int k = 0; k < 3; ++k) {
+                    lf.cam.origin[k] = o[k];
+                    lf.cam.fwd[k] = f[k];
+                    lf.cam.up[k] = u[k];
+                    lf.cam.right[k] = r[k];
+                }
+                if (vxrt_light_frame(c, width, height, d_color, d_keys, d_hit, d_levels, &lf, d_lit, d_pixels, nullptr, d_lf_sum, nullptr) !=
+                        VXRT_OK ||
+                    vxrt_synchronize(c) != VXRT_OK) {
+                    std::cerr << "lit, frame " << i << ": " << vxrt_last_error() << std::endl;
+                    return 3;
+                }
+                (void)hipMemcpy(&lf_sum, d_lf_sum, sizeof(lf_sum), hipMemcpyDeviceToHost);
+            }
         } else {
             RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);
         }
@@ -790,6 +885,8 @@ int main(int argc, char** argv)
         if (temporal)
             std::printf("temporal frame %d max_history %d hit %u reused %u offscreen %u rejected %u\n", i, rp.max_history, rp_sum.hit,
                         rp_sum.reused, rp_sum.offscreen, rp_sum.rejected);
+        if (lit)
+            std::printf("lit frame %d hit %u in_box %u occluded %u dark %u\n", i, lf_sum.hit, lf_sum.in_box, lf_sum.occluded, lf_sum.dark);
         (void)hipMemcpy(pixels.data(), d_pixels, pixels.size() * sizeof(BGRA8888), hipMemcpyDeviceToHost);
         if (dn.iterations > 0) {
             std::vector<uint32_t> keys((size_t)width * height);
@@ -839,6 +936,9 @@ int main(int argc, char** argv)
     }
     (void)hipStreamDestroy(copy_stream);
     (void)hipFree(d_color);
+    (void)hipFree(d_levels);
+    (void)hipFree(d_lit);
+    (void)hipFree(d_lf_sum);
     (void)hipFree(d_hit);
     (void)hipFree(d_keys_pair[0]);
     (void)hipFree(d_keys_pair[1]);

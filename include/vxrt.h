@@ -1026,7 +1026,8 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  *     vxrt_deinterleave_views; and the purely stream-ordered queries vxrt_read_region, vxrt_move_boxes, vxrt_overlap_boxes,
  *     vxrt_distance_field, vxrt_light_field, vxrt_apply_rule (tests/test_gpu_rule.py), vxrt_extract_surface,
  *     vxrt_downsample_region and vxrt_find_islands; and the
- *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame and the temporal filter's vxrt_reproject_frame.  Under
+ *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame, the temporal filter's vxrt_reproject_frame and
+ *     vxrt_light_frame (tests/test_gpu_light_frame.py).  Under
  *     capture they allocate nothing, wait for nothing and read no host memory after they return: a captured multi-view
  *     launch stores its views from kernel arguments, which the graph owns.  Every replay gives what the eager call gives.
  *   Refused under capture, with VXRT_ERR_INVALID and a message that names capture: a render launch with frame_number < 0, in
@@ -1204,6 +1205,78 @@ int vxrt_reproject_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_c
                          const vxrt_reproject_params *params, vxrt_history *d_hist_out,
                          float *d_color_out_or_null, void *d_fb_or_null,
                          vxrt_reproject_summary *d_summary_or_null, void *stream);
+
+/* ---- light on frames -- an EXTENSION (the reference's to-do items "Proper indirect lighting" and "Post process stack",
+ * README.md:14-24, in the voxel-engine form: per-vertex "smooth lighting" and the three-neighbour corner occlusion on every
+ * voxel face).  vxrt_light_field computes sky and emitter light for a box of the world; this call turns those levels into
+ * pixels.  Every surface is an axis-aligned voxel face; the guide key and the hit index name the face a pixel shows, so the
+ * stage is specified bit for bit, like the denoiser and the temporal filter.  A post-process over buffers the renderer,
+ * vxrt_frame_guides and vxrt_light_field already write; the render launches know nothing of it.  In a frame pipeline it
+ * is the last stage: render with AOVs, guide keys, reproject, a-trous, light.
+ *   All float arithmetic is binary32, in the order written, without contraction.
+ *   Frames.  Whole frames with the denoiser's limits: 1 <= W, H <= 65535 and W * H <= 2^26, pixel (x, y) at index x + W * y.
+ *     d_keys are the keys vxrt_frame_guides gives for params->cam, params->ortho and the same d_hit_aov (a key whose axis
+ *     field is above 2 is read as axis 2).  X, Y, Z are the world's voxel extents, at most 2^24 each.
+ *   Miss.  A pixel is a miss when its key is 0 or its hit index lies outside 0 .. X*Y*Z - 1.  Its colour is copied, its terms
+ *     are (0, 0, 0) and it counts nowhere.
+ *   Face.  v is the voxel of the hit index h = v.x + X * (v.y + Y * v.z), a the key's axis, (b, c) the other two axes in
+ *     ascending order, e_k the unit vector of axis k.  The front cell is f = v - e_a when the key's toward bit is set, else
+ *     v + e_a.
+ *   Position on the face.  (o, d) is the pixel's primary ray under params->cam exactly as vxrt_render forms it (the ray of
+ *     vxrt_frame_guides).  t = ((float)plane - o[a]) / d[a]; u = (o[b] + t * d[b]) - (float)v[b] (one multiply, one add, one
+ *     subtract) and w likewise on axis c.  Each is then clamped by x < 0 ? 0 : x > 1 ? 1 : x (an infinity becomes 0 or 1, a
+ *     NaN stays).  If d[a] == 0, or t, u or w is not finite, then u = w = 0.5f: the centre of the face.
+ *   Cells.  cell(i, j) = f + i * e_b + j * e_c for i, j in {-1, 0, 1}: the nine cells in front of the face.  solid(q) is the
+ *     world's voxel; a voxel outside the world is empty, as for every query.  lev(q) is 0 for a solid q; otherwise the byte
+ *     of d_levels at q - box_origin in region order (x fastest, then y, then z: the d_levels of vxrt_light_field for the
+ *     box B = [box_origin, box_origin + box_dims)) when q lies in B and d_levels is given; otherwise outside_level.  The
+ *     sky nibble of a byte is its high one, the block nibble its low one.
+ *   Corner (i, j) in {0, 1}^2, with si = 2i - 1 and sj = 2j - 1: s1 = solid(cell(si, 0)), s2 = solid(cell(0, sj)),
+ *     s3 = solid(cell(si, sj)).  The members are cell(0, 0) always, cell(si, 0) unless s1, cell(0, sj) unless s2, and
+ *     cell(si, sj) unless s3 || (s1 && s2): light does not leak through a closed corner.  cnt = the number of members,
+ *     1 .. 4.  LS = (float)(sum of the members' sky nibbles) / (float)cnt, LB likewise with the block nibbles.
+ *     open = (s1 && s2) ? 0 : 3 - (s1 + s2 + s3) and A = ao_curve[open].  Without VXRT_LF_SMOOTH every corner has LS and LB
+ *     equal to the nibbles of lev(cell(0, 0)) as floats; without VXRT_LF_OCCLUSION every corner has A = 1.0f.
+ *   Interpolation.  For each of LS, LB and A, with i along b and j along c, each step one subtract, one multiply, one add:
+ *     q0 = q00 + u * (q10 - q00);  q1 = q01 + u * (q11 - q01);  q = q0 + w * (q1 - q0).
+ *   Colour.  S = LS / 15.0f and Bk = LB / 15.0f; ks = sky_floor + (1.0f - sky_floor) * S; per channel
+ *     out = (c * ks + block_color[ch] * Bk) * A.
+ *   Stores.  d_color_out takes out (the copied colour on a miss), d_fb (if given) the BGRA8 pixel of what d_color_out takes
+ *     by the rule of the render launches (clamp to 0 .. 1, * 255, truncate; bytes b, g, r, 255), d_terms (if given) the
+ *     three floats (S, Bk, A) per pixel.  d_summary (if given) is zeroed on the stream by the call and then counts: hit (hit
+ *     pixels); in_box (hit pixels with f in B and d_levels given); occluded (hit pixels of which some corner has open < 3,
+ *     counted whether or not VXRT_LF_OCCLUSION is set); dark (hit pixels with S == 0 and Bk == 0).
+ *   Aliasing.  d_color_out may be d_color_in.  Nothing else may overlap.
+ *   Call rules.  The call needs a resident world that is not streamed.  It is asynchronous on `stream`, allocates nothing,
+ *     waits for nothing, reads no host memory after it returns and may be captured (STREAM CAPTURE above).  It never loads
+ *     outside the world tables and never outside the box_dims[0] * box_dims[1] * box_dims[2] bytes of d_levels.  Refusals,
+ *     each before anything is enqueued or written, checked in this order: a NULL ctx; W or H outside the limits; params NULL
+ *     or its struct_size; flags with a bit other than the two, outside_level > 0xFF or a nonzero reserved_; sky_floor outside
+ *     0 .. 1 or NaN; a block_color or ao_curve entry that is negative or not finite; a non-finite component of the pose;
+ *     box dims outside vxrt_light_field's limits on dims (1 <= box_dims[k], their product <= 2^28) or
+ *     box_origin[k] + box_dims[k] > 2^31 - 1; a NULL d_color_in, d_keys, d_hit_aov or d_color_out -- each VXRT_ERR_INVALID;
+ *     then no world: VXRT_ERR_NO_WORLD; then a streamed world, then a world axis longer than 2^24 voxels: VXRT_ERR_INVALID.
+ *   The cost is one launch (and one 16-byte memset with a summary): per hit pixel nine cell records, nine brick words and
+ *     nine level bytes, which neighbouring lanes largely share, 24 bytes read of its own and 12 .. 28 bytes written. */
+#define VXRT_LF_SMOOTH 1u
+#define VXRT_LF_OCCLUSION 2u
+typedef struct vxrt_light_frame_params {
+    uint32_t struct_size;
+    int32_t ortho;
+    uint32_t flags;          /* VXRT_LF_SMOOTH | VXRT_LF_OCCLUSION; other bits are invalid */
+    uint32_t outside_level;  /* (sky << 4) | block of an empty cell outside the light box; <= 0xFF */
+    float sky_floor;         /* 0 .. 1: what stays of a colour where no sky light reaches */
+    float block_color[3];    /* finite, >= 0: the colour emitter light adds at level 15 */
+    float ao_curve[4];       /* finite, >= 0: the factor of a corner with 0, 1, 2, 3 open neighbours */
+    vxrt_camera_pose cam;    /* the pose the frame was rendered with */
+    int32_t box_origin[3], box_dims[3]; /* the box B of the vxrt_light_field call */
+    int32_t reserved_;       /* 0 */
+} vxrt_light_frame_params;
+typedef struct vxrt_light_frame_summary { uint32_t hit, in_box, occluded, dark; } vxrt_light_frame_summary;
+int vxrt_light_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color_in, const uint32_t *d_keys,
+                     const int64_t *d_hit_aov, const uint8_t *d_levels_or_null, const vxrt_light_frame_params *params,
+                     float *d_color_out, void *d_fb_or_null, float *d_terms_or_null /* W*H*3: S, Bk, A */,
+                     vxrt_light_frame_summary *d_summary_or_null, void *stream);
 
 /* ---- batch query.  Replaces VoxelRaytracer3D::Raytrace + kernel dispatch
  * (VoxelRT/VolumeRaytracer.cu:95-117,574-618).  Results follow the reference

@@ -37,7 +37,7 @@ EXPORTS = [
     "vxrt_lod_workspace_bytes", "vxrt_downsample_region", "vxrt_downsample_region_host",
     "vxrt_light_workspace_bytes", "vxrt_light_field", "vxrt_light_field_host",
     "vxrt_rule_workspace_bytes", "vxrt_apply_rule", "vxrt_apply_rule_host",
-    "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame",
+    "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame", "vxrt_light_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
@@ -55,6 +55,7 @@ VOX_SURFACE, VOX_SOLID, VOX_FRAC_BITS, VOX_MAX_DIM, VOX_MAX_COORD, VOX_MAX_TRIAN
 SURF_CAP, SURF_OPEN, SURF_MAX_DIM = 0, 1, 1024
 LOD_MAX_SHIFT = 5
 LIGHT_SKY, LIGHT_BLOCK, LIGHT_MAX, LIGHT_MAX_EMITTERS = 1, 2, 15, 65536
+LF_SMOOTH, LF_OCCLUSION = 1, 2
 RULE_N6, RULE_N18, RULE_N26, RULE_BOX, RULE_WORLD, RULE_MAX_ITERATIONS = 0, 1, 2, 0, 1, 16
 TRANSFORM_MAX_WORDS = 1 << 31
 
@@ -158,6 +159,12 @@ class CameraPose(C.Structure):
 class ReprojectParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("max_history", C.c_int32), ("reserved_", C.c_int32),
                 ("cur", CameraPose), ("prev", CameraPose)]
+
+
+class LightFrameParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("flags", C.c_uint32), ("outside_level", C.c_uint32),
+                ("sky_floor", C.c_float), ("block_color", C.c_float * 3), ("ao_curve", C.c_float * 4), ("cam", CameraPose),
+                ("box_origin", C.c_int32 * 3), ("box_dims", C.c_int32 * 3), ("reserved_", C.c_int32)]
 
 
 class View(C.Structure):
@@ -319,6 +326,8 @@ def load() -> C.CDLL:
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_reproject_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(ReprojectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_light_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(LightFrameParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

@@ -1,5 +1,5 @@
 // vxrt_api_query.hip -- the part of the C ABI (include/vxrt.h) that works on the resident world: the edit path (vxrt_edit_*),
-// every query family with its _host twin, and the entry points of the frame denoiser and the temporal filter.  No kernel is defined here: each family's
+// every query family with its _host twin, and the entry points of the frame denoiser, the temporal filter and the light on frames.  No kernel is defined here: each family's
 // launcher is declared in its header and defined in its own .hip.
 #include "vxrt_collide.hpp"
 #include "vxrt_denoise.hpp"
@@ -8,6 +8,7 @@
 #include "vxrt_host.hpp"
 #include "vxrt_islands.hpp"
 #include "vxrt_light.hpp"
+#include "vxrt_light_frame.hpp"
 #include "vxrt_lod.hpp"
 #include "vxrt_nav.hpp"
 #include "vxrt_place.hpp"
@@ -1177,6 +1178,54 @@ int vxrt_reproject_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_col
         A.pr[k] = params->prev.right[k];
     }
     VX_HIP(vxrt::reproject_frame(R, A, c->cus, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+// ---- light on frames ---------------------------------------------------------------------------------------------------
+int vxrt_light_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_in, const uint32_t* d_keys, const int64_t* d_hit_aov,
+                     const uint8_t* d_levels_or_null, const vxrt_light_frame_params* params, float* d_color_out, void* d_fb_or_null,
+                     float* d_terms_or_null, vxrt_light_frame_summary* d_summary_or_null, void* stream)
+{
+    // the order of include/vxrt.h
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    static const char* const refusal[] = {"", "", "light frame: 1 <= W, H <= 65535 and W * H <= 2^26",
+                                          "vxrt_light_frame_params missing or size mismatch",
+                                          "light frame flags: VXRT_LF_SMOOTH | VXRT_LF_OCCLUSION, outside_level <= 0xFF (and reserved_ 0)",
+                                          "light frame sky_floor: 0 .. 1",
+                                          "light frame: a block_color or ao_curve entry that is negative or not finite",
+                                          "light frame: a camera pose with a non-finite component",
+                                          "light frame box: 1 <= box_dims[k], their product <= 2^28, box_origin + box_dims <= 2^31 - 1"};
+    if (const int r = vxrt::light_frame_check(W, H, params))
+        return fail(VXRT_ERR_INVALID, refusal[r]);
+    if (!d_color_in || !d_keys || !d_hit_aov || !d_color_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = vxrt::world_ready(c, "lit"))
+        return rc;
+    const vxrt::CollideWorld Wd = vxrt::query_world(c);
+    for (int k = 0; k < 3; ++k)
+        if ((uint32_t)Wd.dim[k] > vxrt::kDnMaxAxis)
+            return fail(VXRT_ERR_INVALID, "light frame: a world axis longer than 2^24 voxels");
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::RenderArgs R;
+    memset(&R, 0, sizeof(R));
+    vxrt::camera_args(c, W, H, R);
+    R.ortho = params->ortho ? 1 : 0;
+    R.origin = vxrt::f3{params->cam.origin[0], params->cam.origin[1], params->cam.origin[2]};
+    R.fwd = vxrt::f3{params->cam.fwd[0], params->cam.fwd[1], params->cam.fwd[2]};
+    R.up = vxrt::f3{params->cam.up[0], params->cam.up[1], params->cam.up[2]};
+    R.right = vxrt::f3{params->cam.right[0], params->cam.right[1], params->cam.right[2]};
+    vxrt::LightFrameArgs A{};
+    vxrt::light_frame_args(A, W, H, *params);
+    A.color_in = d_color_in;
+    A.keys = d_keys;
+    A.hit = (const long long*)d_hit_aov;
+    A.levels = d_levels_or_null;
+    A.color_out = d_color_out;
+    A.fb = (uint32_t*)d_fb_or_null;
+    A.terms = d_terms_or_null;
+    A.summary = (uint32_t*)d_summary_or_null;
+    VX_HIP(vxrt::light_frame(R, A, Wd, c->cus, (hipStream_t)stream));
     return VXRT_OK;
 }
 

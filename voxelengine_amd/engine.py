@@ -855,6 +855,66 @@ class Context:
                     C.byref(p), _ptr(out_history), _ptr(out), _ptr(fb), _ptr(words))
         return Reprojected(dims=(width, height), history=out_history, color=out, _summary=words, _stream=call.s)
 
+    # ---- light on frames (extension, include/vxrt.h) ---------------------------------------------------------------------
+    def light_frame(self, color, keys, hit_aov, cam, field=None, flags: int = N.LF_SMOOTH | N.LF_OCCLUSION, outside_level: int = 0xF0,
+                    sky_floor: float = 0.25, block_color=(1.0, 0.8, 0.5), ao_curve=(0.4, 0.6, 0.8, 1.0), ortho: bool = False,
+                    box=None, out=None, fb=None, terms=False, summary: bool = True, stream: int | None = None):
+        """Smooth voxel light and corner occlusion on a frame (include/vxrt.h, vxrt_light_frame): ``color`` a float32 device
+        tensor (height, width, 3) such as the colour AOV of a render or the output of denoise_frame, ``keys`` its guide keys
+        (frame_guides), ``hit_aov`` the int64 hit-index AOV of the same render, ``cam`` the camera the frame was rendered
+        with as (origin, fwd, up, right).  ``field``: the LightField of Context.light_field (its device levels and its box), or
+        a device tensor of one byte per voxel of ``box`` = (origin, dims) in region order, or None: every empty cell has
+        ``outside_level`` ((sky << 4) | block), as have the empty cells outside the box.  Every hit pixel's colour c
+        becomes (c * (sky_floor + (1 - sky_floor) * S) + block_color * Bk) * A with S, Bk the sky and block light 0 .. 1
+        interpolated over the four corners of the voxel face it shows and A the corner occlusion from ``ao_curve`` (the
+        factor for 0, 1, 2, 3 open neighbours).  Asynchronous on ``stream`` (default: torch's current stream), as
+        denoise_frame.  ``out``: float32 (height, width, 3), may be ``color`` itself (default: a new tensor); ``fb``:
+        optional uint8 (height, width, 4) BGRA8 frame written as well; ``terms``: True, or a float32 (height, width, 3) tensor to
+        write them to: also return (S, Bk, A) per pixel.
+        Returns a LitFrame: ``color``, ``terms`` and, with ``summary``, a lazily read LightFrameSummary."""
+        call = _Call(self, stream)
+        torch = call.torch
+        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
+            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
+        height, width = int(color.shape[0]), int(color.shape[1])
+        n = width * height
+        call.reads(color)
+        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
+        call.reads(call.fits(hit_aov, n, 8, "hit_aov: a contiguous device tensor of width * height eight-byte elements"))
+        levels = None
+        if isinstance(field, LightField):
+            levels, box = field.levels, (field.origin, field.dims)
+        elif field is not None:
+            levels = field
+        if box is None:
+            box = ((0, 0, 0), (1, 1, 1))
+        origin, dims = _box(*box)
+        if levels is not None:
+            nvox = max(dims[0], 0) * max(dims[1], 0) * max(dims[2], 0)
+            call.reads(call.fits(levels, nvox, 1, "field: a contiguous device tensor of one byte per voxel of the box"))
+        if out is None:
+            out = torch.empty_like(color)
+        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
+            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
+        if fb is not None:
+            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        if terms is True or terms is False:
+            terms_out = torch.empty((height, width, 3), dtype=torch.float32, device=call.dev) if terms else None
+        elif call.fits(terms, 3 * n, 4, "terms: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
+            raise ValueError("terms: a contiguous float32 device tensor (height, width, 3)")
+        else:
+            terms_out = terms
+        words = call.summary(4) if summary else None
+        p = N.LightFrameParams(struct_size=C.sizeof(N.LightFrameParams), ortho=1 if ortho else 0, flags=_u32(flags),
+                               outside_level=_u32(outside_level), sky_floor=float(sky_floor))
+        p.block_color = (C.c_float * 3)(*[float(v) for v in block_color])
+        p.ao_curve = (C.c_float * 4)(*[float(v) for v in ao_curve])
+        p.cam.origin, p.cam.fwd, p.cam.up, p.cam.right = (_f3(v) for v in cam)
+        p.box_origin, p.box_dims = _i3(origin), _i3(dims)
+        call.launch(self._L.vxrt_light_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), _ptr(hit_aov), _ptr(levels),
+                    C.byref(p), _ptr(out), _ptr(fb), _ptr(terms_out), _ptr(words))
+        return LitFrame(dims=(width, height), color=out, terms=terms_out, _summary=words, _stream=call.s)
+
     # ---- occupancy LOD (extension, include/vxrt.h) ----------------------------------------------------------------------
     def lod_workspace_bytes(self, dims, shift: int) -> int:
         """vxrt_lod_workspace_bytes: the workspace of one downsample call, 0 outside the contract"""
@@ -1743,6 +1803,33 @@ class Reprojected(_LazyResult):
     def summary(self) -> ReprojectSummary | None:
         """the summary; the first read waits for the call's stream"""
         return None if self._summary is None else ReprojectSummary(*self._words()[:4])
+
+
+class LightFrameSummary(NamedTuple):
+    """vxrt_light_frame_summary: hit pixels, and of them those whose front cell lies in the light box (with levels given),
+    those with a solid cell beside their front cell (some corner with fewer than three open neighbours), and those that no
+    light reaches (S == 0 and Bk == 0)"""
+    hit: int
+    in_box: int
+    occluded: int
+    dark: int
+
+
+@dataclass
+class LitFrame(_LazyResult):
+    """The result of Context.light_frame: ``color`` float32 (height, width, 3), ``terms`` float32 (height, width, 3) holding
+    (S, Bk, A) per pixel or None, device tensors; ``dims`` is (width, height).  ``summary`` is a LightFrameSummary, or None
+    when the call was made without one."""
+    dims: tuple
+    color: object
+    terms: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> LightFrameSummary | None:
+        """the summary; the first read waits for the call's stream"""
+        return None if self._summary is None else LightFrameSummary(*self._words()[:4])
 
 
 class NavAgent(NamedTuple):
