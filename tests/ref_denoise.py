@@ -24,10 +24,10 @@ def workspace_bytes(W, H):
     return 2 * W * H * 16 if frame_ok(W, H) else 0
 
 
-def primary_rays(W, H, pos, fwd, up, right, ortho=False, fov=90.0, ortho_size=(10.0, 10.0)):
+def primary_rays(W, H, pos, fwd, up, right, ortho=False, fov=90.0, ortho_size=(10.0, 10.0), rows=None):
     """(origins, directions), each (H, W, 3) binary32: the perspective direction normalised (v * (1 / sqrt(dot(v, v)))), the
-    ortho direction fwd as it is"""
-    o, d = camera_rays(SimpleNamespace(W=W, H=H, camera=(pos, fwd, up, right), ortho=ortho, ortho_size=ortho_size, fov=fov))
+    ortho direction fwd as it is; with rows = (y0, y1) the rows y0 .. y1 - 1 of the W x H frame alone"""
+    o, d = camera_rays(SimpleNamespace(W=W, H=H, camera=(pos, fwd, up, right), ortho=ortho, ortho_size=ortho_size, fov=fov, rows=rows))
     o, d = np.ascontiguousarray(o, F32), np.ascontiguousarray(d, F32)
     if not ortho:
         with np.errstate(**_QUIET):

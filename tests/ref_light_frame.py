@@ -25,16 +25,18 @@ def _clamp(x):
 
 
 # ---- vectorised ------------------------------------------------------------------------------------------------------
-def light_frame_np(color, keys, hit, o, d, world, levels, box, params=None):
+def light_frame_np(color, keys, hit, o, d, world, levels, box, params=None, solid=None):
     """color (H, W, 3) binary32, keys (H, W) uint32, hit (H, W) int64, (o, d) the primary rays (H, W, 3), world bool [x, y, z],
     levels uint8 [x, y, z] over box = (origin, dims) or None -> (colour (H, W, 3), terms (H, W, 3), (hit, in_box, occluded,
-    dark), info); info: what the frame exercises, for the tests of the case sets"""
+    dark), info); info: what the frame exercises, for the tests of the case sets.  With `solid` given, `world` is the
+    world's extents (X, Y, Z) alone and solid(q), q an integer array (..., 3) of voxels inside the world, says which are
+    solid: for worlds too large for a dense array"""
     flags, outside, sky_floor, block_color, ao_curve = _params(params)
     c = np.ascontiguousarray(color, F32)
     k = np.ascontiguousarray(keys, np.uint32)
     hit = np.asarray(hit, np.int64)
     H, W = k.shape
-    X, Y, Z = world.shape
+    X, Y, Z = (int(n) for n in world) if solid is not None else world.shape
     dims = np.array([X, Y, Z])
     bo, bd = np.asarray(box[0], np.int64), np.asarray(box[1], np.int64)
     hitm = (k != 0) & (hit >= 0) & (hit < X * Y * Z)
@@ -48,10 +50,10 @@ def light_frame_np(color, keys, hit, o, d, world, levels, box, params=None):
     eye = np.eye(3, dtype=np.int64)
     f = v + eye[a] * np.where(toward, -1, 1)[..., None]
 
-    def solid(q):
+    def is_solid(q):
         inside = ((q >= 0) & (q < dims)).all(-1)
         qc = np.clip(q, 0, dims - 1)
-        return inside & world[qc[..., 0], qc[..., 1], qc[..., 2]]
+        return inside & (world[qc[..., 0], qc[..., 1], qc[..., 2]] if solid is None else np.asarray(solid(qc), bool))
 
     def in_box(q):
         return np.full(q.shape[:-1], False) if levels is None else ((q >= bo) & (q < bo + bd)).all(-1)
@@ -68,7 +70,7 @@ def light_frame_np(color, keys, hit, o, d, world, levels, box, params=None):
     for i in (-1, 0, 1):
         for j in (-1, 0, 1):
             q = f + i * eye[b] + j * eye[cc]
-            S[i, j] = solid(q)
+            S[i, j] = is_solid(q)
             L[i, j] = lev(q, S[i, j])
             B[i, j] = in_box(q)
     cells_in_box = sum(B[ij].astype(np.int64) for ij in B)
@@ -220,12 +222,15 @@ def light_frame_scalar(color, keys, hit, o, d, world, levels, box, params=None):
 
 
 def light_frame(color, hit, cam, world, levels=None, box=((0, 0, 0), (1, 1, 1)), params=None, ortho=False, fov=90.0,
-                ortho_size=(10.0, 10.0), scalar=False, keys=None):
+                ortho_size=(10.0, 10.0), scalar=False, keys=None, solid=None):
     """the call as the library takes it: the camera as (origin, fwd, up, right); the keys are those of the guide restatement
-    unless given -> (colour, terms, summary) and, vectorised, info"""
+    unless given -> (colour, terms, summary) and, vectorised, info; `solid` (vectorised only): as light_frame_np takes it"""
     H, W = np.asarray(hit).shape
     o, d = R.primary_rays(W, H, *cam, ortho=ortho, fov=fov, ortho_size=ortho_size)
     if keys is None:
-        keys = R.keys_np(hit, world.shape, o, d)
+        keys = R.keys_np(hit, world if solid is not None else world.shape, o, d)
+    if solid is not None:
+        assert not scalar
+        return light_frame_np(color, keys, hit, o, d, world, levels, box, params, solid)
     fn = light_frame_scalar if scalar else light_frame_np
     return fn(color, keys, hit, o, d, world, levels, box, params)

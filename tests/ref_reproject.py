@@ -27,13 +27,20 @@ def _pose(cam):
 
 
 # ---- vectorised ------------------------------------------------------------------------------------------------------
-def reproject_np(color, keys, o, d, prev, consts, hist=None, keys_prev=None, max_history=32, ortho=False):
+def reproject_np(color, keys, o, d, prev, consts, hist=None, keys_prev=None, max_history=32, ortho=False, rows=None, frame_h=None,
+                 hist_rows=None):
     """color (H, W, 3) binary32, keys (H, W) uint32, (o, d) the primary rays under the current camera (H, W, 3), prev the
     previous camera (origin, fwd, up, right), consts = camera_constants(...), hist (H, W, 4) and keys_prev (H, W) or None
-    -> (records (H, W, 4) binary32, (hit, reused, offscreen, rejected))"""
+    -> (records (H, W, 4) binary32, (hit, reused, offscreen, rejected)).
+    With rows = (y0, y1): a band of a frame of frame_h rows -- color, keys, o and d hold the rows y0 .. y1 - 1, hist and
+    keys_prev the rows hist_rows[0] .. hist_rows[1] - 1 of the previous frame, and every tap inside the frame is asserted to
+    lie in them; the counts are the band's"""
     c = np.ascontiguousarray(color, F32)
     k = np.ascontiguousarray(keys, np.uint32)
-    H, W = k.shape
+    Hb, W = k.shape
+    H = Hb if rows is None else int(frame_h)
+    h0, h1 = (0, H) if rows is None else hist_rows
+    assert rows is None or (rows[1] - rows[0] == Hb and 0 <= h0 < h1 <= H)
     kx, ky, ortho_x, ortho_y, ratio = consts
     po, pf, pu, pr = _pose(prev)
     hitm = k != 0
@@ -67,18 +74,19 @@ def reproject_np(color, keys, o, d, prev, consts, hist=None, keys_prev=None, max
         wx, wy = fx - flx, fy - fly
         x0, y0 = flx.astype(np.int64), fly.astype(np.int64)
         weights = ((F32(1) - wx) * (F32(1) - wy), wx * (F32(1) - wy), (F32(1) - wx) * wy, wx * wy)
-        sw = np.zeros((H, W), F32)
-        sc = np.zeros((H, W, 3), F32)
-        nmin = np.full((H, W), np.inf, F32)
-        any_inside = np.zeros((H, W), bool)
-        any_used = np.zeros((H, W), bool)
+        sw = np.zeros((Hb, W), F32)
+        sc = np.zeros((Hb, W, 3), F32)
+        nmin = np.full((Hb, W), np.inf, F32)
+        any_inside = np.zeros((Hb, W), bool)
+        any_used = np.zeros((Hb, W), bool)
         for j, w in enumerate(weights):
             qx, qy = x0 + (j & 1), y0 + (j >> 1)
             inside = on & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
             any_inside |= inside
             if hist is None or keys_prev is None:
                 continue
-            cx, cy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+            assert (~inside | ((qy >= h0) & (qy < h1))).all(), "a tap outside the history rows given"
+            cx, cy = np.clip(qx, 0, W - 1), np.clip(qy - h0, 0, h1 - h0 - 1)
             hq, kq = hist[cy, cx], keys_prev[cy, cx]
             use = inside & (w > 0) & (kq == k) & (hq[..., 3] >= 1)
             any_used |= use
@@ -89,7 +97,7 @@ def reproject_np(color, keys, o, d, prev, consts, hist=None, keys_prev=None, max
         n1 = nmin + F32(1)
         n = np.where(n1 < F32(max_history), n1, F32(max_history))
         blend = m + (c - m) / n[..., None]
-    rec = np.empty((H, W, 4), F32)
+    rec = np.empty((Hb, W, 4), F32)
     rec[..., :3] = np.where(any_used[..., None], blend, c)
     rec[..., 3] = np.where(any_used, n, np.where(hitm, F32(1), F32(0)))
     summary = (int(hitm.sum()), int(any_used.sum()), int((hitm & ~any_inside).sum()), int((hitm & any_inside & ~any_used).sum()))

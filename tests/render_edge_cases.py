@@ -186,10 +186,12 @@ def _valid(o, d):
 
 def camera_rays(case):
     """getRayDirection / getRayDirectionOrtho (Renderer.cu:44-70, vxrt_persist2.hpp camera_ray) restated in binary32 numpy
-    over every pixel: (origins, directions) of shape (H, W, 3), the directions before normalisation"""
+    over every pixel: (origins, directions) of shape (H, W, 3), the directions before normalisation; with case.rows = (y0, y1)
+    over the rows y0 .. y1 - 1 of the frame alone"""
     W, H = case.W, case.H
     pos, fwd, up, right = (np.asarray(v, np.float32) for v in case.camera)
-    y, x = np.mgrid[0:H, 0:W]
+    y0, y1 = getattr(case, "rows", None) or (0, H)
+    y, x = np.mgrid[y0:y1, 0:W]
     u = x.astype(np.float32) / F32(W)
     v = y.astype(np.float32) / F32(H)
     su, sv = (u * F32(2) - F32(1))[..., None], (v * F32(2) - F32(1))[..., None]

@@ -212,7 +212,8 @@ def test_bench_world_window(eng):
 
 
 def test_many_halo_rows_and_the_ends_of_int32(eng, vxo):
-    """dims (1, 300, 300): 302 x 302 halo rows of one word, more than one grid axis of 65 535; the last origins whose halo fits
+    """dims (1, 300, 300): 302 x 302 halo rows of one word, more rows than a grid axis of 65 535 would hold (the launch is 357
+    workgroups on the first axis; tests/test_gpu_rule_frame_limits.py reaches the second); the last origins whose halo fits
     in int32, far from the world, with `outside` 0 and 1: nothing is free, the bits are 0; one voxel further is refused"""
     vx, torch = eng
     rng = np.random.default_rng(9)
