@@ -1075,6 +1075,14 @@ uint32_t vxrt_compact_rows(uint32_t height, int32_t strip_rows, int32_t strip_co
  * the device (every stream).  The device-side counters only grow: "since the previous read" is a host-side snapshot, so a
  * read never clears memory that a running kernel adds to. */
 int vxrt_frame_stats_get(vxrt_ctx *ctx, vxrt_frame_stats *out);
+/* Loop diagnostics of the persistent render kernel's counting launches that vxrt_frame_stats has no field for, as the LAST
+ * vxrt_frame_stats_get on this context read them (their deltas over the same interval; zeros before the first read).  Host
+ * only: nothing is synchronised or copied.  Writes min(capacity, n) words to `out` and returns n, the number of counters:
+ *   [0] rounds in which both the end-of-walk and the ray-finished phase ran
+ *   [1] ... and in which the first restarted a coarse walk and the second launched a ray
+ *   [2] bounce samples launched from the end-of-walk phase (a shadowed pixel's sample 0, whose shadow ray never parked)
+ * A negative return is an error code. */
+int vxrt_loop_counters_get(vxrt_ctx *ctx, uint64_t *out, int32_t capacity);
 /* scatter `strip_count` compact shard buffers (laid out back to back, shard-major, each padded to
  * `shard_stride_bytes`) into a full W*H BGRA8 frame on the device; used by the root after the gather. */
 int vxrt_deinterleave_strips(vxrt_ctx *ctx, uint32_t width, uint32_t height, int32_t strip_rows,

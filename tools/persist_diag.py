@@ -53,3 +53,6 @@ for cname, frac, euler in bench.CAMERAS:
         100.0 * int(st.dbg[10]) / max(life, 1), 100.0 * int(st.dbg[11]) / max(life, 1)), flush=True)
     print("    shadow rays launched from the end-of-walk phase: %d of %d (%.1f%%)" % (
         int(st.dbg[12]), int(st.shadow_rays), 100.0 * int(st.dbg[12]) / max(int(st.shadow_rays), 1)), flush=True)
+    loop = ctx.loop_counters()
+    print("    bounce samples launched from the end-of-walk phase: %d of %d bounce rays (%.1f%%)" % (
+        loop["end_bounce"], int(st.bounce_rays), 100.0 * loop["end_bounce"] / max(int(st.bounce_rays), 1)), flush=True)

@@ -884,12 +884,20 @@ int vxrt_frame_stats_get(vxrt_ctx* c, vxrt_frame_stats* out)
     out->dbg[12] = h[vxrt::kStatDbgEndShadow];
     out->guard_slack_loads = h[vxrt::kStatGuardSlack];
     out->guard_stray_loads = h[vxrt::kStatGuardStray];
-#ifdef VXRT_EXPERIMENTS  // (vxrt_frame_stats has no field for them: a development print of the A/B build)
-    if (getenv("VXRT_PRINT_COSTART"))
-        fprintf(stderr, "vxrt: rounds with the end-of-walk and the ray-finished phase %llu, with walk starts from both %llu, of %llu rounds\n",
-                h[vxrt::kStatDbgCoRuns], h[vxrt::kStatDbgCoStarts], h[vxrt::kStatDbgIters]);
-#endif
+    c->loop_counters[0] = h[vxrt::kStatDbgCoRuns];
+    c->loop_counters[1] = h[vxrt::kStatDbgCoStarts];
+    c->loop_counters[2] = h[vxrt::kStatDbgEndBounce];
     return VXRT_OK;
+}
+
+int vxrt_loop_counters_get(vxrt_ctx* c, uint64_t* out, int32_t capacity)
+{
+    if (!c || !out || capacity < 0)
+        return fail(VXRT_ERR_INVALID, "NULL argument or negative capacity");
+    const int32_t n = capacity < 3 ? capacity : 3;
+    for (int32_t i = 0; i < n; ++i)
+        out[i] = c->loop_counters[i];
+    return 3;
 }
 
 int vxrt_deinterleave_strips(vxrt_ctx* c, uint32_t width, uint32_t height, int32_t strip_rows, int32_t strip_count,

@@ -49,6 +49,8 @@ struct vxrt_ctx {
     // Counters only ever grow on the device (atomics from any stream); "read and clear" is a host-side snapshot that the
     // next read subtracts, so nothing clears device memory under running kernels.
     unsigned long long stats_base[vxrt::kStatCount] = {};
+    // the last read's deltas of the loop diagnostics vxrt_frame_stats has no field for (vxrt_loop_counters_get)
+    unsigned long long loop_counters[3] = {};
     // Rings: queue heads (render tile counters / batch tickets) and per-view argument slots of multi-view launches.  A ring
     // entry carries the event of the launch that used it last; taking an entry that is still in flight waits for that launch
     // (launch 65 of 64 in flight, multi-view launch 17 of 16), so an entry is never shared by two live launches.

@@ -31,6 +31,7 @@ enum StatSlot {
     kStatDbgCoRuns,     // persistent render kernel: rounds in which both the end-of-walk and the ray-finished phase ran
     kStatDbgCoStarts,   // ... and in which the first restarted a coarse walk and the second launched a ray (one shared set-up)
     kStatDbgEndShadow,  // persistent render kernel: shadow rays launched from the end-of-walk phase (primary hits that never parked)
+    kStatDbgEndBounce,  // ... and bounce samples launched there (shadowed pixels whose shadow ray never parked)
     kStatCount
 };
 

@@ -37,8 +37,11 @@ enum : int { PF_STAGE = 0, PF_TX, PF_ROW, PF_POS_X, PF_POS_Y, PF_POS_Z, PF_COL_X
 // The words of the wave's LDS block behind the lanes' columns: the four ray counters, then what the shadow ray has in common
 // for every pixel of the launch (written once per wave, read by the end-of-walk phase's continuation): the tracer's per-ray
 // invariants of the light's direction, the ray's offset from the hit, and whether the launch takes that path at all.
+// Then what the bounce continuation of that phase needs (bounce_from_end): whether the launch takes it, and the colour of a
+// SHADOWED pixel -- a function of the hit normal's code alone -- for each of the eight codes (x, y, z: three rows of eight).
 enum : int { WV_COUNTERS = 0, WV_LIGHT_DX = 4, WV_LIGHT_DY, WV_LIGHT_DZ, WV_LIGHT_IVX, WV_LIGHT_IVY, WV_LIGHT_IVZ, WV_LIGHT_DN,
-             WV_LIGHT_STEP_X, WV_LIGHT_STEP_Y, WV_LIGHT_STEP_Z, WV_SHADOW_FROM_END, WV_WORDS = 16 };
+             WV_LIGHT_STEP_X, WV_LIGHT_STEP_Y, WV_LIGHT_STEP_Z, WV_SHADOW_FROM_END, WV_BOUNCE_FROM_END, WV_SHADOWED_COL = 16,
+             WV_WORDS = WV_SHADOWED_COL + 24 };
 // The launch's arguments as the ray-finished phase reads them.  The ~50 frame arguments (camera, light, mode words, strips,
 // buffers) are used by that phase only, but as kernel arguments the compiler loads them once, before the loop, and keeps
 // them in scalar registers for the kernel's lifetime -- beside the probe loop's wave masks they do not fit (74 spilled
@@ -134,6 +137,9 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     // general instantiations: with the continuation they spill 8 vector registers, so they keep the ray-finished phase's path
     // (their COMMON forms hold 0 spilled VGPRs with it and have it).
     constexpr bool END_SHADOW = !(BOUNCE2 && MULTI) || COMMON;
+    // ... and so is bounce sample 0 of a pixel whose shadow ray hits (bounce_from_end below).  The second-bounce instantiations
+    // keep the ray-finished phase's path for it.
+    constexpr bool END_BOUNCE = END_SHADOW && !BOUNCE2;
     // the round runs the tight-box phase LAST, behind a coarse set-up that probes (below).  Not in the multi-view second-bounce
     // general instantiation of ordinary grids: in that order it spills 8 vector registers, so it keeps box -> end -> next.
     constexpr bool BOX_LAST = !(BOUNCE2 && MULTI && !WIDE && !COMMON);
@@ -196,6 +202,31 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             WV[WV_LIGHT_STEP_Z] = __float_as_uint(A_kern.light_step.z);
             WV[WV_SHADOW_FROM_END] = (END_SHADOW && FT::mode(A_kern) == 0 && A_kern.shadow && !light_special && !aov) ? 1u : 0u;
         }
+        // The bounce continuation serves pixels whose shadow ray has just hit.  With a light whose components are all finite such
+        // a pixel's l_dot is exactly +0, so the bounce gate (Renderer.cu:121) is open for every one of them whenever the launch
+        // has samples at all, and its colour is the ambient term: calculateColor's expressions (the ray-finished phase's, with
+        // `shadowed` true) evaluated here once per normal code instead of once per pixel.  (The API refuses a light that is not
+        // finite; the test stands for launches built by other means.)  Like the shadow continuation, the path is off for a
+        // `special` light and for a launch with a hit-index AOV.
+        if constexpr (END_BOUNCE) {
+            const f3 L = A_kern.light_dir;
+            const uint32_t exps = 0x7F800000u;
+            const bool finite = (__float_as_uint(L.x) & exps) != exps && (__float_as_uint(L.y) & exps) != exps && (__float_as_uint(L.z) & exps) != exps;
+            const f3 pn = normal_decode((uint32_t)lane & 7u);
+            const f3 normal = mk3(-pn.x, -pn.y, -pn.z);
+            const float l_dot = hi(dot3(normal, L), 0) * (float)0;
+            const f3 diffuse = A_kern.light_color * l_dot;
+            const float up_dot = normal.x * 0.0f + normal.y * 1.0f + normal.z * 0.0f;
+            const float t = (float)((double)up_dot * 0.5 + 0.5);
+            const f3 shadowed_col = diffuse + A_kern.ambient * (0.25f + t * (1.0f - 0.25f));
+            if (lane < 8) {
+                WV[WV_SHADOWED_COL + lane] = __float_as_uint(shadowed_col.x);
+                WV[WV_SHADOWED_COL + 8 + lane] = __float_as_uint(shadowed_col.y);
+                WV[WV_SHADOWED_COL + 16 + lane] = __float_as_uint(shadowed_col.z);
+            }
+            if (lane == 0)
+                WV[WV_BOUNCE_FROM_END] = (FT::mode(A_kern) == 0 && A_kern.shadow && A_kern.bounce_samples > 0 && finite && !light_special && !aov) ? 1u : 0u;
+        }
     }
 
     // the wave's share of the tile queue (wave-uniform)
@@ -211,6 +242,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
     unsigned long long dg_next_ticks = 0, dg_park_ticks = 0;
     unsigned long long dg_co_runs = 0, dg_co_starts = 0;  // rounds in which the end-of-walk AND the ray-finished phase ran / started walks
     unsigned long long dg_end_shadow = 0;  // shadow rays launched from the end-of-walk phase
+    unsigned long long dg_end_bounce = 0;  // ... and bounce samples
 #ifdef VXRT_TAIL_DEBUG
     unsigned long long px_t0 = 0;
 #endif
@@ -317,6 +349,65 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             dg_end_shadow += n;
         return launched;
     };
+    // The second continuation: a SHADOW ray that has just ended on a voxel -- the pixel is shadowed -- becomes its pixel's bounce
+    // sample 0 there and then.  What the ray-finished phase does for such a lane (stage == PX_SHADOW, r.hit): the ambient colour
+    // from the wave's table, occlusion and sample count zeroed, the sample direction from the pixel's seed (the same expressions
+    // in the same order, Renderer.cu:128-142), the ray from position + normal * 0.01f with 8 steps -- and the ray's set-up by
+    // WaveTracerT::begin_ray_inside_fast, which has no vote to fall back on: a lane whose sample direction or start is outside
+    // its fast path (and a lane whose sdd is not ordinary) stays ST_DONE with nothing written, for the ray-finished phase.
+    // Skipped as a whole, behind one ballot, by an execution without an ended lane in the shadow stage.
+    auto bounce_from_end = [&](Tracer& Tr, const lanemask_t ended) -> lanemask_t {
+        if (WV[WV_BOUNCE_FROM_END] == 0u)  // (launch-uniform: a launch without the path pays this one read)
+            return 0ull;
+        const lanemask_t mine = __ballot(lane_test(ended) && PX[PF_STAGE * 64] == PX_SHADOW);
+        if (mine == 0ull)
+            return 0ull;
+        bool go = false;
+        if (lane_test(mine)) {
+            const RenderArgs& A = kernarg_reload(A_kern);
+            const uint32_t tx = PX[PF_TX * 64], row = PX[PF_ROW * 64];
+            // (the launch coordinates of the seed do not depend on the frame number: only the frame row of a checkerboard does)
+            const PixelCoords pc = pixel_coords<COMMON>(A, 0u, tx, MULTI ? row & 0xFFFFu : row);
+            const uint32_t seed = pc.ty * A.width + pc.tx;
+            const uint32_t frame_number = MULTI ? A.views[row >> 16].frame_number : A.frame_number;
+            const uint32_t si = seed + (frame_number + 1u) * 1000u;  // sample 0
+            float two = 2.0f;
+            pin(two);
+            f3 sd = mk3(random_float(si) * two - 1, random_float(si * 10u) * two - 1, random_float(si * 100u) * two - 1);
+            const float sdd = dot3(sd, sd);
+            sd = unit3_ordinary(sd, sdd);
+            const uint32_t code = PX[PF_PCODE * 64];
+            const f3 pn = normal_decode(code);
+            const f3 bn = mk3(-pn.x, -pn.y, -pn.z);
+            if (dot3(sd, bn) < 0)
+                sd = reflect3(sd, bn);
+            const f3 bo = mk3(__uint_as_float(PX[PF_POS_X * 64]), __uint_as_float(PX[PF_POS_Y * 64]), __uint_as_float(PX[PF_POS_Z * 64]));
+            if (ordinary(sdd) && Tr.begin_ray_inside_fast(W, bo + bn * 0.01f, sd, 8)) {
+                PX[PF_COL_X * 64] = WV[WV_SHADOWED_COL + (code & 7u)];
+                PX[PF_COL_Y * 64] = WV[WV_SHADOWED_COL + 8 + (code & 7u)];
+                PX[PF_COL_Z * 64] = WV[WV_SHADOWED_COL + 16 + (code & 7u)];
+                PX[PF_OCCL * 64] = 0u;
+                PX[PF_SAMPLE * 64] = 0u;
+                PX[PF_STAGE * 64] = PX_BOUNCE;
+                go = true;
+            }
+        }
+        const lanemask_t launched = __ballot(go);
+        const uint32_t n = (uint32_t)__popcll(launched);
+        if (lane == 0)  // one bounce ray each
+            WV[WV_COUNTERS + 2] += n;
+        if (STATS)
+            dg_end_bounce += n;
+        return launched;
+    };
+    auto end_hook = [&](Tracer& Tr, const lanemask_t ended) -> lanemask_t {
+        lanemask_t launched = shadow_from_end(Tr, ended);
+        if constexpr (END_BOUNCE) {
+            if (ended != 0ull)  // (not the primary hits that have just become shadow rays)
+                launched |= bounce_from_end(Tr, ended & ~launched);
+        }
+        return launched;
+    };
 
     for (;;) {
         const unsigned long long m_walk = __ballot(T.st == ST_WALK);
@@ -362,7 +453,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
                 dg_park_ticks -= wall_clock64();
             }
             if constexpr (END_SHADOW)
-                T.template phase_end_deferred<STATS>(W, shadow_from_end);
+                T.template phase_end_deferred<STATS>(W, end_hook);
             else
                 T.template phase_end_deferred<STATS>(W);
             if (STATS)
@@ -700,6 +791,7 @@ __global__ __launch_bounds__(64, VXRT_PERSIST2_OCC) void k_render_persist2(Rende
             atomicAdd(&stats[kStatDbgCoRuns], dg_co_runs);
             atomicAdd(&stats[kStatDbgCoStarts], dg_co_starts);
             atomicAdd(&stats[kStatDbgEndShadow], dg_end_shadow);
+            atomicAdd(&stats[kStatDbgEndBounce], dg_end_bounce);
         }
     }
 }

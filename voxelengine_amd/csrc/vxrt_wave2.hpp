@@ -509,6 +509,40 @@ struct WaveTracerT {
         dn = (d.x > 0 ? 0u : 1u) | (d.y > 0 ? 0u : 2u) | (d.z > 0 ? 0u : 4u);
         st = ST_WALK;
     }
+    // begin_ray_deferred's fast path alone, per lane and without a vote: for a ray whose operands are all of ordinary size, whose
+    // direction has no component below kMinFastDir and whose start lies inside the coarse grid without a -0.0 component (no sign
+    // bit, below the far faces) it leaves the lane exactly as begin_ray_deferred does -- the short exact forms ARE the plain
+    // operators' results on such operands, whichever of the two that member's wave takes -- and returns true; for every other ray
+    // it returns false and has touched nothing.  For callers that launch a ray where no vote can be held for the wave's sake
+    // (the end-of-walk hook of k_render_persist2); the caller puts the lane into pend_m as after_begin_ray_deferred does.
+    __device__ __forceinline__ bool begin_ray_inside_fast(const WorldView& W, f3 origin, f3 ray, int max_steps_)
+    {
+        const float dd = dot3(ray, ray);
+        const f3 u = unit3_ordinary(ray, dd);
+        const float ix = rcp_rn(u.x), iy = rcp_rn(u.y), iz = rcp_rn(u.z);
+        const f3 s0 = mk3(origin.x * W.inv_f, origin.y * W.inv_f, origin.z * W.inv_f);
+        const uint32_t signs = __float_as_uint(s0.x) | __float_as_uint(s0.y) | __float_as_uint(s0.z);
+        // (the reciprocals' operands need no test of their own: with dd ordinary a component of u is at most 1 and a few ulps,
+        // and one that is not below kMinFastDir = 2^-40 is far inside `ordinary`)
+        const bool ok = ordinary(dd) & (fabsf(u.x) >= kMinFastDir) & (fabsf(u.y) >= kMinFastDir) & (fabsf(u.z) >= kMinFastDir) &
+                        ((int32_t)signs >= 0) & (s0.x < (float)W.cx) & (s0.y < (float)W.cy) & (s0.z < (float)W.cz);
+        if (!ok)
+            return false;
+        d = u;
+        ivx = ix;
+        ivy = iy;
+        ivz = iz;
+        cold[CF_RAY_CODES * 64] = (uint32_t)max_steps_ << 7;  // entry_code = 0: the start is inside
+        cold[CF_START_X * 64] = __float_as_uint(s0.x);
+        cold[CF_START_Y * 64] = __float_as_uint(s0.y);
+        cold[CF_START_Z * 64] = __float_as_uint(s0.z);
+        cold[CF_LAST_CI * 64] = 0xFFFFFFFFu;
+        cold[CF_TOTAL * 64] = 0u;
+        special = false;
+        dn = (u.x > 0 ? 0u : 1u) | (u.y > 0 ? 0u : 2u) | (u.z > 0 ? 0u : 4u);
+        st = ST_WALK;
+        return true;
+    }
     __device__ __forceinline__ void after_begin_ray(bool launched) { fine_m &= ~__ballot(launched); }
     __device__ __forceinline__ void after_begin_ray_deferred(bool launched)
     {

@@ -1107,6 +1107,16 @@ class Context:
         N.check(self._L.vxrt_frame_stats_get(self._h, C.byref(st)))
         return st
 
+    def loop_counters(self) -> dict:
+        """The loop diagnostics the last frame_stats() read that FrameStats has no field for (vxrt_loop_counters_get)."""
+        names = ("co_runs", "co_starts", "end_bounce")
+        out = (C.c_uint64 * len(names))()
+        n = self._L.vxrt_loop_counters_get(self._h, out, len(names))
+        if n < 0:
+            N.check(n)
+        assert n == len(names), "vxrt_loop_counters_get reports %d counters" % n
+        return {k: int(out[i]) for i, k in enumerate(names)}
+
     def deinterleave_strips(self, width, height, strip_rows, strip_count, d_shards, shard_stride_bytes, d_fb,
                             stream: int | None = None) -> None:
         N.check(self._L.vxrt_deinterleave_strips(self._h, width, height, strip_rows, strip_count, _ptr(d_shards),
