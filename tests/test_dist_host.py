@@ -221,7 +221,7 @@ def _layout(harness, tmp_path, origin, dims, radius):
 
 def test_layout_accepts_the_last_origin_whose_halo_fits_int32(harness, tmp_path):
     lo, hi = -2 ** 31, 2 ** 31 - 1
-    for radius, dims in [(1, (8, 8, 8)), (255, (8, 3, 70)), (40, (1, 1, 1))]:
+    for radius, dims in [(1, (8, 8, 8)), (255, (8, 3, 70)), (40, (1, 1, 1)), (2, (33, 2, 2))]:
         for k in range(3):
             for edge, ok in [(lo + radius, True), (lo + radius - 1, False), (hi - dims[k] - radius, True),
                              (hi - dims[k] - radius + 1, False)]:

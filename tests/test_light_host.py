@@ -167,7 +167,7 @@ def _layout(harness, tmp_path, origin, dims, channels):
 
 def test_layout_accepts_the_last_origin_whose_halo_fits_int32(harness, tmp_path):
     lo, hi = -2 ** 31, 2 ** 31 - 1
-    for dims in [(8, 8, 8), (1, 3, 70)]:
+    for dims in [(8, 8, 8), (1, 3, 70), (1, 1, 1), (33, 2, 2)]:
         for k in range(3):
             for edge, ok in [(lo + 14, True), (lo + 13, False), (hi - dims[k] - 14, True), (hi - dims[k] - 13, False)]:
                 origin = [0, 0, 0]

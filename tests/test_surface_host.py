@@ -272,9 +272,9 @@ def test_layout_follows_the_documented_formula_and_limits(harness, tmp_path):
 
 def test_layout_accepts_the_last_origin_whose_halo_fits_int32(harness, tmp_path):
     lo, hi = -2 ** 31, 2 ** 31 - 1
-    dims = (8, 3, 70)
-    for k in range(3):
-        for edge, ok in [(lo + 1, True), (lo, False), (hi - dims[k] - 1, True), (hi - dims[k], False)]:
-            origin = [0, 0, 0]
-            origin[k] = edge
-            assert _layout(harness, tmp_path, origin, dims)[:2] == (ok, True)
+    for dims in [(8, 3, 70), (1, 1, 1), (33, 2, 2)]:
+        for k in range(3):
+            for edge, ok in [(lo + 1, True), (lo, False), (hi - dims[k] - 1, True), (hi - dims[k], False)]:
+                origin = [0, 0, 0]
+                origin[k] = edge
+                assert _layout(harness, tmp_path, origin, dims)[:2] == (ok, True), (dims, k, edge)

@@ -81,9 +81,7 @@ int main(int argc, char** argv)
     A.skip = skip;
 
     // k_read_region of the halo: clipped to the world before any load
-    const int32_t r = (int32_t)radius;
-    const int32_t ho[3] = {o[0] - r, o[1] - r, o[2] - r}, hdim[3] = {d[0] + 2 * r, d[1] + 2 * r, d[2] + 2 * r};
-    const std::vector<uint32_t> halo = read_host(h.world(), ho, hdim);
+    const std::vector<uint32_t> halo = read_host(h.world(), L.ho, L.hd);
     CHECK(halo.size() == L.nhalo);
     for (uint64_t i = 0; i < halo.size(); ++i)
         ((uint32_t*)(work.data() + L.halo))[i] = halo[i];

@@ -81,14 +81,13 @@ static inline HbmWorld to_hbm(const vxo_world* w)
 static inline std::vector<uint32_t> read_host(const vxrt::CollideWorld& W, const int32_t o[3], const int32_t d[3])
 {
     const uint64_t wpr = vxrt::region_words_per_row(d[0]);
-    const uint32_t pad = (d[0] & 31) ? (1u << (d[0] & 31)) - 1u : 0xFFFFFFFFu;
     std::vector<uint32_t> out(vxrt::region_words(d), 0xDEADBEEFu);
     for (int64_t zl = 0; zl < d[2]; ++zl) for (int64_t yl = 0; yl < d[1]; ++yl) for (uint64_t xw = 0; xw < wpr; ++xw) {
         const int64_t x0 = (int64_t)o[0] + 32 * (int64_t)xw, wy = (int64_t)o[1] + yl, wz = (int64_t)o[2] + zl;
         uint32_t w = 0u;
         if (wy >= 0 && wy < W.dim[1] && wz >= 0 && wz < W.dim[2] && x0 + 31 >= 0 && x0 < W.dim[0])
             w = vxrt::region_row_word(W.meta, W.pool, W.f, W.lgf, W.cx, W.cz, x0, (int)wy, (int)wz);
-        out[((uint64_t)yl + (uint64_t)d[1] * zl) * wpr + xw] = w & (xw == wpr - 1 ? pad : 0xFFFFFFFFu);
+        out[((uint64_t)yl + (uint64_t)d[1] * zl) * wpr + xw] = w & (xw == wpr - 1 ? vxrt::row_last_mask(d[0]) : 0xFFFFFFFFu);
     }
     return out;
 }

@@ -64,34 +64,13 @@ int main(int argc, char** argv)
     CHECK(L.blocks + L.nblocks <= work.size() && L.prefix + L.nwords <= L.blocks && L.anchor + L.nwords <= L.prefix &&
           L.roots + L.nwords <= L.anchor && L.parent + L.nvox <= L.roots && L.nbits <= L.parent);
     IslandsArgs A{};
-    uint32_t* ws = work.data();
-    A.bits = ws + L.bits;
-    A.parent = ws + L.parent;
-    A.roots = ws + L.roots;
-    A.anchor = ws + L.anchor;
-    A.prefix = ws + L.prefix;
-    A.blocks = ws + L.blocks;
-    A.floating = floating.data();
-    A.labels = labels.data();
-    A.table = max_islands ? table.data() : nullptr;
-    A.summary = summary.data();
-    A.max_islands = max_islands;
-    A.anchors = anchors;
-    for (int k = 0; k < 3; ++k) {
-        A.d[k] = d[k];
-        A.o[k] = o[k];
-    }
-    A.wpr = L.wpr;
-    A.nvox = L.nvox;
-    A.nwords = L.nwords;
-    A.nblocks = L.nblocks;
-    A.nbits = L.nbits;
+    islands_args(A, L, o, d, anchors, work.data(), floating.data(), labels.data(), table.data(), max_islands, summary.data());
     for (uint32_t k = 0; k < L.nwords; ++k)
         A.anchor[k] = 0u;  // the memset
 
     // k_read_region: the box's words, clipped to the world before any load
     const std::vector<uint32_t> box = read_host(h.world(), o, d);
-    std::copy(box.begin(), box.end(), ws + L.bits);
+    std::copy(box.begin(), box.end(), work.data() + L.bits);
 
     // k_isl_local, tile by tile: the three phases of the workgroup, lane by lane
     const uint32_t ntx = L.wpr, nty = (d[1] + kIslTileY - 1) / kIslTileY, ntz = (d[2] + kIslTileZ - 1) / kIslTileZ;

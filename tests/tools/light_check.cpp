@@ -94,9 +94,7 @@ int main(int argc, char** argv)
     CHECK(A.wide == 1u || ((uintptr_t)levels.data() & 3u) != 0u);
 
     // k_read_region of the halo: clipped to the world before any load
-    const int32_t H = (int32_t)kLightHalo;
-    const int32_t ho[3] = {o[0] - H, o[1] - H, o[2] - H}, hdim[3] = {d[0] + 2 * H, d[1] + 2 * H, d[2] + 2 * H};
-    const std::vector<uint32_t> halo = read_host(W, ho, hdim);
+    const std::vector<uint32_t> halo = read_host(W, L.ho, L.hd);
     CHECK(halo.size() == L.np);
     for (uint64_t i = 0; i < halo.size(); ++i)
         A.empty[i] = halo[i];

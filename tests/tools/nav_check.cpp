@@ -73,43 +73,8 @@ int main(int argc, char** argv)
           L.free - L.fy >= g_size[kNavFy] && L.vis - L.free >= L.nb && L.front[0] - L.vis >= L.nb &&
           L.front[1] - L.front[0] >= L.nb && L.dist - L.front[1] >= L.nb && L.stamp - L.dist >= L.nvox &&
           L.list + 3u * (uint64_t)L.ntiles <= L.ctrl && L.ctrl + kNavCtrlWords <= work.size());
-    uint32_t* ws = work.data();
     NavArgs A{};
-    A.halo = ws + L.halo;
-    A.ex = ws + L.ex;
-    A.dx = ws + L.dx;
-    A.fy = ws + L.fy;
-    A.free = ws + L.free;
-    A.walk = walk.data();
-    A.vis = ws + L.vis;
-    A.front[0] = ws + L.front[0];
-    A.front[1] = ws + L.front[1];
-    A.dist = ws + L.dist;
-    A.stamp = ws + L.stamp;
-    A.mark = ws + L.mark;
-    A.list = ws + L.list;
-    A.ctrl = ws + L.ctrl;
-    A.next = next.data();
-    A.summary = summary.data();
-    A.goals = goals.data();
-    A.ngoals = ngoals;
-    for (int k = 0; k < 3; ++k) {
-        A.o[k] = o[k];
-        A.d[k] = d[k];
-    }
-    A.w = aw;
-    A.h = ah;
-    A.climb = climb;
-    A.drop = drop;
-    A.wb = L.wb;
-    A.wh = L.wh;
-    A.hy = L.hy;
-    A.hz = L.hz;
-    A.nvox = L.nvox;
-    A.nty = L.nty;
-    A.ntz = L.ntz;
-    A.ntiles = L.ntiles;
-    A.nb = L.nb;
+    nav_args(A, L, o, d, aw, ah, climb, drop, goals.data(), ngoals, work.data(), walk.data(), next.data(), nullptr, summary.data());
     // the memsets
     for (uint32_t k = 0; k < kNavCtrlWords; ++k) A.ctrl[k] = 0u;
     for (uint32_t k = 0; k < L.ntiles; ++k) A.mark[k] = 0u;
@@ -122,7 +87,7 @@ int main(int argc, char** argv)
     const std::vector<uint32_t> halo = read_host(h.world(), ho, hdim);
     for (uint64_t i = 0; i < halo.size(); ++i) {
         check_index(kNavHalo, i);
-        ws[L.halo + i] = halo[i];
+        work[L.halo + i] = halo[i];
     }
 
     // k_nav_xpass, k_nav_ypass, k_nav_zpass

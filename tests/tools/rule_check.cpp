@@ -120,9 +120,7 @@ int main(int argc, char** argv)
     rule_args(A, L, W, o, d, rule, has_mask ? mask.data() : nullptr, work.data(), bits.data(), summary);
 
     // k_read_region of the halo: clipped to the world before any load
-    const int32_t H = (int32_t)L.h;
-    const int32_t ho[3] = {o[0] - H, o[1] - H, o[2] - H}, hdim[3] = {d[0] + 2 * H, d[1] + 2 * H, d[2] + 2 * H};
-    const std::vector<uint32_t> halo = read_host(W, ho, hdim);
+    const std::vector<uint32_t> halo = read_host(W, L.ho, L.hd);
     CHECK(halo.size() == L.np);
     for (uint64_t i = 0; i < halo.size(); ++i)
         A.w0[i] = halo[i];
@@ -166,9 +164,8 @@ int main(int argc, char** argv)
         CHECK(work[L.total_bytes + i] == 0xA5);
     }
     CHECK(summary[kRuleSumWords] == 0xC0FFEEu && summary[5] == 0u);
-    if (d[0] & 31)
-        for (uint64_t row = 0; row < (uint64_t)d[1] * d[2]; ++row)
-            CHECK((bits[row * L.mw + L.mw - 1u] >> (d[0] & 31)) == 0u);
+    for (uint64_t row = 0; row < (uint64_t)d[1] * d[2]; ++row)
+        CHECK((bits[row * L.mw + L.mw - 1u] & ~row_last_mask(d[0])) == 0u);
     CHECK(summary[kRuleSumAfter] == summary[kRuleSumBefore] + summary[kRuleSumBorn] - summary[kRuleSumDied]);
 
     FILE* out = fopen(argv[2], "wb");

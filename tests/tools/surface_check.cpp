@@ -87,8 +87,7 @@ int main(int argc, char** argv)
               triangles ? tris.data() : nullptr, summary);
 
     // k_read_region of the halo: clipped to the world before any load
-    const int32_t ho[3] = {o[0] - 1, o[1] - 1, o[2] - 1}, hdim[3] = {d[0] + 2, d[1] + 2, d[2] + 2};
-    const std::vector<uint32_t> halo = read_host(h.world(), ho, hdim);
+    const std::vector<uint32_t> halo = read_host(h.world(), L.ho, L.hd);
     CHECK(halo.size() == L.nhalo);
     for (uint64_t i = 0; i < halo.size(); ++i)
         ((uint32_t*)(work.data() + L.halo))[i] = halo[i];

@@ -723,10 +723,10 @@ static int distance_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t di
     vxrt::DistLayout L;
     if (radius < 1 || radius > vxrt::kDistMaxRadius)
         return fail(VXRT_ERR_INVALID, "distance radius: 1 .. VXRT_DIST_MAX_RADIUS");
-    if (!vxrt::dist_layout(nullptr, dims, radius, L))
-        return fail(VXRT_ERR_INVALID, "distance box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36");
     if (!vxrt::dist_layout(origin, dims, radius, L))
-        return fail(VXRT_ERR_INVALID, "distance box: origin - radius or origin + dims + radius beyond int32");
+        return fail(VXRT_ERR_INVALID, L.fault == vxrt::kBoxDims
+                                          ? "distance box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36"
+                                          : "distance box: origin - radius or origin + dims + radius beyond int32");
     if (mode != VXRT_DIST_TO_SOLID && mode != VXRT_DIST_TO_EMPTY)
         return fail(VXRT_ERR_INVALID, "distance mode: VXRT_DIST_TO_SOLID or VXRT_DIST_TO_EMPTY");
     return vxrt::world_ready(c, "queried");
@@ -839,10 +839,9 @@ static int surface_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dim
     vxrt::SurfLayout L;
     if (mode != VXRT_SURF_CAP && mode != VXRT_SURF_OPEN)
         return fail(VXRT_ERR_INVALID, "surface mode: VXRT_SURF_CAP or VXRT_SURF_OPEN");
-    if (!vxrt::surf_layout(nullptr, dims, L))
-        return fail(VXRT_ERR_INVALID, "surface box dims: each 1 .. VXRT_SURF_MAX_DIM, at most 2^28 voxels");
     if (!vxrt::surf_layout(origin, dims, L))
-        return fail(VXRT_ERR_INVALID, "surface box: origin - 1 or origin + dims + 1 beyond int32");
+        return fail(VXRT_ERR_INVALID, L.fault == vxrt::kBoxDims ? "surface box dims: each 1 .. VXRT_SURF_MAX_DIM, at most 2^28 voxels"
+                                                                : "surface box: origin - 1 or origin + dims + 1 beyond int32");
     if (!quads && capacity)
         return fail(VXRT_ERR_INVALID, "surface: quads NULL with capacity_quads > 0");
     if (!vertices != !triangles)
@@ -904,10 +903,9 @@ static int lod_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3]
         return fail(VXRT_ERR_INVALID, "lod shift: 1 .. VXRT_LOD_MAX_SHIFT");
     if (!vxrt::lod_threshold_ok(shift, threshold))
         return fail(VXRT_ERR_INVALID, "lod threshold: 1 .. f^3 with f = 1 << shift");
-    if (!vxrt::lod_layout(nullptr, dims, shift, L))
-        return fail(VXRT_ERR_INVALID, "lod dims: each at least 1, the source box dims << shift at most 2^32 voxels");
     if (!vxrt::lod_layout(origin, dims, shift, L))
-        return fail(VXRT_ERR_INVALID, "lod box: origin + (dims << shift) beyond 2^31 - 1");
+        return fail(VXRT_ERR_INVALID, L.fault == vxrt::kBoxDims ? "lod dims: each at least 1, the source box dims << shift at most 2^32 voxels"
+                                                                : "lod box: origin + (dims << shift) beyond 2^31 - 1");
     return vxrt::world_ready(c, "queried");
 }
 
@@ -963,10 +961,10 @@ static int light_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[
         return fail(VXRT_ERR_INVALID, "light: more than VXRT_LIGHT_MAX_EMITTERS emitters");
     if (!emitters && n_emitters && (channels & VXRT_LIGHT_BLOCK))
         return fail(VXRT_ERR_INVALID, "light: emitters NULL with n_emitters > 0 and the block channel");
-    if (!vxrt::light_layout(nullptr, dims, channels, L))
-        return fail(VXRT_ERR_INVALID, "light box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36");
     if (!vxrt::light_layout(origin, dims, channels, L))
-        return fail(VXRT_ERR_INVALID, "light box: origin - 14 or origin + dims + 14 beyond int32");
+        return fail(VXRT_ERR_INVALID, L.fault == vxrt::kBoxDims
+                                          ? "light box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36"
+                                          : "light box: origin - 14 or origin + dims + 14 beyond int32");
     return vxrt::world_ready(c, "queried");
 }
 
@@ -1025,10 +1023,10 @@ static int rule_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3
     if (mask && rule->scope == VXRT_RULE_WORLD)
         return fail(VXRT_ERR_INVALID, "rule: a mask with VXRT_RULE_WORLD");
     vxrt::RuleLayout L;
-    if (!vxrt::rule_layout(nullptr, dims, vxrt::rule_halo(*rule), L))
-        return fail(VXRT_ERR_INVALID, "rule box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36");
     if (!vxrt::rule_layout(origin, dims, vxrt::rule_halo(*rule), L))
-        return fail(VXRT_ERR_INVALID, "rule box: origin - halo or origin + dims + halo beyond int32");
+        return fail(VXRT_ERR_INVALID, L.fault == vxrt::kBoxDims
+                                          ? "rule box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36"
+                                          : "rule box: origin - halo or origin + dims + halo beyond int32");
     return vxrt::world_ready(c, "queried");
 }
 

@@ -24,7 +24,7 @@ static_assert(kDistTile == 64 && kDistTile % kDistRows == 0, "a slab row is one 
 
 __global__ __launch_bounds__(256) void k_dist_occ(const DistArgs A, uint64_t n)
 {
-    const uint64_t i = ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint64_t i = flat_thread();
     if (i >= n)
         return;
     const uint64_t q = i / A.wh;
@@ -42,7 +42,7 @@ template <uint32_t kSlabRows>
 __global__ __launch_bounds__(256) void k_dist_ysweep(const DistArgs A)
 {
     __shared__ uint16_t slab[kSlabRows * kDistTile];
-    const uint64_t g = (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x;
+    const uint64_t g = flat_block();
     if (g >= (uint64_t)A.ntx * A.nty * A.hz)
         return;
     const uint32_t tx = (uint32_t)(g % A.ntx), ty = (uint32_t)(g / A.ntx % A.nty), hz = (uint32_t)(g / A.ntx / A.nty);
@@ -57,21 +57,12 @@ __global__ __launch_bounds__(256) void k_dist_ysweep(const DistArgs A)
         dist_y_store(A, slab, tx, ty, hz, j, lane);
 }
 
-__device__ inline uint32_t wave_max(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 template <uint32_t kSlabRows>
 __global__ __launch_bounds__(256) void k_dist_zsweep(const DistArgs A, uint32_t nyc)
 {
     __shared__ uint16_t slab[kSlabRows * kDistTile];
     __shared__ DistTally part[4];
-    const uint64_t g = (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x;
+    const uint64_t g = flat_block();
     if (g >= (uint64_t)A.ntx * nyc * A.ntz)
         return;
     const uint32_t tx = (uint32_t)(g % A.ntx), yc = (uint32_t)(g / A.ntx % nyc), tz = (uint32_t)(g / A.ntx / nyc);
@@ -144,9 +135,7 @@ hipError_t distance_field(const CollideWorld& W, const int32_t o[3], const int32
     hipError_t e;
     if ((e = hipMemsetAsync(summary, 0, sizeof(vxrt_distance_summary), stream)) != hipSuccess)
         return e;
-    const int32_t r = (int32_t)radius;
-    const int32_t ho[3] = {o[0] - r, o[1] - r, o[2] - r}, hd[3] = {d[0] + 2 * r, d[1] + 2 * r, d[2] + 2 * r};
-    if ((e = read_region(W, ho, hd, (uint32_t*)((char*)work + L.halo), stream)) != hipSuccess)
+    if ((e = read_region(W, L.ho, L.hd, (uint32_t*)((char*)work + L.halo), stream)) != hipSuccess)
         return e;
     hipLaunchKernelGGL(k_dist_occ, grid_2d((L.nocc + 255u) / 256u), dim3(256), 0, stream, A, L.nocc);
     hipLaunchKernelGGL(k_dist_tiles, dim3(L.ntiles), dim3(256), 0, stream, A);

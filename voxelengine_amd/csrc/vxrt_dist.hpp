@@ -43,40 +43,24 @@ enum { kDistHalo, kDistG2, kDistOcc, kDistLive, kDistOut, kDistSlab };
 enum { kDistSumZero, kDistSumNear, kDistSumFar, kDistSumMax, kDistSumSum };
 
 // the workspace: sections of bytes, each on a 256-byte boundary (include/vxrt.h states the same formula)
-struct DistLayout {
+struct DistLayout : HaloBox {      // the halo box (vxrt_region.hpp): B grown by the radius
     uint64_t halo, g2, occ, live;  // byte offsets
     uint64_t total_bytes;
-    uint64_t nhalo, ng2, nocc;  // halo words, g2 cells, occupancy cells
-    uint32_t wh, hy, hz;        // words per halo row, halo rows, halo slices
+    uint64_t ng2, nocc;         // g2 cells, occupancy cells
     uint32_t nvox;              // voxels of B
     uint32_t ncy, ncz;          // occupancy cells along y and z (wh along x)
     uint32_t ntx, nty, ntz, ntiles;
 };
 
-// false outside the contract: radius, dims, the halo box within a region read and, when `o` is given, within int32
+// false outside the contract (L.fault: why): radius, dims, the halo box within a region read and, when `o` is given, within
+// int32
 inline bool dist_layout(const int32_t* o, const int32_t d[3], uint32_t r, DistLayout& L)
 {
-    if (r < 1 || r > kDistMaxRadius || d[0] < 1 || d[1] < 1 || d[2] < 1)
+    L.fault = r < 1 || r > kDistMaxRadius ? kBoxDims : halo_box(o, d, (int32_t)r, kDistMaxVoxels, L);
+    if (L.fault != kBoxOk)
         return false;
-    const uint64_t v01 = (uint64_t)d[0] * (uint64_t)d[1];
-    if (v01 > kDistMaxVoxels || (uint64_t)d[2] > kDistMaxVoxels / v01)
-        return false;
-    int32_t hd[3];
-    for (int k = 0; k < 3; ++k) {
-        if ((int64_t)d[k] + 2 * (int64_t)r > INT32_MAX)
-            return false;
-        hd[k] = d[k] + 2 * (int32_t)r;
-        if (o && ((int64_t)o[k] - (int64_t)r < INT32_MIN || (int64_t)o[k] + d[k] + (int64_t)r > INT32_MAX))
-            return false;
-    }
-    L.nhalo = region_words(hd);
-    if (L.nhalo == 0)
-        return false;
-    L.nvox = (uint32_t)(v01 * (uint64_t)d[2]);
-    L.wh = (uint32_t)region_words_per_row(hd[0]);
-    L.hy = (uint32_t)hd[1];
-    L.hz = (uint32_t)hd[2];
-    L.ng2 = v01 * L.hz;
+    L.nvox = (uint32_t)box_voxels(d, kDistMaxVoxels);
+    L.ng2 = (uint64_t)d[0] * (uint64_t)d[1] * L.hz;
     L.ncy = (L.hy + kDistCell - 1) / kDistCell;
     L.ncz = (L.hz + kDistCell - 1) / kDistCell;
     L.nocc = (uint64_t)L.wh * L.ncy * L.ncz;
@@ -84,11 +68,12 @@ inline bool dist_layout(const int32_t* o, const int32_t d[3], uint32_t r, DistLa
     L.nty = ((uint32_t)d[1] + kDistTile - 1) / kDistTile;
     L.ntz = ((uint32_t)d[2] + kDistTile - 1) / kDistTile;
     L.ntiles = L.ntx * L.nty * L.ntz;
-    L.halo = 0;
-    L.g2 = section_up(4u * L.nhalo);
-    L.occ = L.g2 + section_up(2u * L.ng2);
-    L.live = L.occ + section_up(L.nocc);
-    L.total_bytes = L.live + section_up(L.ntiles);
+    Sections S;
+    L.halo = S.take(4u * L.nhalo);
+    L.g2 = S.take(2u * L.ng2);
+    L.occ = S.take(L.nocc);
+    L.live = S.take(L.ntiles);
+    L.total_bytes = S.at;
     return true;
 }
 

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void k_isl_local(const IslandsArgs A, uint32_t
 {
     __shared__ uint32_t lp[kIslTileVoxels];
     __shared__ uint32_t rows[kIslTileRows];
-    const uint32_t b = blockIdx.x + blockIdx.y * gridDim.x;
+    const uint32_t b = (uint32_t)flat_block();
     if (b >= ntiles)
         return;
     const uint32_t tx = b % ntx, t = b / ntx, ty = t % nty, tz = t / nty;
@@ -52,24 +52,11 @@ __global__ __launch_bounds__(256) void k_isl_local(const IslandsArgs A, uint32_t
 
 __global__ __launch_bounds__(256) void k_isl_merge(const IslandsArgs A)
 {
-    const uint64_t wi = ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint64_t wi = flat_thread();
     if (wi >= A.nbits)
         return;
     const uint32_t xw = (uint32_t)(wi % A.wpr), row = (uint32_t)(wi / A.wpr);
     isl_merge_word(A, xw, row % (uint32_t)A.d[1], row / (uint32_t)A.d[1]);
-}
-
-__device__ inline int32_t wave_min(int32_t v)
-{
-    for (int m = 32; m; m >>= 1)
-        v = min(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ inline int32_t wave_max(int32_t v)
-{
-    for (int m = 32; m; m >>= 1)
-        v = max(v, __shfl_xor(v, m, 64));
-    return v;
 }
 
 // one wave per 64 consecutive voxel indices per step (grid-stride): the root words are the waves' ballots
@@ -262,36 +249,14 @@ hipError_t find_islands(const CollideWorld& W, const int32_t o[3], const int32_t
     IslandsLayout L;
     if (!islands_layout(d, L))
         return hipErrorInvalidValue;
-    uint32_t* ws = (uint32_t*)work;
     IslandsArgs A{};
-    A.bits = ws + L.bits;
-    A.parent = ws + L.parent;
-    A.roots = ws + L.roots;
-    A.anchor = ws + L.anchor;
-    A.prefix = ws + L.prefix;
-    A.blocks = ws + L.blocks;
-    A.floating = floating;
-    A.labels = labels;
-    A.table = max_islands ? (int32_t*)table : nullptr;
-    A.summary = (uint32_t*)summary;
-    A.max_islands = max_islands;
-    A.anchors = anchors;
-    for (int k = 0; k < 3; ++k) {
-        A.d[k] = d[k];
-        A.o[k] = o[k];
-    }
-    A.wpr = L.wpr;
-    A.nvox = L.nvox;
-    A.nwords = L.nwords;
-    A.nblocks = L.nblocks;
-    A.nbits = L.nbits;
-
+    islands_args(A, L, o, d, anchors, work, floating, labels, (int32_t*)table, max_islands, (uint32_t*)summary);
     hipError_t e;
     if ((e = hipMemsetAsync(A.anchor, 0, (size_t)L.nwords * 4u, stream)) != hipSuccess)
         return e;
     if ((e = hipMemsetAsync(summary, 0, sizeof(vxrt_island_summary), stream)) != hipSuccess)
         return e;
-    if ((e = read_region(W, o, d, ws + L.bits, stream)) != hipSuccess)
+    if ((e = read_region(W, o, d, (uint32_t*)work + L.bits, stream)) != hipSuccess)
         return e;
     const uint32_t ntx = L.wpr, nty = ((uint32_t)d[1] + kIslTileY - 1) / kIslTileY, ntz = ((uint32_t)d[2] + kIslTileZ - 1) / kIslTileZ;
     const uint64_t ntiles = (uint64_t)ntx * nty * ntz;  // <= 2^28

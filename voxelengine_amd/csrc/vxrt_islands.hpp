@@ -45,23 +45,21 @@ struct IslandsLayout {
 
 inline bool islands_layout(const int32_t d[3], IslandsLayout& L)
 {
-    if (d[0] < 1 || d[1] < 1 || d[2] < 1)
+    L.nvox = (uint32_t)box_voxels(d, kIslMaxVoxels);
+    if (L.nvox == 0)
         return false;
-    const uint64_t v01 = (uint64_t)d[0] * (uint64_t)d[1];
-    if (v01 > kIslMaxVoxels || (uint64_t)d[2] > kIslMaxVoxels / v01)
-        return false;
-    L.nvox = (uint32_t)(v01 * (uint64_t)d[2]);
-    L.wpr = (uint32_t)(((uint64_t)d[0] + 31u) >> 5);
-    L.nbits = (uint64_t)L.wpr * (uint64_t)d[1] * (uint64_t)d[2];
+    L.wpr = (uint32_t)region_words_per_row(d[0]);
+    L.nbits = region_words(d);
     L.nwords = (uint32_t)((((uint64_t)L.nvox + 63u) >> 6) << 1);
     L.nblocks = (L.nwords + kIslScanBlock - 1) / kIslScanBlock;
-    L.bits = 0;
-    L.parent = section_up(L.nbits, 4);
-    L.roots = L.parent + section_up(L.nvox, 4);
-    L.anchor = L.roots + section_up(L.nwords, 4);
-    L.prefix = L.anchor + section_up(L.nwords, 4);
-    L.blocks = L.prefix + section_up(L.nwords, 4);
-    L.total_bytes = 4u * (L.blocks + section_up(L.nblocks, 4));
+    Sections S;
+    L.bits = S.take(L.nbits, 4);
+    L.parent = S.take(L.nvox, 4);
+    L.roots = S.take(L.nwords, 4);
+    L.anchor = S.take(L.nwords, 4);
+    L.prefix = S.take(L.nwords, 4);
+    L.blocks = S.take(L.nblocks, 4);
+    L.total_bytes = 4u * S.at;
     return true;
 }
 
@@ -83,6 +81,33 @@ struct IslandsArgs {
     uint32_t wpr, nvox, nwords, nblocks;
     uint64_t nbits;
 };
+
+inline void islands_args(IslandsArgs& A, const IslandsLayout& L, const int32_t o[3], const int32_t d[3], uint32_t anchors, void* work,
+                         uint32_t* floating, uint32_t* labels, int32_t* table, uint32_t max_islands, uint32_t* summary)
+{
+    uint32_t* ws = (uint32_t*)work;
+    A.bits = ws + L.bits;
+    A.parent = ws + L.parent;
+    A.roots = ws + L.roots;
+    A.anchor = ws + L.anchor;
+    A.prefix = ws + L.prefix;
+    A.blocks = ws + L.blocks;
+    A.floating = floating;
+    A.labels = labels;
+    A.table = max_islands ? table : nullptr;
+    A.summary = summary;
+    A.max_islands = max_islands;
+    A.anchors = anchors;
+    for (int k = 0; k < 3; ++k) {
+        A.d[k] = d[k];
+        A.o[k] = o[k];
+    }
+    A.wpr = L.wpr;
+    A.nvox = L.nvox;
+    A.nwords = L.nwords;
+    A.nblocks = L.nblocks;
+    A.nbits = L.nbits;
+}
 
 // the first bit of the run of set bits of w that holds bit b (bit b set): one past the highest clear bit below b
 __host__ __device__ inline int isl_run_start(uint32_t w, int b)

@@ -30,11 +30,6 @@ static_assert(offsetof(vxrt_light_summary, sum_sky) == 4u * kLightSumSum, "light
 static_assert(offsetof(vxrt_light_summary, emitters_used) == 4u * kLightSumUsed, "light summary layout");
 static_assert(VXRT_LIGHT_MAX == kLightMax && VXRT_LIGHT_MAX_EMITTERS == kLightMaxEmitters, "light limits");
 
-__device__ inline uint64_t flat_thread()
-{
-    return ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
-}
-
 __global__ __launch_bounds__(256) void k_light_above(const LightArgs A, const CollideWorld W, int64_t first, uint64_t n)
 {
     const uint64_t i = flat_thread();
@@ -127,9 +122,7 @@ hipError_t light_field(const CollideWorld& W, const int32_t o[3], const int32_t 
     hipError_t e;
     if ((e = hipMemsetAsync(summary, 0, sizeof(vxrt_light_summary), stream)) != hipSuccess)
         return e;
-    const int32_t h = (int32_t)kLightHalo;
-    const int32_t ho[3] = {o[0] - h, o[1] - h, o[2] - h}, hd[3] = {d[0] + 2 * h, d[1] + 2 * h, d[2] + 2 * h};
-    if ((e = read_region(W, ho, hd, A.empty, stream)) != hipSuccess)
+    if ((e = read_region(W, L.ho, L.hd, A.empty, stream)) != hipSuccess)
         return e;
     const dim3 wg(256);
     if (A.sky < 2u) {

@@ -42,54 +42,35 @@ enum {
 
 // the workspace: sections of bytes, each on a 256-byte boundary (include/vxrt.h states the same formula).  Channel slot 0
 // is the sky channel when it is requested, else the block channel.
-struct LightLayout {
+struct LightLayout : HaloBox {  // the halo box (vxrt_region.hpp): B grown by H
     uint64_t empty, above, set[2][2], level[2], rec;  // byte offsets (set[slot][turn], level[slot]: four planes)
     uint64_t total_bytes;
-    uint64_t np, nabove;  // words of a plane, of the blocked-above mask
-    uint32_t wh, hy, hz;  // words per halo row, halo rows, halo slices
+    uint64_t np, nabove;  // words of a plane (= nhalo), of the blocked-above mask
     uint32_t nvox, nch;   // voxels of B, channels requested
 };
 
-// false outside the contract: channels, dims, the halo box within a region read and, when `o` is given, within int32
+// false outside the contract (L.fault: why): channels, dims, the halo box within a region read and, when `o` is given,
+// within int32
 inline bool light_layout(const int32_t* o, const int32_t d[3], uint32_t channels, LightLayout& L)
 {
-    if (channels < 1 || channels > 3 || d[0] < 1 || d[1] < 1 || d[2] < 1)
+    L.fault = channels < 1 || channels > 3 ? kBoxDims : halo_box(o, d, (int32_t)kLightHalo, kLightMaxVoxels, L);
+    if (L.fault != kBoxOk)
         return false;
-    const uint64_t v01 = (uint64_t)d[0] * (uint64_t)d[1];
-    if (v01 > kLightMaxVoxels || (uint64_t)d[2] > kLightMaxVoxels / v01)
-        return false;
-    const int64_t H = kLightHalo;
-    int32_t hd[3];
-    for (int k = 0; k < 3; ++k) {
-        hd[k] = d[k] + 2 * (int32_t)H;  // at most 2^28 + 28
-        if (o && ((int64_t)o[k] - H < INT32_MIN || (int64_t)o[k] + d[k] + H > INT32_MAX))
-            return false;
-    }
-    L.np = region_words(hd);
-    if (L.np == 0)
-        return false;
-    L.nvox = (uint32_t)(v01 * (uint64_t)d[2]);
-    L.wh = (uint32_t)region_words_per_row(hd[0]);
-    L.hy = (uint32_t)hd[1];
-    L.hz = (uint32_t)hd[2];
+    L.np = L.nhalo;
+    L.nvox = (uint32_t)box_voxels(d, kLightMaxVoxels);
     L.nabove = (uint64_t)L.wh * L.hz;
     L.nch = (channels & kLightSky ? 1u : 0u) + (channels & kLightBlock ? 1u : 0u);
-    const uint64_t plane = section_up(4u * L.np);
-    uint64_t at = 0;
-    L.empty = at;
-    at += plane;
-    L.above = at;
-    at += (channels & kLightSky) ? section_up(4u * L.nabove) : 0u;
+    Sections S;  // (a section that is not requested takes nothing and shares the next one's offset)
+    L.empty = S.take(4u * L.np);
+    L.above = S.take((channels & kLightSky) ? 4u * L.nabove : 0u);
     for (uint32_t c = 0; c < 2; ++c) {
-        const bool on = c < L.nch;
-        L.set[c][0] = at;
-        L.set[c][1] = at + (on ? plane : 0u);
-        L.level[c] = at + (on ? 2u * plane : 0u);
-        at += on ? 6u * plane : 0u;
+        const uint64_t plane = c < L.nch ? section_up(4u * L.np) : 0u;
+        L.set[c][0] = S.take(plane);
+        L.set[c][1] = S.take(plane);
+        L.level[c] = S.take(4u * plane);
     }
-    L.rec = at;
-    at += (channels & kLightBlock) ? 8u * (uint64_t)kLightMaxEmitters : 0u;
-    L.total_bytes = at;
+    L.rec = S.take((channels & kLightBlock) ? 8u * (uint64_t)kLightMaxEmitters : 0u);
+    L.total_bytes = S.at;
     return true;
 }
 

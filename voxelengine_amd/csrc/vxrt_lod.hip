@@ -27,15 +27,6 @@ namespace vxrt {
 static_assert(sizeof(vxrt_lod_summary) == 32, "lod summary layout");
 static_assert(offsetof(vxrt_lod_summary, set) == 8 && offsetof(vxrt_lod_summary, max_count) == 24, "lod summary layout");
 
-__device__ inline uint32_t wave_max(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // the workgroup's tallies into the summary; every thread of the workgroup calls it
 __device__ inline void lod_commit(const LodArgs& A, const LodTally& t)
 {
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void k_lod_reduce(const LodArgs A)
 {
     __shared__ uint32_t part[SPLIT ? 3 : 1][64][2];
     constexpr uint32_t f = 1u << SH;
-    const uint32_t b = blockIdx.x + blockIdx.y * gridDim.x;
+    const uint32_t b = (uint32_t)flat_block();
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t iters = SPLIT ? 1u : A.iters, group = lod_group(A);  // SPLIT: one task, so one barrier per launch
     LodTally t{};

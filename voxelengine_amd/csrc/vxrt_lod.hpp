@@ -38,6 +38,7 @@ enum { kLodSrc, kLodBits, kLodCounts, kLodArrays };
 // the workspace (include/vxrt.h states the same formula) and the launch shape
 struct LodLayout {
     uint64_t total_bytes;
+    BoxFault fault;      // what lod_layout returned false for
     uint64_t nsrc;       // source words
     int32_t S[3];        // the source box
     uint32_t wps, wpo;   // words per source row, per output row
@@ -47,9 +48,10 @@ struct LodLayout {
     uint32_t iters;      // tasks one wave takes in turn, so that a lane loads about 64 words: 16, 4, 1, 1, 1 by shift
 };
 
-// false outside the contract: the shift, the dims and the source box and, when `o` is given, the origin
+// false outside the contract (L.fault: why): the shift, the dims and the source box and, when `o` is given, the origin
 inline bool lod_layout(const int32_t* o, const int32_t d[3], uint32_t shift, LodLayout& L)
 {
+    L.fault = kBoxDims;
     if (shift < 1u || shift > kLodMaxShift)
         return false;
     uint64_t vox = 1u;
@@ -62,9 +64,11 @@ inline bool lod_layout(const int32_t* o, const int32_t d[3], uint32_t shift, Lod
         vox *= s;  // <= 2^32
         L.S[k] = (int32_t)s;
     }
+    L.fault = kBoxOrigin;
     for (int k = 0; k < 3; ++k)
         if (o && (int64_t)o[k] + L.S[k] > INT32_MAX)
             return false;
+    L.fault = kBoxOk;
     L.nsrc = region_words(L.S);
     L.wps = (uint32_t)region_words_per_row(L.S[0]);
     L.wpo = (uint32_t)region_words_per_row(d[0]);

@@ -44,7 +44,7 @@ __device__ inline void nav_split(uint64_t i, uint32_t a, uint32_t b, uint32_t& x
 
 __global__ __launch_bounds__(256) void k_nav_xpass(const NavArgs A, uint64_t n)
 {
-    const uint64_t i = ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint64_t i = flat_thread();
     if (i >= n)
         return;
     uint32_t xw, y, z;
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_nav_xpass(const NavArgs A, uint64_t n)
 
 __global__ __launch_bounds__(256) void k_nav_ypass(const NavArgs A, uint64_t n)
 {
-    const uint64_t i = ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint64_t i = flat_thread();
     if (i >= n)
         return;
     uint32_t xw, y, z;
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_nav_level(const NavArgs A, uint32_t lv)
 
 __global__ __launch_bounds__(256) void k_nav_next(const NavArgs A)
 {
-    const uint64_t i = ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint64_t i = flat_thread();
     if (i >= A.nvox)
         return;
     uint32_t x, y, z;
@@ -175,44 +175,8 @@ hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[
     NavLayout L;
     if (!nav_layout(d, ag.width, ag.height, ag.climb, ag.drop, L))
         return hipErrorInvalidValue;
-    uint32_t* ws = (uint32_t*)work;
     NavArgs A{};
-    A.halo = ws + L.halo;
-    A.ex = ws + L.ex;
-    A.dx = ws + L.dx;
-    A.fy = ws + L.fy;
-    A.free = ws + L.free;
-    A.walk = walkable;
-    A.vis = ws + L.vis;
-    A.front[0] = ws + L.front[0];
-    A.front[1] = ws + L.front[1];
-    A.dist = dist ? dist : ws + L.dist;
-    A.stamp = ws + L.stamp;
-    A.mark = ws + L.mark;
-    A.list = ws + L.list;
-    A.ctrl = ws + L.ctrl;
-    A.next = next;
-    A.summary = (uint32_t*)summary;
-    A.goals = goals;
-    A.ngoals = ngoals;
-    for (int k = 0; k < 3; ++k) {
-        A.o[k] = o[k];
-        A.d[k] = d[k];
-    }
-    A.w = ag.width;
-    A.h = ag.height;
-    A.climb = ag.climb;
-    A.drop = ag.drop;
-    A.wb = L.wb;
-    A.wh = L.wh;
-    A.hy = L.hy;
-    A.hz = L.hz;
-    A.nvox = L.nvox;
-    A.nty = L.nty;
-    A.ntz = L.ntz;
-    A.ntiles = L.ntiles;
-    A.nb = L.nb;
-
+    nav_args(A, L, o, d, ag.width, ag.height, ag.climb, ag.drop, goals, ngoals, work, walkable, next, dist, (uint32_t*)summary);
     hipError_t e;
     if ((e = hipMemsetAsync(summary, 0, sizeof(vxrt_nav_summary), stream)) != hipSuccess ||
         (e = hipMemsetAsync(A.ctrl, 0, kNavCtrlWords * 4u, stream)) != hipSuccess ||
@@ -226,12 +190,12 @@ hipError_t nav_field(const CollideWorld& W, const int32_t o[3], const int32_t d[
     const int64_t hlo = (int64_t)o[1] - 1, hhi[3] = {(int64_t)o[0] + d[0] + ag.width - 1, (int64_t)o[1] + d[1] + ag.height - 1,
                                                     (int64_t)o[2] + d[2] + ag.width - 1};
     if (hlo < INT32_MIN || hhi[0] > INT32_MAX || hhi[1] > INT32_MAX || hhi[2] > INT32_MAX) {
-        if ((e = hipMemsetAsync(ws + L.halo, 0, (size_t)L.wh * L.hy * L.hz * 4u, stream)) != hipSuccess)
+        if ((e = hipMemsetAsync((uint32_t*)work + L.halo, 0, (size_t)L.wh * L.hy * L.hz * 4u, stream)) != hipSuccess)
             return e;
     } else {
         const int32_t ho[3] = {o[0], (int32_t)hlo, o[2]};
         const int32_t hd[3] = {d[0] + ag.width - 1, (int32_t)L.hy, (int32_t)L.hz};
-        if ((e = read_region(W, ho, hd, ws + L.halo, stream)) != hipSuccess)
+        if ((e = read_region(W, ho, hd, (uint32_t*)work + L.halo, stream)) != hipSuccess)
             return e;
     }
     const uint64_t nx = (uint64_t)L.wb * L.hy * L.hz, ny = (uint64_t)L.wb * (uint64_t)d[1] * L.hz;

@@ -39,7 +39,7 @@ constexpr uint32_t kNavUnreached = 0xFFFFFFFFu;
 constexpr uint8_t kNavNone = 0xFF;
 constexpr int kNavTileY = 16, kNavTileZ = 16;  // a tile is 32 x 16 x 16 cells: 256 region words
 constexpr uint32_t kNavSlots = 3;              // tile lists in rotation
-constexpr uint32_t kNavCtrlWords = 64;
+constexpr uint32_t kNavCtrlWords = 64;  // (a whole section: 256 bytes)
 enum { kNavHalo, kNavEx, kNavDx, kNavFy, kNavFree, kNavWalk, kNavVis, kNavFront, kNavDist, kNavStamp, kNavMark, kNavList,
        kNavCtrl, kNavNext, kNavGoals, kNavCells, kNavLengths };
 // summary words (vxrt_nav_summary)
@@ -64,13 +64,10 @@ struct NavLayout {
 
 inline bool nav_layout(const int32_t d[3], int32_t w, int32_t h, int32_t climb, int32_t drop, NavLayout& L)
 {
-    if (d[0] < 1 || d[1] < 1 || d[2] < 1 || !nav_agent_ok(w, h, climb, drop))
+    L.nvox = (uint32_t)box_voxels(d, kNavMaxCells);
+    if (L.nvox == 0 || !nav_agent_ok(w, h, climb, drop))
         return false;
-    const uint64_t v01 = (uint64_t)d[0] * (uint64_t)d[1];
-    if (v01 > kNavMaxCells || (uint64_t)d[2] > kNavMaxCells / v01)
-        return false;
-    L.nvox = (uint32_t)(v01 * (uint64_t)d[2]);
-    L.wb = (uint32_t)(((uint64_t)d[0] + 31u) >> 5);
+    L.wb = (uint32_t)region_words_per_row(d[0]);
     L.wh = (uint32_t)(((uint64_t)d[0] + (uint64_t)w - 1u + 31u) >> 5);
     L.hy = (uint32_t)d[1] + (uint32_t)h;
     L.hz = (uint32_t)d[2] + (uint32_t)w - 1u;
@@ -78,20 +75,21 @@ inline bool nav_layout(const int32_t d[3], int32_t w, int32_t h, int32_t climb, 
     L.nty = ((uint32_t)d[1] + kNavTileY - 1) / kNavTileY;
     L.ntz = ((uint32_t)d[2] + kNavTileZ - 1) / kNavTileZ;
     L.ntiles = L.wb * L.nty * L.ntz;  // <= 2^23
-    L.halo = 0;
-    L.ex = section_up((uint64_t)L.wh * L.hy * L.hz, 4);
-    L.dx = L.ex + section_up((uint64_t)L.wb * L.hy * L.hz, 4);
-    L.fy = L.dx + section_up((uint64_t)L.wb * (uint64_t)d[1] * L.hz, 4);
-    L.free = L.fy + section_up((uint64_t)L.wb * (uint64_t)d[1] * L.hz, 4);
-    L.vis = L.free + section_up(L.nb, 4);
-    L.front[0] = L.vis + section_up(L.nb, 4);
-    L.front[1] = L.front[0] + section_up(L.nb, 4);
-    L.dist = L.front[1] + section_up(L.nb, 4);
-    L.stamp = L.dist + section_up(L.nvox, 4);
+    Sections S;
+    L.halo = S.take((uint64_t)L.wh * L.hy * L.hz, 4);
+    L.ex = S.take((uint64_t)L.wb * L.hy * L.hz, 4);
+    L.dx = S.take((uint64_t)L.wb * (uint64_t)d[1] * L.hz, 4);
+    L.fy = S.take((uint64_t)L.wb * (uint64_t)d[1] * L.hz, 4);
+    L.free = S.take(L.nb, 4);
+    L.vis = S.take(L.nb, 4);
+    L.front[0] = S.take(L.nb, 4);
+    L.front[1] = S.take(L.nb, 4);
+    L.dist = S.take(L.nvox, 4);
+    L.stamp = S.take(6u * (uint64_t)L.ntiles, 4);  // stamp, mark and list packed into one section
     L.mark = L.stamp + 2u * (uint64_t)L.ntiles;
     L.list = L.mark + L.ntiles;
-    L.ctrl = L.stamp + section_up(6u * (uint64_t)L.ntiles, 4);
-    L.total_bytes = 4u * (L.ctrl + kNavCtrlWords);
+    L.ctrl = S.take(kNavCtrlWords, 4);
+    L.total_bytes = 4u * S.at;
     return true;
 }
 
@@ -119,6 +117,49 @@ struct NavArgs {
     uint32_t wb, wh, hy, hz, nvox, nty, ntz, ntiles;
     uint64_t nb;
 };
+
+// dist: the caller's per-cell output, or NULL for the workspace's
+inline void nav_args(NavArgs& A, const NavLayout& L, const int32_t o[3], const int32_t d[3], int32_t w, int32_t h, int32_t climb,
+                     int32_t drop, const int32_t* goals, uint32_t ngoals, void* work, uint32_t* walkable, uint8_t* next, uint32_t* dist,
+                     uint32_t* summary)
+{
+    uint32_t* ws = (uint32_t*)work;
+    A.halo = ws + L.halo;
+    A.ex = ws + L.ex;
+    A.dx = ws + L.dx;
+    A.fy = ws + L.fy;
+    A.free = ws + L.free;
+    A.walk = walkable;
+    A.vis = ws + L.vis;
+    A.front[0] = ws + L.front[0];
+    A.front[1] = ws + L.front[1];
+    A.dist = dist ? dist : ws + L.dist;
+    A.stamp = ws + L.stamp;
+    A.mark = ws + L.mark;
+    A.list = ws + L.list;
+    A.ctrl = ws + L.ctrl;
+    A.next = next;
+    A.summary = summary;
+    A.goals = goals;
+    A.ngoals = ngoals;
+    for (int k = 0; k < 3; ++k) {
+        A.o[k] = o[k];
+        A.d[k] = d[k];
+    }
+    A.w = w;
+    A.h = h;
+    A.climb = climb;
+    A.drop = drop;
+    A.wb = L.wb;
+    A.wh = L.wh;
+    A.hy = L.hy;
+    A.hz = L.hz;
+    A.nvox = L.nvox;
+    A.nty = L.nty;
+    A.ntz = L.ntz;
+    A.ntiles = L.ntiles;
+    A.nb = L.nb;
+}
 
 __host__ __device__ inline uint64_t nav_word(const NavArgs& A, uint32_t xw, uint32_t y, uint32_t z)
 {

@@ -30,14 +30,14 @@ __global__ __launch_bounds__(256) void k_place_init(const PlaceArgs A)
 // one lane per (task, row): the grid holds every lane of the launch (grid_2d), so the task loop of a lane is one step
 __global__ __launch_bounds__(256) void k_place_sweep(const PlaceArgs A, uint64_t n_tasks, uint32_t lg_lanes)
 {
-    const uint64_t t = (((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x) >> lg_lanes;
+    const uint64_t t = flat_thread() >> lg_lanes;
     if (t < n_tasks)
         place_sweep(A, t, threadIdx.x & (A.lanes - 1u));
 }
 
 __global__ __launch_bounds__(256) void k_place_contact(const PlaceArgs A, uint64_t n_tasks, uint32_t lg_lanes)
 {
-    const uint64_t t = (((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x) >> lg_lanes;
+    const uint64_t t = flat_thread() >> lg_lanes;
     if (t < n_tasks)
         place_contact(A, t, threadIdx.x & (A.lanes - 1u));
 }

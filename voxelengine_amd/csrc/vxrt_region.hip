@@ -188,7 +188,7 @@ hipError_t read_region(const CollideWorld& W, const int32_t o[3], const int32_t 
         A.d[k] = d[k];
     }
     A.wpr = (uint32_t)region_words_per_row(d[0]);
-    A.pad_mask = (d[0] & 31) ? (1u << (d[0] & 31)) - 1u : 0xFFFFFFFFu;
+    A.pad_mask = row_last_mask(d[0]);
     A.lgL = 0;
     while ((1u << A.lgL) < A.wpr && A.lgL < 6)
         ++A.lgL;

@@ -2,8 +2,13 @@
 // shared by the kernels of vxrt_region.hip, the host side in vxrt_api_query.hip and the host harnesses of the tests
 // (tests/tools/*_check.cpp, through tests/tools/hoststub): the brick row, the 32-voxel row gather of a read, the
 // funnel-shifted gather of a stamp's bits, the per-row stamp step, the per-brick stamp filter and stamp validation.
-// Every world query (edits, reads, collision, islands, navigation) reads the world through this layer, so it also holds
-// what they share: the world as a query reads it, the 2-D launch grid, workspace sections, the wave sum and the atomics.
+// Every world query (edits, reads, collision, islands, navigation, distance, surface, LOD, light, rules) reads the world
+// through this layer, so it also holds what they share:
+//   host (also under VXRT_HOST_CHECK)  the world as a query reads it; workspace sections and their cursor (Sections); the box
+//                                      contract of a query (box_voxels) and of its halo (halo_box, HaloBox, BoxFault); the
+//                                      mask of a bit row's last word (row_last_mask)
+//   device                             the 2-D launch grid with its flat ids (grid_2d, flat_block, flat_thread), the wave
+//                                      sum, min and max, and the atomics
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -48,13 +53,28 @@ inline uint64_t section_up(uint64_t n, uint64_t unit = 1)
     return (n + a - 1u) / a * a;
 }
 
+// the sections of a workspace in turn: take() returns the offset of the next one and moves past it.  Offsets count units of
+// `unit` bytes (one layout, one unit)
+struct Sections {
+    uint64_t at = 0;
+    uint64_t take(uint64_t n, uint64_t unit = 1)
+    {
+        const uint64_t o = at;
+        at += section_up(n, unit);
+        return o;
+    }
+};
+
 #ifndef VXRT_HOST_CHECK
-// more workgroups than one grid axis holds: x up to 2^20, the rest in y (the kernels flatten blockIdx.x + blockIdx.y * gridDim.x)
+// more workgroups than one grid axis holds: x up to 2^20, the rest in y (the kernels flatten it again: flat_block)
 inline dim3 grid_2d(uint64_t blocks)
 {
     const unsigned gx = blocks > (1u << 20) ? (1u << 20) : (unsigned)(blocks ? blocks : 1);
     return dim3(gx, (unsigned)((blocks + gx - 1) / gx));
 }
+// the workgroup's number in a grid_2d launch, and the lane's with 256-lane workgroups
+__device__ inline uint64_t flat_block() { return (uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x; }
+__device__ inline uint64_t flat_thread() { return flat_block() * 256u + threadIdx.x; }
 
 // k_read_region of the box o, d into `out` (region layout); vxrt_region.hip
 hipError_t read_region(const CollideWorld& W, const int32_t o[3], const int32_t d[3], uint32_t* out, hipStream_t stream);
@@ -66,6 +86,30 @@ __device__ inline uint32_t wave_sum(uint32_t v)
 {
     for (int m = 32; m; m >>= 1)
         v += (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+__device__ inline uint32_t wave_max(uint32_t v)
+{
+    for (int m = 32; m; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+__device__ inline int32_t wave_min(int32_t v)
+{
+    for (int m = 32; m; m >>= 1) {
+        const int32_t o = __shfl_xor(v, m, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ inline int32_t wave_max(int32_t v)
+{
+    for (int m = 32; m; m >>= 1) {
+        const int32_t o = __shfl_xor(v, m, 64);
+        v = o > v ? o : v;
+    }
     return v;
 }
 #endif
@@ -129,16 +173,61 @@ struct StampDev {
     int32_t mode, pad_;    // vxrt_stamp_mode
 };
 
-// words of a region row, and of a region; 0 for dims outside the contract
-__host__ __device__ inline uint64_t region_words_per_row(int32_t d0) { return ((uint64_t)d0 + 31u) >> 5; }
-inline uint64_t region_words(const int32_t d[3])
+// the voxels of a box of dims d; 0 outside the contract: each dim at least 1, at most max_voxels (below 2^62) in all
+inline uint64_t box_voxels(const int32_t d[3], uint64_t max_voxels)
 {
     if (d[0] < 1 || d[1] < 1 || d[2] < 1)
         return 0;
     const uint64_t v01 = (uint64_t)d[0] * (uint64_t)d[1];  // < 2^62
-    if (v01 > kRegionMaxVoxels || (uint64_t)d[2] > kRegionMaxVoxels / v01)
+    if (v01 > max_voxels || (uint64_t)d[2] > max_voxels / v01)
         return 0;
-    return region_words_per_row(d[0]) * (uint64_t)d[1] * (uint64_t)d[2];
+    return v01 * (uint64_t)d[2];
+}
+
+// words of a region row, and of a region; 0 for dims outside the contract
+__host__ __device__ inline uint64_t region_words_per_row(int32_t d0) { return ((uint64_t)d0 + 31u) >> 5; }
+inline uint64_t region_words(const int32_t d[3])
+{
+    return box_voxels(d, kRegionMaxVoxels) ? region_words_per_row(d[0]) * (uint64_t)d[1] * (uint64_t)d[2] : 0;
+}
+// the bits of the last word of a region row of d0 voxels that are voxels (the rest is padding, kept 0)
+__host__ __device__ inline uint32_t row_last_mask(int32_t d0) { return (d0 & 31) ? (1u << (d0 & 31)) - 1u : 0xFFFFFFFFu; }
+
+// ---- the halo box of a query ----------------------------------------------------------------------------------------------
+// why a box is refused: its dims (or its family's own limits), or where its origin puts it
+enum BoxFault { kBoxOk = 0, kBoxDims, kBoxOrigin };
+
+// The box o, d grown by h voxels on every side, as a region read holds it: the base of a family's layout.
+struct HaloBox {
+    BoxFault fault;        // set by the family's layout: what it returned false for
+    int32_t ho[3], hd[3];  // origin (only when an origin was given) and dims of the halo box
+    uint64_t nhalo;        // its region words
+    uint32_t wh, hy, hz;   // words per halo row, halo rows, halo slices
+};
+
+// Fills H (but for H.fault) for 0 <= h < 2^16.  kBoxDims: d outside box_voxels' contract or a halo box beyond what a region
+// read holds; kBoxOrigin (only when `o` is given, and only for dims within the contract): o - h or o + d + h beyond int32.
+inline BoxFault halo_box(const int32_t* o, const int32_t d[3], int32_t h, uint64_t max_voxels, HaloBox& H)
+{
+    if (box_voxels(d, max_voxels) == 0)
+        return kBoxDims;
+    for (int k = 0; k < 3; ++k) {
+        if ((int64_t)d[k] + 2 * (int64_t)h > INT32_MAX)
+            return kBoxDims;
+        H.hd[k] = d[k] + 2 * h;
+    }
+    H.nhalo = region_words(H.hd);
+    if (H.nhalo == 0)
+        return kBoxDims;
+    for (int k = 0; o && k < 3; ++k) {
+        if ((int64_t)o[k] - h < INT32_MIN || (int64_t)o[k] + d[k] + h > INT32_MAX)
+            return kBoxOrigin;
+        H.ho[k] = o[k] - h;
+    }
+    H.wh = (uint32_t)region_words_per_row(H.hd[0]);
+    H.hy = (uint32_t)H.hd[1];
+    H.hz = (uint32_t)H.hd[2];
+    return kBoxOk;
 }
 
 // bits [0, f) of row (ly, lz) of a brick image (HBM order inside a brick: bit x + f * (z + f * y), a row is f bits)

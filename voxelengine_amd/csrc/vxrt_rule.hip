@@ -28,14 +28,9 @@ static_assert(VXRT_RULE_MAX_ITERATIONS == kRuleMaxIterations, "rule limits");
 static_assert(VXRT_RULE_N6 == kRuleN6 && VXRT_RULE_N18 == kRuleN18 && VXRT_RULE_N26 == kRuleN26, "rule neighbourhoods");
 static_assert(VXRT_RULE_BOX == kRuleBox && VXRT_RULE_WORLD == kRuleWorld, "rule scopes");
 
-__device__ inline uint64_t rule_flat_thread()
-{
-    return ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 256u + threadIdx.x;
-}
-
 __global__ __launch_bounds__(256) void k_rule_setup(const RuleArgs A)
 {
-    const uint64_t i = rule_flat_thread();
+    const uint64_t i = flat_thread();
     if (i < kRuleSumWords)
         A.summary[i] = rule_summary_init((uint32_t)i);
     if (i < A.np)
@@ -45,27 +40,9 @@ __global__ __launch_bounds__(256) void k_rule_setup(const RuleArgs A)
 template <int NB>
 __global__ __launch_bounds__(256) void k_rule_round(const RuleArgs A, const uint32_t* __restrict__ src, uint32_t* __restrict__ dst)
 {
-    const uint64_t i = rule_flat_thread();
+    const uint64_t i = flat_thread();
     if (i < A.np)
         rule_round_lane<NB>(A, src, dst, i);
-}
-
-__device__ inline int32_t wave_min(int32_t v)
-{
-    for (int m = 32; m; m >>= 1) {
-        const int32_t o = __shfl_xor(v, m, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ inline int32_t wave_max(int32_t v)
-{
-    for (int m = 32; m; m >>= 1) {
-        const int32_t o = __shfl_xor(v, m, 64);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(256) void k_rule_output(const RuleArgs A, const uint32_t* __restrict__ last, const uint32_t* __restrict__ prev)
@@ -130,10 +107,8 @@ hipError_t apply_rule(const CollideWorld& W, const int32_t o[3], const int32_t d
         return hipErrorInvalidValue;
     RuleArgs A{};
     rule_args(A, L, W, o, d, rule, mask, work, bits, (uint32_t*)summary);
-    const int32_t h = (int32_t)L.h;
-    const int32_t ho[3] = {o[0] - h, o[1] - h, o[2] - h}, hd[3] = {d[0] + 2 * h, d[1] + 2 * h, d[2] + 2 * h};
     hipError_t e;
-    if ((e = read_region(W, ho, hd, A.w0, stream)) != hipSuccess)
+    if ((e = read_region(W, L.ho, L.hd, A.w0, stream)) != hipSuccess)
         return e;
     const dim3 wg(256);
     hipLaunchKernelGGL(k_rule_setup, grid_2d((L.np + 255u) / 256u), wg, 0, stream, A);

@@ -70,44 +70,31 @@ inline int rule_check(const vxrt_rule& r)
 inline int32_t rule_halo(const vxrt_rule& r) { return r.scope == kRuleWorld ? r.iterations : 1; }
 
 // the workspace: four planes, each on a 256-byte boundary (include/vxrt.h states the same formula)
-struct RuleLayout {
+struct RuleLayout : HaloBox {     // the halo box (vxrt_region.hpp): B grown by h
     uint64_t w0, free, turn[2];  // byte offsets
     uint64_t total_bytes;
-    uint64_t np, nb;        // words of a plane, of d_bits
-    uint32_t wh, hy, hz;    // words per halo row, halo rows, halo slices
+    uint64_t np, nb;        // words of a plane (= nhalo), of d_bits
     uint32_t mw;            // words per row of d_bits and of the mask
     uint32_t h;
 };
 
-// false outside the contract: dims, the halo box within a region read and, when `o` is given, within int32 (h: rule_halo)
+// false outside the contract (L.fault: why): dims, the halo box within a region read and, when `o` is given, within int32
+// (h: rule_halo)
 inline bool rule_layout(const int32_t* o, const int32_t d[3], int32_t h, RuleLayout& L)
 {
-    if (h < 1 || h > kRuleMaxIterations || d[0] < 1 || d[1] < 1 || d[2] < 1)
+    L.fault = h < 1 || h > kRuleMaxIterations ? kBoxDims : halo_box(o, d, h, kRuleMaxVoxels, L);
+    if (L.fault != kBoxOk)
         return false;
-    const uint64_t v01 = (uint64_t)d[0] * (uint64_t)d[1];
-    if (v01 > kRuleMaxVoxels || (uint64_t)d[2] > kRuleMaxVoxels / v01)
-        return false;
-    int32_t hd[3];
-    for (int k = 0; k < 3; ++k) {
-        hd[k] = d[k] + 2 * h;  // at most 2^28 + 32
-        if (o && ((int64_t)o[k] - h < INT32_MIN || (int64_t)o[k] + d[k] + h > INT32_MAX))
-            return false;
-    }
-    L.np = region_words(hd);
-    if (L.np == 0)
-        return false;
+    L.np = L.nhalo;
     L.nb = region_words(d);
-    L.wh = (uint32_t)region_words_per_row(hd[0]);
-    L.hy = (uint32_t)hd[1];
-    L.hz = (uint32_t)hd[2];
     L.mw = (uint32_t)region_words_per_row(d[0]);
     L.h = (uint32_t)h;
-    const uint64_t plane = section_up(4u * L.np);
-    L.w0 = 0u;
-    L.free = plane;
-    L.turn[0] = 2u * plane;
-    L.turn[1] = 3u * plane;
-    L.total_bytes = 4u * plane;
+    Sections S;
+    L.w0 = S.take(4u * L.np);
+    L.free = S.take(4u * L.np);
+    L.turn[0] = S.take(4u * L.np);
+    L.turn[1] = S.take(4u * L.np);
+    L.total_bytes = S.at;
     return true;
 }
 

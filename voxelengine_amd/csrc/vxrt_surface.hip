@@ -51,7 +51,7 @@ __device__ inline void surf_commit(const SurfArgs& A, const SurfTally& t, uint32
 
 __global__ __launch_bounds__(256) void k_surf_count_yz(const SurfArgs A)
 {
-    const uint32_t j = (blockIdx.x + blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint32_t j = (uint32_t)flat_block() * 256u + threadIdx.x;
     SurfTally t{};
     uint32_t dir = 0u;
     if (j < A.nryz)
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_surf_count_yz(const SurfArgs A)
 // lane i: x = i % x64, z = i / x64 % dims[2], d = i / x64 / dims[2], with x64 = dims[0] rounded up to whole waves
 __global__ __launch_bounds__(256) void k_surf_count_x(const SurfArgs A, uint32_t x64)
 {
-    const uint32_t i = (blockIdx.x + blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint32_t i = (uint32_t)flat_block() * 256u + threadIdx.x;
     const uint32_t x = i % x64, q = i / x64, z = q % (uint32_t)A.d[2], d = q / (uint32_t)A.d[2];
     const bool live = d < 2u && x < (uint32_t)A.d[0];
     SurfTally t{};
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_surf_count_x(const SurfArgs A, uint32_t
 __global__ __launch_bounds__(256) void k_surf_scan(const SurfArgs A)
 {
     __shared__ uint32_t part[4];
-    const uint32_t i = (blockIdx.x + blockIdx.y * gridDim.x) * kSurfGroup + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t i = (uint32_t)flat_block() * kSurfGroup + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t count = i < A.nrows ? A.counts[i] : 0u;
     uint32_t incl = count;
     for (int s = 1; s < 64; s <<= 1) {
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_surf_groups(const SurfArgs A)
 
 __global__ __launch_bounds__(256) void k_surf_emit_yz(const SurfArgs A)
 {
-    const uint32_t j = (blockIdx.x + blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint32_t j = (uint32_t)flat_block() * 256u + threadIdx.x;
     if (j >= A.nryz)
         return;
     const uint32_t pos = surf_row_start(A, A.nrx + j);
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void k_surf_emit_yz(const SurfArgs A)
 
 __global__ __launch_bounds__(256) void k_surf_emit_x(const SurfArgs A, uint32_t x64)
 {
-    const uint32_t i = (blockIdx.x + blockIdx.y * gridDim.x) * 256u + threadIdx.x;
+    const uint32_t i = (uint32_t)flat_block() * 256u + threadIdx.x;
     const uint32_t x = i % x64, q = i / x64, z = q % (uint32_t)A.d[2], d = q / (uint32_t)A.d[2];
     if (d >= 2u || x >= (uint32_t)A.d[0])
         return;
@@ -158,8 +158,7 @@ hipError_t extract_surface(const CollideWorld& W, const int32_t o[3], const int3
     hipError_t e;
     if ((e = hipMemsetAsync(summary, 0, sizeof(vxrt_surface_summary), stream)) != hipSuccess)
         return e;
-    const int32_t ho[3] = {o[0] - 1, o[1] - 1, o[2] - 1}, hd[3] = {d[0] + 2, d[1] + 2, d[2] + 2};
-    if ((e = read_region(W, ho, hd, (uint32_t*)((char*)work + L.halo), stream)) != hipSuccess)
+    if ((e = read_region(W, L.ho, L.hd, (uint32_t*)((char*)work + L.halo), stream)) != hipSuccess)
         return e;
     const uint32_t x64 = ((uint32_t)d[0] + 63u) / 64u * 64u;
     const dim3 gyz = grid_2d((L.nryz + 255u) / 256u), gx = grid_2d((2u * (uint64_t)d[2] * x64 + 255u) / 256u);

@@ -40,39 +40,29 @@ enum { kSurfHalo, kSurfCounts, kSurfGroups, kSurfQuads, kSurfVerts, kSurfTris, k
 enum { kSurfSumSolid, kSurfSumFaces, kSurfSumQuads, kSurfSumWritten, kSurfSumFacesDir, kSurfSumQuadsDir = kSurfSumFacesDir + 6 };
 
 // the workspace: sections of bytes, each on a 256-byte boundary (include/vxrt.h states the same formula)
-struct SurfLayout {
+struct SurfLayout : HaloBox {       // the halo box (vxrt_region.hpp): B grown by 1
     uint64_t halo, counts, groups;  // byte offsets
     uint64_t total_bytes;
-    uint64_t nhalo;              // halo words
-    uint32_t wh, hy, hz;         // words per halo row, halo rows, halo slices
     uint32_t nrx, nryz, nrows;   // rows of the x directions, of the y and z directions, all
     uint32_t ngroups;
 };
 
-// false outside the contract: the dims and, when `o` is given, the halo box within int32
+// false outside the contract (L.fault: why): the dims and, when `o` is given, the halo box within int32
 inline bool surf_layout(const int32_t* o, const int32_t d[3], SurfLayout& L)
 {
-    for (int k = 0; k < 3; ++k)
-        if (d[k] < 1 || d[k] > kSurfMaxDim)
-            return false;
-    if ((uint64_t)d[0] * (uint64_t)d[1] * (uint64_t)d[2] > kSurfMaxVoxels)
+    const bool wide = d[0] > kSurfMaxDim || d[1] > kSurfMaxDim || d[2] > kSurfMaxDim;
+    L.fault = wide ? kBoxDims : halo_box(o, d, 1, kSurfMaxVoxels, L);
+    if (L.fault != kBoxOk)
         return false;
-    for (int k = 0; k < 3; ++k)
-        if (o && ((int64_t)o[k] - 1 < INT32_MIN || (int64_t)o[k] + d[k] + 1 > INT32_MAX))
-            return false;
-    const int32_t hd[3] = {d[0] + 2, d[1] + 2, d[2] + 2};
-    L.nhalo = region_words(hd);
-    L.wh = (uint32_t)region_words_per_row(hd[0]);
-    L.hy = (uint32_t)hd[1];
-    L.hz = (uint32_t)hd[2];
     L.nrx = 2u * (uint32_t)d[0] * (uint32_t)d[2];
     L.nryz = 4u * (uint32_t)d[1] * (uint32_t)d[2];
     L.nrows = L.nrx + L.nryz;
     L.ngroups = (L.nrows + kSurfGroup - 1u) / kSurfGroup;
-    L.halo = 0;
-    L.counts = section_up(4u * L.nhalo);
-    L.groups = L.counts + section_up(4u * (uint64_t)L.nrows);
-    L.total_bytes = L.groups + section_up(4u * (uint64_t)L.ngroups);
+    Sections S;
+    L.halo = S.take(4u * L.nhalo);
+    L.counts = S.take(4u * (uint64_t)L.nrows);
+    L.groups = S.take(4u * (uint64_t)L.ngroups);
+    L.total_bytes = S.at;
     return true;
 }
 

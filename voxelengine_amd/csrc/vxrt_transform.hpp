@@ -261,9 +261,6 @@ __host__ __device__ inline uint32_t tr_brev(uint32_t x)
 #endif
 }
 
-// the bits of a row's last word that are voxels
-__host__ __device__ inline uint32_t tr_row_mask(int32_t d0) { return (d0 & 31) ? (1u << (d0 & 31)) - 1u : 0xFFFFFFFFu; }
-
 // a lane's tally: the set voxels of the words it stored and their inclusive bounds in destination coordinates
 struct TrTally {
     uint32_t n;
@@ -318,7 +315,7 @@ __host__ __device__ inline void tr_copy_word(const TransformArgs& A, uint32_t w,
         VXRT_TRANSFORM_CHECK(kTrSrc, (uint64_t)base + j);
         word = A.src[(size_t)base + j];
         if (j == A.wps - 1u)
-            word &= tr_row_mask(A.sd[0]);
+            word &= row_last_mask(A.sd[0]);
     }
     VXRT_TRANSFORM_CHECK(kTrDst, w);
     A.dst[(size_t)w] = word;
@@ -368,7 +365,7 @@ __host__ __device__ inline uint32_t tr_load_word(const TransformArgs& A, const T
     const uint32_t i = ps * A.ss + T.sbase + xw;
     VXRT_TRANSFORM_CHECK(kTrSrc, i);
     const uint32_t word = A.src[(size_t)i];
-    return xw == A.wps - 1u ? word & tr_row_mask(A.sd[0]) : word;
+    return xw == A.wps - 1u ? word & row_last_mask(A.sd[0]) : word;
 }
 
 // block b of half-wave `half` (0 .. 7) in the transpose phase: destination word jl and x-word xl of the tile

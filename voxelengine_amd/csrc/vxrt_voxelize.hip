@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void k_vox_work(const VoxArgs A)
 __global__ __launch_bounds__(256) void k_vox_final(const VoxArgs A, uint64_t nrows)
 {
     const uint32_t lane = threadIdx.x & 63u, rpw = 64u / A.wpr;  // whole rows per wave, 2 or more
-    const uint64_t w = ((uint64_t)blockIdx.x + (uint64_t)blockIdx.y * gridDim.x) * 4u + (threadIdx.x >> 6);
+    const uint64_t w = flat_block() * 4u + (threadIdx.x >> 6);
     const uint32_t r = lane / A.wpr, idx = lane - r * A.wpr;
     const uint64_t row = w * rpw + r;
     const bool live = r < rpw && row < nrows;

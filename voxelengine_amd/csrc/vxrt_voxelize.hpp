@@ -76,11 +76,12 @@ inline bool vox_layout(const int32_t d[3], uint64_t n_triangles, VoxLayout& L)
     L.wpr = (uint32_t)region_words_per_row(d[0]);
     L.words = (uint64_t)L.wpr * (uint64_t)d[1] * (uint64_t)d[2];
     L.ngroups = (uint32_t)((n_triangles + kVoxGroup - 1u) / kVoxGroup);
-    L.toggle = 0;
-    L.tri_prefix = section_up(4u * L.words);
-    L.group_prefix = L.tri_prefix + section_up(4u * n_triangles);
-    L.counters = L.group_prefix + section_up(8u * (uint64_t)L.ngroups);
-    L.total_bytes = L.counters + 256u;
+    Sections S;
+    L.toggle = S.take(4u * L.words);
+    L.tri_prefix = S.take(4u * n_triangles);
+    L.group_prefix = S.take(8u * (uint64_t)L.ngroups);
+    L.counters = S.take(256u);
+    L.total_bytes = S.at;
     return true;
 }
 
