@@ -75,6 +75,11 @@
 // line "rule before frame N: before .. after .. born .. died .. changed_last .. box <lo x3> <hi x3>, ... bricks touched".
 // "frame smooth x0 y0 z0 x1 y1 z1 iterations" is the shorthand for the majority rule on the box alone
 // (VoxelRaytracer3D::SmoothVoxels), with the same line.  Both are applied in file order with the edit lines.
+// A line "frame loose sand|water x0 y0 z0 x1 y1 z1 sx0 sy0 sz0 sx1 sy1 sz1 steps wall|open" turns the solid voxels of the source
+// box (sx0, sy0, sz0) .. (sx1, sy1, sz1) loose inside the box (x0, y0, z0) .. (x1, y1, z1) (inclusive corners) and makes exactly
+// `steps` steps with them (VoxelRaytracer3D::SettleVoxels without the early stop), stamps them back and prints one line "loose
+// before frame N: in .. start .. after .. fell_last .. slid_last .. spread_last .. box <lo x3> <hi x3>, ... bricks touched" (the
+// summary of the last call of at most VXRT_LOOSE_MAX_STEPS steps).
 // "frame turn axis quarter_turns [slot=0]" and "frame mirror axis [slot=0]" re-orient the clipboard slot a copy line filled
 // (vxrt_orientation_rotation / a flip of one axis, then vxrt_transform_stamp): the slot's bits are kept on the device from the
 // first such line on, each line transforms them into a second device buffer and swaps the two, and a following paste pastes
@@ -127,7 +132,9 @@ int main(int argc, char** argv)
         int frame;
         vxrt_edit_op op;  // kind 12: a rule line (a = the box's origin, b = its dims; value 1: the smooth shorthand)
                           // kind 13 / 14: a turn / mirror line (value = the slot, a[0] = the axis, a[1] = the quarter turns)
+                          // kind 15: a loose line (a, b = the box's origin and dims; value = the material)
         vxrt_rule rule;
+        int32_t src_o[3], src_d[3], steps, edge;  // kind 15: the source box, the steps and the edge mode
     };
     std::vector<EditLine> edits;
     struct DenoiseLine {
@@ -206,6 +213,30 @@ int main(int argc, char** argv)
                     e.op.value = slot;
                     e.op.a[0] = axis;
                     e.op.a[1] = turns;
+                    edits.push_back(e);
+                    continue;
+                }
+            }
+            {
+                int c[12], steps = 0;
+                char mat[8] = "", edge[8] = "";
+                if (std::sscanf(line.c_str(), "%d loose %7s %d %d %d %d %d %d %d %d %d %d %d %d %d %7s", &e.frame, mat, &c[0], &c[1], &c[2], &c[3],
+                                &c[4], &c[5], &c[6], &c[7], &c[8], &c[9], &c[10], &c[11], &steps, edge) == 16) {
+                    const std::string m(mat), ed(edge);
+                    if ((m != "sand" && m != "water") || (ed != "wall" && ed != "open")) {
+                        std::cerr << "edit script: cannot read \"" << line << "\"" << std::endl;
+                        return 2;
+                    }
+                    e.op.kind = 15;
+                    e.op.value = m == "water" ? VXRT_LOOSE_WATER : VXRT_LOOSE_SAND;
+                    for (int k = 0; k < 3; ++k) {
+                        e.op.a[k] = c[k];
+                        e.op.b[k] = c[3 + k] - c[k] + 1;
+                        e.src_o[k] = c[6 + k];
+                        e.src_d[k] = c[9 + k] - c[6 + k] + 1;
+                    }
+                    e.steps = steps;
+                    e.edge = ed == "open" ? VXRT_LOOSE_OPEN : VXRT_LOOSE_WALL;
                     edits.push_back(e);
                     continue;
                 }
@@ -483,6 +514,18 @@ int main(int argc, char** argv)
                             "touched\n", from, sum.solid_before, sum.solid_after, sum.born, sum.died, sum.changed_last, sum.changed_min[0],
                             sum.changed_min[1], sum.changed_min[2], sum.changed_max[0], sum.changed_max[1], sum.changed_max[2],
                             (unsigned long long)st.bricks_touched);
+            } else if (e.op.kind == 15) {  // the source box's voxels turned loose, stepped and stamped back
+                flush_ops();
+                vxrt_loose_summary sum{};
+                vxrt_edit_stats st{};
+                if (raytracer->SettleVoxels(e.op.a, e.op.b, e.src_o, e.src_d, e.op.value, e.steps, e.edge, &sum, nullptr, &st, false) != VXRT_OK) {
+                    std::cerr << "loose before frame " << from << ": " << vxrt_last_error() << std::endl;
+                    std::exit(3);
+                }
+                std::printf("loose before frame %d: in %u start %u after %u fell_last %u slid_last %u spread_last %u box %d %d %d %d %d %d, "
+                            "%llu bricks touched\n", from, sum.loose_in, sum.loose_start, sum.loose_after, sum.fell_last, sum.slid_last,
+                            sum.spread_last, sum.changed_min[0], sum.changed_min[1], sum.changed_min[2], sum.changed_max[0],
+                            sum.changed_max[1], sum.changed_max[2], (unsigned long long)st.bricks_touched);
             } else if (e.op.kind == 11) {  // drop the islands
                 flush_ops();
                 std::vector<VoxelRaytracer3D::DroppedIsland> rows;

@@ -39,6 +39,8 @@ struct vxrt_lod_summary;
 struct vxrt_light_summary;
 struct vxrt_rule;
 struct vxrt_rule_summary;
+struct vxrt_loose;
+struct vxrt_loose_summary;
 
 constexpr auto FLT_EPS_DDA = 1e-6;  // VolumeRaytracer.cuh:20 (a double)
 constexpr auto FLT_INF = std::numeric_limits<float>::infinity();
@@ -248,6 +250,20 @@ public:
     // then one StampVoxels of the result in VXRT_STAMP_REPLACE: the box is smoothed in place.  Returns the vxrt_status.
     int SmoothVoxels(const int32_t origin[3], const int32_t dims[3], int32_t iterations = 1, vxrt_edit_stats* stats = nullptr,
                      vxrt_rule_summary* summary = nullptr);
+
+    // loose voxels (extension, include/vxrt.h, vxrt_loose_step_host): the loose layer `loose` (region words of `dims`) of the
+    // box origin .. origin + dims - 1 advanced by params.steps steps of falling, sliding and (water) spreading over the
+    // world's solids, in place, and the summary; the world is not changed.  Flushes queued edits first.  Returns the
+    // vxrt_status.
+    int StepLoose(const int32_t origin[3], const int32_t dims[3], const vxrt_loose& params, std::vector<uint32_t>& loose,
+                  vxrt_loose_summary& summary);
+    // The solid voxels of the source box, which must lie inside the box, turned loose and settled: lifted out of the world
+    // (VXRT_STAMP_SUBTRACT), stepped with StepLoose in calls of at most VXRT_LOOSE_MAX_STEPS steps with the phase carried
+    // until a call's last step neither drops nor slides a voxel (`early_stop`) or max_steps steps are made, and stamped back
+    // with VXRT_STAMP_UNION.  *steps: the steps made.  Returns the vxrt_status.
+    int SettleVoxels(const int32_t origin[3], const int32_t dims[3], const int32_t source_origin[3], const int32_t source_dims[3],
+                     int32_t material, int32_t max_steps, int32_t edge, vxrt_loose_summary* summary = nullptr,
+                     int32_t* steps = nullptr, vxrt_edit_stats* stats = nullptr, bool early_stop = true);
 
 private:
     void Flush();

@@ -926,6 +926,78 @@ int vxrt_apply_rule(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3
 int vxrt_apply_rule_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_rule *rule,
                          const uint32_t *mask_or_null, uint32_t *bits, vxrt_rule_summary *summary);
 
+/* ---- loose voxels -- an EXTENSION: a layer of sand or water that falls, slides and spreads over the world's solids.  The
+ * neighbour-count rules above have no "down"; this is the directional step rule that conserves mass.  A call looks at one
+ * box B = [origin, origin + dims) of world voxels and changes nothing in the world.
+ *   Loose layer.  The loose material is a second bit volume that the caller owns, in B's region layout
+ *     (vxrt_region_words(dims) words; its padding bits are ignored).  The call advances it by `steps` steps against the
+ *     world's solids and returns the new layer in the same layout: directly usable as a stamp at `origin`.
+ *   Gravity is -y (the world is Y-up).  Every coordinate below is a world coordinate, so a result does not depend on where
+ *     the box was cut.
+ *   Sets.  W = the world's solid bits.  Live = B intersected with the world.  Under VXRT_LOOSE_WALL a voxel outside Live is
+ *     BLOCKED.  Under VXRT_LOOSE_OPEN a voxel outside Live is blocked where W is 1 and a SINK where W is 0 (outside the world
+ *     W reads 0, as in vxrt_read_region): material that moves into a sink disappears.  A Live voxel is blocked where W is 1.
+ *     For a layer L, free(v) = v is not blocked and v is not in L; a sink is always free.  L_start = the input's valid bits
+ *     that are Live and not solid: bits on solids, outside the world or in padding are dropped.
+ *   Step t = phase + i (mod 2^32), i = 0 .. steps - 1.  A step is two passes for sand and three for water, strictly one
+ *     after the other, each evaluated on the layer the pass before left; all moves of a pass are simultaneous.
+ *     1. FALL.  Every v in L with free(v - e_y) moves to v - e_y.
+ *     2. SLIDE.  a = t & 1 (0: the x axis, 1: the z axis).  For v = (x, y, z), c = z when a = 0 and c = x when a = 1,
+ *        s = (c + y + (t >> 1)) & 1, and d(v) = +e_a if s = 0, else -e_a.  Every v in L that is resting (not free(v - e_y))
+ *        with free(v + d) and free(v + d - e_y) moves to v + d - e_y.
+ *     3. SPREAD (VXRT_LOOSE_WATER only).  With the same d(v), every resting v in L with free(v + d) moves to v + d.
+ *     A mover whose target is a sink is removed.  Within a pass two movers never share a target: two sources of one target
+ *     lie on one axis line with the same y and the same c, hence have the same sign, and a target is one voxel away from its
+ *     source along that sign.  The direction varies with position parity and is not one global rotation, under which a lone
+ *     voxel and a lone hole both walk a closed four-cell loop and water never finds a pit.  Water here spreads and fills, but
+ *     it is not a pressure solver: it does not level perfectly over isolated one-cell pits.
+ *     Sand reaches a fixed point: fell_last = slid_last = 0 is "at rest".  Water at rest in a basin still moves its top layer
+ *     sideways; fell_last = slid_last = 0 is its "level" signal.  A step offers every voxel one direction only, so one quiet
+ *     step is a signal, not a proof: the layer is a fixed point once four steps running, one of each phase & 3, move nothing.
+ *   Steps across calls.  `steps` steps in one call equal `steps` calls of one step, each fed the previous output with `phase`
+ *     advanced by one.  Only phase & 3 matters.
+ *   Limits.  1 <= dims[k]; dims[0] * dims[1] * dims[2] <= 2^28; the halo box (dims[k] + 2 per axis) within vxrt_read_region's
+ *     2^36 voxels; origin[k] - 1 >= -2^31 and origin[k] + dims[k] + 1 <= 2^31 - 1; 1 <= steps <= VXRT_LOOSE_MAX_STEPS = 64.
+ * Outputs:
+ *   d_loose_out: L_n over B in region layout, padding bits 0.  It may be exactly d_loose_in (a call in place); no other
+ *     overlap is allowed.
+ *   d_summary: loose_in = the input's valid bits over B (padding excluded); loose_start = |L_start|, loose_after = |L_n|, so
+ *     dropped = loose_in - loose_start and drained = loose_start - loose_after; fell_last, slid_last, spread_last = the movers
+ *     of each pass of the last step (spread_last is 0 for sand); changed_min / changed_max = the inclusive world box of the
+ *     voxels where L_n differs from the input's valid bits, INT32_MAX / INT32_MIN on every axis when there is none.
+ * Workspace.  d_work holds vxrt_loose_workspace_bytes(dims) bytes, 0 outside the limits on dims.  With r(n) = n rounded up to a
+ *   multiple of 256, hd[k] = dims[k] + 2, wh = ceil(hd[0] / 32) and P = 4 * wh * hd[1] * hd[2] (one bit plane of the halo box,
+ *   as for vxrt_apply_rule with h = 1):
+ *     bytes = 4 * r(P)
+ *   (blocked, live and the two planes the passes write in turn).  The caller owns it; the library allocates nothing per call.
+ * Call rules (as vxrt_apply_rule): asynchronous on `stream`; the launches follow from the arguments alone (one region read, one
+ *   set-up, `steps` times two or three passes, one output), the call never synchronises with the host and can be captured.
+ *   Checked in this order: a NULL ctx, origin, dims, params, d_loose_in, d_work, d_loose_out or d_summary; struct_size;
+ *   material; steps; edge; a nonzero reserved_; the dims and the halo box; the origin -- each VXRT_ERR_INVALID; then no world:
+ *   VXRT_ERR_NO_WORLD; then a streamed world: VXRT_ERR_INVALID.  A refused call enqueues and writes nothing.
+ * vxrt_loose_step_host takes host buffers (the layer in and out, the summary out), allocates its own workspace and is
+ *   synchronous. */
+#define VXRT_LOOSE_MAX_STEPS 64
+typedef enum vxrt_loose_material { VXRT_LOOSE_SAND = 0, VXRT_LOOSE_WATER = 1 } vxrt_loose_material;
+typedef enum vxrt_loose_edge { VXRT_LOOSE_WALL = 0, VXRT_LOOSE_OPEN = 1 } vxrt_loose_edge;
+typedef struct vxrt_loose {
+    uint32_t struct_size;
+    int32_t material;  /* vxrt_loose_material */
+    int32_t steps;     /* 1 .. VXRT_LOOSE_MAX_STEPS */
+    int32_t edge;      /* vxrt_loose_edge */
+    uint32_t phase;    /* the number t of the call's first step */
+    int32_t reserved_[3]; /* 0 */
+} vxrt_loose;
+typedef struct vxrt_loose_summary {
+    uint32_t loose_in, loose_start, loose_after, fell_last, slid_last, spread_last;
+    int32_t changed_min[3], changed_max[3];
+} vxrt_loose_summary;
+uint64_t vxrt_loose_workspace_bytes(const int32_t dims[3]); /* 0 outside the contract */
+int vxrt_loose_step(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_loose *params,
+                    const uint32_t *d_loose_in, void *d_work, uint32_t *d_loose_out, vxrt_loose_summary *d_summary, void *stream);
+int vxrt_loose_step_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_loose *params,
+                         const uint32_t *loose_in, uint32_t *loose_out, vxrt_loose_summary *summary);
+
 /* ---- camera / lighting state.  Replaces Graphics::SetEnvironment, ::SetFOV,
  * ::SetOrthoWindowSize, ::GetDirections (VoxelRT/Renderer.cu:27-42,278-303). */
 int vxrt_set_environment(vxrt_ctx *ctx, const float light_dir[3], const float light_color[3],
@@ -1024,7 +1096,7 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  * holds the sentences below to the references of the eager paths).
  *   May be captured: vxrt_render, vxrt_render_views and vxrt_trace_batch without stats; vxrt_deinterleave_strips and
  *     vxrt_deinterleave_views; and the purely stream-ordered queries vxrt_read_region, vxrt_move_boxes, vxrt_overlap_boxes,
- *     vxrt_distance_field, vxrt_light_field, vxrt_apply_rule (tests/test_gpu_rule.py), vxrt_extract_surface,
+ *     vxrt_distance_field, vxrt_light_field, vxrt_apply_rule (tests/test_gpu_rule.py), vxrt_loose_step (tests/test_gpu_loose.py), vxrt_extract_surface,
  *     vxrt_downsample_region and vxrt_find_islands; and the
  *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame, the temporal filter's vxrt_reproject_frame and
  *     vxrt_light_frame (tests/test_gpu_light_frame.py).  Under

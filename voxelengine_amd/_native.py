@@ -38,6 +38,7 @@ EXPORTS = [
     "vxrt_lod_workspace_bytes", "vxrt_downsample_region", "vxrt_downsample_region_host",
     "vxrt_light_workspace_bytes", "vxrt_light_field", "vxrt_light_field_host",
     "vxrt_rule_workspace_bytes", "vxrt_apply_rule", "vxrt_apply_rule_host",
+    "vxrt_loose_workspace_bytes", "vxrt_loose_step", "vxrt_loose_step_host",
     "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame", "vxrt_light_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
@@ -58,6 +59,7 @@ LOD_MAX_SHIFT = 5
 LIGHT_SKY, LIGHT_BLOCK, LIGHT_MAX, LIGHT_MAX_EMITTERS = 1, 2, 15, 65536
 LF_SMOOTH, LF_OCCLUSION = 1, 2
 RULE_N6, RULE_N18, RULE_N26, RULE_BOX, RULE_WORLD, RULE_MAX_ITERATIONS = 0, 1, 2, 0, 1, 16
+LOOSE_SAND, LOOSE_WATER, LOOSE_WALL, LOOSE_OPEN, LOOSE_MAX_STEPS = 0, 1, 0, 1, 64
 TRANSFORM_MAX_WORDS = 1 << 31
 
 
@@ -151,6 +153,12 @@ class RuleDesc(C.Structure):
     """vxrt_rule: a neighbour-count rule (include/vxrt.h, vxrt_apply_rule)."""
     _fields_ = [("struct_size", C.c_uint32), ("neighbours", C.c_int32), ("born", C.c_uint32), ("survive", C.c_uint32),
                 ("iterations", C.c_int32), ("scope", C.c_int32), ("outside", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class LooseDesc(C.Structure):
+    """vxrt_loose: the parameters of a loose-voxel call (include/vxrt.h, vxrt_loose_step)."""
+    _fields_ = [("struct_size", C.c_uint32), ("material", C.c_int32), ("steps", C.c_int32), ("edge", C.c_int32),
+                ("phase", C.c_uint32), ("reserved_", C.c_int32 * 3)]
 
 
 class CameraPose(C.Structure):
@@ -320,6 +328,12 @@ def load() -> C.CDLL:
     L.vxrt_apply_rule.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_apply_rule_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+    L.vxrt_loose_workspace_bytes.restype = C.c_uint64
+    L.vxrt_loose_workspace_bytes.argtypes = [C.POINTER(C.c_int32)]
+    L.vxrt_loose_step.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_loose_step_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
     L.vxrt_frame_guides.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, f3, f3, f3, f3, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_denoise_workspace_bytes.restype = C.c_uint64

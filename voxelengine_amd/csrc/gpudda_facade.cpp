@@ -424,6 +424,66 @@ int VoxelRaytracer3D::SmoothVoxels(const int32_t origin[3], const int32_t dims[3
     return StampVoxels(origin, dims, bits.data(), VXRT_STAMP_REPLACE, stats);
 }
 
+int VoxelRaytracer3D::StepLoose(const int32_t origin[3], const int32_t dims[3], const vxrt_loose& params, std::vector<uint32_t>& loose,
+                                vxrt_loose_summary& summary)
+{
+    Flush();
+    // the vector is sized only for a box within the limits; the call itself refuses anything else, in its own order
+    const bool sized = vxrt_loose_workspace_bytes(dims) != 0;
+    loose.resize(sized ? (size_t)vxrt_region_words(dims) : 1u, 0u);
+    std::vector<uint32_t> out(loose.size(), 0u);
+    const int rc = vxrt_loose_step_host(ctx, origin, dims, &params, loose.data(), out.data(), &summary);
+    if (rc == VXRT_OK)
+        loose.swap(out);
+    return rc;
+}
+
+int VoxelRaytracer3D::SettleVoxels(const int32_t origin[3], const int32_t dims[3], const int32_t source_origin[3],
+                                   const int32_t source_dims[3], int32_t material, int32_t max_steps, int32_t edge,
+                                   vxrt_loose_summary* summary, int32_t* steps, vxrt_edit_stats* stats, bool early_stop)
+{
+    // everything a step would refuse is refused here, before the world is touched
+    if (max_steps < 1 || vxrt_loose_workspace_bytes(dims) == 0 || vxrt_region_words(source_dims) == 0 ||
+        (material != VXRT_LOOSE_SAND && material != VXRT_LOOSE_WATER) || (edge != VXRT_LOOSE_WALL && edge != VXRT_LOOSE_OPEN))
+        return VXRT_ERR_INVALID;
+    for (int k = 0; k < 3; ++k)
+        if (source_origin[k] < origin[k] || (int64_t)source_origin[k] + source_dims[k] > (int64_t)origin[k] + dims[k])
+            return VXRT_ERR_INVALID;
+    // the voxels the subtract stamp takes out, in the box's layout: the box before, and not after
+    std::vector<uint32_t> before, after, source;
+    int rc = ReadRegion(origin, dims, before);
+    if (rc == VXRT_OK)
+        rc = ReadRegion(source_origin, source_dims, source);
+    if (rc == VXRT_OK)
+        rc = StampVoxels(source_origin, source_dims, source.data(), VXRT_STAMP_SUBTRACT);
+    if (rc == VXRT_OK)
+        rc = ReadRegion(origin, dims, after);
+    if (rc != VXRT_OK)
+        return rc;
+    for (size_t i = 0; i < before.size(); ++i)
+        before[i] &= ~after[i];
+    vxrt_loose_summary sum{};
+    int32_t done = 0;
+    while (done < max_steps) {
+        vxrt_loose p{};
+        p.struct_size = sizeof(p);
+        p.material = material;
+        p.steps = max_steps - done < VXRT_LOOSE_MAX_STEPS ? max_steps - done : VXRT_LOOSE_MAX_STEPS;
+        p.edge = edge;
+        p.phase = (uint32_t)done;
+        if ((rc = StepLoose(origin, dims, p, before, sum)) != VXRT_OK)
+            return rc;
+        done += p.steps;
+        if (early_stop && sum.fell_last + sum.slid_last == 0u)
+            break;
+    }
+    if (summary)
+        *summary = sum;
+    if (steps)
+        *steps = done;
+    return StampVoxels(origin, dims, before.data(), VXRT_STAMP_UNION, stats);
+}
+
 int VoxelRaytracer3D::DownsampleRegion(const int32_t origin[3], const int32_t dims[3], uint32_t shift, uint32_t threshold,
                                        std::vector<uint32_t>& bits, vxrt_lod_summary& summary, std::vector<uint16_t>* counts)
 {

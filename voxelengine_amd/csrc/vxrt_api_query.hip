@@ -14,6 +14,7 @@
 #include "vxrt_place.hpp"
 #include "vxrt_reproject.hpp"
 #include "vxrt_rule.hpp"
+#include "vxrt_loose.hpp"
 #include "vxrt_surface.hpp"
 #include "vxrt_transform.hpp"
 #include "vxrt_voxelize.hpp"
@@ -1060,6 +1061,62 @@ int vxrt_apply_rule_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dim
     if (int rc = T.alloc(VXRT_ERR_NOMEM, "apply_rule_host"))
         return rc;
     VX_HIP(vxrt::apply_rule(vxrt::query_world(c), origin, dims, *rule, d_mask, d_work, d_bits, d_sum, nullptr));
+    return T.finish();
+}
+
+// ---- loose voxels -----------------------------------------------------------------------------------------------------------
+uint64_t vxrt_loose_workspace_bytes(const int32_t dims[3])
+{
+    vxrt::LooseLayout L;
+    return dims && vxrt::loose_layout(nullptr, dims, L) ? L.total_bytes : 0;
+}
+
+// the checks both loose calls make after their NULL checks, in the order of include/vxrt.h
+static int loose_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_loose* params)
+{
+    static const char* const what[] = {"", "vxrt_loose size mismatch", "loose material: VXRT_LOOSE_SAND or VXRT_LOOSE_WATER",
+                                       "loose steps: 1 .. VXRT_LOOSE_MAX_STEPS", "loose edge: VXRT_LOOSE_WALL or VXRT_LOOSE_OPEN",
+                                       "loose reserved_: 0"};
+    if (const int bad = vxrt::loose_check(*params))
+        return fail(VXRT_ERR_INVALID, what[bad]);
+    vxrt::LooseLayout L;
+    if (!vxrt::loose_layout(origin, dims, L))
+        return fail(VXRT_ERR_INVALID, L.fault == vxrt::kBoxDims
+                                          ? "loose box dims: each at least 1, at most 2^28 voxels, the halo box at most 2^36"
+                                          : "loose box: origin - 1 or origin + dims + 1 beyond int32");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_loose_step(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_loose* params, const uint32_t* d_loose_in,
+                    void* d_work, uint32_t* d_loose_out, vxrt_loose_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !params || !d_loose_in || !d_work || !d_loose_out || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = loose_ready(c, origin, dims, params))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    VX_HIP(vxrt::loose_step(vxrt::query_world(c), origin, dims, *params, d_loose_in, d_work, d_loose_out, d_summary, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_loose_step_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_loose* params, const uint32_t* loose_in,
+                         uint32_t* loose_out, vxrt_loose_summary* summary)
+{
+    if (!c || !origin || !dims || !params || !loose_in || !loose_out || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = loose_ready(c, origin, dims, params))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::LooseLayout L;
+    vxrt::loose_layout(origin, dims, L);
+    vxrt::HostScratch T;
+    const auto d_work = T.work(L.total_bytes);
+    const auto d_sum = T.out(sizeof(vxrt_loose_summary), summary);
+    const auto d_out = T.out(4u * (size_t)L.nb, loose_out);
+    const auto d_in = T.in(4u * (size_t)L.nb, loose_in);
+    if (int rc = T.alloc(VXRT_ERR_NOMEM, "loose_step_host"))
+        return rc;
+    VX_HIP(vxrt::loose_step(vxrt::query_world(c), origin, dims, *params, d_in, d_work, d_out, d_sum, nullptr));
     return T.finish();
 }
 

@@ -628,6 +628,78 @@ class Context:
         st = self.edit_stamps([res.stamp()])
         return st, res.summary
 
+    # ---- loose voxels (extension, include/vxrt.h) -----------------------------------------------------------------------------
+    def loose_workspace_bytes(self, dims) -> int:
+        """vxrt_loose_workspace_bytes: the workspace of one loose_step call, 0 outside the contract"""
+        return int(self._L.vxrt_loose_workspace_bytes(_i3(dims)))
+
+    def loose_step(self, origin, dims, loose, params: "Loose | None" = None, stream: int | None = None, *, out=None,
+                   work=None) -> "LooseResult":
+        """The loose layer ``loose`` of the box ``origin`` .. ``origin + dims - 1`` after ``params.steps`` steps of falling,
+        sliding and (water) spreading over the world's solids: include/vxrt.h, vxrt_loose_step.  The world is not changed.
+        ``loose``: a bool [x, y, z] numpy grid of ``dims`` or a device tensor of region words.  Asynchronous on ``stream``
+        (default: torch's current stream).  ``out``: a device tensor of at least region_words(dims) words for the new layer --
+        it may be ``loose`` itself (a call in place); ``work``: one of at least loose_workspace_bytes bytes (defaults: new
+        ones).  Returns a LooseResult; reading its ``summary`` waits for the call."""
+        call = _Call(self, stream)
+        origin, dims = _box(origin, dims)
+        p = (params or Loose())._c()
+        ws = self.loose_workspace_bytes(dims)
+        _, nw = _counts(dims, ws)
+        what = "a contiguous device tensor of at least region_words(dims) words"
+        work = call.work(ws, work, "work: a contiguous device tensor of at least loose_workspace_bytes(dims) bytes")
+        if isinstance(loose, np.ndarray):
+            loose = call.upload(_mask_words(loose, dims))
+        else:
+            loose = call.reads(call.fits(loose, nw, 4, "loose: " + what, any_size=True))
+        bits = call.out(nw, 4, call.torch.int32, out, "out: " + what, any_size=True)
+        summary = call.summary(12)
+        call.launch(self._L.vxrt_loose_step, _i3(origin), _i3(dims), C.byref(p), _ptr(loose), _ptr(work), _ptr(bits), _ptr(summary))
+        return LooseResult(bits=bits.view(-1)[:nw] if bits.element_size() == 4 else bits, origin=origin, dims=dims, _summary=summary,
+                           _stream=call.s)
+
+    def loose_step_host(self, origin, dims, loose, params: "Loose | None" = None) -> "LooseResult":
+        """loose_step through the synchronous host call (vxrt_loose_step_host): ``loose`` and the result's ``bits`` are bool
+        [x, y, z] numpy grids."""
+        origin, dims = _box(origin, dims)
+        p = (params or Loose())._c()
+        _, nw = _counts(dims, self.loose_workspace_bytes(dims))
+        words = np.zeros(max(nw, 1), np.uint32)
+        summary = np.zeros(12, np.uint32)
+        m = _mask_words(loose, dims) if nw else np.zeros(1, np.uint32)
+        N.check(self._L.vxrt_loose_step_host(self._h, _i3(origin), _i3(dims), C.byref(p), m.ctypes.data, words.ctypes.data,
+                                             summary.ctypes.data))
+        return LooseResult(bits=unpack_region(words, dims), origin=origin, dims=dims, _summary=summary, _stream=None)
+
+    def settle_voxels(self, origin, dims, source_origin, source_dims, material: int = N.LOOSE_SAND, max_steps: int = 256,
+                      edge: int = N.LOOSE_WALL):
+        """Turn the solid voxels of the source box loose and let them settle inside the box ``origin`` .. ``origin + dims -
+        1``, which must contain the source box: the source's voxels are lifted out of the world (one STAMP_SUBTRACT), stepped
+        in place on the device in calls of at most LOOSE_MAX_STEPS steps with the phase carried, until a call's last step
+        neither drops nor slides a voxel or ``max_steps`` steps are made, and stamped back with STAMP_UNION.  Returns
+        (LooseSummary of the last call, steps made)."""
+        origin, dims = _box(origin, dims)
+        so, sd = _box(source_origin, source_dims)
+        if int(max_steps) < 1 or material not in (N.LOOSE_SAND, N.LOOSE_WATER) or edge not in (N.LOOSE_WALL, N.LOOSE_OPEN):
+            raise ValueError("max_steps: at least 1; material: LOOSE_SAND or LOOSE_WATER; edge: LOOSE_WALL or LOOSE_OPEN")
+        if any(a < o or a + b > o + d for a, b, o, d in zip(so, sd, origin, dims)):
+            raise ValueError("the source box must lie inside the box")
+        before = self.read_region(origin, dims)
+        self.edit_stamps([Stamp(so, self.read_region(so, sd), N.STAMP_SUBTRACT, sd)])
+        layer = before & ~self.read_region(origin, dims)  # the voxels the stamp took out, in the box's layout
+        import torch
+        work = torch.empty(max(self.loose_workspace_bytes(dims), 4), dtype=torch.uint8, device=layer.device)
+        done, res = 0, None
+        while done < int(max_steps):
+            n = min(N.LOOSE_MAX_STEPS, int(max_steps) - done)
+            res = self.loose_step(origin, dims, layer, Loose(material, n, edge, done & 0xFFFFFFFF), out=layer, work=work)
+            done += n
+            s = res.summary
+            if s.fell_last + s.slid_last == 0:
+                break
+        self.edit_stamps([res.stamp()])
+        return res.summary, done
+
     # ---- mesh voxelization (extension, include/vxrt.h) ----------------------------------------------------------------
     def voxelize_workspace_bytes(self, dims, n_triangles: int) -> int:
         """vxrt_voxelize_workspace_bytes: the workspace of one voxelize_mesh call, 0 outside the contract"""
@@ -1632,6 +1704,64 @@ class RuleResult(_LazyResult):
     def stamp(self) -> "Stamp":
         """the result as a STAMP_REPLACE stamp at the box's origin, for edit_stamps"""
         return Stamp(self.origin, self.bits, N.STAMP_REPLACE, self.dims)
+
+
+@dataclass
+class Loose:
+    """The parameters of a loose-voxel call (include/vxrt.h, vxrt_loose): ``material`` LOOSE_SAND (falls and slides) or
+    LOOSE_WATER (also spreads sideways); ``steps`` 1 .. LOOSE_MAX_STEPS; ``edge``: LOOSE_WALL (the box's faces hold the
+    material) or LOOSE_OPEN (what leaves the box through an empty voxel is gone); ``phase``: the number of the call's first
+    step -- carry it across calls: the phase of the next call is this one's plus its steps."""
+    material: int = N.LOOSE_SAND
+    steps: int = 1
+    edge: int = N.LOOSE_WALL
+    phase: int = 0
+
+    def _c(self) -> "N.LooseDesc":
+        i32 = lambda v: max(-1 << 31, min(int(v), (1 << 31) - 1))  # a value outside int32 is the library's to refuse
+        return N.LooseDesc(C.sizeof(N.LooseDesc), i32(self.material), i32(self.steps), i32(self.edge), int(self.phase) & 0xFFFFFFFF,
+                           (C.c_int32 * 3)(0, 0, 0))
+
+
+class LooseSummary(NamedTuple):
+    """vxrt_loose_summary: the input's valid bits over the box, those of them that are loose voxels (in the world and not on a
+    solid), the loose voxels after the steps (fewer only under LOOSE_OPEN), the voxels the last step's passes moved (at rest:
+    fell_last = slid_last = 0), and the inclusive world box of the voxels where the new layer differs from the input
+    (INT32_MAX / INT32_MIN per axis when none does)"""
+    loose_in: int
+    loose_start: int
+    loose_after: int
+    fell_last: int
+    slid_last: int
+    spread_last: int
+    changed_min: tuple
+    changed_max: tuple
+
+
+@dataclass
+class LooseResult(_LazyResult):
+    """The result of Context.loose_step: ``bits`` the new layer as region words on the device (a numpy bool [x, y, z] grid
+    from loose_step_host), ``summary`` a LooseSummary."""
+    bits: object
+    origin: tuple
+    dims: tuple
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> LooseSummary:
+        """the summary; for a device result this waits for the call's stream"""
+        self._summary = self._host(self._summary, np.uint32)
+        box = [int(v) for v in np.asarray(self._summary[6:12]).view(np.int32)]
+        return LooseSummary(*(int(v) for v in self._summary[:6]), tuple(box[:3]), tuple(box[3:]))
+
+    def grid(self) -> np.ndarray:
+        """the layer as a bool [x, y, z] numpy grid (device words are copied to the host)"""
+        return self._bits(self.bits)
+
+    def stamp(self, mode: int = N.STAMP_UNION) -> "Stamp":
+        """the layer as a stamp at the box's origin, for edit_stamps: STAMP_UNION makes the loose voxels solid"""
+        return Stamp(self.origin, self.bits, mode, self.dims)
 
 
 @dataclass(frozen=True)
