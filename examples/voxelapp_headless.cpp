@@ -69,6 +69,12 @@
 // the denoiser, every hit pixel is relit with both flags, outside_level 0xF0, the block colour (1, 0.8, 0.5) and the occlusion
 // curve (0.4, 0.6, 0.8, 1) -- the dumped PPMs are the lit frames -- with one line "lit frame N hit .. in_box .. occluded ..
 // dark ..".  The same restrictions as for the denoiser.
+// A line "frame materials" switches the voxel materials on from that frame (vxrt_material_frame; "frame materials off" switches
+// them off again): after the denoiser and before the light, every hit pixel's colour is multiplied with the albedo of the voxel
+// it shows -- five built-in materials in two altitude bands (grass over dirt over stone; from 5/8 of the world's height snow
+// over sand over stone), each with a tile of an 8 x 8 atlas made on the host from an integer hash (grass has a side tile of
+// its own) -- with one line "materials frame N hit .. painted .. top .. textured ..".  The dumped PPMs are the coloured frames.
+// The same restrictions as for the denoiser.
 // A line "frame rule x0 y0 z0 x1 y1 z1 n6|n18|n26 born_hex survive_hex iterations box|world" applies a neighbour-count rule
 // (VoxelRaytracer3D::ApplyRule) to the box of the inclusive corners (x0, y0, z0) .. (x1, y1, z1) -- born_hex / survive_hex: bit
 // c set = an empty voxel is born / a solid voxel survives with c solid neighbours -- stamps the result (replace) and prints one
@@ -155,6 +161,11 @@ int main(int argc, char** argv)
         std::vector<int32_t> emitters;  // x, y, z, level each
     };
     std::vector<LitLine> lit_lines;
+    struct MaterialsLine {
+        int frame;
+        bool on;
+    };
+    std::vector<MaterialsLine> materials_lines;
     if (argc > 12 && std::string(argv[12]) != "-") {
         std::ifstream in(argv[12]);
         if (!in) {
@@ -179,6 +190,20 @@ int main(int argc, char** argv)
                 tl.on = std::string(word) == "on";
                 temporal_lines.push_back(tl);
                 continue;
+            }
+            {
+                MaterialsLine ml{0, true};
+                char what[12] = "", arg[8] = "";
+                const int got = std::sscanf(line.c_str(), "%d %11s %7s", &ml.frame, what, arg);
+                if (got >= 2 && std::string(what) == "materials") {
+                    if (got == 3 && std::string(arg) != "off") {
+                        std::cerr << "bad materials line: " << line << std::endl;
+                        return 2;
+                    }
+                    ml.on = got == 2;
+                    materials_lines.push_back(ml);
+                    continue;
+                }
             }
             {
                 std::istringstream words(line);
@@ -785,10 +810,14 @@ int main(int argc, char** argv)
     uint8_t* d_levels = nullptr;
     float* d_lit = nullptr;  // the lit colours: the frame's own colours stay what the next frame's history expects
     vxrt_light_frame_summary* d_lf_sum = nullptr;
-    if (!denoise_lines.empty() || !temporal_lines.empty() || !lit_lines.empty()) {
+    float* d_mat = nullptr;  // the coloured frame: as d_lit, beside the frame's own colours
+    vxrt_material* d_palette = nullptr;
+    uint32_t* d_atlas = nullptr;
+    vxrt_material_frame_summary* d_mat_sum = nullptr;
+    if (!denoise_lines.empty() || !temporal_lines.empty() || !lit_lines.empty() || !materials_lines.empty()) {
         const size_t n = (size_t)width * height;
         if (batch > 1 || in_flight >= 2 || shade_mode == 1 || vxrt_denoise_workspace_bytes(width, height) == 0) {
-            std::cerr << "denoise, temporal, lit: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
+            std::cerr << "denoise, temporal, lit, materials: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
             return 2;
         }
         if (hipMalloc((void**)&d_color, n * 12) != hipSuccess || hipMalloc((void**)&d_hit, n * 8) != hipSuccess ||
@@ -802,7 +831,46 @@ int main(int argc, char** argv)
         if (!lit_lines.empty() &&
             (hipMalloc((void**)&d_lit, n * 12) != hipSuccess || hipMalloc((void**)&d_lf_sum, sizeof(vxrt_light_frame_summary)) != hipSuccess))
             return 1;
+        if (!materials_lines.empty()) {
+            // grass, dirt, stone, sand, snow (materials 1 .. 5): white tints, tiles 0 .. 4, and tile 5 on the sides of grass
+            std::vector<vxrt_material> palette(256);
+            for (auto& m : palette) {
+                m.tint[0] = m.tint[1] = m.tint[2] = 1.0f;
+                m.tile_top = m.tile_side = m.tile_bottom = VXRT_MATERIAL_NO_TILE;
+                m.reserved = 0;
+            }
+            for (uint16_t m = 1; m <= 5; ++m)
+                palette[m].tile_top = palette[m].tile_side = palette[m].tile_bottom = (uint16_t)(m - 1);
+            palette[1].tile_side = 5;
+            palette[1].tile_bottom = 1;  // dirt under a grass block
+            const uint32_t base[6][3] = {{80, 180, 60}, {134, 96, 67}, {128, 128, 128}, {220, 205, 140}, {245, 245, 255}, {110, 140, 70}};
+            std::vector<uint32_t> atlas(6 * 64);
+            for (uint32_t t = 0; t < 6; ++t)
+                for (uint32_t r = 0; r < 8; ++r)
+                    for (uint32_t s2 = 0; s2 < 8; ++s2) {
+                        const uint32_t n = (((t * 73856093u) ^ (r * 19349663u) ^ (s2 * 83492791u)) * 2654435761u) >> 24;
+                        const uint32_t shade = 192u + (n >> 2);  // 192 .. 255
+                        atlas[(t * 8 + r) * 8 + s2] = (base[t][0] * shade / 255u) | (base[t][1] * shade / 255u) << 8 | (base[t][2] * shade / 255u) << 16 | 0xFF000000u;
+                    }
+            if (hipMalloc((void**)&d_mat, n * 12) != hipSuccess || hipMalloc((void**)&d_palette, 256 * sizeof(vxrt_material)) != hipSuccess ||
+                hipMalloc((void**)&d_atlas, atlas.size() * 4) != hipSuccess || hipMalloc((void**)&d_mat_sum, sizeof(vxrt_material_frame_summary)) != hipSuccess ||
+                hipMemcpy(d_palette, palette.data(), 256 * sizeof(vxrt_material), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_atlas, atlas.data(), atlas.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+                return 1;
+        }
     }
+    vxrt_material_rules mat_rules{};
+    mat_rules.struct_size = sizeof(vxrt_material_rules);
+    mat_rules.n_bands = 2;
+    mat_rules.bands[0] = vxrt_material_band{INT32_MIN, 1, 2, 3, 3};              // grass, three of dirt, stone
+    mat_rules.bands[1] = vxrt_material_band{(int32_t)((wy ? wy : edge) / 8 * 5), 5, 4, 3, 1};  // snow, one of sand, stone
+    mat_rules.paint_dims[0] = mat_rules.paint_dims[1] = mat_rules.paint_dims[2] = 1;
+    vxrt_material_frame_params mf{};
+    mf.struct_size = sizeof(vxrt_material_frame_params);
+    mf.n_tiles = 6;
+    mf.tile_shift = 3;
+    bool materials = false;
+    vxrt_material_frame_summary mat_sum{};
     vxrt_denoise_params dn{sizeof(vxrt_denoise_params), 0, 0.0f, 0};
     vxrt_reproject_params rp{};
     rp.struct_size = sizeof(vxrt_reproject_params);
@@ -829,6 +897,9 @@ int main(int argc, char** argv)
                 temporal = l.on;
                 rp.max_history = l.max_history;
             }
+        for (const MaterialsLine& l : materials_lines)
+            if (l.frame == i)
+                materials = l.on;
         for (const LitLine& l : lit_lines)
             if (l.frame == i) {
                 lit = l.on;
@@ -861,7 +932,7 @@ int main(int argc, char** argv)
         pose_for(i);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
-        if (dn.iterations > 0 || temporal || lit) {
+        if (dn.iterations > 0 || temporal || lit || materials) {
             // the frame with its AOVs through the C ABI (the facade's RenderScreen has no AOV arguments), then keys and filter
             vxrt_ctx* c = raytracer->Context();
             const float o[3] = {cam_pos.x, cam_pos.y, cam_pos.z}, f[3] = {cam_forward.x, cam_forward.y, cam_forward.z},
@@ -906,6 +977,21 @@ int main(int argc, char** argv)
             }
             if (temporal)
                 (void)hipMemcpy(&rp_sum, d_rp_sum, sizeof(rp_sum), hipMemcpyDeviceToHost);
+            if (materials) {
+                for (int k = 0; k < 3; ++k) {
+                    mf.cam.origin[k] = o[k];
+                    mf.cam.fwd[k] = f[k];
+                    mf.cam.up[k] = u[k];
+                    mf.cam.right[k] = r[k];
+                }
+                if (vxrt_material_frame(c, width, height, d_color, d_keys, d_hit, &mat_rules, nullptr, d_palette, d_atlas, &mf, d_mat, d_pixels,
+                                        nullptr, d_mat_sum, nullptr) != VXRT_OK ||
+                    vxrt_synchronize(c) != VXRT_OK) {
+                    std::cerr << "materials, frame " << i << ": " << vxrt_last_error() << std::endl;
+                    return 3;
+                }
+                (void)hipMemcpy(&mat_sum, d_mat_sum, sizeof(mat_sum), hipMemcpyDeviceToHost);
+            }
             if (lit) {
                 for (int k = 0; k < 3; ++k) {
                     lf.cam.origin[k] = o[k];
@@ -913,7 +999,8 @@ int main(int argc, char** argv)
                     lf.cam.up[k] = u[k];
                     lf.cam.right[k] = r[k];
                 }
-                if (vxrt_light_frame(c, width, height, d_color, d_keys, d_hit, d_levels, &lf, d_lit, d_pixels, nullptr, d_lf_sum, nullptr) !=
+                if (vxrt_light_frame(c, width, height, materials ? d_mat : d_color, d_keys, d_hit, d_levels, &lf, d_lit, d_pixels, nullptr, d_lf_sum,
+                                     nullptr) !=
                         VXRT_OK ||
                     vxrt_synchronize(c) != VXRT_OK) {
                     std::cerr << "lit, frame " << i << ": " << vxrt_last_error() << std::endl;
@@ -928,6 +1015,8 @@ int main(int argc, char** argv)
         if (temporal)
             std::printf("temporal frame %d max_history %d hit %u reused %u offscreen %u rejected %u\n", i, rp.max_history, rp_sum.hit,
                         rp_sum.reused, rp_sum.offscreen, rp_sum.rejected);
+        if (materials)
+            std::printf("materials frame %d hit %u painted %u top %u textured %u\n", i, mat_sum.hit, mat_sum.painted, mat_sum.top, mat_sum.textured);
         if (lit)
             std::printf("lit frame %d hit %u in_box %u occluded %u dark %u\n", i, lf_sum.hit, lf_sum.in_box, lf_sum.occluded, lf_sum.dark);
         (void)hipMemcpy(pixels.data(), d_pixels, pixels.size() * sizeof(BGRA8888), hipMemcpyDeviceToHost);
@@ -982,6 +1071,10 @@ int main(int argc, char** argv)
     (void)hipFree(d_levels);
     (void)hipFree(d_lit);
     (void)hipFree(d_lf_sum);
+    (void)hipFree(d_mat);
+    (void)hipFree(d_palette);
+    (void)hipFree(d_atlas);
+    (void)hipFree(d_mat_sum);
     (void)hipFree(d_hit);
     (void)hipFree(d_keys_pair[0]);
     (void)hipFree(d_keys_pair[1]);

@@ -37,6 +37,8 @@ struct vxrt_quad;
 struct vxrt_surface_summary;
 struct vxrt_lod_summary;
 struct vxrt_light_summary;
+struct vxrt_material_rules;
+struct vxrt_material_summary;
 struct vxrt_rule;
 struct vxrt_rule_summary;
 struct vxrt_loose;
@@ -239,6 +241,13 @@ public:
     // queued edits first.  Returns the vxrt_status.
     int LightField(const int32_t origin[3], const int32_t dims[3], const std::vector<int32_t>& emitters, uint32_t channels,
                    std::vector<uint8_t>& levels, vxrt_light_summary& summary);
+
+    // voxel materials (extension, include/vxrt.h, vxrt_material_field_host): the material byte of every voxel of the box
+    // origin .. origin + dims - 1 in region order -- 0 for an empty voxel, else the paint byte or the strata rule -- and the
+    // summary.  `paint`: one byte per voxel of rules.paint_origin / paint_dims in region order, or NULL.  Flushes queued edits
+    // first.  Returns the vxrt_status.
+    int MaterialField(const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules& rules, std::vector<uint8_t>& materials,
+                      vxrt_material_summary& summary, const uint8_t* paint = nullptr);
 
     // voxel rules (extension, include/vxrt.h, vxrt_apply_rule_host): the box origin .. origin + dims - 1 after the rule's
     // iterations as region words (a StampVoxels argument as it is) and the summary; the world is not changed.  `mask`:

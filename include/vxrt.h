@@ -1099,7 +1099,8 @@ int vxrt_render(vxrt_ctx *ctx, uint32_t width, uint32_t height, void *d_fb, cons
  *     vxrt_distance_field, vxrt_light_field, vxrt_apply_rule (tests/test_gpu_rule.py), vxrt_loose_step (tests/test_gpu_loose.py), vxrt_extract_surface,
  *     vxrt_downsample_region and vxrt_find_islands; and the
  *     frame denoiser's vxrt_frame_guides and vxrt_denoise_frame, the temporal filter's vxrt_reproject_frame and
- *     vxrt_light_frame (tests/test_gpu_light_frame.py).  Under
+ *     vxrt_light_frame (tests/test_gpu_light_frame.py); and the voxel materials' vxrt_material_field and vxrt_material_frame
+ *     (tests/test_gpu_material.py; vxrt_material_field_host synchronises and is outside, like every _host call).  Under
  *     capture they allocate nothing, wait for nothing and read no host memory after they return: a captured multi-view
  *     launch stores its views from kernel arguments, which the graph owns.  Every replay gives what the eager call gives.
  *   Refused under capture, with VXRT_ERR_INVALID and a message that names capture: a render launch with frame_number < 0, in
@@ -1357,6 +1358,104 @@ int vxrt_light_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color
                      const int64_t *d_hit_aov, const uint8_t *d_levels_or_null, const vxrt_light_frame_params *params,
                      float *d_color_out, void *d_fb_or_null, float *d_terms_or_null /* W*H*3: S, Bk, A */,
                      vxrt_light_frame_summary *d_summary_or_null, void *stream);
+
+/* ---- voxel materials -- an EXTENSION (the reference's to-do item "Texture mapping and materials", README.md:14-24; its
+ * calculateColor has no albedo: every surface is white).  A world is one bit per voxel, so the material of a voxel is a pure
+ * function of the world's geometry -- terrain strata by altitude band: a top material, a layer under it, a deep one -- with an
+ * optional caller-owned byte box of paint on top.  vxrt_material_field gives the material bytes of a box; vxrt_material_frame
+ * multiplies the colours of a frame with tint and texture of the material each hit pixel shows.  Both use the same per-voxel
+ * function; the render launches know nothing of either.
+ *   The material of a voxel.  Material ids are 1 .. 255; 0 is "empty" in a field and "not painted" in a paint box.  +y is
+ *     up; a voxel outside the world is empty.  run(v) is the number of consecutive solid voxels directly above v, at
+ *     (v.x, v.y + j, v.z) for j = 1, 2, ...  band(v) is the last i < n_bands with bands[i].y_from <= v.y.  With
+ *     b = bands[band(v)]: rule(v) = b.top when run(v) == 0, b.under when 1 <= run(v) <= b.under_depth, else b.deep.  No
+ *     implementation looks more than under_depth + 1 <= 16 voxels up.
+ *   Rules.  n_bands is 1 .. 8; bands[0].y_from == INT32_MIN and y_from ascends strictly over the bands in use; top, under
+ *     and deep are 1 .. 255, under_depth is 0 .. 15 (bands at and behind n_bands are not looked at); reserved_ is 0.
+ *   Paint.  d_paint, optional, holds one byte per voxel of the box P = [paint_origin, paint_origin + paint_dims) in region
+ *     order (x fastest, then y, then z).  material(v) is that byte when d_paint is given, v lies in P and the byte is not 0;
+ *     otherwise rule(v).  paint_dims and paint_origin are checked only when d_paint is given, with the limits of
+ *     vxrt_light_frame's box: 1 <= paint_dims[k], their product <= 2^28, paint_origin[k] + paint_dims[k] <= 2^31 - 1.
+ *   Field (vxrt_material_field).  d_materials takes one byte per voxel of B = [origin, origin + dims) in region order: 0
+ *     for an empty voxel, material(v) otherwise.  d_summary is zeroed on the stream by the call and then counts: solid;
+ *     painted (solid voxels whose material came from paint); top (solid voxels with run == 0); hist[m] (voxels by output
+ *     byte: hist[0] the empty voxels of B).  Limits: 1 <= dims[k], their product <= 2^28, origin[k] >= -2^31 and
+ *     origin[k] + dims[k] + 16 <= 2^31 - 1.  No workspace.  d_paint, d_materials and d_summary must not overlap.
+ *     vxrt_material_field_host takes host buffers (paint in; materials and summary out), allocates its own device memory
+ *     and synchronises.
+ *   Field call rules (as vxrt_light_field).  Asynchronous on `stream`; allocates nothing, never synchronises, reads no host
+ *     memory after it returns; may be captured (STREAM CAPTURE above).  It never loads outside the world tables, outside the
+ *     paint_dims[0] * paint_dims[1] * paint_dims[2] bytes of d_paint or behind d_materials, and writes exactly dims[0] *
+ *     dims[1] * dims[2] bytes and the summary.  Two calls give the same bytes.  Refusals, each before anything is enqueued
+ *     or written, in this order: a NULL ctx, origin, dims, rules, d_materials or d_summary; rules->struct_size; n_bands; a
+ *     band (y_from, a material 0, under_depth > 15); reserved_; the paint box when d_paint is given; dims; origin -- each
+ *     VXRT_ERR_INVALID; then no world: VXRT_ERR_NO_WORLD; then a streamed world: VXRT_ERR_INVALID.
+ *   Frame (vxrt_material_frame).  Frames, keys, the miss rule, the voxel v, the axis a with (b, c), the primary ray, t, the
+ *     position (u, w) on the face with its clamps and its centre fallback, and the BGRA8 store are exactly those of
+ *     vxrt_light_frame.  All float arithmetic is binary32, in the order written, without contraction.
+ *     Face class: a == 1 with the key's toward bit clear is a top face, a == 1 with it set a bottom face, every other face a
+ *     side face.  With m = material(v), tile = d_palette[m].tile_top, tile_bottom or tile_side by that class.
+ *     Texel: T = 1 << tile_shift; iu = min((int)(u * (float)T), T - 1) and iw likewise from w.  Column s and row r (image rows
+ *     top-down): a == 1: s = iu, r = iw; a == 0 (b = y, c = z): s = iw, r = T - 1 - iu; a == 2 (b = x, c = y): s = iu,
+ *     r = T - 1 - iw.  The atlas is RGBA8 packed in a uint32, r in the low byte, tile-major and row-major inside a tile:
+ *     texel = d_atlas[(tile * T + r) * T + s].  If d_atlas is NULL or tile >= n_tiles (0xFFFF: "none") the texel colour is
+ *     (1, 1, 1) and nothing is loaded -- the palette's contents cannot be checked on the host; this rule keeps every load
+ *     inside the n_tiles * T * T words of the atlas.  Otherwise tex.ch = (float)byte / 255.0f, an IEEE division.
+ *     Colour, per channel: alb = tint[ch] * tex.ch; out = c * alb.  The colour AOV is what the pixel store gets, after the
+ *     renderer's tonemap; multiplying there is deliberate, as in vxrt_light_frame.  In a frame pipeline the stage runs after
+ *     the a-trous filter (which then works on demodulated lighting) and before vxrt_light_frame.
+ *     A miss copies its colour, writes 0 to the material AOV and counts nowhere.
+ *     Outputs: d_color_out (may be d_color_in; nothing else may overlap), d_fb (if given) the BGRA8 pixel of it,
+ *     d_material_aov (if given) m per pixel, d_summary (if given; zeroed on the stream by the call): hit; painted (hit pixels
+ *     whose material came from paint); top (hit pixels with run(v) == 0); textured (hit pixels that loaded a texel).
+ *   Frame call rules (as vxrt_light_frame).  Needs a resident world that is not streamed; asynchronous on `stream`, allocates
+ *     nothing, waits for nothing, reads rules and params before it returns and no host memory after; may be captured.
+ *     Refusals, each before anything is enqueued or written, in this order: a NULL ctx; W or H outside the limits; params
+ *     NULL or its struct_size; n_tiles > 4096, tile_shift > 6 or a nonzero reserved_; the rules (as above: NULL or
+ *     struct_size, n_bands, a band, reserved_); a non-finite component of the pose; the paint box when d_paint is given; a
+ *     NULL d_color_in, d_keys, d_hit_aov, d_palette or d_color_out -- each VXRT_ERR_INVALID; then no world:
+ *     VXRT_ERR_NO_WORLD; then a streamed world, then a world axis longer than 2^24 voxels: VXRT_ERR_INVALID.
+ *   The cost.  Field: one launch and one memset; a lane owns four x-consecutive voxels and marches down y, one row word of
+ *     the world per 32 voxels and row, 16 rows of warm-up per y segment.  Frame: one launch (and a 16-byte memset with a
+ *     summary); per hit pixel up to under_depth + 2 solidity lookups, one palette entry and one texel. */
+#define VXRT_MATERIAL_MAX_BANDS 8
+#define VXRT_MATERIAL_NO_TILE 0xFFFFu
+typedef struct vxrt_material_band {
+    int32_t y_from;       /* the band holds the voxels with y >= y_from, below the next band's y_from */
+    uint8_t top, under, deep;  /* material ids, 1 .. 255 */
+    uint8_t under_depth;  /* 0 .. 15: how many voxels of `under` lie below a top voxel */
+} vxrt_material_band;
+typedef struct vxrt_material_rules {
+    uint32_t struct_size;
+    uint32_t n_bands;     /* 1 .. 8 */
+    vxrt_material_band bands[VXRT_MATERIAL_MAX_BANDS];
+    int32_t paint_origin[3], paint_dims[3]; /* the box P of d_paint; looked at only when d_paint is given */
+    int32_t reserved_;    /* 0 */
+} vxrt_material_rules;
+typedef struct vxrt_material_summary { uint32_t solid, painted, top, reserved; uint32_t hist[256]; } vxrt_material_summary;
+typedef struct vxrt_material {     /* a palette entry, 20 bytes; entry m belongs to material m */
+    float tint[3];
+    uint16_t tile_top, tile_side, tile_bottom; /* atlas tiles; >= n_tiles (VXRT_MATERIAL_NO_TILE): no texture */
+    uint16_t reserved;
+} vxrt_material;
+typedef struct vxrt_material_frame_params {
+    uint32_t struct_size;
+    int32_t ortho;
+    uint32_t n_tiles;      /* tiles in d_atlas, <= 4096 */
+    uint32_t tile_shift;   /* 0 .. 6: a tile is T x T texels, T = 1 << tile_shift */
+    vxrt_camera_pose cam;  /* the pose the frame was rendered with */
+    int32_t reserved_;     /* 0 */
+} vxrt_material_frame_params;
+typedef struct vxrt_material_frame_summary { uint32_t hit, painted, top, textured; } vxrt_material_frame_summary;
+int vxrt_material_field(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules *rules,
+                        const uint8_t *d_paint_or_null, uint8_t *d_materials, vxrt_material_summary *d_summary, void *stream);
+int vxrt_material_field_host(vxrt_ctx *ctx, const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules *rules,
+                             const uint8_t *paint_or_null, uint8_t *materials, vxrt_material_summary *summary);
+int vxrt_material_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color_in, const uint32_t *d_keys,
+                        const int64_t *d_hit_aov, const vxrt_material_rules *rules, const uint8_t *d_paint_or_null,
+                        const vxrt_material *d_palette /* 256 entries */, const uint32_t *d_atlas_or_null,
+                        const vxrt_material_frame_params *params, float *d_color_out, void *d_fb_or_null,
+                        uint8_t *d_material_aov_or_null, vxrt_material_frame_summary *d_summary_or_null, void *stream);
 
 /* ---- batch query.  Replaces VoxelRaytracer3D::Raytrace + kernel dispatch
  * (VoxelRT/VolumeRaytracer.cu:95-117,574-618).  Results follow the reference

@@ -40,6 +40,7 @@ EXPORTS = [
     "vxrt_rule_workspace_bytes", "vxrt_apply_rule", "vxrt_apply_rule_host",
     "vxrt_loose_workspace_bytes", "vxrt_loose_step", "vxrt_loose_step_host",
     "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame", "vxrt_light_frame",
+    "vxrt_material_field", "vxrt_material_field_host", "vxrt_material_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
@@ -174,6 +175,23 @@ class LightFrameParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("flags", C.c_uint32), ("outside_level", C.c_uint32),
                 ("sky_floor", C.c_float), ("block_color", C.c_float * 3), ("ao_curve", C.c_float * 4), ("cam", CameraPose),
                 ("box_origin", C.c_int32 * 3), ("box_dims", C.c_int32 * 3), ("reserved_", C.c_int32)]
+
+
+MATERIAL_MAX_BANDS, MATERIAL_NO_TILE, MATERIAL_MAX_TILES, MATERIAL_MAX_TILE_SHIFT = 8, 0xFFFF, 4096, 6
+
+
+class MaterialBand(C.Structure):
+    _fields_ = [("y_from", C.c_int32), ("top", C.c_uint8), ("under", C.c_uint8), ("deep", C.c_uint8), ("under_depth", C.c_uint8)]
+
+
+class MaterialRulesDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_bands", C.c_uint32), ("bands", MaterialBand * 8), ("paint_origin", C.c_int32 * 3),
+                ("paint_dims", C.c_int32 * 3), ("reserved_", C.c_int32)]
+
+
+class MaterialFrameParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("n_tiles", C.c_uint32), ("tile_shift", C.c_uint32),
+                ("cam", CameraPose), ("reserved_", C.c_int32)]
 
 
 class View(C.Structure):
@@ -344,6 +362,13 @@ def load() -> C.CDLL:
                                        C.POINTER(ReprojectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_light_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(LightFrameParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_material_field.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(MaterialRulesDesc), C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_material_field_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(MaterialRulesDesc),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_material_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MaterialRulesDesc),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MaterialFrameParams), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_trace_batch_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FrameStats)]
     for name in EXPORTS:  # every symbol the header declares must resolve

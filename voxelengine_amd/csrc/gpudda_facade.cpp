@@ -394,6 +394,17 @@ int VoxelRaytracer3D::LightField(const int32_t origin[3], const int32_t dims[3],
                                  channels, levels.data(), &summary);
 }
 
+int VoxelRaytracer3D::MaterialField(const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules& rules,
+                                    std::vector<uint8_t>& materials, vxrt_material_summary& summary, const uint8_t* paint)
+{
+    Flush();
+    // the vector is sized only for a box within the limits; the call itself refuses anything else, in its own order
+    const bool sized = dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 && (uint64_t)dims[0] * (uint64_t)dims[1] <= (1ull << 28) &&
+                       (uint64_t)dims[0] * (uint64_t)dims[1] * (uint64_t)dims[2] <= (1ull << 28);
+    materials.assign(sized ? (size_t)dims[0] * dims[1] * dims[2] : 1u, 0u);
+    return vxrt_material_field_host(ctx, origin, dims, &rules, paint, materials.data(), &summary);
+}
+
 int VoxelRaytracer3D::ApplyRule(const int32_t origin[3], const int32_t dims[3], const vxrt_rule& rule, std::vector<uint32_t>& bits,
                                 vxrt_rule_summary& summary, const uint32_t* mask)
 {

@@ -1,5 +1,5 @@
 // vxrt_api_query.hip -- the part of the C ABI (include/vxrt.h) that works on the resident world: the edit path (vxrt_edit_*),
-// every query family with its _host twin, and the entry points of the frame denoiser, the temporal filter and the light on frames.  No kernel is defined here: each family's
+// every query family with its _host twin, and the entry points of the frame denoiser, the temporal filter, the light on frames and the voxel materials.  No kernel is defined here: each family's
 // launcher is declared in its header and defined in its own .hip.
 #include "vxrt_collide.hpp"
 #include "vxrt_denoise.hpp"
@@ -10,6 +10,7 @@
 #include "vxrt_light.hpp"
 #include "vxrt_light_frame.hpp"
 #include "vxrt_lod.hpp"
+#include "vxrt_material.hpp"
 #include "vxrt_nav.hpp"
 #include "vxrt_place.hpp"
 #include "vxrt_reproject.hpp"
@@ -1281,6 +1282,118 @@ int vxrt_light_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_i
     A.terms = d_terms_or_null;
     A.summary = (uint32_t*)d_summary_or_null;
     VX_HIP(vxrt::light_frame(R, A, Wd, c->cus, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+// ---- voxel materials ---------------------------------------------------------------------------------------------------
+static const char* const kRulesRefusal[] = {"", "vxrt_material_rules missing or size mismatch", "material rules: n_bands 1 .. 8",
+                                            "material rules: bands[0].y_from INT32_MIN, y_from ascending, top, under and deep "
+                                            "1 .. 255, under_depth 0 .. 15",
+                                            "material rules: reserved_ must be 0"};
+static const char* const kPaintRefusal =
+    "material paint box: 1 <= paint_dims[k], their product <= 2^28, paint_origin + paint_dims <= 2^31 - 1";
+
+// the checks both field calls make after their NULL checks, in the order of include/vxrt.h
+static int material_field_ready(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules* rules,
+                                const void* paint)
+{
+    if (const int r = vxrt::material_rules_check(rules))
+        return fail(VXRT_ERR_INVALID, kRulesRefusal[r]);
+    if (paint && !vxrt::material_paint_ok(*rules))
+        return fail(VXRT_ERR_INVALID, kPaintRefusal);
+    if (const int r = vxrt::material_box_check(origin, dims))
+        return fail(VXRT_ERR_INVALID, r == 1 ? "material box dims: each at least 1, at most 2^28 voxels"
+                                             : "material box: origin + dims + 16 beyond 2^31 - 1");
+    return vxrt::world_ready(c, "queried");
+}
+
+int vxrt_material_field(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules* rules,
+                        const uint8_t* d_paint_or_null, uint8_t* d_materials, vxrt_material_summary* d_summary, void* stream)
+{
+    if (!c || !origin || !dims || !rules || !d_materials || !d_summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = material_field_ready(c, origin, dims, rules, d_paint_or_null))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::MaterialFieldArgs A{};
+    vxrt::material_field_args(A, *rules, origin, dims, vxrt::material_field_segment(dims, c->cus), d_materials);
+    A.paint = d_paint_or_null;
+    A.summary = (uint32_t*)d_summary;
+    VX_HIP(vxrt::material_field(A, vxrt::query_world(c), (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+int vxrt_material_field_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dims[3], const vxrt_material_rules* rules,
+                             const uint8_t* paint_or_null, uint8_t* materials, vxrt_material_summary* summary)
+{
+    if (!c || !origin || !dims || !rules || !materials || !summary)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = material_field_ready(c, origin, dims, rules, paint_or_null))
+        return rc;
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::HostScratch T;
+    const auto d_sum = T.out(sizeof(vxrt_material_summary), summary);
+    const auto d_mat = T.out((size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2], materials);
+    const auto d_paint = T.in(paint_or_null ? (size_t)rules->paint_dims[0] * (size_t)rules->paint_dims[1] * (size_t)rules->paint_dims[2] : 0,
+                              paint_or_null);
+    if (int rc = T.alloc(VXRT_ERR_NOMEM, "material_field_host"))
+        return rc;
+    vxrt::MaterialFieldArgs A{};
+    vxrt::material_field_args(A, *rules, origin, dims, vxrt::material_field_segment(dims, c->cus), d_mat);
+    A.paint = d_paint;
+    A.summary = (uint32_t*)(vxrt_material_summary*)d_sum;
+    VX_HIP(vxrt::material_field(A, vxrt::query_world(c), nullptr));
+    return T.finish();
+}
+
+int vxrt_material_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_in, const uint32_t* d_keys, const int64_t* d_hit_aov,
+                        const vxrt_material_rules* rules, const uint8_t* d_paint_or_null, const vxrt_material* d_palette,
+                        const uint32_t* d_atlas_or_null, const vxrt_material_frame_params* params, float* d_color_out, void* d_fb_or_null,
+                        uint8_t* d_material_aov_or_null, vxrt_material_frame_summary* d_summary_or_null, void* stream)
+{
+    // the order of include/vxrt.h
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    if (const int r = vxrt::material_frame_check(W, H, params, rules, d_paint_or_null != nullptr)) {
+        static const char* const refusal[] = {"", "", "material frame: 1 <= W, H <= 65535 and W * H <= 2^26",
+                                              "vxrt_material_frame_params missing or size mismatch",
+                                              "material frame: n_tiles <= 4096, tile_shift <= 6 (and reserved_ 0)"};
+        return fail(VXRT_ERR_INVALID, r <= 4 ? refusal[r] : r <= 8 ? kRulesRefusal[r - 4] : r == 9 ? "material frame: a camera pose with a non-finite component" : kPaintRefusal);
+    }
+    if (!d_color_in || !d_keys || !d_hit_aov || !d_palette || !d_color_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    if (int rc = vxrt::world_ready(c, "queried"))
+        return rc;
+    const vxrt::CollideWorld Wd = vxrt::query_world(c);
+    for (int k = 0; k < 3; ++k)
+        if ((uint32_t)Wd.dim[k] > vxrt::kDnMaxAxis)
+            return fail(VXRT_ERR_INVALID, "material frame: a world axis longer than 2^24 voxels");
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::RenderArgs R;
+    memset(&R, 0, sizeof(R));
+    vxrt::camera_args(c, W, H, R);
+    R.ortho = params->ortho ? 1 : 0;
+    R.origin = vxrt::f3{params->cam.origin[0], params->cam.origin[1], params->cam.origin[2]};
+    R.fwd = vxrt::f3{params->cam.fwd[0], params->cam.fwd[1], params->cam.fwd[2]};
+    R.up = vxrt::f3{params->cam.up[0], params->cam.up[1], params->cam.up[2]};
+    R.right = vxrt::f3{params->cam.right[0], params->cam.right[1], params->cam.right[2]};
+    vxrt::MaterialFrameArgs A{};
+    A.rules = *rules;
+    A.color_in = d_color_in;
+    A.keys = d_keys;
+    A.hit = (const long long*)d_hit_aov;
+    A.paint = d_paint_or_null;
+    A.palette = d_palette;
+    A.atlas = d_atlas_or_null;
+    A.color_out = d_color_out;
+    A.fb = (uint32_t*)d_fb_or_null;
+    A.aov = d_material_aov_or_null;
+    A.summary = (uint32_t*)d_summary_or_null;
+    A.W = W;
+    A.H = H;
+    A.n_tiles = params->n_tiles;
+    A.tile_shift = params->tile_shift;
+    VX_HIP(vxrt::material_frame(R, A, Wd, c->cus, (hipStream_t)stream));
     return VXRT_OK;
 }
 

@@ -208,7 +208,9 @@ struct LfPixel {
     bool toward, hit;
 };
 
-__host__ __device__ inline LfPixel lf_load(const LightFrameArgs& A, const CollideWorld& Wd, uint32_t x, uint32_t y)
+// (Args: what a frame stage's launch reads -- color_in, keys, hit and W; vxrt_material.hpp's stage loads its pixels here too)
+template <class Args>
+__host__ __device__ inline LfPixel lf_load(const Args& A, const CollideWorld& Wd, uint32_t x, uint32_t y)
 {
     const uint32_t i = y * A.W + x;  // W * H <= 2^26: every index fits 32 bits
     VXRT_LF_CHECK(kLfColorIn, 3u * i + 2u);
@@ -238,6 +240,23 @@ __host__ __device__ inline LfPixel lf_load(const LightFrameArgs& A, const Collid
     return P;
 }
 
+// The position (u, w) of hit pixel P on its face, on the axes (b, c), under the primary ray (o, d): clamped to 0 .. 1, the
+// centre of the face where the ray does not give one
+__host__ __device__ inline void lf_position(const LfPixel& P, const float o[3], const float d[3], float& u, float& w)
+{
+    const uint32_t a = P.a;
+    const float pl = (float)(P.key & 0x1FFFFFFu);
+    // (selects, not indexing: the vectors stay in registers)
+    const float oa = a == 0u ? o[0] : a == 1u ? o[1] : o[2], da = a == 0u ? d[0] : a == 1u ? d[1] : d[2];
+    const float ob = a == 0u ? o[1] : o[0], db = a == 0u ? d[1] : d[0], oc = a >= 2u ? o[1] : o[2], dc = a >= 2u ? d[1] : d[2];
+    const float vb = (float)(a == 0u ? P.v[1] : P.v[0]), vc = (float)(a >= 2u ? P.v[1] : P.v[2]);
+    const float t = (pl - oa) / da;
+    u = lf_clamp01((ob + t * db) - vb);
+    w = lf_clamp01((oc + t * dc) - vc);
+    if (da == 0.0f || !lf_finite(t) || !lf_finite(u) || !lf_finite(w))
+        u = w = 0.5f;
+}
+
 // Pixel (x, y), loaded into P, with primary ray (o, d) and the corners F of its face (a miss: F is not looked at): its
 // colour, terms and BGRA8 pixel stored; returns the kLf* bits of the counters it adds to.
 __host__ __device__ inline uint32_t lf_shade(const LightFrameArgs& A, uint32_t x, uint32_t y, const LfPixel& P, const LfFace& F,
@@ -247,16 +266,8 @@ __host__ __device__ inline uint32_t lf_shade(const LightFrameArgs& A, uint32_t x
     float out[3] = {P.c[0], P.c[1], P.c[2]}, term[3] = {0.0f, 0.0f, 0.0f};
     uint32_t bits = 0u;
     if (P.hit) {
-        const uint32_t a = P.a;
-        const float pl = (float)(P.key & 0x1FFFFFFu);
-        // (selects, not indexing: the vectors stay in registers)
-        const float oa = a == 0u ? o[0] : a == 1u ? o[1] : o[2], da = a == 0u ? d[0] : a == 1u ? d[1] : d[2];
-        const float ob = a == 0u ? o[1] : o[0], db = a == 0u ? d[1] : d[0], oc = a >= 2u ? o[1] : o[2], dc = a >= 2u ? d[1] : d[2];
-        const float vb = (float)(a == 0u ? P.v[1] : P.v[0]), vc = (float)(a >= 2u ? P.v[1] : P.v[2]);
-        const float t = (pl - oa) / da;
-        float u = lf_clamp01((ob + t * db) - vb), w = lf_clamp01((oc + t * dc) - vc);
-        if (da == 0.0f || !lf_finite(t) || !lf_finite(u) || !lf_finite(w))
-            u = w = 0.5f;
+        float u, w;
+        lf_position(P, o, d, u, w);
         const float S = lf_bilinear(F.ls, u, w) / 15.0f, Bk = lf_bilinear(F.lb, u, w) / 15.0f, Ao = lf_bilinear(F.ao, u, w);
         const float ks = A.sky_floor + (1.0f - A.sky_floor) * S;
 #pragma unroll

@@ -987,6 +987,104 @@ class Context:
                     C.byref(p), _ptr(out), _ptr(fb), _ptr(terms_out), _ptr(words))
         return LitFrame(dims=(width, height), color=out, terms=terms_out, _summary=words, _stream=call.s)
 
+    # ---- voxel materials (extension, include/vxrt.h) -------------------------------------------------------------------------
+    def _paint(self, call, paint, paint_box):
+        """(device bytes or None, box) of a paint argument: a MaterialField (its bytes and its box), a device uint8 tensor or a
+        numpy uint8 [x, y, z] grid over ``paint_box`` = (origin, dims), or None"""
+        if isinstance(paint, MaterialField):
+            paint, paint_box = paint.materials, (paint.origin, paint.dims)
+        if paint_box is None:
+            paint_box = ((0, 0, 0), (1, 1, 1))
+        origin, dims = _box(*paint_box)
+        if paint is None:
+            return None, (origin, dims)
+        if isinstance(paint, np.ndarray):
+            if paint.shape != tuple(dims):
+                raise ValueError("paint: a uint8 [x, y, z] grid of the paint box's dims")
+            host = np.ascontiguousarray(np.asarray(paint, np.uint8).transpose(2, 1, 0)).reshape(-1)  # region order
+            return call.upload_bytes(host), (origin, dims)
+        nvox = max(dims[0], 0) * max(dims[1], 0) * max(dims[2], 0)
+        return call.reads(call.fits(paint, nvox, 1, "paint: a contiguous device tensor of one byte per voxel of the paint box")), (origin, dims)
+
+    def material_field(self, origin, dims, rules: "MaterialRules", paint=None, paint_box=None, out=None,
+                       stream: int | None = None) -> "MaterialField":
+        """The material bytes of the box ``origin`` .. ``origin + dims - 1`` (include/vxrt.h, vxrt_material_field): 0 for an
+        empty voxel, else the paint byte where ``paint`` has one, else the strata rule of ``rules``.  ``paint``: a
+        MaterialField, a device uint8 tensor of one byte per voxel of ``paint_box`` = (origin, dims) in region order, a numpy
+        uint8 [x, y, z] grid over it, or None.  Asynchronous on ``stream`` (default: torch's current stream).  ``out``: a
+        device tensor of one-byte elements to write to (default: a new one).  Returns a MaterialField; reading its
+        ``summary`` waits for the call."""
+        call = _Call(self, stream)
+        origin, dims = _box(origin, dims)
+        d_paint, pbox = self._paint(call, paint, paint_box)
+        r = rules._c(pbox)
+        ok = all(d >= 1 for d in dims) and dims[0] * dims[1] * dims[2] <= 1 << 28
+        nvox = dims[0] * dims[1] * dims[2] if ok else 0
+        out = call.out(nvox, 1, call.torch.uint8, out,
+                       "out: a contiguous device tensor of at least dims[0] * dims[1] * dims[2] one-byte elements")
+        summary = call.summary(260)
+        call.launch(self._L.vxrt_material_field, _i3(origin), _i3(dims), C.byref(r), _ptr(d_paint), _ptr(out), _ptr(summary))
+        return MaterialField(origin=origin, dims=dims, materials=out.view(-1)[:nvox], _summary=summary, _stream=call.s)
+
+    def material_field_host(self, origin, dims, rules: "MaterialRules", paint=None, paint_box=None) -> "MaterialField":
+        """material_field through the synchronous host call (vxrt_material_field_host): ``paint`` a numpy uint8 [x, y, z] grid
+        over ``paint_box`` or None; ``materials`` is a numpy uint8 [x, y, z] grid."""
+        origin, dims = _box(origin, dims)
+        pbox = _box(*(paint_box or ((0, 0, 0), (1, 1, 1))))
+        host = None
+        if paint is not None:
+            if tuple(np.shape(paint)) != tuple(pbox[1]):
+                raise ValueError("paint: a uint8 [x, y, z] grid of the paint box's dims")
+            host = np.ascontiguousarray(np.asarray(paint, np.uint8).transpose(2, 1, 0)).reshape(-1)
+        r = rules._c(pbox)
+        ok = all(d >= 1 for d in dims) and dims[0] * dims[1] * dims[2] <= 1 << 28
+        nvox = dims[0] * dims[1] * dims[2] if ok else 0
+        out = np.zeros(max(nvox, 1), np.uint8)
+        summary = np.zeros(260, np.uint32)
+        N.check(self._L.vxrt_material_field_host(self._h, _i3(origin), _i3(dims), C.byref(r), host.ctypes.data if host is not None else None,
+                                                 out.ctypes.data, summary.ctypes.data))
+        return MaterialField(origin=origin, dims=dims, materials=_grid(out, dims) if nvox else out[:0], _summary=summary, _stream=None)
+
+    def material_frame(self, color, keys, hit_aov, cam, rules: "MaterialRules", palette: "Palette", paint=None, paint_box=None,
+                       ortho: bool = False, out=None, fb=None, material_aov=False, summary: bool = True, stream: int | None = None):
+        """Albedo and textures on a frame (include/vxrt.h, vxrt_material_frame): ``color``, ``keys``, ``hit_aov`` and ``cam``
+        as Context.light_frame takes them.  Every hit pixel's colour is multiplied with the tint of the material of the voxel
+        it shows (``rules``, ``paint`` as in material_field) and with the texel of that material's tile for the face's class
+        (top, side, bottom) in ``palette``'s atlas.  In a frame pipeline the stage runs after denoise_frame and before
+        light_frame.  Asynchronous on ``stream`` (default: torch's current stream).  ``out``: float32 (height, width, 3), may
+        be ``color`` itself (default: a new tensor); ``fb``: optional uint8 (height, width, 4) BGRA8 frame written as well;
+        ``material_aov``: True, or a uint8 (height, width) device tensor to write to: also return the material id per pixel.
+        Returns a MaterialFrame: ``color``, ``materials`` and, with ``summary``, a lazily read MaterialFrameSummary."""
+        call = _Call(self, stream)
+        torch = call.torch
+        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
+            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
+        height, width = int(color.shape[0]), int(color.shape[1])
+        n = width * height
+        call.reads(color)
+        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
+        call.reads(call.fits(hit_aov, n, 8, "hit_aov: a contiguous device tensor of width * height eight-byte elements"))
+        d_paint, pbox = self._paint(call, paint, paint_box)
+        r = rules._c(pbox)
+        d_palette, d_atlas = palette._device(call)
+        if out is None:
+            out = torch.empty_like(color)
+        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
+            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
+        if fb is not None:
+            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        if material_aov is True or material_aov is False:
+            aov = torch.empty((height, width), dtype=torch.uint8, device=call.dev) if material_aov else None
+        else:
+            aov = call.fits(material_aov, n, 1, "material_aov: a contiguous uint8 device tensor (height, width)")
+        words = call.summary(4) if summary else None
+        p = N.MaterialFrameParams(struct_size=C.sizeof(N.MaterialFrameParams), ortho=1 if ortho else 0, n_tiles=_u32(palette.n_tiles),
+                                  tile_shift=_u32(palette.tile_shift))
+        p.cam.origin, p.cam.fwd, p.cam.up, p.cam.right = (_f3(v) for v in cam)
+        call.launch(self._L.vxrt_material_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), _ptr(hit_aov), C.byref(r),
+                    _ptr(d_paint), _ptr(d_palette), _ptr(d_atlas), C.byref(p), _ptr(out), _ptr(fb), _ptr(aov), _ptr(words))
+        return MaterialFrame(dims=(width, height), color=out, materials=aov, _summary=words, _stream=call.s)
+
     # ---- occupancy LOD (extension, include/vxrt.h) ----------------------------------------------------------------------
     def lod_workspace_bytes(self, dims, shift: int) -> int:
         """vxrt_lod_workspace_bytes: the workspace of one downsample call, 0 outside the contract"""
@@ -1972,6 +2070,130 @@ class LitFrame(_LazyResult):
         return None if self._summary is None else LightFrameSummary(*self._words()[:4])
 
 
+class MaterialRules(NamedTuple):
+    """vxrt_material_rules: ``bands`` a sequence of up to eight (y_from, top, under, deep, under_depth) rows in ascending
+    y_from, the first None or -2^31 -- the voxels of a band with no solid voxel above them get ``top``, those with 1 ..
+    ``under_depth`` (0 .. 15) above them ``under``, the rest ``deep``; material ids are 1 .. 255"""
+    bands: tuple
+
+    def _c(self, paint_box=((0, 0, 0), (1, 1, 1))) -> "N.MaterialRulesDesc":
+        rows = list(self.bands)
+        r = N.MaterialRulesDesc(struct_size=C.sizeof(N.MaterialRulesDesc), n_bands=_u32(len(rows)))
+        for i, (y_from, top, under, deep, depth) in enumerate(rows[:N.MATERIAL_MAX_BANDS]):
+            b = r.bands[i]
+            b.y_from = -(1 << 31) if y_from is None else int(y_from)
+            # (a value outside a byte is the library's to refuse: 0 is no material, 255 no depth)
+            b.top, b.under, b.deep = (int(v) if 0 <= int(v) <= 255 else 0 for v in (top, under, deep))
+            b.under_depth = int(depth) if 0 <= int(depth) <= 255 else 255
+        r.paint_origin, r.paint_dims = _i3(paint_box[0]), _i3(paint_box[1])
+        return r
+
+
+class Palette:
+    """The 256 entries of vxrt_material and the atlas: ``tints`` float32 (256, 3) (entry m belongs to material m; default
+    white), ``tiles`` uint16 (256, 3) holding the atlas tile of the top, side and bottom faces (default MATERIAL_NO_TILE: no
+    texture), ``atlas`` an optional uint8 array [n_tiles, T, T, 4] of RGBA8 texels, rows top-down, T a power of two up to 64.
+    The first material_frame call with a palette copies it to the device; to capture such a call in a graph, make one eager
+    call with the same Palette first."""
+
+    def __init__(self, tints=None, tiles=None, atlas=None):
+        self.tints = np.ones((256, 3), np.float32) if tints is None else np.ascontiguousarray(tints, np.float32).reshape(256, 3)
+        self.tiles = np.full((256, 3), N.MATERIAL_NO_TILE, np.uint16) if tiles is None else np.ascontiguousarray(tiles, np.uint16).reshape(256, 3)
+        self.atlas = None
+        self._dev = {}
+        self.n_tiles, self.tile_shift = 0, 0
+        if atlas is not None:
+            a = np.ascontiguousarray(atlas, np.uint8)
+            if a.ndim != 4 or a.shape[3] != 4 or a.shape[1] != a.shape[2] or a.shape[1] < 1 or a.shape[1] & (a.shape[1] - 1):
+                raise ValueError("atlas: uint8 [n_tiles, T, T, 4] with T a power of two")
+            self.atlas, self.n_tiles, self.tile_shift = a, int(a.shape[0]), int(a.shape[1]).bit_length() - 1
+
+    def set(self, material: int, tint=(1.0, 1.0, 1.0), top=N.MATERIAL_NO_TILE, side=None, bottom=None) -> "Palette":
+        """entry ``material``: its tint and its tiles (``side`` and ``bottom`` default to ``top``)"""
+        self.tints[material] = tint
+        self.tiles[material] = (top, top if side is None else side, top if bottom is None else bottom)
+        self._dev = {}
+        return self
+
+    def _device(self, call: "_Call") -> tuple:
+        """(entries, atlas or None) as device tensors on the call's device: uploaded by the first call that uses the palette
+        there and kept, so that later calls -- a captured one among them -- copy nothing.  ``set`` drops them; an array
+        changed in place needs a new Palette."""
+        if call.dev not in self._dev:
+            atlas = self.atlas_words()
+            self._dev[call.dev] = (call.upload(self.entries()), call.upload(atlas) if atlas is not None else None)
+        return tuple(None if t is None else call.reads(t) for t in self._dev[call.dev])
+
+    def entries(self) -> np.ndarray:
+        """the 256 entries as the library reads them: 5 words each"""
+        e = np.zeros((256, 5), np.uint32)
+        e[:, :3] = self.tints.view(np.uint32)
+        t = self.tiles.astype(np.uint32)
+        e[:, 3] = t[:, 0] | t[:, 1] << 16
+        e[:, 4] = t[:, 2]
+        return e
+
+    def atlas_words(self):
+        """the atlas as packed texels (r in the low byte), or None"""
+        return None if self.atlas is None else self.atlas.reshape(-1, 4).view(np.uint32).reshape(-1).copy()
+
+
+class MaterialSummary(NamedTuple):
+    """vxrt_material_summary: solid voxels of the box, those whose material came from paint, those with no solid voxel above
+    them, and the voxels by output byte (hist[0]: the empty ones)"""
+    solid: int
+    painted: int
+    top: int
+    hist: tuple
+
+
+@dataclass
+class MaterialField(_LazyResult):
+    """The result of Context.material_field: ``materials`` one byte per voxel in region order on the device (a numpy uint8
+    [x, y, z] grid from material_field_host), ``summary`` a MaterialSummary."""
+    origin: tuple
+    dims: tuple
+    materials: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> MaterialSummary:
+        """the summary; for a device field this waits for the call's stream"""
+        v = self._words()
+        return MaterialSummary(v[0], v[1], v[2], tuple(v[4:260]))
+
+    def grid(self) -> np.ndarray:
+        """the bytes as a numpy uint8 [x, y, z] grid (a device field is copied to the host)"""
+        return self._xyz(self.materials, np.uint8)
+
+
+class MaterialFrameSummary(NamedTuple):
+    """vxrt_material_frame_summary: hit pixels, and of them those whose material came from paint, those that show a voxel
+    with no solid voxel above it, and those that loaded a texel"""
+    hit: int
+    painted: int
+    top: int
+    textured: int
+
+
+@dataclass
+class MaterialFrame(_LazyResult):
+    """The result of Context.material_frame: ``color`` float32 (height, width, 3), ``materials`` uint8 (height, width) or
+    None, device tensors; ``dims`` is (width, height).  ``summary`` is a MaterialFrameSummary, or None when the call was made
+    without one."""
+    dims: tuple
+    color: object
+    materials: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> MaterialFrameSummary | None:
+        """the summary; the first read waits for the call's stream"""
+        return None if self._summary is None else MaterialFrameSummary(*self._words()[:4])
+
+
 class NavAgent(NamedTuple):
     """vxrt_nav_agent: a width x height x width box of cells standing on its minimum corner, that steps up at most
     ``climb`` cells and down at most ``drop``"""
@@ -2124,6 +2346,11 @@ class _Call:
         """a host array of four-byte values as an int32 device tensor of its shape, copied on torch's current stream"""
         self._uploaded = self._uploaded or a.size > 0
         return self.reads(self.torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(self.dev))
+
+    def upload_bytes(self, a: np.ndarray):
+        """a host array of bytes as a uint8 device tensor of its shape, copied on torch's current stream"""
+        self._uploaded = self._uploaded or a.size > 0
+        return self.reads(self.torch.from_numpy(np.ascontiguousarray(a, np.uint8).copy()).to(self.dev))
 
     def launch(self, fn, *args) -> None:
         """``fn(ctx, *args, stream)`` checked.  An upload was queued on torch's current stream, which need not be the call's:
