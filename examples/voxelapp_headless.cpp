@@ -75,6 +75,11 @@
 // over sand over stone), each with a tile of an 8 x 8 atlas made on the host from an integer hash (grass has a side tile of
 // its own) -- with one line "materials frame N hit .. painted .. top .. textured ..".  The dumped PPMs are the coloured frames.
 // The same restrictions as for the denoiser.
+// A line "frame sky [clouds]" switches the sky on from that frame (vxrt_sky_frame; "frame sky off" switches it off again): as the
+// last stage, after the light, every pixel that misses the world gets a sky -- a built-in daytime preset whose sun stands in the
+// environment's light direction, with "clouds" also a layer of clouds at twice the world's height -- and every hit pixel fades
+// into it with its distance, with one line "sky frame N miss .. ground .. sun .. cloud .. fogged ..".  The dumped PPMs are the
+// finished frames.  The same restrictions as for the denoiser.
 // A line "frame rule x0 y0 z0 x1 y1 z1 n6|n18|n26 born_hex survive_hex iterations box|world" applies a neighbour-count rule
 // (VoxelRaytracer3D::ApplyRule) to the box of the inclusive corners (x0, y0, z0) .. (x1, y1, z1) -- born_hex / survive_hex: bit
 // c set = an empty voxel is born / a solid voxel survives with c solid neighbours -- stamps the result (replace) and prints one
@@ -166,6 +171,11 @@ int main(int argc, char** argv)
         bool on;
     };
     std::vector<MaterialsLine> materials_lines;
+    struct SkyLine {
+        int frame;
+        bool on, clouds;
+    };
+    std::vector<SkyLine> sky_lines;
     if (argc > 12 && std::string(argv[12]) != "-") {
         std::ifstream in(argv[12]);
         if (!in) {
@@ -202,6 +212,21 @@ int main(int argc, char** argv)
                     }
                     ml.on = got == 2;
                     materials_lines.push_back(ml);
+                    continue;
+                }
+            }
+            {
+                SkyLine sl{0, true, false};
+                char what[12] = "", arg[8] = "";
+                const int got = std::sscanf(line.c_str(), "%d %11s %7s", &sl.frame, what, arg);
+                if (got >= 2 && std::string(what) == "sky") {
+                    if (got == 3 && std::string(arg) != "off" && std::string(arg) != "clouds") {
+                        std::cerr << "bad sky line: " << line << std::endl;
+                        return 2;
+                    }
+                    sl.on = !(got == 3 && std::string(arg) == "off");
+                    sl.clouds = got == 3 && std::string(arg) == "clouds";
+                    sky_lines.push_back(sl);
                     continue;
                 }
             }
@@ -814,10 +839,12 @@ int main(int argc, char** argv)
     vxrt_material* d_palette = nullptr;
     uint32_t* d_atlas = nullptr;
     vxrt_material_frame_summary* d_mat_sum = nullptr;
-    if (!denoise_lines.empty() || !temporal_lines.empty() || !lit_lines.empty() || !materials_lines.empty()) {
+    float* d_sky = nullptr;  // the finished frame: as d_lit, beside the frame's own colours
+    vxrt_sky_summary* d_sky_sum = nullptr;
+    if (!denoise_lines.empty() || !temporal_lines.empty() || !lit_lines.empty() || !materials_lines.empty() || !sky_lines.empty()) {
         const size_t n = (size_t)width * height;
         if (batch > 1 || in_flight >= 2 || shade_mode == 1 || vxrt_denoise_workspace_bytes(width, height) == 0) {
-            std::cerr << "denoise, temporal, lit, materials: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
+            std::cerr << "denoise, temporal, lit, materials, sky: whole frames only (shaded=0 or 2, views_per_launch=1, frames_in_flight=1)" << std::endl;
             return 2;
         }
         if (hipMalloc((void**)&d_color, n * 12) != hipSuccess || hipMalloc((void**)&d_hit, n * 8) != hipSuccess ||
@@ -830,6 +857,9 @@ int main(int argc, char** argv)
             return 1;
         if (!lit_lines.empty() &&
             (hipMalloc((void**)&d_lit, n * 12) != hipSuccess || hipMalloc((void**)&d_lf_sum, sizeof(vxrt_light_frame_summary)) != hipSuccess))
+            return 1;
+        if (!sky_lines.empty() &&
+            (hipMalloc((void**)&d_sky, n * 12) != hipSuccess || hipMalloc((void**)&d_sky_sum, sizeof(vxrt_sky_summary)) != hipSuccess))
             return 1;
         if (!materials_lines.empty()) {
             // grass, dirt, stone, sand, snow (materials 1 .. 5): white tints, tiles 0 .. 4, and tile 5 on the sides of grass
@@ -885,6 +915,34 @@ int main(int argc, char** argv)
     std::memcpy(lf.ao_curve, lf_curve, sizeof lf_curve);
     bool lit = false;
     vxrt_light_frame_summary lf_sum{};
+    // the daytime preset (the defaults of the Python mirror's Sky), its sun in the environment's light direction
+    vxrt_sky_params sp{};
+    sp.struct_size = sizeof(vxrt_sky_params);
+    sp.glow_log2 = 3;
+    sp.octaves = 4;
+    sp.seed = 1;
+    const float sky_colours[5][3] = {{0.18f, 0.38f, 0.80f}, {0.70f, 0.82f, 0.95f}, {0.30f, 0.28f, 0.25f}, {1.0f, 0.95f, 0.80f}, {1.0f, 1.0f, 1.0f}};
+    float* const sky_slots[5] = {sp.zenith, sp.horizon, sp.ground, sp.sun_color, sp.cloud_color};
+    for (int k = 0; k < 5; ++k)
+        std::memcpy(sky_slots[k], sky_colours[k], sizeof sky_colours[k]);
+    sp.sun_dir[0] = env.LightDirection.x;
+    sp.sun_dir[1] = env.LightDirection.y;
+    sp.sun_dir[2] = env.LightDirection.z;
+    sp.glow_strength = 0.35f;
+    sp.ground_fade = 4.0f;
+    sp.cos_inner = 0.9995f;
+    sp.cos_outer = 0.9985f;
+    sp.cloud_y = 2.0f * (float)(wy ? wy : edge);
+    sp.cloud_scale = 0.004f;
+    sp.cloud_max_t = 20000.0f;
+    sp.cloud_cover = 0.5f;
+    sp.cloud_sharp = 3.0f;
+    sp.cloud_fade = 6.0f;
+    sp.fog_start = 64.0f;
+    sp.fog_density = 0.0015f;
+    sp.fog_max = 0.85f;
+    bool sky = false;
+    vxrt_sky_summary sky_sum{};
     for (int i = 0; batch <= 1 && in_flight < 2 && i < nframes; ++i) {
         apply_edits(i, i + 1);
         for (const DenoiseLine& l : denoise_lines)
@@ -900,6 +958,11 @@ int main(int argc, char** argv)
         for (const MaterialsLine& l : materials_lines)
             if (l.frame == i)
                 materials = l.on;
+        for (const SkyLine& l : sky_lines)
+            if (l.frame == i) {
+                sky = l.on;
+                sp.flags = l.clouds ? VXRT_SKY_CLOUDS : 0u;
+            }
         for (const LitLine& l : lit_lines)
             if (l.frame == i) {
                 lit = l.on;
@@ -932,7 +995,7 @@ int main(int argc, char** argv)
         pose_for(i);
         auto f0 = std::chrono::high_resolution_clock::now();
         GetDirections(cam_eular, &cam_forward, &cam_up, &cam_right);
-        if (dn.iterations > 0 || temporal || lit || materials) {
+        if (dn.iterations > 0 || temporal || lit || materials || sky) {
             // the frame with its AOVs through the C ABI (the facade's RenderScreen has no AOV arguments), then keys and filter
             vxrt_ctx* c = raytracer->Context();
             const float o[3] = {cam_pos.x, cam_pos.y, cam_pos.z}, f[3] = {cam_forward.x, cam_forward.y, cam_forward.z},
@@ -1008,6 +1071,21 @@ int main(int argc, char** argv)
                 }
                 (void)hipMemcpy(&lf_sum, d_lf_sum, sizeof(lf_sum), hipMemcpyDeviceToHost);
             }
+            if (sky) {
+                for (int k = 0; k < 3; ++k) {
+                    sp.cam.origin[k] = o[k];
+                    sp.cam.fwd[k] = f[k];
+                    sp.cam.up[k] = u[k];
+                    sp.cam.right[k] = r[k];
+                }
+                if (vxrt_sky_frame(c, width, height, lit ? d_lit : materials ? d_mat : d_color, d_keys, &sp, d_sky, d_pixels, d_sky_sum, nullptr) !=
+                        VXRT_OK ||
+                    vxrt_synchronize(c) != VXRT_OK) {
+                    std::cerr << "sky, frame " << i << ": " << vxrt_last_error() << std::endl;
+                    return 3;
+                }
+                (void)hipMemcpy(&sky_sum, d_sky_sum, sizeof(sky_sum), hipMemcpyDeviceToHost);
+            }
         } else {
             RenderScreen(raytracer, width, height, d_pixels, cam_pos, cam_forward, cam_up, cam_right);
         }
@@ -1019,6 +1097,9 @@ int main(int argc, char** argv)
             std::printf("materials frame %d hit %u painted %u top %u textured %u\n", i, mat_sum.hit, mat_sum.painted, mat_sum.top, mat_sum.textured);
         if (lit)
             std::printf("lit frame %d hit %u in_box %u occluded %u dark %u\n", i, lf_sum.hit, lf_sum.in_box, lf_sum.occluded, lf_sum.dark);
+        if (sky)
+            std::printf("sky frame %d miss %u ground %u sun %u cloud %u fogged %u\n", i, sky_sum.miss, sky_sum.ground, sky_sum.sun, sky_sum.cloud,
+                        sky_sum.fogged);
         (void)hipMemcpy(pixels.data(), d_pixels, pixels.size() * sizeof(BGRA8888), hipMemcpyDeviceToHost);
         if (dn.iterations > 0) {
             std::vector<uint32_t> keys((size_t)width * height);
@@ -1075,6 +1156,8 @@ int main(int argc, char** argv)
     (void)hipFree(d_palette);
     (void)hipFree(d_atlas);
     (void)hipFree(d_mat_sum);
+    (void)hipFree(d_sky);
+    (void)hipFree(d_sky_sum);
     (void)hipFree(d_hit);
     (void)hipFree(d_keys_pair[0]);
     (void)hipFree(d_keys_pair[1]);

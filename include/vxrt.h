@@ -1457,6 +1457,88 @@ int vxrt_material_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_co
                         const vxrt_material_frame_params *params, float *d_color_out, void *d_fb_or_null,
                         uint8_t *d_material_aov_or_null, vxrt_material_frame_summary *d_summary_or_null, void *stream);
 
+/* ---- sky on frames -- an EXTENSION (the reference's to-do item "Sky rendering", README.md:14-24; its setPixelColor stores the
+ * primary ray's direction as the colour of a pixel that misses the world, Renderer.cu:254-257, and every stage above copies
+ * that colour).  This call gives every miss pixel a sky -- a gradient from horizon to zenith, a ground colour below the
+ * horizon, a sun glow and a sun disc, a layer of value-noise clouds on a plane -- and fades every hit pixel towards the sky
+ * behind it with the distance of its surface point (aerial perspective).  A post-process over buffers the renderer and
+ * vxrt_frame_guides already write; the render launches know nothing of it.  In a frame pipeline it is the last stage:
+ * render with AOVs, guide keys, reproject, a-trous, materials, light, sky.  The colour AOV is the colour handed to the pixel
+ * store, after the tonemap: the stage works in display space, 0 .. 1.
+ *   Frames.  Whole frames with the denoiser's limits: 1 <= W, H <= 65535 and W * H <= 2^26, pixel (x, y) at index x + W * y.
+ *     d_keys are the keys vxrt_frame_guides gives for params->cam and params->ortho.  No world is needed: the keys carry the
+ *     geometry.  The camera constants are the context's FOV and ortho window at the time of the call and params->ortho.
+ *   Arithmetic.  All float arithmetic is binary32, in the order written, without contraction: add, subtract, multiply, IEEE
+ *     divide, compare, select, floorf and conversions between int32 and float; the one square root is taken on the host.
+ *     dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z;  clamp01(x) = x < 0 ? 0 : x > 1 ? 1 : x (a NaN stays);
+ *     mix(a, b, w) = a + (b - a) * w (one subtract, one multiply, one add);  smooth(x) = (x * x) * (3 - 2 * x).
+ *   Ray.  (o, d) is the pixel's primary ray under params->cam exactly as vxrt_render forms it (the ray of vxrt_frame_guides);
+ *     h = d.y (+y is up).
+ *   Sun.  s = sun_dir / n per component with n = sqrtf(dot(sun_dir, sun_dir)), once on the host; sd = dot(d, s).
+ *   base(d), the sky without disc and clouds, per channel:
+ *     h >= 0:  a = 1 - h; a2 = a * a; a4 = a2 * a2; c = mix(zenith, horizon, a4).  g = sd > 0 ? sd : 0, then g = g * g
+ *       glow_log2 times; c = c + sun_color * (glow_strength * g).
+ *     otherwise (h < 0, or a NaN):  c = mix(horizon, ground, clamp01((-h) * ground_fade)).  No glow.
+ *   Miss pixel (key 0).  c = base(d); what d_color_in holds there is not looked at.  For h >= 0 two further steps:
+ *     Disc.  e = smooth(clamp01((sd - cos_outer) / (cos_inner - cos_outer))); c = mix(c, sun_color, e).
+ *     Clouds, only with VXRT_SKY_CLOUDS, and only when every condition of this list holds (else the pixel has no cloud):
+ *       h > 0 and o.y < cloud_y;  t = (cloud_y - o.y) / h is finite and t <= cloud_max_t;
+ *       px = (o.x + t * d.x) * cloud_scale + cloud_offset[0] and pz = (o.z + t * d.z) * cloud_scale + cloud_offset[1] satisfy
+ *       -2^30 < px * S < 2^30 and likewise pz, with S = (float)2^(octaves - 1): every cell of every octave converts to int32
+ *       exactly.
+ *       n = 0; for i = 0 .. octaves - 1 in ascending order: n = n + (float)2^-(i+1) * vnoise(px * (float)2^i, pz * (float)2^i,
+ *       seed + i).  dens = clamp01((n - (1 - cloud_cover)) * cloud_sharp); alpha = dens * clamp01(h * cloud_fade);
+ *       c = mix(c, cloud_color, alpha).
+ *     vnoise(qx, qz, k): fx = floorf(qx), ix = (int32)fx, wx = smooth(qx - fx); fz, iz and wz likewise.  With
+ *       v(i, j) = value(ix + i, iz + j, k): x0 = mix(v(0,0), v(1,0), wx); x1 = mix(v(0,1), v(1,1), wx); the result is
+ *       mix(x0, x1, wz).
+ *     value(i, j, k), all in uint32 wraparound arithmetic: m = (uint32)i * 0x8DA6B343 ^ (uint32)j * 0xD8163841 ^
+ *       k * 0xCB1AB31F;  m ^= m >> 16; m *= 0x7FEB352D;  m ^= m >> 15; m *= 0x846CA68B;  m ^= m >> 16;  the value is
+ *       (float)(m >> 8) * 2^-24, in 0 .. 1 - 2^-24.
+ *   Hit pixel (key != 0): aerial perspective.  a = the key's axis (a field above 2 reads as 2), pl = (float)plane,
+ *     t = (pl - o[a]) / d[a].  If d[a] == 0, or t is not finite, or t < 0, the colour is copied.  Otherwise
+ *     u = t - fog_start; u = u > 0 ? u : 0; x = u * fog_density; f = x / (1 + x); f = f < fog_max ? f : fog_max (a NaN f, from
+ *     an infinite x, becomes fog_max).  If f > 0 the pixel is fogged: out = mix(c_in, base(d), f) per channel -- the fog takes
+ *     the colour of the sky behind the surface, sun-side glow included.  Otherwise the colour is copied: fog_density == 0 or
+ *     fog_max == 0 copies every hit bit for bit (a mix with f = 0 would turn -0 into +0 and an infinity into a NaN).
+ *   Stores.  d_color_out takes out, d_fb (if given) the BGRA8 pixel of it by the rule of the render launches (clamp to
+ *     0 .. 1, * 255, truncate; bytes b, g, r, 255).  d_summary (if given) is zeroed on the stream by the call and then counts:
+ *     miss and hit (miss + hit = W * H); ground (misses with h < 0); sun (misses with e > 0); cloud (misses with alpha > 0);
+ *     fogged (hits with f > 0).
+ *   Aliasing.  d_color_out may be d_color_in.  Nothing else may overlap.
+ *   Call rules.  Asynchronous on `stream`; allocates nothing, waits for nothing and reads no host memory after it returns;
+ *     may be captured (STREAM CAPTURE above).  Refusals, each VXRT_ERR_INVALID before anything is enqueued or written, checked
+ *     in this order: a NULL ctx; W or H outside the limits; params NULL or its struct_size; a flag bit other than
+ *     VXRT_SKY_CLOUDS or a nonzero reserved_; a component of zenith, horizon, ground, sun_color or cloud_color that is negative
+ *     or not finite; glow_log2 above 8, or octaves outside 1 .. 6; one of glow_strength, ground_fade, cloud_scale, cloud_max_t,
+ *     cloud_cover, cloud_sharp, cloud_fade, fog_start, fog_density, fog_max that is negative, NaN or infinite, or a cloud_y or
+ *     cloud_offset entry that is not finite; fog_max or cloud_cover above 1; cos_inner <= cos_outer, or either outside -1 .. 1
+ *     (a NaN fails); a sun_dir whose n is zero or not finite; a non-finite component of the pose; a NULL d_color_in, d_keys or
+ *     d_color_out.
+ *   The cost is one launch (two with a summary: one wave zeroes it first): per pixel 4 .. 16 bytes read and 12 .. 16 written; a
+ *     cloud pixel evaluates four hashes and two smooth weights per octave. */
+#define VXRT_SKY_CLOUDS 1u
+typedef struct vxrt_sky_params {
+    uint32_t struct_size;
+    int32_t ortho;
+    uint32_t flags;          /* VXRT_SKY_CLOUDS; other bits are invalid */
+    uint32_t glow_log2;      /* 0 .. 8: the glow is max(sd, 0) ^ (2 ^ glow_log2) */
+    uint32_t octaves;        /* 1 .. 6 */
+    uint32_t seed;           /* of the cloud noise */
+    float zenith[3], horizon[3], ground[3], sun_color[3], cloud_color[3]; /* finite, >= 0 */
+    float sun_dir[3];        /* towards the sun; any length */
+    float glow_strength, ground_fade;
+    float cos_inner, cos_outer; /* -1 <= cos_outer < cos_inner <= 1: the disc is full inside cos_inner, gone outside cos_outer */
+    float cloud_y, cloud_scale, cloud_offset[2], cloud_max_t, cloud_cover /* 0 .. 1 */, cloud_sharp, cloud_fade;
+    float fog_start, fog_density, fog_max /* 0 .. 1 */;
+    vxrt_camera_pose cam;    /* the pose the frame was rendered with */
+    int32_t reserved_;       /* 0 */
+} vxrt_sky_params;           /* 208 bytes */
+typedef struct vxrt_sky_summary { uint32_t miss, hit, ground, sun, cloud, fogged; } vxrt_sky_summary;
+int vxrt_sky_frame(vxrt_ctx *ctx, uint32_t W, uint32_t H, const float *d_color_in, const uint32_t *d_keys,
+                   const vxrt_sky_params *params, float *d_color_out, void *d_fb_or_null,
+                   vxrt_sky_summary *d_summary_or_null, void *stream);
+
 /* ---- batch query.  Replaces VoxelRaytracer3D::Raytrace + kernel dispatch
  * (VoxelRT/VolumeRaytracer.cu:95-117,574-618).  Results follow the reference
  * convention: miss -> point = +inf; normal (step direction, zero on a miss) and

@@ -40,7 +40,7 @@ EXPORTS = [
     "vxrt_rule_workspace_bytes", "vxrt_apply_rule", "vxrt_apply_rule_host",
     "vxrt_loose_workspace_bytes", "vxrt_loose_step", "vxrt_loose_step_host",
     "vxrt_frame_guides", "vxrt_denoise_workspace_bytes", "vxrt_denoise_frame", "vxrt_reproject_frame", "vxrt_light_frame",
-    "vxrt_material_field", "vxrt_material_field_host", "vxrt_material_frame",
+    "vxrt_material_field", "vxrt_material_field_host", "vxrt_material_frame", "vxrt_sky_frame",
 ]
 EDIT_BOX, EDIT_SPHERE = 0, 1
 EDIT_MAX_OPS = 1024
@@ -59,6 +59,7 @@ SURF_CAP, SURF_OPEN, SURF_MAX_DIM = 0, 1, 1024
 LOD_MAX_SHIFT = 5
 LIGHT_SKY, LIGHT_BLOCK, LIGHT_MAX, LIGHT_MAX_EMITTERS = 1, 2, 15, 65536
 LF_SMOOTH, LF_OCCLUSION = 1, 2
+SKY_CLOUDS, SKY_MAX_GLOW_LOG2, SKY_MAX_OCTAVES = 1, 8, 6
 RULE_N6, RULE_N18, RULE_N26, RULE_BOX, RULE_WORLD, RULE_MAX_ITERATIONS = 0, 1, 2, 0, 1, 16
 LOOSE_SAND, LOOSE_WATER, LOOSE_WALL, LOOSE_OPEN, LOOSE_MAX_STEPS = 0, 1, 0, 1, 64
 TRANSFORM_MAX_WORDS = 1 << 31
@@ -192,6 +193,17 @@ class MaterialRulesDesc(C.Structure):
 class MaterialFrameParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("n_tiles", C.c_uint32), ("tile_shift", C.c_uint32),
                 ("cam", CameraPose), ("reserved_", C.c_int32)]
+
+
+class SkyParams(C.Structure):
+    """vxrt_sky_params: the parameters of a sky call (include/vxrt.h, vxrt_sky_frame)."""
+    _fields_ = [("struct_size", C.c_uint32), ("ortho", C.c_int32), ("flags", C.c_uint32), ("glow_log2", C.c_uint32), ("octaves", C.c_uint32),
+                ("seed", C.c_uint32), ("zenith", C.c_float * 3), ("horizon", C.c_float * 3), ("ground", C.c_float * 3),
+                ("sun_color", C.c_float * 3), ("cloud_color", C.c_float * 3), ("sun_dir", C.c_float * 3), ("glow_strength", C.c_float),
+                ("ground_fade", C.c_float), ("cos_inner", C.c_float), ("cos_outer", C.c_float), ("cloud_y", C.c_float),
+                ("cloud_scale", C.c_float), ("cloud_offset", C.c_float * 2), ("cloud_max_t", C.c_float), ("cloud_cover", C.c_float),
+                ("cloud_sharp", C.c_float), ("cloud_fade", C.c_float), ("fog_start", C.c_float), ("fog_density", C.c_float),
+                ("fog_max", C.c_float), ("cam", CameraPose), ("reserved_", C.c_int32)]
 
 
 class View(C.Structure):
@@ -360,6 +372,8 @@ def load() -> C.CDLL:
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_reproject_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(ReprojectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.vxrt_sky_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(SkyParams), C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
     L.vxrt_light_frame.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(LightFrameParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.vxrt_material_field.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(MaterialRulesDesc), C.c_void_p,

@@ -1,5 +1,5 @@
 // vxrt_api_query.hip -- the part of the C ABI (include/vxrt.h) that works on the resident world: the edit path (vxrt_edit_*),
-// every query family with its _host twin, and the entry points of the frame denoiser, the temporal filter, the light on frames and the voxel materials.  No kernel is defined here: each family's
+// every query family with its _host twin, and the entry points of the frame denoiser, the temporal filter, the light on frames, the voxel materials and the sky on frames.  No kernel is defined here: each family's
 // launcher is declared in its header and defined in its own .hip.
 #include "vxrt_collide.hpp"
 #include "vxrt_denoise.hpp"
@@ -16,6 +16,7 @@
 #include "vxrt_reproject.hpp"
 #include "vxrt_rule.hpp"
 #include "vxrt_loose.hpp"
+#include "vxrt_sky.hpp"
 #include "vxrt_surface.hpp"
 #include "vxrt_transform.hpp"
 #include "vxrt_voxelize.hpp"
@@ -1394,6 +1395,47 @@ int vxrt_material_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_colo
     A.n_tiles = params->n_tiles;
     A.tile_shift = params->tile_shift;
     VX_HIP(vxrt::material_frame(R, A, Wd, c->cus, (hipStream_t)stream));
+    return VXRT_OK;
+}
+
+// ---- sky on frames -----------------------------------------------------------------------------------------------------
+int vxrt_sky_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_in, const uint32_t* d_keys, const vxrt_sky_params* params,
+                   float* d_color_out, void* d_fb_or_null, vxrt_sky_summary* d_summary_or_null, void* stream)
+{
+    // the order of include/vxrt.h
+    if (!c)
+        return fail(VXRT_ERR_INVALID, "ctx is NULL");
+    static const char* const refusal[] = {"", "", "sky frame: 1 <= W, H <= 65535 and W * H <= 2^26",
+                                          "vxrt_sky_params missing or size mismatch",
+                                          "sky frame flags: VXRT_SKY_CLOUDS (and reserved_ 0)",
+                                          "sky frame: a colour component that is negative or not finite",
+                                          "sky frame: glow_log2 0 .. 8, octaves 1 .. 6",
+                                          "sky frame: a scalar that is negative or not finite",
+                                          "sky frame: fog_max and cloud_cover 0 .. 1",
+                                          "sky frame: -1 <= cos_outer < cos_inner <= 1",
+                                          "sky frame: a sun_dir that is zero or not finite",
+                                          "sky frame: a camera pose with a non-finite component"};
+    if (const int r = vxrt::sky_frame_check(W, H, params))
+        return fail(VXRT_ERR_INVALID, refusal[r]);
+    if (!d_color_in || !d_keys || !d_color_out)
+        return fail(VXRT_ERR_INVALID, "NULL argument");
+    VX_HIP(hipSetDevice(c->device));
+    vxrt::RenderArgs R;
+    memset(&R, 0, sizeof(R));
+    vxrt::camera_args(c, W, H, R);
+    R.ortho = params->ortho ? 1 : 0;
+    R.origin = vxrt::f3{params->cam.origin[0], params->cam.origin[1], params->cam.origin[2]};
+    R.fwd = vxrt::f3{params->cam.fwd[0], params->cam.fwd[1], params->cam.fwd[2]};
+    R.up = vxrt::f3{params->cam.up[0], params->cam.up[1], params->cam.up[2]};
+    R.right = vxrt::f3{params->cam.right[0], params->cam.right[1], params->cam.right[2]};
+    vxrt::SkyArgs A{};
+    vxrt::sky_frame_args(A, W, H, *params);
+    A.color_in = d_color_in;
+    A.keys = d_keys;
+    A.color_out = d_color_out;
+    A.fb = (uint32_t*)d_fb_or_null;
+    A.summary = (uint32_t*)d_summary_or_null;
+    VX_HIP(vxrt::sky_frame(R, A, c->cus, (hipStream_t)stream));
     return VXRT_OK;
 }
 

@@ -987,6 +987,37 @@ class Context:
                     C.byref(p), _ptr(out), _ptr(fb), _ptr(terms_out), _ptr(words))
         return LitFrame(dims=(width, height), color=out, terms=terms_out, _summary=words, _stream=call.s)
 
+    # ---- sky on frames (extension, include/vxrt.h) -------------------------------------------------------------------------
+    def sky_frame(self, color, keys, cam, sky=None, ortho: bool = False, out=None, fb=None, summary: bool = False, stream: int | None = None):
+        """A sky behind a frame and distance fog on it (include/vxrt.h, vxrt_sky_frame): ``color`` a float32 device tensor
+        (height, width, 3) such as the colour AOV of a render or the output of light_frame, ``keys`` its guide keys
+        (frame_guides), ``cam`` the camera the frame was rendered with as (origin, fwd, up, right), ``sky`` a Sky (default:
+        Sky(), a daytime sky without clouds).  Every miss pixel takes the sky colour of its primary ray -- gradient, ground,
+        sun glow and disc, and with SKY_CLOUDS a layer of value-noise clouds --, every hit pixel is faded towards the sky
+        behind it with the distance of the surface it shows.  The last stage of a frame pipeline, after light_frame.  No
+        world is needed.  Asynchronous on ``stream`` (default: torch's current stream), as denoise_frame.  ``out``: float32
+        (height, width, 3), may be ``color`` itself (default: a new tensor); ``fb``: optional uint8 (height, width, 4) BGRA8
+        frame written as well.  ``summary`` (default False: no counting, the cheaper launch): also count the pixels.  Returns a
+        SkyFrame: ``color`` and, with ``summary``, a lazily read SkySummary."""
+        call = _Call(self, stream)
+        torch = call.torch
+        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
+            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
+        height, width = int(color.shape[0]), int(color.shape[1])
+        n = width * height
+        call.reads(color)
+        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
+        if out is None:
+            out = torch.empty_like(color)
+        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
+            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
+        if fb is not None:
+            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        words = call.summary(6) if summary else None
+        p = (Sky() if sky is None else sky)._c(cam, ortho)
+        call.launch(self._L.vxrt_sky_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), C.byref(p), _ptr(out), _ptr(fb), _ptr(words))
+        return SkyFrame(dims=(width, height), color=out, _summary=words, _stream=call.s)
+
     # ---- voxel materials (extension, include/vxrt.h) -------------------------------------------------------------------------
     def _paint(self, call, paint, paint_box):
         """(device bytes or None, box) of a paint argument: a MaterialField (its bytes and its box), a device uint8 tensor or a
@@ -2068,6 +2099,81 @@ class LitFrame(_LazyResult):
     def summary(self) -> LightFrameSummary | None:
         """the summary; the first read waits for the call's stream"""
         return None if self._summary is None else LightFrameSummary(*self._words()[:4])
+
+
+@dataclass
+class Sky:
+    """vxrt_sky_params without the camera: the default is a clear daytime sky.  ``flags``: SKY_CLOUDS or 0.  Colours are
+    display-space rgb, >= 0.  ``sun_dir`` points towards the sun (any length); the glow around it is
+    ``glow_strength`` * max(cos, 0) ^ (2 ^ ``glow_log2``), the disc is full inside ``cos_inner`` and gone outside
+    ``cos_outer``.  Below the horizon the colour runs from ``horizon`` to ``ground`` over 1 / ``ground_fade`` of d.y.
+    Clouds: ``octaves`` (1 .. 6) of value noise of seed ``seed`` on the plane y = ``cloud_y``, ``cloud_scale`` noise cells per
+    voxel, shifted by ``cloud_offset`` (move it to make them drift), not beyond ``cloud_max_t`` along the ray; ``cloud_cover``
+    0 .. 1 is how much of the sky they take, ``cloud_sharp`` how hard their edge is, ``cloud_fade`` how fast they fade in
+    above the horizon.  Fog: starts ``fog_start`` voxels from the camera, f = x / (1 + x) with x = distance *
+    ``fog_density``, at most ``fog_max`` (0 .. 1)."""
+    flags: int = 0
+    glow_log2: int = 3
+    octaves: int = 4
+    seed: int = 1
+    zenith: tuple = (0.18, 0.38, 0.80)
+    horizon: tuple = (0.70, 0.82, 0.95)
+    ground: tuple = (0.30, 0.28, 0.25)
+    sun_color: tuple = (1.0, 0.95, 0.80)
+    cloud_color: tuple = (1.0, 1.0, 1.0)
+    sun_dir: tuple = (0.577, 0.577, 0.577)
+    glow_strength: float = 0.35
+    ground_fade: float = 4.0
+    cos_inner: float = 0.9995
+    cos_outer: float = 0.9985
+    cloud_y: float = 400.0
+    cloud_scale: float = 0.004
+    cloud_offset: tuple = (0.0, 0.0)
+    cloud_max_t: float = 20000.0
+    cloud_cover: float = 0.5
+    cloud_sharp: float = 3.0
+    cloud_fade: float = 6.0
+    fog_start: float = 64.0
+    fog_density: float = 0.0015
+    fog_max: float = 0.85
+
+    def _c(self, cam, ortho: bool = False) -> "N.SkyParams":
+        p = N.SkyParams(struct_size=C.sizeof(N.SkyParams), ortho=1 if ortho else 0, flags=_u32(self.flags), glow_log2=_u32(self.glow_log2),
+                        octaves=_u32(self.octaves), seed=int(self.seed) & 0xFFFFFFFF)
+        for name in ("zenith", "horizon", "ground", "sun_color", "cloud_color", "sun_dir"):
+            setattr(p, name, _f3(getattr(self, name)))
+        for name in ("glow_strength", "ground_fade", "cos_inner", "cos_outer", "cloud_y", "cloud_scale", "cloud_max_t", "cloud_cover",
+                     "cloud_sharp", "cloud_fade", "fog_start", "fog_density", "fog_max"):
+            setattr(p, name, float(getattr(self, name)))
+        p.cloud_offset = (C.c_float * 2)(*[float(v) for v in self.cloud_offset])
+        p.cam.origin, p.cam.fwd, p.cam.up, p.cam.right = (_f3(v) for v in cam)
+        return p
+
+
+class SkySummary(NamedTuple):
+    """vxrt_sky_summary: miss and hit pixels; of the misses those below the horizon, those the sun disc touches and those
+    with a cloud; of the hits those the fog changed"""
+    miss: int
+    hit: int
+    ground: int
+    sun: int
+    cloud: int
+    fogged: int
+
+
+@dataclass
+class SkyFrame(_LazyResult):
+    """The result of Context.sky_frame: ``color`` float32 (height, width, 3), a device tensor; ``dims`` is (width, height).
+    ``summary`` is a SkySummary, or None when the call was made without one."""
+    dims: tuple
+    color: object
+    _summary: object
+    _stream: object
+
+    @property
+    def summary(self) -> SkySummary | None:
+        """the summary; the first read waits for the call's stream"""
+        return None if self._summary is None else SkySummary(*self._words()[:6])
 
 
 class MaterialRules(NamedTuple):
