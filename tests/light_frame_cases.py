@@ -15,6 +15,8 @@ FLAG_SETS = (LF.SMOOTH | LF.OCCLUSION, LF.SMOOTH, LF.OCCLUSION, 0)
 # (W, H, ortho, pose): the frames of the contract's tests in both camera kinds, and one frame under a camera whose forward
 # vector is zero -- an ortho ray with d = 0 on every axis: the centre of the face
 CASES = [(W, H, ortho, "slant") for W, H in ((67, 35), (64, 1), (1, 64), (160, 96)) for ortho in (False, True)] + [(64, 1, True, "zero")]
+# one pixel (fifteen of the counting workgroup's sixteen waves walk no tile) and partial tiles on both axes
+CASES += [(1, 1, False, "slant"), (65, 5, False, "slant")]
 
 
 def random_case(W, H, ortho, pose="slant", seed=0):

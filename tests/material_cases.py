@@ -25,7 +25,8 @@ POSES = {  # (origin, fwd, up, right)
 }
 # (W, H, ortho, pose): the frames of the contract's tests in both camera kinds and under every pose
 FRAME_CASES = [(1, 1, False, "slant"), (63, 5, False, "slant"), (64, 4, True, "up"), (65, 9, False, "up"), (257, 3, True, "slant"),
-               (64, 4, True, "zero"), (65, 9, True, "axis"), (96, 64, False, "up"), (96, 64, True, "slant")]
+               (64, 4, True, "zero"), (65, 9, True, "axis"), (96, 64, False, "up"), (96, 64, True, "slant"),
+               (65, 5, False, "slant")]  # partial tiles on both axes
 # field boxes (origin, dims): widths 1, 31, 32, 33, 63, 64, 65 and 257 (byte and dword rows, one and several x chunks, rows
 # shared by several z per wave), heights that cross a y-segment boundary and the 16-row warm-up, boxes over every face of
 # the world

@@ -13,7 +13,8 @@ ORTHO_SIZE = (24.0, 20.0)
 FRAMES = ((1, 1), (63, 5), (64, 4), (65, 3), (130, 9), (257, 2))
 # (W, H, ortho, pose)
 CASES = ([(W, H, ortho, "level") for W, H in FRAMES for ortho in (False, True)] +
-         [(130, 9, False, "up"), (130, 9, True, "up"), (130, 9, False, "down"), (65, 3, False, "high"), (64, 4, True, "axis"), (67, 35, False, "level")])
+         [(130, 9, False, "up"), (130, 9, True, "up"), (130, 9, False, "down"), (65, 3, False, "high"), (64, 4, True, "axis"), (67, 35, False, "level"),
+          (65, 5, False, "level")])  # partial tiles on both axes
 POSES = {  # origin, fwd, up, right
     "level": ((100.5, 60.25, 80.75), (0.8, 0.1, 0.6), (0.05, 0.99, -0.1), (0.6, 0.0, -0.8)),
     "up": ((100.5, 60.25, 80.75), (0.3, 0.9, 0.3), (0.6, -0.4, 0.6), (0.7, 0.0, -0.7)),

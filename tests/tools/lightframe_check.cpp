@@ -3,8 +3,7 @@
 // the CPU through tests/tools/hoststub and run workgroup by workgroup and lane by lane.  The world is the oracle's brickmap
 // (oracle/vxo_world.c) of a dense grid, laid out as the library holds it in HBM.  The harness restates what
 // vxrt_light_frame.hip adds around that code, which the GPU suite covers:
-//   the launch      rp_launch_shape's workgroups, every lane on the pixels rp_wave_pixel gives its wave (every pixel of the
-//                   frame exactly once), lanes outside the frame idle;
+//   the launch      frame_launch.h;
 //   the camera      one lane per pixel, its primary ray handed in (the camera is the renderer's, covered on the GPU);
 //   the summary     zeroed, then the lanes' results counted.
 // Every index the code forms into an input, an output, the cell table, the brick pool or the level bytes is checked against
@@ -38,6 +37,7 @@ static bool check_or_report(int array, uint64_t index);
 #include "../../voxelengine_amd/csrc/vxrt_light_frame.hpp"
 #include "hbm_world.h"
 using namespace vxrt;
+#include "frame_launch.h"
 
 static bool check_or_report(int array, uint64_t index)
 {
@@ -129,32 +129,13 @@ int main(int argc, char** argv)
     g_size[kLfMeta] = h.meta.size();
     g_size[kLfPool] = h.pool.size();
 
-    // the launch of vxrt_light_frame.hip, restated: every lane of every workgroup walks its wave's tiles
-    uint32_t block = 0u, grid = 0u;
-    rp_launch_shape(W, H, summary, (uint32_t)hd[16], block, grid);
-    CHECK(grid >= 1u && (block == kRpPlain || block == kRpCounted) && (summary || grid == rp_tiles(W, H)));
-    CHECK(!summary || grid <= (uint32_t)hd[16] * kRpCountedPerCu);
-    const uint32_t per = block >> 6, waves = grid * per;
     uint32_t count[4] = {0u, 0u, 0u, 0u};
-    uint64_t pixels = 0;
-    std::vector<uint8_t> seen(n, 0);
-    for (uint32_t b = 0; b < grid; ++b)
-        for (uint32_t tid = 0; tid < block; ++tid) {
-            uint32_t x, y;
-            for (uint32_t i = 0; rp_wave_pixel(W, H, b * per + (tid >> 6), waves, i, tid & 63u, x, y); ++i) {
-                if (x >= W || y >= H)
-                    continue;
-                const uint64_t at = (uint64_t)y * W + x;
-                CHECK(!seen[at]);
-                seen[at] = 1;
-                const uint32_t bits = lf_pixel(A, Wd, x, y, &o[3u * at], &d[3u * at]);
-                CHECK(bits < 16u && ((bits & kLfHitBit) != 0u || bits == 0u));
-                for (int k = 0; k < 4; ++k)
-                    count[k] += (bits >> k) & 1u;
-                ++pixels;
-            }
-        }
-    CHECK(pixels == n);
+    frame_launch(W, H, summary, (uint32_t)hd[16], [&](uint32_t x, uint32_t y, uint64_t at) {
+        const uint32_t bits = lf_pixel(A, Wd, x, y, &o[3u * at], &d[3u * at]);
+        CHECK(bits < 16u && ((bits & kLfHitBit) != 0u || bits == 0u));
+        for (int k = 0; k < 4; ++k)
+            count[k] += (bits >> k) & 1u;
+    });
     if (summary)
         for (int k = 0; k < 4; ++k)
             sum[k] = count[k];

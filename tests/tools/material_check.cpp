@@ -5,8 +5,7 @@
 // adds around that code, which the GPU suite covers:
 //   the field launch  every lane of every task of material_field_args' cut, the tally of a workgroup (here: one for all)
 //                     added to the zeroed summary;
-//   the frame launch  rp_launch_shape's workgroups, every lane on the pixels rp_wave_pixel gives its wave, the primary ray
-//                     handed in, the summary zeroed, then the lanes' results counted.
+//   the frame launch  frame_launch.h, the primary ray handed in, the summary zeroed, then the lanes' results counted.
 // Every index the code forms into an input, an output, the cell table, the brick pool, the paint, the palette, the atlas or
 // the tally is checked against that array's size (an array the call was not given has size 0); every array carries a guard
 // behind it.  Run by tests/test_material_host.py, which compares with tests/ref_material.py.
@@ -43,6 +42,7 @@ static bool check_or_report(int array, uint64_t index);
 #include "../../voxelengine_amd/csrc/vxrt_material.hpp"
 #include "hbm_world.h"
 using namespace vxrt;
+#include "frame_launch.h"
 
 static bool check_or_report(int array, uint64_t index)
 {
@@ -174,31 +174,13 @@ static int run_frame(FILE* in, const int32_t* hd, const vxrt_material_rules& rul
     g_size[kMatPalette] = 256u;
     g_size[kMatAtlas] = atlas_given ? texels : 0u;
 
-    // the launch of vxrt_material.hip, restated: every lane of every workgroup walks its wave's tiles
-    uint32_t block = 0u, grid = 0u;
-    rp_launch_shape(W, H, summary, cus, block, grid);
-    CHECK(grid >= 1u && (block == kRpPlain || block == kRpCounted) && (summary || grid == rp_tiles(W, H)));
-    const uint32_t per = block >> 6, waves = grid * per;
     uint32_t count[4] = {0u, 0u, 0u, 0u};
-    uint64_t pixels = 0;
-    std::vector<uint8_t> seen(n, 0);
-    for (uint32_t b = 0; b < grid; ++b)
-        for (uint32_t tid = 0; tid < block; ++tid) {
-            uint32_t x, y;
-            for (uint32_t i = 0; rp_wave_pixel(W, H, b * per + (tid >> 6), waves, i, tid & 63u, x, y); ++i) {
-                if (x >= W || y >= H)
-                    continue;
-                const uint64_t at = (uint64_t)y * W + x;
-                CHECK(!seen[at]);
-                seen[at] = 1;
-                const uint32_t bits = mat_pixel(A, Wd, x, y, &o[3u * at], &d[3u * at]);
-                CHECK(bits < 16u && ((bits & kMatHitBit) != 0u || bits == 0u));
-                for (int k = 0; k < 4; ++k)
-                    count[k] += (bits >> k) & 1u;
-                ++pixels;
-            }
-        }
-    CHECK(pixels == n);
+    frame_launch(W, H, summary, cus, [&](uint32_t x, uint32_t y, uint64_t at) {
+        const uint32_t bits = mat_pixel(A, Wd, x, y, &o[3u * at], &d[3u * at]);
+        CHECK(bits < 16u && ((bits & kMatHitBit) != 0u || bits == 0u));
+        for (int k = 0; k < 4; ++k)
+            count[k] += (bits >> k) & 1u;
+    });
     if (summary)
         for (int k = 0; k < 4; ++k)
             sum[k] = count[k];

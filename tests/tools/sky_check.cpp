@@ -1,8 +1,7 @@
 // Host harness of the sky on frames (voxelengine_amd/csrc/vxrt_sky.hpp: the sky without disc and clouds, the disc, the cloud
 // noise, the fog of a hit pixel and the stores), compiled for the CPU through tests/tools/hoststub and run workgroup by
 // workgroup and lane by lane.  The harness restates what vxrt_sky.hip adds around that code, which the GPU suite covers:
-//   the launch      rp_launch_shape's workgroups, every lane on the pixels rp_wave_pixel gives its wave (every pixel of the
-//                   frame exactly once), lanes outside the frame idle;
+//   the launch      frame_launch.h;
 //   the camera      one lane per pixel, its primary ray handed in (the camera is the renderer's, covered on the GPU);
 //   the summary     zeroed, then the lanes' results counted.
 // Every index the code forms into an input or an output is checked against that array's size (an array the call was not
@@ -45,6 +44,7 @@ static int fails = 0;
 
 #include "../../voxelengine_amd/csrc/vxrt_sky.hpp"
 using namespace vxrt;
+#include "frame_launch.h"
 
 int main(int argc, char** argv)
 {
@@ -91,33 +91,14 @@ int main(int argc, char** argv)
     g_size[kSkyColorOut] = 3u * n;
     g_size[kSkyFb] = fb ? n : 0u;
 
-    // the launch of vxrt_sky.hip, restated: every lane of every workgroup walks its wave's tiles
-    uint32_t block = 0u, grid = 0u;
-    rp_launch_shape(W, H, summary, cus, block, grid);
-    CHECK(grid >= 1u && (block == kRpPlain || block == kRpCounted) && (summary || grid == rp_tiles(W, H)));
-    CHECK(!summary || grid <= cus * kRpCountedPerCu);
-    const uint32_t per = block >> 6, waves = grid * per;
     uint32_t count[kSkyCounters] = {0u, 0u, 0u, 0u, 0u, 0u};
-    uint64_t pixels = 0;
-    std::vector<uint8_t> seen(n, 0);
-    for (uint32_t b = 0; b < grid; ++b)
-        for (uint32_t tid = 0; tid < block; ++tid) {
-            uint32_t x, y;
-            for (uint32_t i = 0; rp_wave_pixel(W, H, b * per + (tid >> 6), waves, i, tid & 63u, x, y); ++i) {
-                if (x >= W || y >= H)
-                    continue;
-                const uint64_t at = (uint64_t)y * W + x;
-                CHECK(!seen[at]);
-                seen[at] = 1;
-                const uint32_t bits = sky_pixel(A, x, y, &o[3u * at], &d[3u * at]);
-                const bool miss = bits & kSkyMissBit, hit = bits & kSkyHitBit;
-                CHECK(bits < 64u && miss != hit && (miss || !(bits & (kSkyGroundBit | kSkySunBit | kSkyCloudBit))) && (hit || !(bits & kSkyFoggedBit)));
-                for (uint32_t k = 0; k < kSkyCounters; ++k)
-                    count[k] += (bits >> k) & 1u;
-                ++pixels;
-            }
-        }
-    CHECK(pixels == n);
+    frame_launch(W, H, summary, cus, [&](uint32_t x, uint32_t y, uint64_t at) {
+        const uint32_t bits = sky_pixel(A, x, y, &o[3u * at], &d[3u * at]);
+        const bool miss = bits & kSkyMissBit, hit = bits & kSkyHitBit;
+        CHECK(bits < 64u && miss != hit && (miss || !(bits & (kSkyGroundBit | kSkySunBit | kSkyCloudBit))) && (hit || !(bits & kSkyFoggedBit)));
+        for (uint32_t k = 0; k < kSkyCounters; ++k)
+            count[k] += (bits >> k) & 1u;
+    });
     if (summary)
         for (uint32_t k = 0; k < kSkyCounters; ++k)
             sum[k] = count[k];

@@ -1122,6 +1122,39 @@ int vxrt_loose_step_host(vxrt_ctx* c, const int32_t origin[3], const int32_t dim
     return T.finish();
 }
 
+// ---- what the frame calls share ----------------------------------------------------------------------------------------
+// the camera of a W x H frame as camera_ray reads it: the context's constants (camera_args), the camera kind and the pose;
+// everything else of R zero
+static void frame_camera(const vxrt_ctx* c, uint32_t W, uint32_t H, int32_t ortho, const float origin[3], const float fwd[3],
+                         const float up[3], const float right[3], vxrt::RenderArgs& R)
+{
+    memset(&R, 0, sizeof(R));
+    vxrt::camera_args(c, W, H, R);
+    R.ortho = ortho ? 1 : 0;
+    R.origin = vxrt::f3{origin[0], origin[1], origin[2]};
+    R.fwd = vxrt::f3{fwd[0], fwd[1], fwd[2]};
+    R.up = vxrt::f3{up[0], up[1], up[2]};
+    R.right = vxrt::f3{right[0], right[1], right[2]};
+}
+
+static void frame_camera(const vxrt_ctx* c, uint32_t W, uint32_t H, int32_t ortho, const vxrt_camera_pose& p, vxrt::RenderArgs& R)
+{
+    frame_camera(c, W, H, ortho, p.origin, p.fwd, p.up, p.right, R);
+}
+
+// the checks of a frame stage that decodes hit indices against the resident world (world_ready's `verb`; `stage`: the
+// message's subject): a world that is not streamed, and no axis longer than a face plane's 2^24
+static int frame_world_ready(const vxrt_ctx* c, const char* verb, const char* stage)
+{
+    if (int rc = vxrt::world_ready(c, verb))
+        return rc;
+    const vxrt::CollideWorld Wd = vxrt::query_world(c);
+    for (int k = 0; k < 3; ++k)
+        if ((uint32_t)Wd.dim[k] > vxrt::kDnMaxAxis)
+            return fail(VXRT_ERR_INVALID, std::string(stage) + ": a world axis longer than 2^24 voxels");
+    return VXRT_OK;
+}
+
 // ---- frame denoiser ----------------------------------------------------------------------------------------------------
 uint64_t vxrt_denoise_workspace_bytes(uint32_t W, uint32_t H) { return vxrt::denoise_workspace_bytes(W, H); }
 
@@ -1142,15 +1175,9 @@ int vxrt_frame_guides(vxrt_ctx* c, uint32_t W, uint32_t H, const float origin[3]
         return fail(VXRT_ERR_INVALID, "frame guides: a world axis longer than 2^24 voxels");
     VX_HIP(hipSetDevice(c->device));
     vxrt::RenderArgs A;
-    memset(&A, 0, sizeof(A));
+    frame_camera(c, W, H, ortho, origin, fwd, up, right, A);
     A.W.X = (int)X;
     A.W.Y = (int)Y;
-    vxrt::camera_args(c, W, H, A);
-    A.ortho = ortho ? 1 : 0;
-    A.origin = vxrt::f3{origin[0], origin[1], origin[2]};
-    A.fwd = vxrt::f3{fwd[0], fwd[1], fwd[2]};
-    A.up = vxrt::f3{up[0], up[1], up[2]};
-    A.right = vxrt::f3{right[0], right[1], right[2]};
     A.hit_aov = (long long*)d_hit_aov;
     VX_HIP(vxrt::frame_guides(A, (uint32_t)Z, d_keys, (hipStream_t)stream));
     return VXRT_OK;
@@ -1193,22 +1220,13 @@ int vxrt_reproject_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_col
         return fail(VXRT_ERR_INVALID, "vxrt_reproject_params missing or size mismatch");
     if (!vxrt::reproject_history_ok(params->max_history) || params->reserved_ != 0)
         return fail(VXRT_ERR_INVALID, "reproject max_history: 1 .. 65535 (and reserved_ 0)");
-    const vxrt_camera_pose* const poses[2] = {&params->cur, &params->prev};
-    for (const vxrt_camera_pose* p : poses)
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(p->origin[k]) || !std::isfinite(p->fwd[k]) || !std::isfinite(p->up[k]) || !std::isfinite(p->right[k]))
-                return fail(VXRT_ERR_INVALID, "reproject: a camera pose with a non-finite component");
+    if (!vxrt::pose_finite(params->cur) || !vxrt::pose_finite(params->prev))
+        return fail(VXRT_ERR_INVALID, "reproject: a camera pose with a non-finite component");
     if (!d_color_in || !d_keys || !d_hist_out)
         return fail(VXRT_ERR_INVALID, "NULL argument");
     VX_HIP(hipSetDevice(c->device));
     vxrt::RenderArgs R;
-    memset(&R, 0, sizeof(R));
-    vxrt::camera_args(c, W, H, R);
-    R.ortho = params->ortho ? 1 : 0;
-    R.origin = vxrt::f3{params->cur.origin[0], params->cur.origin[1], params->cur.origin[2]};
-    R.fwd = vxrt::f3{params->cur.fwd[0], params->cur.fwd[1], params->cur.fwd[2]};
-    R.up = vxrt::f3{params->cur.up[0], params->cur.up[1], params->cur.up[2]};
-    R.right = vxrt::f3{params->cur.right[0], params->cur.right[1], params->cur.right[2]};
+    frame_camera(c, W, H, params->ortho, params->cur, R);
     vxrt::ReprojectArgs A{};
     const bool history = d_hist_in_or_null && d_keys_prev_or_null;
     A.color_in = d_color_in;
@@ -1257,21 +1275,11 @@ int vxrt_light_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_i
         return fail(VXRT_ERR_INVALID, refusal[r]);
     if (!d_color_in || !d_keys || !d_hit_aov || !d_color_out)
         return fail(VXRT_ERR_INVALID, "NULL argument");
-    if (int rc = vxrt::world_ready(c, "lit"))
+    if (int rc = frame_world_ready(c, "lit", "light frame"))
         return rc;
-    const vxrt::CollideWorld Wd = vxrt::query_world(c);
-    for (int k = 0; k < 3; ++k)
-        if ((uint32_t)Wd.dim[k] > vxrt::kDnMaxAxis)
-            return fail(VXRT_ERR_INVALID, "light frame: a world axis longer than 2^24 voxels");
     VX_HIP(hipSetDevice(c->device));
     vxrt::RenderArgs R;
-    memset(&R, 0, sizeof(R));
-    vxrt::camera_args(c, W, H, R);
-    R.ortho = params->ortho ? 1 : 0;
-    R.origin = vxrt::f3{params->cam.origin[0], params->cam.origin[1], params->cam.origin[2]};
-    R.fwd = vxrt::f3{params->cam.fwd[0], params->cam.fwd[1], params->cam.fwd[2]};
-    R.up = vxrt::f3{params->cam.up[0], params->cam.up[1], params->cam.up[2]};
-    R.right = vxrt::f3{params->cam.right[0], params->cam.right[1], params->cam.right[2]};
+    frame_camera(c, W, H, params->ortho, params->cam, R);
     vxrt::LightFrameArgs A{};
     vxrt::light_frame_args(A, W, H, *params);
     A.color_in = d_color_in;
@@ -1282,7 +1290,7 @@ int vxrt_light_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_i
     A.fb = (uint32_t*)d_fb_or_null;
     A.terms = d_terms_or_null;
     A.summary = (uint32_t*)d_summary_or_null;
-    VX_HIP(vxrt::light_frame(R, A, Wd, c->cus, (hipStream_t)stream));
+    VX_HIP(vxrt::light_frame(R, A, vxrt::query_world(c), c->cus, (hipStream_t)stream));
     return VXRT_OK;
 }
 
@@ -1363,21 +1371,11 @@ int vxrt_material_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_colo
     }
     if (!d_color_in || !d_keys || !d_hit_aov || !d_palette || !d_color_out)
         return fail(VXRT_ERR_INVALID, "NULL argument");
-    if (int rc = vxrt::world_ready(c, "queried"))
+    if (int rc = frame_world_ready(c, "queried", "material frame"))
         return rc;
-    const vxrt::CollideWorld Wd = vxrt::query_world(c);
-    for (int k = 0; k < 3; ++k)
-        if ((uint32_t)Wd.dim[k] > vxrt::kDnMaxAxis)
-            return fail(VXRT_ERR_INVALID, "material frame: a world axis longer than 2^24 voxels");
     VX_HIP(hipSetDevice(c->device));
     vxrt::RenderArgs R;
-    memset(&R, 0, sizeof(R));
-    vxrt::camera_args(c, W, H, R);
-    R.ortho = params->ortho ? 1 : 0;
-    R.origin = vxrt::f3{params->cam.origin[0], params->cam.origin[1], params->cam.origin[2]};
-    R.fwd = vxrt::f3{params->cam.fwd[0], params->cam.fwd[1], params->cam.fwd[2]};
-    R.up = vxrt::f3{params->cam.up[0], params->cam.up[1], params->cam.up[2]};
-    R.right = vxrt::f3{params->cam.right[0], params->cam.right[1], params->cam.right[2]};
+    frame_camera(c, W, H, params->ortho, params->cam, R);
     vxrt::MaterialFrameArgs A{};
     A.rules = *rules;
     A.color_in = d_color_in;
@@ -1394,7 +1392,7 @@ int vxrt_material_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_colo
     A.H = H;
     A.n_tiles = params->n_tiles;
     A.tile_shift = params->tile_shift;
-    VX_HIP(vxrt::material_frame(R, A, Wd, c->cus, (hipStream_t)stream));
+    VX_HIP(vxrt::material_frame(R, A, vxrt::query_world(c), c->cus, (hipStream_t)stream));
     return VXRT_OK;
 }
 
@@ -1421,13 +1419,7 @@ int vxrt_sky_frame(vxrt_ctx* c, uint32_t W, uint32_t H, const float* d_color_in,
         return fail(VXRT_ERR_INVALID, "NULL argument");
     VX_HIP(hipSetDevice(c->device));
     vxrt::RenderArgs R;
-    memset(&R, 0, sizeof(R));
-    vxrt::camera_args(c, W, H, R);
-    R.ortho = params->ortho ? 1 : 0;
-    R.origin = vxrt::f3{params->cam.origin[0], params->cam.origin[1], params->cam.origin[2]};
-    R.fwd = vxrt::f3{params->cam.fwd[0], params->cam.fwd[1], params->cam.fwd[2]};
-    R.up = vxrt::f3{params->cam.up[0], params->cam.up[1], params->cam.up[2]};
-    R.right = vxrt::f3{params->cam.right[0], params->cam.right[1], params->cam.right[2]};
+    frame_camera(c, W, H, params->ortho, params->cam, R);
     vxrt::SkyArgs A{};
     vxrt::sky_frame_args(A, W, H, *params);
     A.color_in = d_color_in;

@@ -12,8 +12,8 @@
 //
 // No atomics, no host synchronisation, no allocation: every pixel is a pure function of the iteration's input.
 #include "../../include/vxrt.h"
-#include "vxrt_camera.hpp"
 #include "vxrt_denoise.hpp"
+#include "vxrt_frame_stage.hpp"  // frame_ray
 
 #include <cstdlib>
 
@@ -27,16 +27,10 @@ __global__ __launch_bounds__(256) void k_frame_guides(const RenderArgs A, uint32
     const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
     if (x >= A.width || y >= A.height)
         return;
-    LaneView V;
-    V.origin = A.origin;
-    V.fwd = A.fwd;
-    V.up = A.up;
-    V.right = A.right;
-    f3 o, d;
-    camera_ray<FrameTraits<false>>(A, V, (int)x, (int)y, o, d);
+    float o[3], d[3];
+    frame_ray(A, x, y, o, d);
     const uint64_t i = (uint64_t)y * A.width + x;
-    const float of[3] = {o.x, o.y, o.z}, df[3] = {d.x, d.y, d.z};
-    keys[i] = guide_key(A.hit_aov[i], (uint32_t)A.W.X, (uint32_t)A.W.Y, Z, of, df);
+    keys[i] = guide_key(A.hit_aov[i], (uint32_t)A.W.X, (uint32_t)A.W.Y, Z, o, d);
 }
 
 template <bool STAGED, bool FIRST>

@@ -1,20 +1,15 @@
 // vxrt_light_frame.hip -- light on frames (include/vxrt.h, vxrt_light_frame; host side in vxrt_api_query.hip, the per-pixel
-// logic in vxrt_light_frame.hpp).  One launch on the caller's stream:
+// logic in vxrt_light_frame.hpp).  One launch on the caller's stream, by the frame stages' launcher (vxrt_frame_stage.hpp):
 //
-//   k_light_frame   one lane per pixel, lanes along x, the launch shape of k_reproject (vxrt_reproject.hpp): four waves on a
-//                 tile of 64 x 4 pixels without a summary; with one, few large workgroups whose waves walk several tiles,
-//                 count by ballot and popcount, add up in LDS and issue one set of atomics per workgroup.  The pixel's
-//                 primary ray comes from the render kernel's own camera_ray (vxrt_camera.hpp, the general instantiation).
-//                 Solidity is read through the query layer's world (CollideWorld, vxrt_region.hpp).  Every hit lane makes
+//   k_light_frame   Solidity is read through the query layer's world (CollideWorld, vxrt_region.hpp).  Every hit lane makes
 //                 the four corner triples of its own face (lf_face: nine cell records, nine brick words, nine level bytes)
 //                 and shades (lf_shade).  A form in which the first lane of a run of equal (hit index, key) within the wave
 //                 made the corners and the run's other lanes took the thirteen words by shuffle gave the same bits and the
 //                 same time within 4 % either way (profiles/light_frame.md): neighbouring lanes' loads of the same cells
 //                 already coalesce, and the wave runs lf_face once in both forms.  It was dropped.
-//
-// No host synchronisation, no allocation: every pixel is a pure function of the call's inputs.
-#include "../../include/vxrt.h"
-#include "vxrt_camera.hpp"
+//                 The kernel has the frame stages' body (frame_stage of vxrt_frame_stage.hpp) written out: as an instance of the
+//                 shared body it measured 0.4 .. 1.4 us of 77 .. 89 slower with a summary at 1080p (profiles/frame_stage.md).
+#include "vxrt_frame_stage.hpp"
 #include "vxrt_light_frame.hpp"
 
 namespace vxrt {
@@ -69,13 +64,7 @@ __global__ __launch_bounds__(1024) void k_light_frame(const RenderArgs R, const 
 // host entry point (vxrt_api_query.hip): arguments validated there.  Asynchronous on `stream`.
 hipError_t light_frame(const RenderArgs& R, const LightFrameArgs& A, const CollideWorld& Wd, uint32_t cus, hipStream_t stream)
 {
-    if (A.summary)
-        if (hipError_t e = hipMemsetAsync(A.summary, 0, 4u * sizeof(uint32_t), stream))
-            return e;
-    uint32_t block, grid;
-    rp_launch_shape(A.W, A.H, A.summary != nullptr, cus, block, grid);
-    hipLaunchKernelGGL(k_light_frame, dim3(grid), dim3(block), 0, stream, R, A, Wd);
-    return hipGetLastError();
+    return frame_stage_launch<4u, false>(k_light_frame, A.W, A.H, A.summary, cus, stream, R, A, Wd);
 }
 
 }  // namespace vxrt

@@ -4,20 +4,14 @@
 // face a pixel shows, the nine cells in front of it with their solidity and light levels, the four corner triples
 // (sky, block, occlusion), the position of the pixel on the face, the interpolation, the colour and the stores.
 //
-// Frame.  W x H pixels, x fastest, the denoiser's limits (denoise_frame_ok); the launch is the temporal filter's
-// (rp_launch_shape, rp_wave_pixel).  A lane owns one pixel: it reads its own colour, key and hit index, the cell records
-// and brick words of nine voxels and up to nine level bytes, and writes its own colour, terms and BGRA8 pixel: no pixel reads
-// what another writes, so the colour output may be the colour input.
+// The frame and the shared helpers are vxrt_frame.hpp's, the launch is the temporal filter's (rp_launch_shape,
+// rp_wave_pixel).  A pixel reads its own colour, key and hit index, the cell records and brick words of nine voxels and up to nine level bytes, and writes its own colour, terms and BGRA8 pixel.
 // The work splits in three: lf_load reads the pixel's own inputs and names its voxel face, lf_face makes the four corner
-// triples of a face from the world and the levels alone, lf_shade places the pixel on its face and relights it.  The primary
-// ray (o, d) of the pixel is an input here: camera_ray (vxrt_camera.hpp) votes across the wave and stays with the kernel.
+// triples of a face from the world and the levels alone, lf_shade places the pixel on its face and relights it.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "vxrt_region.hpp"  // CollideWorld (and with it include/vxrt.h)
-#include "vxrt_reproject.hpp"  // the launch shape (and with it vxrt_denoise.hpp: the frame limits, dn_bgra8)
+#include "vxrt_region.hpp"     // CollideWorld
+#include "vxrt_reproject.hpp"  // the launch shape (and with it vxrt_frame.hpp)
 
 // The harness defines this to check every index the code forms into an input, an output, the world tables or the level
 // bytes against that array's size (array: one of the kLf* ids below).  The kernel leaves it empty.
@@ -49,8 +43,6 @@ struct LightFrameArgs {
     int32_t bo[3], bd[3];    // the light box
 };
 
-__host__ __device__ inline bool lf_finite(float x) { return x - x == 0.0f; }  // (x - x: 0 for a finite x, NaN otherwise)
-
 // The parameter checks of include/vxrt.h that need neither the context nor a pointer of the call: 0 when all pass, else
 // the place of the first that fails in the documented order (2: W or H; 3: params or its struct_size; 4: flags,
 // outside_level or reserved_; 5: sky_floor; 6: block_color or ao_curve; 7: the pose; 8: the box).
@@ -65,14 +57,13 @@ inline int light_frame_check(uint32_t W, uint32_t H, const vxrt_light_frame_para
     if (!(p->sky_floor >= 0.0f && p->sky_floor <= 1.0f))  // (a NaN fails)
         return 5;
     for (int k = 0; k < 3; ++k)
-        if (!(p->block_color[k] >= 0.0f) || !lf_finite(p->block_color[k]))
+        if (!(p->block_color[k] >= 0.0f) || !frame_finite(p->block_color[k]))
             return 6;
     for (int k = 0; k < 4; ++k)
-        if (!(p->ao_curve[k] >= 0.0f) || !lf_finite(p->ao_curve[k]))
+        if (!(p->ao_curve[k] >= 0.0f) || !frame_finite(p->ao_curve[k]))
             return 6;
-    for (int k = 0; k < 3; ++k)
-        if (!lf_finite(p->cam.origin[k]) || !lf_finite(p->cam.fwd[k]) || !lf_finite(p->cam.up[k]) || !lf_finite(p->cam.right[k]))
-            return 7;
+    if (!pose_finite(p->cam))
+        return 7;
     uint64_t voxels = 1u;
     for (int k = 0; k < 3; ++k) {
         if (p->box_dims[k] < 1 || (int64_t)p->box_origin[k] + p->box_dims[k] > INT32_MAX)
@@ -191,7 +182,6 @@ __host__ __device__ inline LfFace lf_face(const LightFrameArgs& A, const Collide
     return F;
 }
 
-__host__ __device__ inline float lf_clamp01(float x) { return x < 0.0f ? 0.0f : x > 1.0f ? 1.0f : x; }
 __host__ __device__ inline float lf_bilinear(const float q[4], float u, float w)
 {
     const float q0 = q[0] + u * (q[1] - q[0]), q1 = q[2] + u * (q[3] - q[2]);
@@ -205,6 +195,7 @@ struct LfPixel {
     long long hit_index;
     int32_t v[3];
     uint32_t a;
+    float pl;  // the plane of the face
     bool toward, hit;
 };
 
@@ -223,9 +214,10 @@ __host__ __device__ inline LfPixel lf_load(const Args& A, const CollideWorld& Wd
     P.key = A.keys[i];
     P.hit_index = A.hit[i];
     P.v[0] = P.v[1] = P.v[2] = 0;
-    P.a = (P.key >> 26) & 31u;
-    P.a = P.a > 2u ? 2u : P.a;
-    P.toward = (P.key >> 25) & 1u;
+    const FrameFace face = frame_face(P.key);
+    P.a = face.a;
+    P.pl = face.pl;
+    P.toward = face.toward;
     P.hit = false;
     if (P.key == 0u || P.hit_index < 0)
         return P;
@@ -245,15 +237,14 @@ __host__ __device__ inline LfPixel lf_load(const Args& A, const CollideWorld& Wd
 __host__ __device__ inline void lf_position(const LfPixel& P, const float o[3], const float d[3], float& u, float& w)
 {
     const uint32_t a = P.a;
-    const float pl = (float)(P.key & 0x1FFFFFFu);
     // (selects, not indexing: the vectors stay in registers)
-    const float oa = a == 0u ? o[0] : a == 1u ? o[1] : o[2], da = a == 0u ? d[0] : a == 1u ? d[1] : d[2];
     const float ob = a == 0u ? o[1] : o[0], db = a == 0u ? d[1] : d[0], oc = a >= 2u ? o[1] : o[2], dc = a >= 2u ? d[1] : d[2];
     const float vb = (float)(a == 0u ? P.v[1] : P.v[0]), vc = (float)(a >= 2u ? P.v[1] : P.v[2]);
-    const float t = (pl - oa) / da;
-    u = lf_clamp01((ob + t * db) - vb);
-    w = lf_clamp01((oc + t * dc) - vc);
-    if (da == 0.0f || !lf_finite(t) || !lf_finite(u) || !lf_finite(w))
+    float da;
+    const float t = frame_plane_t(a, P.pl, o, d, da);
+    u = frame_clamp01((ob + t * db) - vb);
+    w = frame_clamp01((oc + t * dc) - vc);
+    if (da == 0.0f || !frame_finite(t) || !frame_finite(u) || !frame_finite(w))
         u = w = 0.5f;
 }
 
@@ -279,9 +270,7 @@ __host__ __device__ inline uint32_t lf_shade(const LightFrameArgs& A, uint32_t x
         bits = kLfHitBit | F.bits | (S == 0.0f && Bk == 0.0f ? (uint32_t)kLfDarkBit : 0u);
     }
     VXRT_LF_CHECK(kLfColorOut, 3u * i + 2u);
-    A.color_out[3u * i] = out[0];
-    A.color_out[3u * i + 1u] = out[1];
-    A.color_out[3u * i + 2u] = out[2];
+    frame_store_color(A.color_out, i, out);
     if (A.fb) {
         VXRT_LF_CHECK(kLfFb, i);
         A.fb[i] = dn_bgra8(out[0], out[1], out[2]);

@@ -7,14 +7,15 @@
 //                     region layer's row words.  The bytes of a lane and row are one dword store where the row length is a
 //                     multiple of four and the output 4-byte aligned, else byte stores.  The summary is tallied in LDS and
 //                     leaves the workgroup as one atomic per non-zero counter.
-//   k_material_frame  one lane per pixel on k_light_frame's launch shape (rp_launch_shape, rp_wave_pixel), the primary ray
-//                     from the render kernel's camera_ray; every hit lane walks at most under_depth + 1 voxels up its
-//                     column through CollideWorld (mat_pixel), loads one palette entry and at most one texel.  The rules
+//   k_material_frame  the frame stages' body (frame_stage of vxrt_frame_stage.hpp) written out, as in k_light_frame, on their
+//                     launcher (an instance of the body measured level with this form, profiles/frame_stage.md, but the
+//                     suite has not run on it): every hit lane walks at most under_depth + 1 voxels up its column through
+//                     CollideWorld (mat_pixel), loads one palette entry and at most one texel.  The rules
 //                     travel by value in the kernel arguments.
 //
 // No host synchronisation, no allocation: every byte and every pixel is a pure function of the call's inputs.
 #include "../../include/vxrt.h"
-#include "vxrt_camera.hpp"
+#include "vxrt_frame_stage.hpp"
 #include "vxrt_material.hpp"
 
 namespace vxrt {
@@ -95,13 +96,7 @@ hipError_t material_field(const MaterialFieldArgs& A, const CollideWorld& Wd, hi
 
 hipError_t material_frame(const RenderArgs& R, const MaterialFrameArgs& A, const CollideWorld& Wd, uint32_t cus, hipStream_t stream)
 {
-    if (A.summary)
-        if (hipError_t e = hipMemsetAsync(A.summary, 0, 4u * sizeof(uint32_t), stream))
-            return e;
-    uint32_t block, grid;
-    rp_launch_shape(A.W, A.H, A.summary != nullptr, cus, block, grid);
-    hipLaunchKernelGGL(k_material_frame, dim3(grid), dim3(block), 0, stream, R, A, Wd);
-    return hipGetLastError();
+    return frame_stage_launch<4u, false>(k_material_frame, A.W, A.H, A.summary, cus, stream, R, A, Wd);
 }
 
 }  // namespace vxrt

@@ -13,10 +13,7 @@
 // lf_position); the run of the hit voxel is a walk of at most under_depth + 1 voxels up its column (lf_solid).
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "vxrt_light_frame.hpp"  // lf_load, lf_position, lf_solid, the launch shape (and with it vxrt_region.hpp)
+#include "vxrt_light_frame.hpp"  // lf_load, lf_position, lf_solid (and with it vxrt_frame.hpp and vxrt_region.hpp)
 
 // The harness defines this to check every index the code forms into the paint, the palette, the atlas, an output or the
 // tally against that array's size (array: one of the kMat* ids below; the frame's inputs and the world tables are checked
@@ -290,9 +287,8 @@ inline int material_frame_check(uint32_t W, uint32_t H, const vxrt_material_fram
         return 4;
     if (const int r = material_rules_check(rules))
         return 4 + r;
-    for (int k = 0; k < 3; ++k)
-        if (!lf_finite(p->cam.origin[k]) || !lf_finite(p->cam.fwd[k]) || !lf_finite(p->cam.up[k]) || !lf_finite(p->cam.right[k]))
-            return 9;
+    if (!pose_finite(p->cam))
+        return 9;
     return paint && !material_paint_ok(*rules) ? 10 : 0;
 }
 
@@ -340,9 +336,7 @@ __host__ __device__ inline uint32_t mat_pixel(const MaterialFrameArgs& A, const 
         }
     }
     VXRT_MAT_CHECK(kLfColorOut, 3u * i + 2u);
-    A.color_out[3u * i] = out[0];
-    A.color_out[3u * i + 1u] = out[1];
-    A.color_out[3u * i + 2u] = out[2];
+    frame_store_color(A.color_out, i, out);
     if (A.fb) {
         VXRT_MAT_CHECK(kLfFb, i);
         A.fb[i] = dn_bgra8(out[0], out[1], out[2]);

@@ -3,18 +3,12 @@
 // reproject_check.cpp, through tests/tools/hoststub): the limits, the hit point of a pixel on its face plane, its position
 // in the previous camera's frame, the four taps with their weights, the blend and the stores.
 //
-// Frame.  W x H pixels, x fastest, the denoiser's limits (denoise_frame_ok).  The history is one 16-byte record {r, g, b, n}
-// per pixel: a tap is one dwordx4 load and one key load.  A lane owns one pixel; a pixel reads its own colour and key, the
-// four taps of the previous frame, and writes its own record, colour and BGRA8 pixel: no pixel reads what another writes,
-// so the colour output may be the colour input.
-// The primary ray (o, d) of the pixel is an input here: camera_ray (vxrt_camera.hpp) votes across the wave and stays with
-// the kernel, as guide_key is split from k_frame_guides.
+// The frame and the shared helpers are vxrt_frame.hpp's; the launch shape of every frame stage is defined here ("launch").  The history is one 16-byte record {r, g, b, n} per
+// pixel: a tap is one dwordx4 load and one key load.  A pixel reads its own colour and key and the four taps of the previous
+// frame, and writes its own record, colour and BGRA8 pixel.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "vxrt_denoise.hpp"
+#include "vxrt_frame.hpp"
 
 // The harness defines this to check every index the code forms into an input or an output against that array's size
 // (array: one of the kRp* ids below).  The kernel leaves it empty.
@@ -52,31 +46,30 @@ struct ReprojectArgs {
     float po[3], pf[3], pu[3], pr[3];       // the previous camera: origin, fwd, up, right
 };
 
-__host__ __device__ inline float rp_dot(const float u[3], const float v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-
 // Where the surface point that pixel of key `key` and primary ray (o, d) shows lay in the previous frame: (fx, fy) in pixel
 // units; false when it has no such position (the contract's steps 2 and 3).
 __host__ __device__ inline bool rp_previous_position(const ReprojectArgs& A, uint32_t key, const float o[3], const float d[3], float& fx,
                                                      float& fy)
 {
-    const uint32_t a = (key >> 26) & 31u;  // (selects, not indexing: the vectors stay in registers; a guide key has a <= 2)
-    const float pl = (float)(key & 0x1FFFFFFu);
-    const float oa = a == 0u ? o[0] : a == 1u ? o[1] : o[2], da = a == 0u ? d[0] : a == 1u ? d[1] : d[2];
-    const float t = (pl - oa) / da;
-    if (da == 0.0f || !(t - t == 0.0f))  // (t - t: 0 for a finite t, NaN otherwise)
+    const FrameFace face = frame_face(key);
+    const uint32_t a = face.a;  // (the clamp of frame_face changes none of the selects below)
+    const float pl = face.pl;
+    float da;
+    const float t = frame_plane_t(a, pl, o, d, da);
+    if (da == 0.0f || !frame_finite(t))
         return false;
     const float P[3] = {a == 0u ? pl : o[0] + t * d[0], a == 1u ? pl : o[1] + t * d[1], a >= 2u ? pl : o[2] + t * d[2]};
     const float r[3] = {P[0] - A.po[0], P[1] - A.po[1], P[2] - A.po[2]};
     float su, sv;
     if (A.ortho) {
-        su = rp_dot(r, A.pr) / (A.ortho_x * A.ratio);
-        sv = rp_dot(r, A.pu) / A.ortho_y;
+        su = frame_dot(r, A.pr) / (A.ortho_x * A.ratio);
+        sv = frame_dot(r, A.pu) / A.ortho_y;
     } else {
-        const float z = rp_dot(r, A.pf);
+        const float z = frame_dot(r, A.pf);
         if (!(z > 0.0f))
             return false;
-        su = rp_dot(r, A.pr) / (z * A.kx);
-        sv = rp_dot(r, A.pu) / (z * A.ky);
+        su = frame_dot(r, A.pr) / (z * A.kx);
+        sv = frame_dot(r, A.pu) / (z * A.ky);
     }
     fx = ((su + 1.0f) * 0.5f) * (float)A.W;
     fy = ((sv + 1.0f) * 0.5f) * (float)A.H;
@@ -148,9 +141,8 @@ __host__ __device__ inline uint32_t rp_pixel(const ReprojectArgs& A, uint32_t x,
     A.hist_out[i] = out;
     if (A.color_out) {
         VXRT_RP_CHECK(kRpColorOut, 3u * i + 2u);
-        A.color_out[3u * i] = out.r;
-        A.color_out[3u * i + 1u] = out.g;
-        A.color_out[3u * i + 2u] = out.b;
+        const float rgb[3] = {out.r, out.g, out.b};
+        frame_store_color(A.color_out, i, rgb);
     }
     if (A.fb) {
         VXRT_RP_CHECK(kRpFb, i);
@@ -170,12 +162,15 @@ __host__ __device__ inline uint32_t rp_pixel(const ReprojectArgs& A, uint32_t x,
 // (profiles/reproject.md: one set per wave of a 1080p frame cost 0.8 ms beside a 45 us kernel).
 constexpr uint32_t kRpPlain = 256u, kRpCounted = 1024u, kRpCountedPerCu = 2u;
 
+// the lanes of a workgroup: the one rule that the launch, the kernel body (frame_stage) and the harnesses take them from
+constexpr uint32_t rp_block(bool summary) { return summary ? kRpCounted : kRpPlain; }
+
 inline uint32_t rp_tiles(uint32_t W, uint32_t H) { return ((W + 63u) / 64u) * ((H + 3u) / 4u); }  // <= 1024 * 16384
 
 inline void rp_launch_shape(uint32_t W, uint32_t H, bool summary, uint32_t cus, uint32_t& block, uint32_t& grid)
 {
     const uint32_t tiles = rp_tiles(W, H);
-    block = summary ? kRpCounted : kRpPlain;
+    block = rp_block(summary);
     grid = tiles;
     if (summary) {
         const uint32_t most = (cus ? cus : 1u) * kRpCountedPerCu, need = (tiles + kRpCounted / 256u - 1u) / (kRpCounted / 256u);

@@ -3,18 +3,12 @@
 // through tests/tools/hoststub): the checks of the parameters, the sky without disc and clouds (sky_base), the cloud noise
 // (sky_value, sky_vnoise, sky_clouds), the miss pixel, the fog of a hit pixel and the stores.
 //
-// Frame.  W x H pixels, x fastest, the denoiser's limits (denoise_frame_ok); the launch is the temporal filter's
-// (rp_launch_shape, rp_wave_pixel).  A lane owns one pixel: it reads its own key and, on a hit, its own colour, and writes
-// its own colour and BGRA8 pixel: no pixel reads what another writes, so the colour output may be the colour input.
-// The primary ray (o, d) of the pixel is an input here: camera_ray (vxrt_camera.hpp) votes across the wave and stays with
-// the kernel.  Nothing here calls libm but floorf: the host and the device forms give the same bits.
+// The frame and the shared helpers are vxrt_frame.hpp's, the launch is the temporal filter's (rp_launch_shape,
+// rp_wave_pixel).  A pixel reads its own key and, on a hit, its own colour, and writes its own colour and BGRA8 pixel.  Nothing here calls libm but floorf: the host and the device forms give
+// the same bits.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/vxrt.h"
-#include "vxrt_reproject.hpp"  // the launch shape (and with it vxrt_denoise.hpp: the frame limits, dn_bgra8)
+#include "vxrt_reproject.hpp"  // the launch shape (and with it vxrt_frame.hpp)
 
 // The harness defines this to check every index the code forms into an input or an output against that array's size
 // (array: one of the kSky* ids below).  The kernel leaves it empty.
@@ -47,14 +41,11 @@ struct SkyArgs {
     float fog_start, fog_density, fog_max;
 };
 
-__host__ __device__ inline bool sky_finite(float x) { return x - x == 0.0f; }  // (x - x: 0 for a finite x, NaN otherwise)
-__host__ __device__ inline float sky_dot(const float u[3], const float v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
-__host__ __device__ inline float sky_clamp01(float x) { return x < 0.0f ? 0.0f : x > 1.0f ? 1.0f : x; }
 __host__ __device__ inline float sky_mix(float a, float b, float w) { return a + (b - a) * w; }
 __host__ __device__ inline float sky_smooth(float x) { return (x * x) * (3.0f - 2.0f * x); }
 
 // n of the contract, in float as the device would form it: the square root is correctly rounded in both, and taken once, here
-inline float sky_sun_norm(const float v[3]) { return __builtin_sqrtf(sky_dot(v, v)); }
+inline float sky_sun_norm(const float v[3]) { return __builtin_sqrtf(frame_dot(v, v)); }
 
 // The parameter checks of include/vxrt.h that need neither the context nor a pointer of the call: 0 when all pass, else
 // the place of the first that fails in the documented order (2: W or H; 3: params or its struct_size; 4: flags or reserved_;
@@ -71,28 +62,25 @@ inline int sky_frame_check(uint32_t W, uint32_t H, const vxrt_sky_params* p)
     const float* const colours[5] = {p->zenith, p->horizon, p->ground, p->sun_color, p->cloud_color};
     for (const float* c : colours)
         for (int k = 0; k < 3; ++k)
-            if (!(c[k] >= 0.0f) || !sky_finite(c[k]))
+            if (!(c[k] >= 0.0f) || !frame_finite(c[k]))
                 return 5;
     if (p->glow_log2 > kSkyMaxGlowLog2 || p->octaves < 1u || p->octaves > kSkyMaxOctaves)
         return 6;
     const float scalars[10] = {p->glow_strength, p->ground_fade, p->cloud_scale, p->cloud_max_t, p->cloud_cover,
                                p->cloud_sharp,   p->cloud_fade,  p->fog_start,   p->fog_density, p->fog_max};
     for (float v : scalars)
-        if (!(v >= 0.0f) || !sky_finite(v))
+        if (!(v >= 0.0f) || !frame_finite(v))
             return 7;
-    if (!sky_finite(p->cloud_y) || !sky_finite(p->cloud_offset[0]) || !sky_finite(p->cloud_offset[1]))
+    if (!frame_finite(p->cloud_y) || !frame_finite(p->cloud_offset[0]) || !frame_finite(p->cloud_offset[1]))
         return 7;
     if (p->fog_max > 1.0f || p->cloud_cover > 1.0f)
         return 8;
     if (!(p->cos_inner > p->cos_outer) || !(p->cos_outer >= -1.0f) || !(p->cos_inner <= 1.0f))  // (a NaN fails)
         return 9;
     const float n = sky_sun_norm(p->sun_dir);
-    if (!(n > 0.0f) || !sky_finite(n))
+    if (!(n > 0.0f) || !frame_finite(n))
         return 10;
-    for (int k = 0; k < 3; ++k)
-        if (!sky_finite(p->cam.origin[k]) || !sky_finite(p->cam.fwd[k]) || !sky_finite(p->cam.up[k]) || !sky_finite(p->cam.right[k]))
-            return 11;
-    return 0;
+    return pose_finite(p->cam) ? 0 : 11;
 }
 
 // the call's arguments as the launch takes them (params checked before)
@@ -144,7 +132,7 @@ __host__ __device__ inline void sky_base(const SkyArgs& A, float h, float sd, fl
         for (int ch = 0; ch < 3; ++ch)
             c[ch] = sky_mix(A.zenith[ch], A.horizon[ch], a4) + A.sun_color[ch] * k;
     } else {
-        const float w = sky_clamp01((-h) * A.ground_fade);
+        const float w = frame_clamp01((-h) * A.ground_fade);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch)
             c[ch] = sky_mix(A.horizon[ch], A.ground[ch], w);
@@ -181,7 +169,7 @@ __host__ __device__ inline bool sky_cloud_point(const SkyArgs& A, const float o[
     if ((A.flags & kSkyClouds) == 0u || !(h > 0.0f) || !(o[1] < A.cloud_y))
         return false;
     const float t = (A.cloud_y - o[1]) / h;
-    if (!sky_finite(t) || !(t <= A.cloud_max_t))
+    if (!frame_finite(t) || !(t <= A.cloud_max_t))
         return false;
     px = (o[0] + t * d[0]) * A.cloud_scale + A.cloud_offset[0];
     pz = (o[2] + t * d[2]) * A.cloud_scale + A.cloud_offset[1];
@@ -198,8 +186,8 @@ __host__ __device__ inline float sky_clouds(const SkyArgs& A, float px, float pz
         freq = freq * 2.0f;
         amp = amp * 0.5f;
     }
-    const float dens = sky_clamp01((n - A.cloud_floor) * A.cloud_sharp);
-    return dens * sky_clamp01(h * A.cloud_fade);
+    const float dens = frame_clamp01((n - A.cloud_floor) * A.cloud_sharp);
+    return dens * frame_clamp01(h * A.cloud_fade);
 }
 
 // Pixel (x, y) with primary ray (o, d): its colour and BGRA8 pixel stored; returns the kSky* bits of the counters it adds to.
@@ -209,14 +197,14 @@ __host__ __device__ inline uint32_t sky_pixel(const SkyArgs& A, uint32_t x, uint
     const uint32_t i = y * A.W + x;  // W * H <= 2^26: every index fits 32 bits
     VXRT_SKY_CHECK(kSkyKeys, i);
     const uint32_t key = A.keys[i];
-    const float h = d[1], sd = sky_dot(d, A.sun);
+    const float h = d[1], sd = frame_dot(d, A.sun);
     float c[3];
     sky_base(A, h, sd, c);
     uint32_t bits;
     if (key == 0u) {
         bits = kSkyMissBit | (h < 0.0f ? (uint32_t)kSkyGroundBit : 0u);
         if (h >= 0.0f) {
-            const float e = sky_smooth(sky_clamp01((sd - A.cos_outer) / A.disc_span));
+            const float e = sky_smooth(frame_clamp01((sd - A.cos_outer) / A.disc_span));
             bits |= e > 0.0f ? (uint32_t)kSkySunBit : 0u;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch)
@@ -235,13 +223,11 @@ __host__ __device__ inline uint32_t sky_pixel(const SkyArgs& A, uint32_t x, uint
         bits = kSkyHitBit;
         VXRT_SKY_CHECK(kSkyColorIn, 3u * i + 2u);
         const float in[3] = {A.color_in[3u * i], A.color_in[3u * i + 1u], A.color_in[3u * i + 2u]};
-        uint32_t a = (key >> 26) & 31u;  // (selects, not indexing: the vectors stay in registers)
-        a = a > 2u ? 2u : a;
-        const float pl = (float)(key & 0x1FFFFFFu);
-        const float oa = a == 0u ? o[0] : a == 1u ? o[1] : o[2], da = a == 0u ? d[0] : a == 1u ? d[1] : d[2];
-        const float t = (pl - oa) / da;
+        const FrameFace face = frame_face(key);
+        float da;
+        const float t = frame_plane_t(face.a, face.pl, o, d, da);
         float f = 0.0f;
-        if (da != 0.0f && sky_finite(t) && t >= 0.0f) {
+        if (da != 0.0f && frame_finite(t) && t >= 0.0f) {
             float u = t - A.fog_start;
             u = u > 0.0f ? u : 0.0f;
             const float q = u * A.fog_density;
@@ -255,9 +241,7 @@ __host__ __device__ inline uint32_t sky_pixel(const SkyArgs& A, uint32_t x, uint
             c[ch] = fogged ? sky_mix(in[ch], c[ch], f) : in[ch];
     }
     VXRT_SKY_CHECK(kSkyColorOut, 3u * i + 2u);
-    A.color_out[3u * i] = c[0];
-    A.color_out[3u * i + 1u] = c[1];
-    A.color_out[3u * i + 2u] = c[2];
+    frame_store_color(A.color_out, i, c);
     if (A.fb) {
         VXRT_SKY_CHECK(kSkyFb, i);
         A.fb[i] = dn_bgra8(c[0], c[1], c[2]);

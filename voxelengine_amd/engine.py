@@ -23,6 +23,11 @@ def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
 
+def _pose(dst, cam) -> None:
+    """``cam`` = (origin, fwd, up, right) into the camera pose ``dst`` of a params struct"""
+    dst.origin, dst.fwd, dst.up, dst.right = (_f3(v) for v in cam)
+
+
 def GetDirections(euler):
     """Graphics::GetDirections (VoxelRT/Renderer.cu:27-42). Host math only."""
     f, u, r = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 3)()
@@ -861,19 +866,8 @@ class Context:
         (height, width, 4) BGRA8 frame written as well; ``work``: a device tensor of at least
         denoise_workspace_bytes(width, height) bytes (default: a new one).  Returns ``out``."""
         call = _Call(self, stream)
-        torch = call.torch
-        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
-            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
-        height, width = int(color.shape[0]), int(color.shape[1])
-        n = width * height
-        call.reads(color)
-        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
-        if out is None:
-            out = torch.empty_like(color)
-        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
-            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
-        if fb is not None:
-            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        width, height, n = call.frame_inputs(color, keys)
+        out = call.frame_outputs(color, n, out, fb)
         work = call.work(self.denoise_workspace_bytes(width, height), work,
                          "work: a contiguous device tensor of at least denoise_workspace_bytes(width, height) bytes", least=16)
         p = N.DenoiseParams(struct_size=C.sizeof(N.DenoiseParams), iterations=int(iterations), color_scale=float(color_scale))
@@ -896,33 +890,20 @@ class Context:
         frame written as well.  Returns a Reprojected: ``history``, ``color`` and, with ``summary``, a lazily read
         ReprojectSummary."""
         call = _Call(self, stream)
-        torch = call.torch
-        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
-            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
-        height, width = int(color.shape[0]), int(color.shape[1])
-        n = width * height
-        call.reads(color)
-        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
+        width, height, n = call.frame_inputs(color, keys)
         if history is not None:
-            if call.fits(history, 4 * n, 4, "history: a contiguous float32 device tensor (height, width, 4)").dtype != torch.float32:
-                raise ValueError("history: a contiguous float32 device tensor (height, width, 4)")
-            call.reads(history)
+            call.reads(call.fits_f32(history, 4 * n, "history: a contiguous float32 device tensor (height, width, 4)"))
         if prev_keys is not None:
             call.reads(call.fits(prev_keys, n, 4, "prev_keys: a contiguous device tensor of width * height four-byte elements"))
         if out_history is None:
-            out_history = torch.empty((height, width, 4), dtype=torch.float32, device=call.dev)
-        elif call.fits(out_history, 4 * n, 4, "out_history: a contiguous float32 device tensor (height, width, 4)").dtype != torch.float32:
-            raise ValueError("out_history: a contiguous float32 device tensor (height, width, 4)")
-        if out is None:
-            out = torch.empty_like(color)
-        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
-            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
-        if fb is not None:
-            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+            out_history = call.torch.empty((height, width, 4), dtype=call.torch.float32, device=call.dev)
+        else:
+            call.fits_f32(out_history, 4 * n, "out_history: a contiguous float32 device tensor (height, width, 4)")
+        out = call.frame_outputs(color, n, out, fb)
         words = call.summary(4) if summary else None
         p = N.ReprojectParams(struct_size=C.sizeof(N.ReprojectParams), ortho=1 if ortho else 0, max_history=int(max_history))
-        for pose, cam in ((p.cur, cur), (p.prev, prev)):
-            pose.origin, pose.fwd, pose.up, pose.right = (_f3(v) for v in cam)
+        _pose(p.cur, cur)
+        _pose(p.prev, prev)
         call.launch(self._L.vxrt_reproject_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), _ptr(history), _ptr(prev_keys),
                     C.byref(p), _ptr(out_history), _ptr(out), _ptr(fb), _ptr(words))
         return Reprojected(dims=(width, height), history=out_history, color=out, _summary=words, _stream=call.s)
@@ -945,14 +926,7 @@ class Context:
         write them to: also return (S, Bk, A) per pixel.
         Returns a LitFrame: ``color``, ``terms`` and, with ``summary``, a lazily read LightFrameSummary."""
         call = _Call(self, stream)
-        torch = call.torch
-        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
-            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
-        height, width = int(color.shape[0]), int(color.shape[1])
-        n = width * height
-        call.reads(color)
-        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
-        call.reads(call.fits(hit_aov, n, 8, "hit_aov: a contiguous device tensor of width * height eight-byte elements"))
+        width, height, n = call.frame_inputs(color, keys, hit_aov)
         levels = None
         if isinstance(field, LightField):
             levels, box = field.levels, (field.origin, field.dims)
@@ -964,24 +938,14 @@ class Context:
         if levels is not None:
             nvox = max(dims[0], 0) * max(dims[1], 0) * max(dims[2], 0)
             call.reads(call.fits(levels, nvox, 1, "field: a contiguous device tensor of one byte per voxel of the box"))
-        if out is None:
-            out = torch.empty_like(color)
-        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
-            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
-        if fb is not None:
-            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
-        if terms is True or terms is False:
-            terms_out = torch.empty((height, width, 3), dtype=torch.float32, device=call.dev) if terms else None
-        elif call.fits(terms, 3 * n, 4, "terms: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
-            raise ValueError("terms: a contiguous float32 device tensor (height, width, 3)")
-        else:
-            terms_out = terms
+        out = call.frame_outputs(color, n, out, fb)
+        terms_out = call.frame_plane(terms, (height, width, 3), call.torch.float32, "terms: a contiguous float32 device tensor (height, width, 3)")
         words = call.summary(4) if summary else None
         p = N.LightFrameParams(struct_size=C.sizeof(N.LightFrameParams), ortho=1 if ortho else 0, flags=_u32(flags),
                                outside_level=_u32(outside_level), sky_floor=float(sky_floor))
         p.block_color = (C.c_float * 3)(*[float(v) for v in block_color])
         p.ao_curve = (C.c_float * 4)(*[float(v) for v in ao_curve])
-        p.cam.origin, p.cam.fwd, p.cam.up, p.cam.right = (_f3(v) for v in cam)
+        _pose(p.cam, cam)
         p.box_origin, p.box_dims = _i3(origin), _i3(dims)
         call.launch(self._L.vxrt_light_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), _ptr(hit_aov), _ptr(levels),
                     C.byref(p), _ptr(out), _ptr(fb), _ptr(terms_out), _ptr(words))
@@ -1000,19 +964,8 @@ class Context:
         frame written as well.  ``summary`` (default False: no counting, the cheaper launch): also count the pixels.  Returns a
         SkyFrame: ``color`` and, with ``summary``, a lazily read SkySummary."""
         call = _Call(self, stream)
-        torch = call.torch
-        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
-            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
-        height, width = int(color.shape[0]), int(color.shape[1])
-        n = width * height
-        call.reads(color)
-        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
-        if out is None:
-            out = torch.empty_like(color)
-        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
-            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
-        if fb is not None:
-            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        width, height, n = call.frame_inputs(color, keys)
+        out = call.frame_outputs(color, n, out, fb)
         words = call.summary(6) if summary else None
         p = (Sky() if sky is None else sky)._c(cam, ortho)
         call.launch(self._L.vxrt_sky_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), C.byref(p), _ptr(out), _ptr(fb), _ptr(words))
@@ -1087,31 +1040,16 @@ class Context:
         ``material_aov``: True, or a uint8 (height, width) device tensor to write to: also return the material id per pixel.
         Returns a MaterialFrame: ``color``, ``materials`` and, with ``summary``, a lazily read MaterialFrameSummary."""
         call = _Call(self, stream)
-        torch = call.torch
-        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != torch.float32 or not color.is_contiguous():
-            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
-        height, width = int(color.shape[0]), int(color.shape[1])
-        n = width * height
-        call.reads(color)
-        call.reads(call.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
-        call.reads(call.fits(hit_aov, n, 8, "hit_aov: a contiguous device tensor of width * height eight-byte elements"))
+        width, height, n = call.frame_inputs(color, keys, hit_aov)
         d_paint, pbox = self._paint(call, paint, paint_box)
         r = rules._c(pbox)
         d_palette, d_atlas = palette._device(call)
-        if out is None:
-            out = torch.empty_like(color)
-        elif call.fits(out, 3 * n, 4, "out: a contiguous float32 device tensor (height, width, 3)").dtype != torch.float32:
-            raise ValueError("out: a contiguous float32 device tensor (height, width, 3)")
-        if fb is not None:
-            call.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
-        if material_aov is True or material_aov is False:
-            aov = torch.empty((height, width), dtype=torch.uint8, device=call.dev) if material_aov else None
-        else:
-            aov = call.fits(material_aov, n, 1, "material_aov: a contiguous uint8 device tensor (height, width)")
+        out = call.frame_outputs(color, n, out, fb)
+        aov = call.frame_plane(material_aov, (height, width), call.torch.uint8, "material_aov: a contiguous uint8 device tensor (height, width)")
         words = call.summary(4) if summary else None
         p = N.MaterialFrameParams(struct_size=C.sizeof(N.MaterialFrameParams), ortho=1 if ortho else 0, n_tiles=_u32(palette.n_tiles),
                                   tile_shift=_u32(palette.tile_shift))
-        p.cam.origin, p.cam.fwd, p.cam.up, p.cam.right = (_f3(v) for v in cam)
+        _pose(p.cam, cam)
         call.launch(self._L.vxrt_material_frame, _u32(width), _u32(height), _ptr(color), _ptr(keys), _ptr(hit_aov), C.byref(r),
                     _ptr(d_paint), _ptr(d_palette), _ptr(d_atlas), C.byref(p), _ptr(out), _ptr(fb), _ptr(aov), _ptr(words))
         return MaterialFrame(dims=(width, height), color=out, materials=aov, _summary=words, _stream=call.s)
@@ -2146,7 +2084,7 @@ class Sky:
                      "cloud_sharp", "cloud_fade", "fog_start", "fog_density", "fog_max"):
             setattr(p, name, float(getattr(self, name)))
         p.cloud_offset = (C.c_float * 2)(*[float(v) for v in self.cloud_offset])
-        p.cam.origin, p.cam.fwd, p.cam.up, p.cam.right = (_f3(v) for v in cam)
+        _pose(p.cam, cam)
         return p
 
 
@@ -2442,6 +2380,45 @@ class _Call:
 
     def summary(self, nwords: int):
         return self.torch.zeros(nwords, dtype=self.torch.int32, device=self.dev)
+
+    # ---- what the frame stages share (denoise_frame, reproject_frame, light_frame, sky_frame, material_frame)
+    def fits_f32(self, t, count: int, what: str):
+        """``t``, the caller's, if it fits ``count`` float32 elements; ValueError(``what``) otherwise"""
+        if self.fits(t, count, 4, what).dtype != self.torch.float32:
+            raise ValueError(what)
+        return t
+
+    def frame_inputs(self, color, keys, *hit_aov):
+        """the colour tensor, the keys and (a stage that decodes hit indices) the hit AOV of a frame, checked and noted as
+        read; returns (width, height, width * height)"""
+        if color.dim() != 3 or color.shape[2] != 3 or color.dtype != self.torch.float32 or not color.is_contiguous():
+            raise ValueError("color: a contiguous float32 device tensor (height, width, 3)")
+        height, width = int(color.shape[0]), int(color.shape[1])
+        n = width * height
+        self.reads(color)
+        self.reads(self.fits(keys, n, 4, "keys: a contiguous device tensor of width * height four-byte elements"))
+        for hit in hit_aov:
+            self.reads(self.fits(hit, n, 8, "hit_aov: a contiguous device tensor of width * height eight-byte elements"))
+        return width, height, n
+
+    def frame_outputs(self, color, n: int, out, fb):
+        """the colour output of a frame of ``n`` pixels -- a new tensor like ``color``, or ``out`` if it fits -- with ``fb``,
+        where one is given, checked"""
+        if out is None:
+            out = self.torch.empty_like(color)
+        else:
+            self.fits_f32(out, 3 * n, "out: a contiguous float32 device tensor (height, width, 3)")
+        if fb is not None:
+            self.fits(fb, n, 4, "fb: a contiguous device tensor of width * height * 4 bytes", any_size=True)
+        return out
+
+    def frame_plane(self, given, shape, dtype, what: str):
+        """an optional output plane of a frame: None for False, a new tensor of ``shape`` for True, else ``given``, the
+        caller's, if it holds ``shape`` elements of ``dtype``'s size (a float32 plane: of that type)"""
+        if given is True or given is False:
+            return self.torch.empty(shape, dtype=dtype, device=self.dev) if given else None
+        count = int(np.prod(shape))
+        return self.fits_f32(given, count, what) if dtype == self.torch.float32 else self.fits(given, count, 1, what)
 
     def reads(self, t):
         """``t``, a device tensor the launch reads or scratches: the caller's, or a temporary dropped when the method returns"""
